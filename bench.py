@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- clouds/sec, fwd+bwd, pointnet_pp_vonMises, N=1024 (BASELINE.json metric) on N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -14,11 +14,18 @@ von-Mises KL + backward + [one flat-gradient all-reduce when N > 1] + fused Adam
 clouds per GPU that is already resident in HBM.  float32 end to end (the large products as six exact bf16 x bf16 partial products of
 three-way operand splits, float32 accumulate: --f32-products; `f32_mfma_variant` = the same step on v_mfma_f32_32x32x2_f32), weak scaling.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
-  roofline      -- the kernel that took the most time: achieved rate from HIP events recorded by the library
-                   around every launch in a SEPARATE instrumented pass (never while throughput is timed)
-  cpu_baseline  -- the CPU oracle (float32 restatement of the reference step) timed on the host cores on a
-                   bounded sample of the same workload (rank 0, N=1 only); baseline only, not a target.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step
+(--dump-outputs) and prints the line.  Everything else is measured only with --full, after the timed steps:
+  roofline         -- the kernel that took the most time: achieved rate from HIP events recorded by the library
+                      around every launch in a SEPARATE instrumented pass (never while throughput is timed)
+  cpu_baseline     -- the CPU oracle (float32 restatement of the reference step) timed on the host cores on a
+                      bounded sample of the same workload (rank 0, N=1 only); baseline only, not a target.
+  f32_mfma_variant -- the same step with the float32 products on v_mfma_f32_32x32x2_f32 (N=1, float32 split products only)
+  allreduce_exposed_us, replicas_rel_spread -- N > 1: the step without its collective, and the replicas' parameters compared
+
+--dump-outputs DIR writes, right after the timed steps, what the timed step left for its caller as float32 .npy files: the
+loss of the last step, the parameters and BatchNorm running statistics, and the Adam moments (rank 0, dump_outputs).  The inputs
+(weights, clouds, centre and dropout draws) are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -67,6 +74,25 @@ CAPTURED_SCHEDULES = ("captured_single", "captured_overlap")
 DP_SCHEDULES = CAPTURED_SCHEDULES + SAFE_SCHEDULES
 SCHEDULE_MODE_PREFIX = {"captured_overlap": "ONE hipGraph (fwd + bwd, the two", "captured_single": "ONE hipGraph (fwd + bwd + the captured",
                         "overlap": "two hipGraphs", "single": "hipGraph(fwd+loss+bwd) + eager", "eager": "eager"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, model, opt, loss):
+    """--dump-outputs: what the last timed step left for its caller, as float32 .npy files under `path` -- loss.npy (the step's
+    mean loss), model.<name>.npy for every floating-point entry of the state_dict (parameters after the Adam update, BatchNorm
+    running statistics after the forward pass), adam.exp_avg.npy / adam.exp_avg_sq.npy (the optimiser's flat moments)."""
+    import numpy as np
+    arrays = {"loss": loss.detach().reshape(1)}
+    arrays.update({f"model.{k}": v for k, v in model.state_dict().items() if v.is_floating_point()})
+    arrays.update({"adam.exp_avg": opt.exp_avg, "adam.exp_avg_sq": opt.exp_avg_sq})
+    total = sum(4 * t.numel() for t in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+    return total
 
 
 def run_bounded(fn, limit_s, thread_setup=None):
@@ -783,14 +809,22 @@ def main():
                          "three-way operand splits on the bf16 matrix pipe, float32 accumulate -- float32 results to float32 rounding) or "
                          "mfma (v_mfma_f32_32x32x2_f32)")
     ap.add_argument("--no-mfma-variant", action="store_true",
-                    help="skip the second line measured with --f32-products mfma (N = 1, float32 only; reported as f32_mfma_variant)")
+                    help="--full: skip the second line measured with --f32-products mfma (N = 1, float32 only; reported as f32_mfma_variant)")
     ap.add_argument("--bf16-variant", action="store_true",
-                    help="also measure the secondary bf16-operand line (never the headline; off by default since round 4)")
+                    help="--full: also measure the secondary bf16-operand line (never the headline; off by default since round 4)")
     ap.add_argument("--no-bf16-variant", action="store_true", help="accepted for older command lines: the variant is off by default")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline pass, the CPU baseline, the float32-MFMA (and opt-in bf16) variant "
+                         "and, with N > 1, the exposed all-reduce time and the replicas' agreement; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, parameters, Adam moments, BatchNorm running statistics) "
+                         "to DIR/<name>.npy in float32")
     ap.add_argument("--rehearse", action="store_true",
                     help="CPU/gloo rehearsal of the launcher, the schedule selection and the collective plumbing only (no kernels)")
     ap.add_argument("--rehearse-inject", default="", help="--rehearse only: name=raise|raise_build|capture_error|hang[@rank][,name=...]")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:   # no launcher around us: become one (no GPU call made so far)
         sys.exit(self_launch(args))
@@ -854,6 +888,7 @@ def main():
             "mfma_fraction": per_gpu * FLOPS_PER_CLOUD / (MFMA_F32_PEAK_TFLOPS * 1e12),
             "hbm_fraction": per_gpu * BYTES_PER_CLOUD / (HBM_PEAK_GBS * 1e9),
             "kernel_ms_per_step": kernel_ms, **({"f32_mfma_variant": mfma} if mfma else {}), **({"bf16_variant": bf16} if bf16 else {}),
+            "full": args.full,
             **({"note": note} if note else {}),
             "roofline": roof, "cpu_baseline": cpu, "top_kernels": list(table),
         }
@@ -890,21 +925,23 @@ def main():
                      note="a captured schedule left the device or the communicator unusable; this is the host-issued measurement taken before it")
             sys.stderr.flush()
             os._exit(0)
-        if step_local is None:                             # captured collective: its collective-free twin is the plain graph
+        if step_local is None and args.full:               # captured collective: its collective-free twin is the plain graph
             step_local = build_step(model, opt, xyz, mu_gt, kappa_gt, world, True, collective=False)[0]
     else:
         step, launch_mode, step_local = build_step(model, opt, xyz, mu_gt, kappa_gt, world, not args.no_graph, schedule=forced)
-        if step_local is None:
+        if step_local is None and args.full:
             step_local = build_step(model, opt, xyz, mu_gt, kappa_gt, world, not args.no_graph, collective=False)[0]
         for _ in range(args.warmup):
             step()
         el, loss = timed(step, args.steps, fence)
         elapsed = ctrl.max(el)
     final_loss = float(loss.detach())
-    eager_step, _, _ = build_step(model, opt, xyz, mu_gt, kappa_gt, world, False, collective=False)   # rank-local, for the roofline pass
+    if args.dump_outputs and rank == 0:                    # before anything else steps the model
+        dump_outputs(args.dump_outputs, model, opt, loss)
 
+    # what follows measures or checks something other than the headline: only with --full
     exposed_us, replicas = None, None
-    if world > 1:
+    if world > 1 and args.full:
         # every replica took the same reduced gradients: their parameters must still be the same numbers (a collective that ran in
         # the wrong place of a schedule shows up here, not in the timing)
         chk = opt.flat_p.double().abs().sum().reshape(1)
@@ -922,7 +959,7 @@ def main():
     # the same step with the float32 products on v_mfma_f32_32x32x2_f32 (what rounds 1-3 measured): beside the headline, so that what
     # the split products buy -- and that they change nothing else -- is read off one run
     mfma = None
-    if args.precision == "f32" and args.f32_products == "split" and world == 1 and not args.no_mfma_variant:
+    if args.full and args.precision == "f32" and args.f32_products == "split" and world == 1 and not args.no_mfma_variant:
         ops.set_float32_products("mfma")
         torch.manual_seed(42)
         mm = PointNetPPVonMises(sampler="device").to(dev).train()
@@ -940,7 +977,7 @@ def main():
 
     # secondary line (never the headline, opt-in): the same step with bf16 MFMA operands in the grouped layers' large GEMMs
     bf16 = None
-    if args.precision == "f32" and world == 1 and args.bf16_variant and not args.no_bf16_variant:
+    if args.full and args.precision == "f32" and world == 1 and args.bf16_variant and not args.no_bf16_variant:
         ops.set_matmul_precision("bf16")
         torch.manual_seed(42)
         m16 = PointNetPPVonMises(sampler="device").to(dev).train()
@@ -958,13 +995,14 @@ def main():
         del step16, m16, o16
 
     roof, table, kernel_ms = (None, [], None)
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
+        eager_step, _, _ = build_step(model, opt, xyz, mu_gt, kappa_gt, world, False, collective=False)   # rank-local
         roof, table, kernel_ms = roofline_leg(eager_step)  # per-launch events need individual launches, not a graph replay
     cpu = None
     if world > 1:
         tdist.barrier()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(B)
         emit(elapsed, final_loss, launch_mode, dp_schedule, exposed_us, replicas, bf16, roof, table, kernel_ms, cpu, mfma=mfma)
     elif rccl_log and os.path.exists(rccl_log):

@@ -21,7 +21,7 @@ def _run_bench(extra, env_extra=None, timeout=600):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update({"PNPP_DIST_BACKEND": "gloo", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     env.update(env_extra or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-bf16-variant", "--no-roofline", *extra],
                        capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

@@ -18,10 +18,10 @@ echo "[2/8] WRITE_SIZE of the step"; rocprofv3 --pmc WRITE_SIZE -d $OUT/write -o
 python3 tools/summarize_rocprof.py pmc $OUT/fetch $OUT/write $P/pmc_traffic.json $P/${TAG}_pmc_traffic.csv
 python3 tools/summarize_rocprof.py pmc-all $OUT/fetch $OUT/write $P/${TAG}_pmc_traffic_all_kernels.json $P/${TAG}_pmc_traffic_all_kernels.csv
 cp $P/pmc_traffic.json profiles/pmc_traffic.json   # the bench line below reads the counters that belong to THESE kernel sources
-echo "[3/8] bench line"; python3 bench.py --steps 200 --warmup 20 > $P/${TAG}_bench.json 2> $OUT/bench.err
-PNPP_BENCH_DUMP=$P/${TAG}_kernel_table_events.txt python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-bf16-variant --no-mfma-variant > /dev/null 2>> $OUT/bench.err
-PNPP_BENCH_DUMP=$P/${TAG}_kernel_table_events_mfma.txt python3 bench.py --f32-products mfma --steps 50 --warmup 10 --no-cpu-baseline > $P/${TAG}_bench_mfma.json 2>> $OUT/bench.err
-PNPP_BENCH_DUMP=$P/${TAG}_kernel_table_events_bf16.txt python3 bench.py --precision bf16 --steps 50 --warmup 10 --no-cpu-baseline > $P/${TAG}_bench_bf16.json 2>> $OUT/bench.err
+echo "[3/8] bench line"; python3 bench.py --full --steps 200 --warmup 20 > $P/${TAG}_bench.json 2> $OUT/bench.err
+PNPP_BENCH_DUMP=$P/${TAG}_kernel_table_events.txt python3 bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-bf16-variant --no-mfma-variant > /dev/null 2>> $OUT/bench.err
+PNPP_BENCH_DUMP=$P/${TAG}_kernel_table_events_mfma.txt python3 bench.py --full --f32-products mfma --steps 50 --warmup 10 --no-cpu-baseline > $P/${TAG}_bench_mfma.json 2>> $OUT/bench.err
+PNPP_BENCH_DUMP=$P/${TAG}_kernel_table_events_bf16.txt python3 bench.py --full --precision bf16 --steps 50 --warmup 10 --no-cpu-baseline > $P/${TAG}_bench_bf16.json 2>> $OUT/bench.err
 echo "[4/8] kernel trace of the step"; rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace --output-format csv -- python3 $BENCH --no-roofline --no-bf16-variant > $OUT/trace.log 2>&1
 python3 tools/summarize_rocprof.py stats $OUT/trace $P/${TAG}_kernel_stats.csv
 fi
