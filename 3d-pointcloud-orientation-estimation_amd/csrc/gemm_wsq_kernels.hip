@@ -768,11 +768,11 @@ bool try_launch_wsq(const AOperand &A, const BOperand &B, int M, int Nout, int K
     *dw_slabs = workers;
     constexpr size_t lds = ((size_t)64 * KD + 64 * (KD + 4) + 2 * KD + 64 + 2 * 4 * 64) * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    ProfScope ps(st, "gemm_wsq_kernel<%d,A%d> M=%d N=%d K=%d grid=%dx1", Kd, A.mode, M, Nout, Kd, workers * ncol);
     // 1: weight panel in LDS, one image (default); 2: panel in registers, two images filled by LDS-DMA.  Form 2's stamped wave ends
     // 1.6 us earlier inside the step (5 - 7 % fewer shader cycles at a 1 - 2 % lower clock) and the launch takes the same time at every
     // batch size (49.3 / 49.8 us at 32 clouds, 93.3 k / 93.4 k clouds/s at 512): DESIGN section 9
     static const int form = getenv("PNPP_WSQ_FORM") ? atoi(getenv("PNPP_WSQ_FORM")) : 1;
+    ProfScope ps(st, "gemm_wsq_kernel<%d,A%d%s> M=%d N=%d K=%d grid=%dx1", Kd, A.mode, form == 2 ? ",F2" : "", M, Nout, Kd, workers * ncol);
     if (form == 2) {
         constexpr size_t lds2 = ((size_t)2 * 64 * (KD + 4) + 2 * KD + 2 * 4 * 64) * sizeof(float);
         static_assert(lds2 <= 160 * 1024, "LDS budget");

@@ -268,9 +268,10 @@ def test_sa2_shape_backward_of_the_256_channel_last_layer(oracle, training, B):
 
 def test_sa2_shape_second_form_of_the_kernel_in_a_child_process():
     """gemm_wsq2_kernel (PNPP_WSQ_FORM=2: weight panel in registers, two tile images filled by LDS-DMA; measured equal, not the default)
-    stays under the same gate.  The switch is read once per process, so the test above runs again in a fresh child."""
+    stays under the same gate.  The switch is read once per process, so the test above runs again in a fresh child -- with split products
+    off: in the split form the launch goes to gemm_wsd3_kernel<256> and gemm_wsq is never reached."""
     import os, subprocess, sys
-    env = dict(os.environ, PNPP_WSQ_FORM="2")
+    env = dict(os.environ, PNPP_WSQ_FORM="2", PNPP_SPLIT_PRODUCTS="0")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-p", "no:cacheprovider", "-k",
                         "test_sa2_shape_backward_of_the_256_channel_last_layer"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "3 passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
