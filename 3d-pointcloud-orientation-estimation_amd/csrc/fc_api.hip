@@ -192,6 +192,71 @@ fc_bwd_cols_kernel(const float *__restrict__ dy, const float *__restrict__ z, co
     }
 }
 
+// ---- backward, BatchNorm1d over many rows (the per-point layers of models/pointnet.py, M = B * N) ------------------------------
+// The same arithmetic as fc_bwd_cols_kernel (phase 0) with the rows split over workgroups: 256-row chunks write float64 partial
+// sums [chunk][2N] (sum g, sum g * xhat), the apply pass adds them up in chunk order (deterministic) and writes dz and the
+// normalisation's parameter gradients.  grid = (N / 64 column blocks, M / 256 row chunks).
+__global__ void __launch_bounds__(256)
+fc_bwd_bn_rows_sums_kernel(const float *__restrict__ dy, const float *__restrict__ z, const uint8_t *__restrict__ mask,
+                           float drop_scale, int relu, const float *__restrict__ scale, const float *__restrict__ shift,
+                           const float *__restrict__ mean, const float *__restrict__ istd, int M, int N, double *__restrict__ part) {
+    __shared__ double red[4][2][64];
+    const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+    const int n = blockIdx.x * 64 + cl, m0 = blockIdx.y * 256;
+    double s1 = 0.0, s2 = 0.0;
+    if (n < N) {
+        const float sc = scale[n], sh = shift[n], mu = mean[n], is = istd[n];
+        for (int r = rl; r < 256; r += 4) {
+            const int m = m0 + r;
+            if (m >= M) break;
+            const size_t i = (size_t)m * N + n;
+            const float zz = z[i];
+            float g = dy[i];
+            if (mask) g = mask[i] ? g * drop_scale : 0.f;
+            if (relu && !(fmaf(zz, sc, sh) > 0.f)) g = 0.f;
+            s1 += (double)g;
+            s2 += (double)g * (double)((zz - mu) * is);
+        }
+    }
+    red[rl][0][cl] = s1;
+    red[rl][1][cl] = s2;
+    __syncthreads();
+    if (rl == 0 && n < N) {
+        part[(size_t)blockIdx.y * 2 * N + n] = (red[0][0][cl] + red[1][0][cl]) + (red[2][0][cl] + red[3][0][cl]);
+        part[(size_t)blockIdx.y * 2 * N + N + n] = (red[0][1][cl] + red[1][1][cl]) + (red[2][1][cl] + red[3][1][cl]);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+fc_bwd_bn_rows_apply_kernel(const float *__restrict__ dy, const float *__restrict__ z, const uint8_t *__restrict__ mask,
+                            float drop_scale, int relu, const float *__restrict__ scale, const float *__restrict__ shift,
+                            const float *__restrict__ mean, const float *__restrict__ istd, int M, int N, int training, int chunks,
+                            const double *__restrict__ part, float *__restrict__ dz, float *__restrict__ dnw,
+                            float *__restrict__ dnb, float *__restrict__ db) {
+    const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+    const int n = blockIdx.x * 64 + cl, m0 = blockIdx.y * 256;
+    if (n >= N) return;
+    double s1 = 0.0, s2 = 0.0;
+    for (int c = 0; c < chunks; ++c) s1 += part[(size_t)c * 2 * N + n], s2 += part[(size_t)c * 2 * N + N + n];
+    const float sc = scale[n], sh = shift[n], mu = mean[n], is = istd[n];
+    const float c1 = training ? (float)(s1 / M) : 0.f, c2 = training ? (float)(s2 / M) : 0.f;
+    for (int r = rl; r < 256; r += 4) {
+        const int m = m0 + r;
+        if (m >= M) break;
+        const size_t i = (size_t)m * N + n;
+        const float zz = z[i];
+        float g = dy[i];
+        if (mask) g = mask[i] ? g * drop_scale : 0.f;
+        if (relu && !(fmaf(zz, sc, sh) > 0.f)) g = 0.f;
+        dz[i] = sc * (g - c1 - (zz - mu) * is * c2);
+    }
+    if (blockIdx.y == 0 && rl == 0) {
+        if (dnw) dnw[n] = (float)s2;
+        if (dnb) dnb[n] = (float)s1;
+        if (db) db[n] = training ? 0.f : (float)((double)sc * s1);
+    }
+}
+
 // ---- backward of a head block with at most 32 rows, ONE launch (round 3) ------------------------------------------------------------
 // Linear -> BatchNorm1d (or none) -> ReLU -> Dropout, M <= 32 (models/pointnet_pp_vonMises.py:32-35 at batch 32): fc_bwd_cols_kernel
 // (dz and the normalisation's parameter gradients, 5 us) and fc_dx_dw_kernel (dx = dz W, dW = dz^T x, 6 - 7 us) only differ by WHO holds
@@ -721,6 +786,19 @@ static int fc_backward_impl(const pnpp_fc_desc *d, const pnpp_fc_bwd_args *a, hi
             PNPP_CHECK_LAUNCH("fc_backward(rows)");
         }
         PNPP_TRY(launch_slab_reduce(sc.gbuf, chunks, 1, d->N, d->N, -1, a->db, d->N, st));
+    } else if (d->norm == PNPP_NORM_BATCH && d->M > 4096 && !stats_sync_on()) {
+        const int chunks = cdiv(d->M, 256);  // sc.gbuf (M x N floats) holds the [chunks][2N] float64 partials
+        double *part = reinterpret_cast<double *>(sc.gbuf);
+        {
+            ProfScope ps(st, "fc_bwd_bn_rows_sums_kernel M=%d N=%d", d->M, d->N);
+            hipLaunchKernelGGL(fc_bwd_bn_rows_sums_kernel, dim3(cdiv(d->N, 64), chunks), dim3(256), 0, st, a->dy, sv.z, a->mask,
+                               d->drop_scale, d->relu, sv.scale, sv.shift, sv.mean, sv.istd, d->M, d->N, part);
+            PNPP_CHECK_LAUNCH("fc_backward(bn sums)");
+        }
+        ProfScope ps(st, "fc_bwd_bn_rows_apply_kernel M=%d N=%d", d->M, d->N);
+        hipLaunchKernelGGL(fc_bwd_bn_rows_apply_kernel, dim3(cdiv(d->N, 64), chunks), dim3(256), 0, st, a->dy, sv.z, a->mask,
+                           d->drop_scale, d->relu, sv.scale, sv.shift, sv.mean, sv.istd, d->M, d->N, d->training, chunks, part, sc.dz,
+                           a->dnw, a->dnb, a->db);
     } else {
         const int bn = d->norm == PNPP_NORM_BATCH;
         // head blocks of at most 32 rows with a gradient to pass on: dz is never written (fc_bwd_fused_kernel); PNPP_NO_FC_FUSED=1 keeps
@@ -830,4 +908,20 @@ extern "C" int pnpp_fc_forward(const pnpp_fc_desc *d, const pnpp_fc_fwd_args *a,
 }
 extern "C" int pnpp_fc_backward(const pnpp_fc_desc *d, const pnpp_fc_bwd_args *a, void *stream) {
     return fc_backward_impl(d, a, as_stream(stream));
+}
+// y of a BatchNorm block with more than 32 rows, recomputed from what its forward call kept (the same launch as the forward pass's
+// last one, so the same bits): lets a caller drop y between forward and backward (models/pointnet.py's per-point trunks)
+extern "C" int pnpp_fc_recompute_output(const pnpp_fc_desc *d, const void *saved, const uint8_t *mask, float *y, void *stream) {
+    PNPP_TRY(fc_check(d));
+    PNPP_REQUIRE(saved && y, PNPP_ERR_ARG, "fc_recompute_output: null pointer");
+    PNPP_REQUIRE(d->norm == PNPP_NORM_BATCH && d->M > 32, PNPP_ERR_ARG,
+                 "fc_recompute_output: only BatchNorm blocks with more than 32 rows (M=%d norm=%d)", d->M, d->norm);
+    const FcSaved sv = fc_saved_layout(d, const_cast<void *>(saved));
+    const size_t total = (size_t)d->M * d->N;
+    const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    ProfScope ps(as_stream(stream), "fc_apply_cols_kernel M=%d N=%d", d->M, d->N);
+    hipLaunchKernelGGL(fc_apply_cols_kernel, dim3(grid), dim3(256), 0, as_stream(stream), sv.z, sv.scale, sv.shift, mask, d->drop_scale,
+                       d->relu, d->M, d->N, y);
+    PNPP_CHECK_LAUNCH("fc_recompute_output");
+    return PNPP_OK;
 }

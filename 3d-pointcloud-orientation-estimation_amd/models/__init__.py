@@ -1,6 +1,8 @@
-"""Drop-in `models` package.  The reference's models/__init__.py:1-9 re-exports seven classes; the five built on the
-set-abstraction backbone are here (plus the von-Mises models the training scripts import from their submodules).
-Vanilla PointNet and PointTransformer are outside the hot path this repository implements."""
+"""Drop-in `models` package.  The reference's models/__init__.py:1-9 re-exports seven classes; all seven are here: vanilla
+PointNet (models/pointnet.py), PointTransformer (models/point_transformer.py) and the five built on the set-abstraction
+backbone (plus the von-Mises models the training scripts import from their submodules)."""
+from .pointnet import PointNet
+from .point_transformer import PointTransformer
 from .pointnet_pp import PointNetPP
 from .Pointnet_pp_xyz import PointNetPPXYZ
 from .Pointnet_pp_xyz_Schedmit import PointNetPPXYZ_Schedmit
@@ -9,5 +11,5 @@ from .pointnet_pp_Fwd import PointNetPPFwd
 from .pointnet_pp_vonMises import PointNetPPVonMises
 from .pointnet_pp_mvM import PointNetPPMvM
 
-__all__ = ["PointNetPP", "PointNetPPXYZ", "PointNetPPXYZ_Schedmit", "PointNetPP8Dir", "PointNetPPFwd",
+__all__ = ["PointNet", "PointTransformer", "PointNetPP", "PointNetPPXYZ", "PointNetPPXYZ_Schedmit", "PointNetPP8Dir", "PointNetPPFwd",
            "PointNetSetAbstraction", "DIRS_8", "PointNetPPVonMises", "PointNetPPMvM"]

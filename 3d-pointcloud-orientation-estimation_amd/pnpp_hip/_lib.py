@@ -55,6 +55,21 @@ class FcBwdArgs(C.Structure):
                 ("saved", _fp), ("scratch", _fp), ("dx", _fp), ("dw", _fp), ("db", _fp), ("dnw", _fp), ("dnb", _fp)]
 
 
+class PnPoolDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("K", C.c_int), ("C", C.c_int), ("relu", C.c_int), ("training", C.c_int),
+                ("eps", C.c_float), ("momentum", C.c_float)]
+
+
+class PnPoolFwdArgs(C.Structure):
+    _fields_ = [("a", _fp), ("w", _fp), ("b", _fp), ("gamma", _fp), ("beta", _fp), ("rm", _fp), ("rv", _fp), ("nbt", _fp),
+                ("out", _fp), ("saved", _fp), ("scratch", _fp)]
+
+
+class PnPoolBwdArgs(C.Structure):
+    _fields_ = [("a", _fp), ("w", _fp), ("gamma", _fp), ("dout", _fp), ("saved", _fp), ("scratch", _fp), ("da", _fp), ("dw", _fp),
+                ("db", _fp), ("dgamma", _fp), ("dbeta", _fp)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 _i, _f, _u64, _sz = C.c_int, C.c_float, C.c_uint64, C.c_size_t
 # int fn(double *buf, size_t n_doubles, void *stream, void *user): sums buf over the ranks in place (SyncBN, pnpp_set_stats_exchange)
@@ -131,6 +146,23 @@ SIGNATURES = {
     "pnpp_adam_step_clip": (_i, [_fp, _fp, _fp, _fp, _sz, _i, _f, _f, _f, _f, _f, _fp, _f, _i, _fp]),
     "pnpp_adam_step_dev_clip": (_i, [_fp, _fp, _fp, _fp, _sz, _fp, _f, _f, _f, _f, _f, _fp, _f, _i, _fp]),
     "pnpp_sumsq": (_i, [_fp, _sz, _fp, _fp, _sz, _fp]),
+    "pnpp_pn_pool_saved_bytes": (_sz, [C.POINTER(PnPoolDesc)]),
+    "pnpp_pn_pool_scratch_bytes": (_sz, [C.POINTER(PnPoolDesc)]),
+    "pnpp_pn_pool_forward": (_i, [C.POINTER(PnPoolDesc), C.POINTER(PnPoolFwdArgs), _fp]),
+    "pnpp_pn_pool_backward": (_i, [C.POINTER(PnPoolDesc), C.POINTER(PnPoolBwdArgs), _fp]),
+    "pnpp_pn_pool_saved_route": (_fp, [C.POINTER(PnPoolDesc), _fp]),
+    "pnpp_pn_pool_saved_zsel": (_fp, [C.POINTER(PnPoolDesc), _fp]),
+    "pnpp_pn_pool_saved_ypre": (_fp, [C.POINTER(PnPoolDesc), _fp]),
+    "pnpp_fc_recompute_output": (_i, [C.POINTER(FcDesc), _fp, _fp, _fp, _fp]),
+    "pnpp_pn_transform": (_i, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, _i, _i, _i, _i, _i, _fp, _fp]),
+    "pnpp_pn_transform_bwd": (_i, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _fp]),
+    "pnpp_pn_regularizer": (_i, [_fp, _i, _i, _fp, _fp, _fp]),
+    "pnpp_pn_regularizer_bwd": (_i, [_fp, _fp, _fp, _i, _i, _fp, _fp]),
+    "pnpp_pn_add_identity": (_i, [_fp, _i, _i, _fp, _fp]),
+    "pnpp_pn_concat": (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp]),
+    "pnpp_pn_concat_bwd": (_i, [_fp, _i, _i, _i, _i, _fp, _fp, _fp]),
+    "pnpp_pn_bn_relu": (_i, [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _f, _f, _fp, _fp, _fp, _fp]),
+    "pnpp_pn_bn_relu_bwd": (_i, [_fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp]),
 }
 
 _lib = None

@@ -42,6 +42,8 @@ SOURCES = {
     "sa_api.hip": [],
     "fc_api.hip": [],
     "transformer_kernels.hip": [],
+    "pointnet_kernels.hip": [],
+    "pointnet_api.hip": [],
 }
 
 

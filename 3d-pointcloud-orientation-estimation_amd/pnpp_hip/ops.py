@@ -970,3 +970,363 @@ class _ProjProbs(torch.autograd.Function):
 def proj_probs(vec: torch.Tensor, dirs: torch.Tensor) -> torch.Tensor:
     """train_multi_8dir.py:41-44: unit vector -> non-negative cosine to each of the D directions -> normalised to sum 1."""
     return _ProjProbs.apply(vec, dirs)
+
+
+# ------------------------------------------------------------------------------------------------
+# vanilla PointNet (models/pointnet.py): pooled wide layer, per-cloud transforms, regulariser, head pieces.
+# float32 products whatever set_matmul_precision / set_float32_products say (those switch the set-abstraction GEMMs only).
+# ------------------------------------------------------------------------------------------------
+# set to a list to receive, per pooled-layer forward call, {"route": (B,C) int32, "zsel": (B,C) float32} (views into the call's
+# saved workspace): the row each pooled value came from and z there -- the parity tests hand these to a float64 evaluation
+pn_pool_tap: Optional[list] = None
+
+
+def _pn_pool_desc(B, N, K, C_, relu, training, eps, momentum):
+    d = L.PnPoolDesc()
+    d.B, d.N, d.K, d.C, d.relu, d.training = int(B), int(N), int(K), int(C_), int(relu), int(training)
+    d.eps, d.momentum = float(eps), float(momentum)
+    return d
+
+
+class _PnPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, w, b, gamma, beta, cfg):
+        B, N, relu, training, eps, momentum, rm, rv, nbt = cfg
+        a, w, b = _f32(a, "a"), _f32(w, "conv weight"), _f32(b, "conv bias")
+        gamma, beta = _f32(gamma, "bn weight"), _f32(beta, "bn bias")
+        if a.dim() != 2 or a.shape[0] != B * N:
+            raise ValueError(f"pn_pool: expected ({B * N}, K) rows, got {tuple(a.shape)}")
+        K, Cc = a.shape[1], w.shape[0]
+        if w.numel() != Cc * K:
+            raise ValueError(f"pn_pool: weight {tuple(w.shape)} does not map {K} inputs")
+        d = _pn_pool_desc(B, N, K, Cc, relu, training, eps, momentum)
+        lib = L.lib()
+        sb = lib.pnpp_pn_pool_saved_bytes(C.byref(d))
+        if sb == 0:
+            L.check(L.PNPP_ERR_ARG)
+        saved = torch.empty(sb, dtype=torch.uint8, device=a.device)
+        scratch = _scratch(lib.pnpp_pn_pool_scratch_bytes(C.byref(d)), a.device)
+        out = torch.empty(B, Cc, device=a.device, dtype=torch.float32)
+        x = L.PnPoolFwdArgs()
+        x.a, x.w, x.b, x.gamma, x.beta = a.data_ptr(), w.data_ptr(), b.data_ptr(), gamma.data_ptr(), beta.data_ptr()
+        x.rm, x.rv, x.nbt = rm.data_ptr(), rv.data_ptr(), _p(nbt)
+        x.out, x.saved, x.scratch = out.data_ptr(), saved.data_ptr(), scratch.data_ptr()
+        L.check(lib.pnpp_pn_pool_forward(C.byref(d), C.byref(x), _stream()))
+        if pn_pool_tap is not None:
+            r = lib.pnpp_pn_pool_saved_route(C.byref(d), saved.data_ptr()) - saved.data_ptr()
+            z = lib.pnpp_pn_pool_saved_zsel(C.byref(d), saved.data_ptr()) - saved.data_ptr()
+            pn_pool_tap.append({"route": saved[r:r + 4 * B * Cc].view(torch.int32).view(B, Cc),
+                                "zsel": saved[z:z + 4 * B * Cc].view(torch.float32).view(B, Cc)})
+        ctx.desc = d
+        ctx.save_for_backward(a, w, gamma, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        a, w, gamma, saved = ctx.saved_tensors
+        d = ctx.desc
+        dout = _f32(dout, "dout")
+        lib = L.lib()
+        scratch = _scratch(lib.pnpp_pn_pool_scratch_bytes(C.byref(d)), a.device)
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        dw, db = torch.empty_like(w), torch.empty(d.C, device=a.device, dtype=torch.float32)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+        x = L.PnPoolBwdArgs()
+        x.a, x.w, x.gamma, x.dout, x.saved, x.scratch = a.data_ptr(), w.data_ptr(), gamma.data_ptr(), dout.data_ptr(), \
+            saved.data_ptr(), scratch.data_ptr()
+        x.da, x.dw, x.db, x.dgamma, x.dbeta = _p(da), dw.data_ptr(), db.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
+        L.check(lib.pnpp_pn_pool_backward(C.byref(d), C.byref(x), _stream()))
+        return da, dw, db, dgamma, dbeta, None
+
+
+def pn_pool(a: torch.Tensor, B: int, N: int, conv, bn, relu: bool, training: bool) -> torch.Tensor:
+    """max over each cloud's N rows of act(bn(conv(a))): a (B*N, K) rows, conv a 1x1 nn.Conv1d, bn its nn.BatchNorm1d (running
+    statistics updated in place when training).  Returns (B, C).  Keeps O(B*C + K*K) for the backward pass, not (B*N) x C."""
+    momentum = bn.momentum if bn.momentum is not None else 0.1
+    nbt = _nbt(bn) if training else None
+    cfg = (int(B), int(N), bool(relu), bool(training), bn.eps, momentum, bn.running_mean, bn.running_var, nbt)
+    return _PnPool.apply(a, conv.weight, conv.bias, bn.weight, bn.bias, cfg)
+
+
+class _PnTransform(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, k, ldy):
+        _need_gpu(x, "x")
+        if x.dtype != torch.float32:
+            raise TypeError(f"x must be float32, got {x.dtype}")
+        if not (x.is_contiguous() or x.transpose(1, 2).is_contiguous()):
+            x = x.contiguous()
+        B, N, D = x.shape
+        if t is not None:
+            t = _f32(t, "transform")
+            if tuple(t.shape) != (B, k, k):
+                raise ValueError(f"pn_transform: transform {tuple(t.shape)} is not ({B}, {k}, {k})")
+        y = torch.empty(B * N, ldy, device=x.device, dtype=torch.float32)
+        sb, sn, sd = x.stride()
+        L.check(L.lib().pnpp_pn_transform(x.data_ptr(), sb, sn, sd, _p(t), B, N, D, k, ldy, y.data_ptr(), _stream()))
+        ctx.k, ctx.ldy, ctx.has_t = k, ldy, t is not None
+        ctx.save_for_backward(x, t if t is not None else x.new_empty(0))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, t = ctx.saved_tensors
+        t = t if ctx.has_t else None
+        dy = _f32(dy, "dy")
+        B, N, D = x.shape
+        dx = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        dt = torch.empty_like(t) if (t is not None and ctx.needs_input_grad[1]) else None
+        if dx is None and dt is None:
+            return None, None, None, None
+        sb, sn, sd = x.stride()
+        L.check(L.lib().pnpp_pn_transform_bwd(x.data_ptr(), sb, sn, sd, _p(t), dy.data_ptr(), B, N, D, ctx.k, ctx.ldy, _p(dx), _p(dt),
+                                              _stream()))
+        return dx, dt, None, None
+
+
+def pn_transform(x: torch.Tensor, t: Optional[torch.Tensor], ldy: int) -> torch.Tensor:
+    """x (B, N, D) -- any dense layout, e.g. the transpose of a (B, D, N) input, read in place -- times the per-cloud transform
+    t (B, k, k) on its first k columns, the other D - k columns passed through, zero columns up to ldy: (B*N, ldy) rows.
+    t None: the strided copy into (B*N, ldy) rows alone."""
+    k = t.shape[-1] if t is not None else 0
+    return _PnTransform.apply(x, t, k, int(ldy))
+
+
+class _PnRegularizer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t):
+        t = _f32(t, "trans")
+        if t.dim() != 3 or t.shape[1] != t.shape[2]:
+            raise ValueError(f"feature_transform_regularizer: expected (B, k, k), got {tuple(t.shape)}")
+        B, k = t.shape[0], t.shape[1]
+        norms = torch.empty(B, device=t.device, dtype=torch.float64)
+        out = torch.empty((), device=t.device, dtype=torch.float32)
+        L.check(L.lib().pnpp_pn_regularizer(t.data_ptr(), B, k, norms.data_ptr(), out.data_ptr(), _stream()))
+        ctx.save_for_backward(t, norms)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        t, norms = ctx.saved_tensors
+        g = _f32(g, "grad")
+        dt = torch.empty_like(t)
+        L.check(L.lib().pnpp_pn_regularizer_bwd(t.data_ptr(), norms.data_ptr(), g.data_ptr(), t.shape[0], t.shape[1], dt.data_ptr(),
+                                                _stream()))
+        return dt
+
+
+def feature_transform_regularizer(trans: torch.Tensor) -> torch.Tensor:
+    """mean_b ||T_b T_b^T - I||_F of (B, k, k) transforms (PointNetDemo.py's feature_transform_reguliarzer), a 0-d tensor;
+    forward and backward on the device."""
+    return _PnRegularizer.apply(trans)
+
+
+class _PnAddIdentity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, k):
+        x = _f32(x, "x")
+        B = x.shape[0]
+        if x.numel() != B * k * k:
+            raise ValueError(f"pn_add_identity: {tuple(x.shape)} is not ({B}, {k * k})")
+        y = torch.empty(B, k, k, device=x.device, dtype=torch.float32)
+        L.check(L.lib().pnpp_pn_add_identity(x.data_ptr(), B, k, y.data_ptr(), _stream()))
+        ctx.shape = x.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy.reshape(ctx.shape), None
+
+
+def pn_add_identity(x: torch.Tensor, k: int) -> torch.Tensor:
+    """(B, k*k) -> (B, k, k) + I: the T-Nets' `fc3(x) + iden`."""
+    return _PnAddIdentity.apply(x, int(k))
+
+
+class _PnConcat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, pf, N):
+        g, pf = _f32(g, "global feature"), _f32(pf, "point features")
+        B, C1 = g.shape
+        C2 = pf.shape[1]
+        if pf.shape[0] != B * N:
+            raise ValueError(f"pn_concat: point features {tuple(pf.shape)} are not ({B * N}, C)")
+        out = torch.empty(B, C1 + C2, N, device=g.device, dtype=torch.float32)
+        L.check(L.lib().pnpp_pn_concat(g.data_ptr(), pf.data_ptr(), B, N, C1, C2, out.data_ptr(), _stream()))
+        ctx.dims = (B, N, C1, C2)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, N, C1, C2 = ctx.dims
+        dout = _f32(dout, "dout")
+        dg = torch.empty(B, C1, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        dpf = torch.empty(B * N, C2, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        if dg is None and dpf is None:
+            return None, None, None
+        L.check(L.lib().pnpp_pn_concat_bwd(dout.data_ptr(), B, N, C1, C2, _p(dg), _p(dpf), _stream()))
+        return dg, dpf, None
+
+
+def pn_concat(g: torch.Tensor, pf: torch.Tensor, N: int) -> torch.Tensor:
+    """cat([g (B, C1) repeated over the N points, pf (B*N, C2) rows transposed], 1) -> (B, C1 + C2, N)."""
+    return _PnConcat.apply(g, pf, int(N))
+
+
+class _PnBnRelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, cfg):
+        training, eps, momentum, rm, rv, nbt = cfg
+        x, gamma, beta = _f32(x, "x"), _f32(gamma, "bn weight"), _f32(beta, "bn bias")
+        M, Cc = x.shape
+        mean, istd = torch.empty(Cc, device=x.device, dtype=torch.float32), torch.empty(Cc, device=x.device, dtype=torch.float32)
+        y = torch.empty_like(x)
+        L.check(L.lib().pnpp_pn_bn_relu(x.data_ptr(), M, Cc, gamma.data_ptr(), beta.data_ptr(), rm.data_ptr(), rv.data_ptr(), _p(nbt),
+                                        int(training), float(eps), float(momentum), mean.data_ptr(), istd.data_ptr(), y.data_ptr(),
+                                        _stream()))
+        ctx.training = bool(training)
+        ctx.save_for_backward(x, y, gamma, mean, istd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, gamma, mean, istd = ctx.saved_tensors
+        dy = _f32(dy, "dy")
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+        L.check(L.lib().pnpp_pn_bn_relu_bwd(x.data_ptr(), y.data_ptr(), dy.data_ptr(), x.shape[0], x.shape[1], gamma.data_ptr(),
+                                            mean.data_ptr(), istd.data_ptr(), int(ctx.training), _p(dx), dgamma.data_ptr(),
+                                            dbeta.data_ptr(), _stream()))
+        return dx, dgamma, dbeta, None
+
+
+def pn_bn_relu(x: torch.Tensor, bn, training: bool) -> torch.Tensor:
+    """relu(bn(x)) for (M, C) rows with an nn.BatchNorm1d on its own (running statistics updated in place when training)."""
+    momentum = bn.momentum if bn.momentum is not None else 0.1
+    nbt = _nbt(bn) if training else None
+    return _PnBnRelu.apply(x, bn.weight, bn.bias, (bool(training), bn.eps, momentum, bn.running_mean, bn.running_var, nbt))
+
+
+# set to a list to receive, per narrow layer of a pn_trunk call, its (B*N, C) ReLU decisions (y > 0, on the host) in call order
+pn_relu_tap: Optional[list] = None
+
+
+class _PnTrunk(torch.autograd.Function):
+    """Per-point layers (1x1 conv -> train/eval BatchNorm -> ReLU) followed by the pooled wide layer, as one autograd node that
+    keeps only the input rows, each narrow layer's pre-BatchNorm output (its fc workspace) and the pooled layer's small workspace:
+    the narrow layers' outputs are recomputed from their workspaces in the backward pass (pnpp_fc_recompute_output)."""
+
+    @staticmethod
+    def forward(ctx, rows, cfg, *params):
+        B, N, nl, pool_relu, training, eps, mom, running, nbts, sinks = cfg
+        rows = _f32(rows, "rows")
+        M = B * N
+        if rows.dim() != 2 or rows.shape[0] != M:
+            raise ValueError(f"pn_trunk: expected ({M}, K) rows, got {tuple(rows.shape)}")
+        lib = L.lib()
+        x, descs, saveds = rows, [], []
+        for l in range(nl):
+            w, b, nw, nb = (_f32(t, "trunk parameter") for t in params[4 * l:4 * l + 4])
+            d = L.FcDesc()
+            d.M, d.K, d.N, d.norm, d.relu, d.training = M, x.shape[1], w.shape[0], L.NORM_BATCH, 1, int(training)
+            d.eps, d.momentum, d.drop_scale = float(eps[l]), float(mom[l]), 1.0
+            sb = lib.pnpp_fc_saved_bytes(C.byref(d))
+            if sb == 0 or M <= 32:
+                L.check(L.PNPP_ERR_ARG)
+            saved = torch.empty(sb, dtype=torch.uint8, device=rows.device)
+            scratch = _scratch(lib.pnpp_fc_scratch_bytes(C.byref(d)), rows.device)
+            y = torch.empty(M, d.N, device=rows.device, dtype=torch.float32)
+            a = L.FcFwdArgs()
+            a.x, a.w, a.b, a.nw, a.nb = x.data_ptr(), w.data_ptr(), b.data_ptr(), nw.data_ptr(), nb.data_ptr()
+            a.rm, a.rv, a.nbt = running[2 * l].data_ptr(), running[2 * l + 1].data_ptr(), _p(nbts[l])
+            a.y, a.saved, a.scratch = y.data_ptr(), saved.data_ptr(), scratch.data_ptr()
+            L.check(lib.pnpp_fc_forward(C.byref(d), C.byref(a), _stream()))
+            if pn_relu_tap is not None:
+                pn_relu_tap.append((y > 0).cpu())
+            descs.append(d)
+            saveds.append(saved)
+            x = y
+        w, b, nw, nb = (_f32(t, "pooled layer parameter") for t in params[4 * nl:4 * nl + 4])
+        pd = _pn_pool_desc(B, N, x.shape[1], w.shape[0], pool_relu, training, eps[nl], mom[nl])
+        sb = lib.pnpp_pn_pool_saved_bytes(C.byref(pd))
+        if sb == 0:
+            L.check(L.PNPP_ERR_ARG)
+        psaved = torch.empty(sb, dtype=torch.uint8, device=rows.device)
+        scratch = _scratch(lib.pnpp_pn_pool_scratch_bytes(C.byref(pd)), rows.device)
+        out = torch.empty(B, pd.C, device=rows.device, dtype=torch.float32)
+        a = L.PnPoolFwdArgs()
+        a.a, a.w, a.b, a.gamma, a.beta = x.data_ptr(), w.data_ptr(), b.data_ptr(), nw.data_ptr(), nb.data_ptr()
+        a.rm, a.rv, a.nbt = running[2 * nl].data_ptr(), running[2 * nl + 1].data_ptr(), _p(nbts[nl])
+        a.out, a.saved, a.scratch = out.data_ptr(), psaved.data_ptr(), scratch.data_ptr()
+        L.check(lib.pnpp_pn_pool_forward(C.byref(pd), C.byref(a), _stream()))
+        if pn_pool_tap is not None:
+            r = lib.pnpp_pn_pool_saved_route(C.byref(pd), psaved.data_ptr()) - psaved.data_ptr()
+            pn_pool_tap.append({"route": psaved[r:r + 4 * B * pd.C].view(torch.int32).view(B, pd.C)})
+        ctx.descs, ctx.pdesc, ctx.sinks, ctx.nl = descs, pd, sinks, nl
+        ctx.save_for_backward(rows, psaved, *saveds, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        nl, descs, pd = ctx.nl, ctx.descs, ctx.pdesc
+        t = ctx.saved_tensors
+        rows, psaved, saveds, params = t[0], t[1], t[2:2 + nl], t[2 + nl:]
+        sinks = ctx.sinks or [None] * len(params)
+        dout = _f32(dout, "dout")
+        lib = L.lib()
+        dev = rows.device
+        ys = []
+        for l in range(nl):   # the narrow layers' outputs, bit-identical to the forward pass's
+            y = torch.empty(descs[l].M, descs[l].N, device=dev, dtype=torch.float32)
+            L.check(lib.pnpp_fc_recompute_output(C.byref(descs[l]), saveds[l].data_ptr(), None, y.data_ptr(), _stream()))
+            ys.append(y)
+        grads = [None] * len(params)
+
+        def dest(i):
+            if sinks[i] is not None:
+                return sinks[i]
+            grads[i] = torch.empty_like(params[i])
+            return grads[i]
+
+        a_in = ys[-1] if nl else rows
+        da = torch.empty_like(a_in) if (nl or ctx.needs_input_grad[0]) else None
+        w, _, nw, _ = params[4 * nl:4 * nl + 4]
+        scratch = _scratch(lib.pnpp_pn_pool_scratch_bytes(C.byref(pd)), dev)
+        a = L.PnPoolBwdArgs()
+        a.a, a.w, a.gamma, a.dout, a.saved, a.scratch = a_in.data_ptr(), w.data_ptr(), nw.data_ptr(), dout.data_ptr(), \
+            psaved.data_ptr(), scratch.data_ptr()
+        a.da = _p(da)
+        a.dw, a.db, a.dgamma, a.dbeta = (dest(4 * nl + j).data_ptr() for j in range(4))
+        L.check(lib.pnpp_pn_pool_backward(C.byref(pd), C.byref(a), _stream()))
+        dy = da
+        for l in reversed(range(nl)):
+            d = descs[l]
+            x = ys[l - 1] if l else rows
+            w, b, nw, nb = params[4 * l:4 * l + 4]
+            dx = torch.empty_like(x) if (l or ctx.needs_input_grad[0]) else None
+            scratch = _scratch(lib.pnpp_fc_scratch_bytes(C.byref(d)), dev)
+            bw = L.FcBwdArgs()
+            bw.x, bw.w, bw.b, bw.nw, bw.nb, bw.mask = x.data_ptr(), w.data_ptr(), b.data_ptr(), nw.data_ptr(), nb.data_ptr(), None
+            bw.dy, bw.saved, bw.scratch = dy.data_ptr(), saveds[l].data_ptr(), scratch.data_ptr()
+            bw.dx = _p(dx)
+            bw.dw, bw.db, bw.dnw, bw.dnb = (dest(4 * l + j).data_ptr() for j in range(4))
+            L.check(lib.pnpp_fc_backward(C.byref(d), C.byref(bw), _stream()))
+            dy = dx
+        return (dy, None, *grads)
+
+
+def pn_trunk(rows: torch.Tensor, B: int, N: int, layers, pooled, pool_relu: bool, training: bool) -> torch.Tensor:
+    """(B*N, K) point rows -> relu(bn(conv)) for each (conv, bn) of `layers` (0 - 2 of them, 1x1 nn.Conv1d + nn.BatchNorm1d) ->
+    the pooled wide layer `pooled` = (conv, bn) with its max over each cloud's N points: (B, C).  Keeps for the backward pass
+    only the rows, the narrow layers' pre-BatchNorm outputs and O(B*C + K^2) for the pooled layer."""
+    params, running, nbts, eps, mom = [], [], [], [], []
+    for conv, bn in list(layers) + [pooled]:
+        params += [conv.weight, conv.bias, bn.weight, bn.bias]
+        running += [bn.running_mean, bn.running_var]
+        nbts.append(_nbt(bn) if training else None)
+        eps.append(bn.eps)
+        mom.append(bn.momentum if bn.momentum is not None else 0.1)
+    sinks = [grad_sink(p) for p in params]
+    cfg = (int(B), int(N), len(layers), bool(pool_relu), bool(training), eps, mom, running, nbts,
+           sinks if any(s is not None for s in sinks) else None)
+    return _PnTrunk.apply(rows, cfg, *params)

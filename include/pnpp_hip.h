@@ -236,6 +236,9 @@ size_t pnpp_fc_saved_bytes(const pnpp_fc_desc *d);
 size_t pnpp_fc_scratch_bytes(const pnpp_fc_desc *d);
 int pnpp_fc_forward(const pnpp_fc_desc *d, const pnpp_fc_fwd_args *a, void *stream);
 int pnpp_fc_backward(const pnpp_fc_desc *d, const pnpp_fc_bwd_args *a, void *stream);
+/* y of a BatchNorm block with M > 32 recomputed from its forward call's `saved` (bit-identical to the forward output), so that a
+ * caller need not keep y for the backward pass; `mask` as given to the forward call */
+int pnpp_fc_recompute_output(const pnpp_fc_desc *d, const void *saved, const uint8_t *mask, float *y, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Output heads and losses (forward value and analytic gradient in one launch)
@@ -406,6 +409,81 @@ int pnpp_debug_wsd3_timeouts(void);
 typedef int (*pnpp_stats_exchange_fn)(double *buf, size_t n_doubles, void *stream, void *user);
 int pnpp_set_stats_exchange(pnpp_stats_exchange_fn fn, void *user, double *buf, size_t buf_doubles);
 int pnpp_stats_exchange_enabled(void);
+
+/* ------------------------------------------------------------------------------------------
+ * Vanilla PointNet (models/pointnet.py; additive to ABI 5).  float32 products whatever pnpp_set_matmul_precision /
+ * pnpp_set_split_products say; statistics and reductions over points in float64; no float atomics (bitwise replay).
+ * The training-mode entry points return PNPP_ERR_ARG while a statistics exchange (SyncBN) is registered.
+ *
+ * Sizes: B <= 65535 (clouds are a grid dimension).
+ * Pooled wide layer: out[b, c] = max over the cloud's N rows of act(BN(A W^T + b))[n, c], A = (B*N, K) rows.  Nothing of size
+ * (B*N) x C is stored: the forward pass keeps the cloud's max / min of z = A W^T + b per channel and its row (first on ties), the
+ * training statistics come from the column sums and the Gram matrix of A; the backward pass is one (B*N) x K x K product plus
+ * a routed scatter ("Vanilla PointNet").
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int B, N;            /* clouds, points per cloud                                                      */
+    int K, C;            /* input width (multiple of 4, <= 128), channels (multiple of 64, <= 1024)        */
+    int relu;            /* ReLU after the BatchNorm (the T-Nets' conv3) or none (the encoder's conv3)     */
+    int training;        /* batch statistics + running update, or the running statistics                  */
+    float eps, momentum;
+} pnpp_pn_pool_desc;
+
+typedef struct {
+    const float *a;      /* (B*N, K), 16-byte aligned                                                     */
+    const float *w, *b;  /* (C, K), (C)                                                                   */
+    const float *gamma, *beta;
+    float *rm, *rv;      /* running statistics (C), updated in training                                   */
+    int64_t *nbt;        /* num_batches_tracked (+1 in training) or NULL                                   */
+    float *out;          /* (B, C)                                                                        */
+    void *saved;         /* pnpp_pn_pool_saved_bytes()                                                    */
+    void *scratch;       /* pnpp_pn_pool_scratch_bytes()                                                  */
+} pnpp_pn_pool_fwd_args;
+
+typedef struct {
+    const float *a, *w, *gamma;
+    const float *dout;   /* (B, C)                                                                        */
+    const void *saved;
+    void *scratch;
+    float *da;           /* (B*N, K) or NULL                                                              */
+    float *dw, *db, *dgamma, *dbeta;  /* db is 0 in training (the BatchNorm removes the bias)               */
+} pnpp_pn_pool_bwd_args;
+
+size_t pnpp_pn_pool_saved_bytes(const pnpp_pn_pool_desc *d);     /* 0: bad descriptor (pnpp_last_error) */
+size_t pnpp_pn_pool_scratch_bytes(const pnpp_pn_pool_desc *d);
+int pnpp_pn_pool_forward(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_fwd_args *a, void *stream);
+int pnpp_pn_pool_backward(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_bwd_args *a, void *stream);
+/* diagnostics: views into a forward call's saved workspace -- the (B, C) int32 row each pooled value came from (its max route,
+ * local to the cloud) and the (B, C) float32 z at that row */
+void *pnpp_pn_pool_saved_route(const pnpp_pn_pool_desc *d, void *saved);
+void *pnpp_pn_pool_saved_zsel(const pnpp_pn_pool_desc *d, void *saved);
+/* ... and the (B, C) float32 pre-activation act() was applied to: with relu, the ReLU decision at the pooled value is ypre > 0 */
+void *pnpp_pn_pool_saved_ypre(const pnpp_pn_pool_desc *d, void *saved);
+
+/* Per-cloud transform: y[b, n, j] = sum_i x[b, n, i] t[b, i, j] for j < k, x[b, n, j] for k <= j < D, 0 for D <= j < ldy;
+ * x element (b, n, d) at x[b*sb + n*sn + d*sd] (so (B, D, N) and (B, N, D) inputs are both read in place), y (B*N, ldy) rows.
+ * t == NULL: no product (a strided copy into padded rows).  D <= 64, k <= D, D <= ldy <= 64.
+ * Backward: dx (x's strides, D columns) = dy t^T on the transformed columns, dy on the others; dt[b] = x_b^T dy_b over the cloud's
+ * points in float64, fixed order.  dx / dt may be NULL. */
+int pnpp_pn_transform(const float *x, int64_t sb, int64_t sn, int64_t sd, const float *t, int B, int N, int D, int k, int ldy,
+                      float *y, void *stream);
+int pnpp_pn_transform_bwd(const float *x, int64_t sb, int64_t sn, int64_t sd, const float *t, const float *dy, int B, int N, int D,
+                          int k, int ldy, float *dx, float *dt, void *stream);
+/* feature-transform regulariser out[0] = mean_b ||t_b t_b^T - I||_F, norms (B doubles, caller-owned) kept for the backward pass;
+ * backward: dt_b = dout[0] * 2 (t_b t_b^T - I) t_b / (B ||.||_F) (0 where the norm is 0) */
+int pnpp_pn_regularizer(const float *t, int B, int k, double *norms, float *out, void *stream);
+int pnpp_pn_regularizer_bwd(const float *t, const double *norms, const float *dout, int B, int k, float *dt, void *stream);
+/* y = x + I per cloud (the T-Nets' "fc3 + iden"); its backward is the identity */
+int pnpp_pn_add_identity(const float *x, int B, int k, float *y, void *stream);
+/* out (B, C1 + C2, N) = [g repeated over the points; pf (B*N, C2) rows transposed] and its backward (dg: sum over the points) */
+int pnpp_pn_concat(const float *g, const float *pf, int B, int N, int C1, int C2, float *out, void *stream);
+int pnpp_pn_concat_bwd(const float *dout, int B, int N, int C1, int C2, float *dg, float *dpf, void *stream);
+/* relu(BatchNorm1d(x)) over (M, C) rows on its own -- the PointNet head's relu(bn2(dropout(fc2(x)))); mean / istd (C) kept for
+ * the backward pass, which reads the forward output y for the ReLU decisions.  dx may be NULL. */
+int pnpp_pn_bn_relu(const float *x, int M, int C, const float *gamma, const float *beta, float *rm, float *rv, int64_t *nbt,
+                    int training, float eps, float momentum, float *mean, float *istd, float *y, void *stream);
+int pnpp_pn_bn_relu_bwd(const float *x, const float *y, const float *dy, int M, int C, const float *gamma, const float *mean,
+                        const float *istd, int training, float *dx, float *dgamma, float *dbeta, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step glue on one flat parameter / gradient buffer
