@@ -22,12 +22,11 @@ int launch_pn_pool_bwd_channels(const float *a, const float *w, const float *gam
                                 const float *istd, const float *zsel, const float *ypre, const int32_t *route, const double *S,
                                 const double *Cc, int B, int N, int K, int C, int relu, int training, float *dw, float *db,
                                 float *dgamma, float *dbeta, float *coef, float *u, float *v, hipStream_t st);
-// backward, train mode: Q = W^T diag(v) W and cvec = Q S / M - W^T u
-int launch_pn_pool_bwd_q(const float *w, const float *u, const float *v, const double *S, int N_total, int K, int C, float *Q,
-                         float *cvec, hipStream_t st);
-// backward: dA_n = R_n + cvec - Q A_n (train) or R_n (eval), R the routed scatter of coef_{b,c} w_c
+// backward, train mode: Q = W^T diag(v) W and cvec = -W^T u
+int launch_pn_pool_bwd_q(const float *w, const float *u, const float *v, int K, int C, float *Q, float *cvec, hipStream_t st);
+// backward: dA_n = R_n + cvec - Q (A_n - S/M) (train) or R_n (eval), R the routed scatter of coef_{b,c} w_c
 int launch_pn_pool_bwd_da(const float *a, const float *w, const float *Q, const float *cvec, const float *coef, const int32_t *route,
-                          int B, int N, int K, int C, int training, float *da, hipStream_t st);
+                          const double *S, int B, int N, int K, int C, int training, float *da, hipStream_t st);
 
 // ---- per-cloud transform Y_b = X_b T_b (first k columns), columns k..D-1 passed through, columns D..ldy-1 zero ----
 int launch_pn_transform(const float *x, long long sb, long long sn, long long sd, const float *t, int B, int N, int D, int k, int ldy,

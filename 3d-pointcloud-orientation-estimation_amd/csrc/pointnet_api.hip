@@ -147,8 +147,8 @@ extern "C" int pnpp_pn_pool_backward(const pnpp_pn_pool_desc *d, const pnpp_pn_p
                                        d->N, d->K, d->C, d->relu, d->training, a->dw, a->db, a->dgamma, a->dbeta, sc.coef, sc.u, sc.v,
                                        st));
     if (!a->da) return PNPP_OK;
-    if (d->training) PN_TRY(launch_pn_pool_bwd_q(a->w, sc.u, sc.v, sv.S, d->B * d->N, d->K, d->C, sc.Q, sc.cvec, st));
-    return launch_pn_pool_bwd_da(a->a, a->w, sc.Q, sc.cvec, sc.coef, sv.route, d->B, d->N, d->K, d->C, d->training, a->da, st);
+    if (d->training) PN_TRY(launch_pn_pool_bwd_q(a->w, sc.u, sc.v, d->K, d->C, sc.Q, sc.cvec, st));
+    return launch_pn_pool_bwd_da(a->a, a->w, sc.Q, sc.cvec, sc.coef, sv.route, sv.S, d->B, d->N, d->K, d->C, d->training, a->da, st);
 }
 
 static int transform_check(const float *x, const float *t, int B, int N, int D, int k, int ldy) {

@@ -85,7 +85,7 @@ int pn_gram_slices(int N) { return N >= 8 * 128 ? 8 : N >= 4 * 64 ? 4 : 1; }
 int launch_pn_gram(const float *a, int B, int N, int K, double *gp, double *sp, double *S, double *Cc, hipStream_t st) {
     const int nt = cdiv(K, 64), ns = pn_gram_slices(N), rps = cdiv(cdiv(N, ns), 32) * 32;
     {
-        ProfScope ps(st, "pn_gram_kernel B=%d N=%d K=%d", B, N, K);
+        ProfScope ps(st, "pn_gram_kernel B=%d N=%d K=%d slices=%d", B, N, K, ns);
         hipLaunchKernelGGL(pn_gram_kernel, dim3(nt * nt, B, ns), dim3(256), 0, st, a, N, K, rps, gp, sp);
         PNPP_CHECK_LAUNCH("pn_gram");
     }
@@ -304,12 +304,10 @@ int launch_pn_pool_bwd_channels(const float *a, const float *w, const float *gam
     return PNPP_OK;
 }
 
-// Q = W^T diag(v) W (one row per workgroup) and cvec = Q S / M - W^T u
+// Q = W^T diag(v) W (one row per workgroup) and cvec = -W^T u
 __global__ void __launch_bounds__(PN_KMAX) pn_pool_bwd_q_kernel(const float *__restrict__ w, const float *__restrict__ u,
-                                                                const float *__restrict__ v, const double *__restrict__ S,
-                                                                double M, int K, int C, float *__restrict__ Q,
+                                                                const float *__restrict__ v, int K, int C, float *__restrict__ Q,
                                                                 float *__restrict__ cvec) {
-    __shared__ double row[PN_KMAX];
     __shared__ double part[PN_KMAX];
     __shared__ float Wc[32][PN_KMAX];
     __shared__ float vc[32], uc[32];
@@ -325,37 +323,38 @@ __global__ void __launch_bounds__(PN_KMAX) pn_pool_bwd_q_kernel(const float *__r
         // W^T u split over the threads by channel, summed in a fixed order below
         if (j < 32) r += (double)Wc[j][i] * (double)uc[j];
     }
-    row[j] = j < K ? q : 0.0;
     part[j] = r;
     __syncthreads();
     if (j < K) Q[(size_t)i * K + j] = (float)q;
     if (j == 0) {
-        double s = 0.0, r0 = 0.0;
-        for (int jj = 0; jj < K; ++jj) s += row[jj] * S[jj];
+        double r0 = 0.0;
         for (int jj = 0; jj < PN_KMAX; ++jj) r0 += part[jj];
-        cvec[i] = (float)(s / M - r0);
+        cvec[i] = (float)(-r0);
     }
 }
 
-int launch_pn_pool_bwd_q(const float *w, const float *u, const float *v, const double *S, int N_total, int K, int C, float *Q,
-                         float *cvec, hipStream_t st) {
+int launch_pn_pool_bwd_q(const float *w, const float *u, const float *v, int K, int C, float *Q, float *cvec, hipStream_t st) {
     ProfScope ps(st, "pn_pool_bwd_q_kernel K=%d C=%d", K, C);
-    hipLaunchKernelGGL(pn_pool_bwd_q_kernel, dim3(K), dim3(PN_KMAX), 0, st, w, u, v, S, (double)N_total, K, C, Q, cvec);
+    hipLaunchKernelGGL(pn_pool_bwd_q_kernel, dim3(K), dim3(PN_KMAX), 0, st, w, u, v, K, C, Q, cvec);
     PNPP_CHECK_LAUNCH("pn_pool_bwd_q");
     return PNPP_OK;
 }
 
-// dA for one (64-row tile, cloud): cvec - Q A_n (train), then the routed rows gathered in ascending channel order
+// dA for one (64-row tile, cloud): cvec - Q (A_n - S/M) (train; the tile is centred as it is loaded, so a column whose mean is large
+// against its spread loses no digits), then the routed rows gathered in ascending channel order
 __global__ void __launch_bounds__(256) pn_pool_bwd_da_kernel(const float *__restrict__ a, const float *__restrict__ w,
                                                               const float *__restrict__ Q, const float *__restrict__ cvec,
                                                               const float *__restrict__ coef, const int32_t *__restrict__ route,
-                                                              int N, int K, int C, int training, float *__restrict__ da) {
+                                                              const double *__restrict__ S, double M, int N, int K, int C,
+                                                              int training, float *__restrict__ da) {
     __shared__ __attribute__((aligned(16))) float Qs[PN_KMAX][PN_KMAX];
     __shared__ __attribute__((aligned(16))) float As[PN_KMAX * PN_RT];  // A tile [K][64] (k-major), then the output tile [64][K]
     __shared__ int ent_c[PN_CMAX];
     __shared__ short ent_r[PN_CMAX];
     __shared__ int cnt[257];
+    __shared__ double mcol[PN_KMAX];
     const int n0 = blockIdx.x * PN_RT, b = blockIdx.y, t = threadIdx.x;
+    if (training && t < K) mcol[t] = S[t] / M;
     // 1. the (row, channel) pairs routed into this tile, in ascending channel order
     const int cpt = (C + 255) / 256;
     int mine = 0;
@@ -389,7 +388,7 @@ __global__ void __launch_bounds__(256) pn_pool_bwd_da_kernel(const float *__rest
         for (int idx = t; idx < K * K; idx += 256) Qs[idx / K][idx % K] = Q[idx];
         for (int idx = t; idx < PN_RT * K; idx += 256) {
             const int r = idx / K, k = idx % K, n = n0 + r;
-            As[k * PN_RT + r] = n < N ? a[((size_t)b * N + n) * K + k] : 0.f;
+            As[k * PN_RT + r] = n < N ? (float)((double)a[((size_t)b * N + n) * K + k] - mcol[k]) : 0.f;
         }
         __syncthreads();
         if (tc * 8 < K)
@@ -425,10 +424,10 @@ __global__ void __launch_bounds__(256) pn_pool_bwd_da_kernel(const float *__rest
 }
 
 int launch_pn_pool_bwd_da(const float *a, const float *w, const float *Q, const float *cvec, const float *coef, const int32_t *route,
-                          int B, int N, int K, int C, int training, float *da, hipStream_t st) {
+                          const double *S, int B, int N, int K, int C, int training, float *da, hipStream_t st) {
     ProfScope ps(st, "pn_pool_bwd_da_kernel B=%d N=%d K=%d C=%d", B, N, K, C);
-    hipLaunchKernelGGL(pn_pool_bwd_da_kernel, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, a, w, Q, cvec, coef, route, N, K, C, training,
-                       da);
+    hipLaunchKernelGGL(pn_pool_bwd_da_kernel, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, a, w, Q, cvec, coef, route, S, (double)B * N, N,
+                       K, C, training, da);
     PNPP_CHECK_LAUNCH("pn_pool_bwd_da");
     return PNPP_OK;
 }

@@ -1223,6 +1223,8 @@ class _PnTrunk(torch.autograd.Function):
         M = B * N
         if rows.dim() != 2 or rows.shape[0] != M:
             raise ValueError(f"pn_trunk: expected ({M}, K) rows, got {tuple(rows.shape)}")
+        if M <= 32:
+            raise ValueError(f"pn_trunk: {B} clouds x {N} points = {M} point rows; the per-point layers need more than 32")
         lib = L.lib()
         x, descs, saveds = rows, [], []
         for l in range(nl):
@@ -1231,7 +1233,7 @@ class _PnTrunk(torch.autograd.Function):
             d.M, d.K, d.N, d.norm, d.relu, d.training = M, x.shape[1], w.shape[0], L.NORM_BATCH, 1, int(training)
             d.eps, d.momentum, d.drop_scale = float(eps[l]), float(mom[l]), 1.0
             sb = lib.pnpp_fc_saved_bytes(C.byref(d))
-            if sb == 0 or M <= 32:
+            if sb == 0:
                 L.check(L.PNPP_ERR_ARG)
             saved = torch.empty(sb, dtype=torch.uint8, device=rows.device)
             scratch = _scratch(lib.pnpp_fc_scratch_bytes(C.byref(d)), rows.device)
