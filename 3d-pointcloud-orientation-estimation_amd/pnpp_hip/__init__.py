@@ -5,5 +5,13 @@
     build   hipcc build of the shared library (gfx950)
     optim   flat-buffer Adam / gradient clipping on the device
     dist    one-process-per-GPU data parallelism (RCCL all-reduce of one flat gradient buffer)
+    inference  Predictor: forward-only evaluation, one fused launch per set-abstraction level
 """
-__all__ = ["ops", "build", "optim", "dist", "sampling"]
+__all__ = ["ops", "build", "optim", "dist", "sampling", "inference", "Predictor"]
+
+
+def __getattr__(name):
+    if name == "Predictor":   # resolved on first use: importing the package stays free of torch
+        from .inference import Predictor
+        return Predictor
+    raise AttributeError(f"module 'pnpp_hip' has no attribute '{name}'")

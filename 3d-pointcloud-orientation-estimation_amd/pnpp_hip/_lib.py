@@ -39,6 +39,11 @@ class SaBwdArgs(C.Structure):
                 ("d_conv_w", _PL), ("d_conv_b", _PL), ("d_bn_w", _PL), ("d_bn_b", _PL), ("dpoints", _fp)]
 
 
+class SaInferArgs(C.Structure):
+    _fields_ = [("xyz", _fp), ("points", _fp), ("centre_idx", _fp), ("neighbour_idx", _fp), ("idx_out", _fp), ("weights", _fp),
+                ("new_xyz", _fp), ("out", _fp)]
+
+
 class FcDesc(C.Structure):
     _fields_ = [("M", C.c_int), ("K", C.c_int), ("N", C.c_int), ("norm", C.c_int), ("relu", C.c_int),
                 ("training", C.c_int), ("eps", C.c_float), ("momentum", C.c_float), ("drop_scale", C.c_float)]
@@ -97,6 +102,13 @@ SIGNATURES = {
     "pnpp_sa_group_pair": (_i, [C.POINTER(SaDesc), C.POINTER(SaDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnpp_sa_saved_argmax": (_fp, [C.POINTER(SaDesc), _fp]),
     "pnpp_sa_saved_relu_mask": (_i, [C.POINTER(SaDesc), _fp, _fp, _fp, _i, _fp, _fp]),
+    "pnpp_sa_infer_supported": (_i, [C.POINTER(SaDesc)]),
+    "pnpp_sa_infer_weights_bytes": (_sz, [C.POINTER(SaDesc)]),
+    "pnpp_sa_infer_weights_layout": (_i, [C.POINTER(SaDesc), _i, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_sz)]),
+    "pnpp_sa_infer_fold": (_i, [C.POINTER(SaDesc), C.POINTER(SaFwdArgs), _fp, _fp]),
+    "pnpp_sa_infer": (_i, [C.POINTER(SaDesc), C.POINTER(SaInferArgs), _fp]),
+    "pnpp_sa_infer_group_pair": (_i, [C.POINTER(SaDesc), C.POINTER(SaDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "pnpp_fc_infer_fold": (_i, [_i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _f, _fp, _fp, _fp]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

@@ -486,6 +486,61 @@ int pnpp_pn_bn_relu_bwd(const float *x, const float *y, const float *dy, int M, 
                         const float *istd, int training, float *dx, float *dgamma, float *dbeta, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Forward-only (inference) path of the set-abstraction levels (additive to ABI 5; csrc/sa_infer_kernels.hip).
+ * models/pointnet_pp_8dir.py:21-43 with the BatchNorms in eval mode: running statistics make each BatchNorm an affine map,
+ * which is folded into the convolution in front of it ONCE (pnpp_sa_infer_fold, float64 rounded once to float32):
+ *     a = gamma / sqrt(running_var + eps),  W' = a (.) W row-wise,  b' = (b - running_mean) * a + beta.
+ * A level is then ONE launch: gather -> 3 x (product + b' + ReLU) -> max over the neighbourhood; the intermediate M x C tiles
+ * stay in LDS / registers, only (B,S,C_last) and new_xyz are written.  No backward pass exists for this path, there is no
+ * `saved` and no `scratch`: pnpp_sa_forward with training = 0 remains the differentiable eval path and the path for every other shape.
+ *
+ * Shapes the fused kernel takes (pnpp_sa_infer_supported answers for a descriptor; d->training and d->momentum are ignored):
+ *   L == 3;  every C[l] a multiple of 32, at most 1024;  K == 16 or K == 32 (group_all: N == 16 or N == 32);  D <= 1021;
+ *   a 32-row tile of widths max(round16(D+3), C[1]) + 8 and C[0] + 8, three bfloat16 planes each, must fit 160 KiB of LDS;  any B, N, S within int32 sizes.
+ * float32 products formed on the bf16 matrix pipe from exact three-way operand splits (the arithmetic pnpp_set_split_products(1)
+ * describes: float32 results to float32 rounding, same parity gates) whatever pnpp_set_matmul_precision / pnpp_set_split_products say;
+ * the weights' planes are written once by pnpp_sa_infer_fold, an activation is split once where it is produced.
+ *
+ * The folded-parameter blob (pnpp_sa_infer_weights_bytes, caller-owned device memory) holds per layer W'_l (C[l] x ld_l, xyz columns
+ * first, zeros beyond the layer's input width; ld_0 = D + 3 rounded up to 16, ld_l = C[l-1]) and b'_l (C[l], float32).  W'_l is stored
+ * as the THREE bfloat16 planes of its exact three-way split (W' = high + middle + low, 8 + 8 + 8 significand bits: the operands of the
+ * split products below), each C[l] * ld_l elements, one after the other, each in the order the kernel's lanes read it
+ * ("fragment-major"): element (n, k) of a plane at bf16 index
+ *     (((n / 32) * (ld_l / 16) + k / 16) * 64 + 32 * ((k % 16) / 8) + n % 32) * 8 + k % 8,
+ * i.e. the blob holds [3][C/32][ld/16][2][32][8] bfloat16 per layer.  pnpp_sa_infer_weights_layout gives the byte offsets and ld_l of a layer (the documented
+ * view the parity tests read back).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *xyz;             /* (B,N,3)                                                                          */
+    const float *points;          /* (B,N,D) or NULL                                                                  */
+    const int32_t *centre_idx;    /* (B,S) centre indices (unused when group_all)                                     */
+    const int32_t *neighbour_idx; /* (B,S,K) neighbours (ball query, injection), or NULL: the level searches kNN itself */
+    int32_t *idx_out;             /* (B,S,K) caller-owned; receives the kNN result when neighbour_idx is NULL         */
+    const void *weights;          /* blob written by pnpp_sa_infer_fold for the same descriptor                       */
+    float *new_xyz;               /* out (B,S,3): the gathered centres, zeros when group_all                          */
+    float *out;                   /* out (B,S,C[2])                                                                   */
+} pnpp_sa_infer_args;
+
+/* 1: the fused kernel takes the shape.  0: it does not, pnpp_last_error() names the reason */
+int pnpp_sa_infer_supported(const pnpp_sa_desc *d);
+/* bytes of the folded-parameter blob; 0 for a refused descriptor */
+size_t pnpp_sa_infer_weights_bytes(const pnpp_sa_desc *d);
+int pnpp_sa_infer_weights_layout(const pnpp_sa_desc *d, int layer, size_t *w_offset_host, int *w_ld_host, size_t *b_offset_host);
+/* reads conv_w / conv_b / bn_w / bn_b / bn_rm / bn_rv of `params` (every other member is ignored, nothing is written to them) and
+ * writes the blob: one launch per layer */
+int pnpp_sa_infer_fold(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *params, void *weights, void *stream);
+int pnpp_sa_infer(const pnpp_sa_desc *d, const pnpp_sa_infer_args *a, void *stream);
+/* pnpp_sa_group_pair for this path (models/pointnet_pp_8dir.py:28-31 of sa1 and sa2 in ONE launch): the neighbour indices go to
+ * plain (B,S,K) int32 buffers, the centre coordinates to new_xyz1 / new_xyz2; pass idx1 / idx2 as neighbour_idx to pnpp_sa_infer */
+int pnpp_sa_infer_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *centre1,
+                             const int32_t *centre2, int32_t *idx1, float *new_xyz1, int32_t *idx2, float *new_xyz2, void *stream);
+/* The same fold for a head block, nn.Linear (N,K) + eval-mode nn.BatchNorm1d (models/pointnet_pp_vonMises.py:32-33,
+ * pointnet_pp_8dir.py:81-84): w_out (N,K), b_out (N).  The folded block then runs as pnpp_fc_forward with norm = PNPP_NORM_NONE,
+ * training = 0 on (w_out, b_out): y = relu(x W'^T + b'). */
+int pnpp_fc_infer_fold(int N, int K, const float *w, const float *b, const float *gamma, const float *beta, const float *rm,
+                       const float *rv, float eps, float *w_out, float *b_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Step glue on one flat parameter / gradient buffer
  * (train_single_peak_vonMises_KL.py:80,85; train_multi_peaks_vonMises_KL.py:221,235-236)
  * ---------------------------------------------------------------------------------------- */
