@@ -253,4 +253,11 @@ int launch_pool_bwd(const float *dout, const int32_t *arg, const float *z, const
 
 int launch_fill_zero(void *p, size_t bytes, hipStream_t st);
 
+// ---- sa_infer_kernels.hip ----
+// conv / linear weight (C x Cin) + eval-mode BatchNorm folded in float64, rounded once; W' written as the three fragment-major bf16
+// planes of C x ld (zeros beyond Cin) the forward-only kernels multiply with, b' as C floats
+int launch_bn_fold_split(const float *w, int Cin, const float *b, const float *gamma, const float *beta, const float *rm, const float *rv,
+                         float eps, int C, int ld, unsigned short *wout, float *bout, hipStream_t st);
+int infer_target_wgs();   // workgroups a forward-only launch should reach: one per CU of the current device
+
 }  // namespace pnpp

@@ -21,17 +21,13 @@
 // Shapes taken (pnpp_sa_infer_supported): L == 3; C[l] multiples of 32, <= 1024; K in {16, 32} (group_all: N in {16, 32});
 // D + 3 <= 1024; the two LDS tiles (three bf16 planes each) of a 32-row workgroup fit 160 KiB.
 #include "kernels.h"
+#include "split_infer.h"
 
 namespace pnpp {
 
-namespace {
-
-constexpr int kInferThreads = 256;
-constexpr int kInferMaxLds = 160 * 1024;
-
 // workgroups a launch should reach before the last layer's columns stop being split: one per CU of the current device.
 // Cached process-wide, unsynchronised, like the library's other process state (one process drives one GPU: pnpp_hip.dist)
-static int infer_target_wgs() {
+int infer_target_wgs() {
     static int cus = 0;
     if (cus <= 0) {
         int dev = 0, n = 0;
@@ -41,6 +37,11 @@ static int infer_target_wgs() {
     }
     return cus;
 }
+
+namespace {
+
+constexpr int kInferThreads = 256;
+constexpr int kInferMaxLds = 160 * 1024;
 
 struct InferPlan {
     int TM;        // rows per workgroup (32 or 64)
@@ -111,26 +112,6 @@ static InferBlob infer_blob(const pnpp_sa_desc *d, const InferPlan &p, void *bas
     return b;
 }
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-
-// Exact three-way split of float32 into bfloat16 pieces (24 significand bits = 8 + 8 + 8), as csrc/gemm_wsf3_kernels.hip:
-// v = h + m + l with h = bf16(v), m = bf16(v - h), l = v - h - m (exact in bf16); two values at a time, packed low / high.
-__device__ __forceinline__ unsigned i3_pk(float lo, float hi) {
-    const f32x2v v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
-}
-__device__ __forceinline__ float i3_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float i3_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ void i3_split2(float v0, float v1, unsigned &h, unsigned &m, unsigned &l) {
-    h = i3_pk(v0, v1);
-    float r0 = v0 - i3_lo(h), r1 = v1 - i3_hi(h);
-    m = i3_pk(r0, r1);
-    r0 -= i3_lo(m), r1 -= i3_hi(m);
-    l = i3_pk(r0, r1);
-}
-
 // W' (C x ld row-major, zero beyond Cin) and b' (C) of one linear + eval-mode BatchNorm pair (head blocks); float64, one rounding
 __global__ __launch_bounds__(256) void bn_fold_kernel(const float *__restrict__ w, int Cin, const float *__restrict__ b,
                                                       const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -174,65 +155,6 @@ struct InferArgs {
     int group_all;
     int c2_per_wg;       // columns of the last layer this workgroup's blockIdx.y owns
 };
-
-// acc[j] + accl[j] += act[32 rows][0 .. Kd) * W[col_j .. +32][0 .. Kd)^T for NJ column blocks `colstep` apart, float32 products formed
-// on v_mfma_f32_32x32x16_bf16 from the three-way splits of both operands: a b = a_h b_h + (a_l b_h + a_h b_l + a_m b_m + a_m b_h +
-// a_h b_m) + [below 2^-25 |a b|, dropped]; every product kept is exact in float32.  The leading products accumulate in acc, the five
-// small ones in accl (the instruction aligns its addends to the largest exponent and drops what lies 2^-26 below: small addends must
-// not meet the large sum inside it); the caller adds the two once.  Six instructions of 32 cycles per 16 reduction steps against
-// eight of 64 on v_mfma_f32_32x32x2_f32.  Lane l = 32 h + r holds A[row r][k = 8 h + j] and B[k = 8 h + j][column r], j = 0 .. 7.
-template <int NJ>
-__device__ __forceinline__ void infer_chunk(const unsigned short *__restrict__ act, int ld, size_t aplane, int Kd,
-                                            const unsigned short *__restrict__ W, size_t wplane, int col0, int colstep, f32x16 (&acc)[NJ],
-                                            f32x16 (&accl)[NJ]) {
-    const int r = threadIdx.x & 31, h = (threadIdx.x >> 5) & 1;
-    const unsigned short *ap = act + (size_t)r * ld + 8 * h;
-    const unsigned short *bp[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) bp[j] = W + (size_t)((col0 + j * colstep) >> 5) * (Kd >> 4) * 512 + (threadIdx.x & 63) * 8;
-    uint4 a[3], bv[NJ][3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-        a[p] = *reinterpret_cast<const uint4 *>(ap + p * aplane);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) bv[j][p] = *reinterpret_cast<const uint4 *>(bp[j] + p * wplane);
-    }
-    for (int k0 = 0; k0 < Kd; k0 += 16) {
-        uint4 an[3], bn[NJ][3];
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            an[p] = a[p];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) bn[j][p] = bv[j][p];
-        }
-        if (k0 + 16 < Kd) {   // the next step's fragments are in flight while this one is multiplied
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                an[p] = *reinterpret_cast<const uint4 *>(ap + p * aplane + k0 + 16);
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) bn[j][p] = *reinterpret_cast<const uint4 *>(bp[j] + p * wplane + (size_t)(k0 + 16) * 32);
-            }
-        }
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, a[0]), am = __builtin_bit_cast(bf16x8, a[1]), al = __builtin_bit_cast(bf16x8, a[2]);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const bf16x8 bh = __builtin_bit_cast(bf16x8, bv[j][0]), bm = __builtin_bit_cast(bf16x8, bv[j][1]),
-                         bl = __builtin_bit_cast(bf16x8, bv[j][2]);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[j], 0, 0, 0);
-            accl[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, accl[j], 0, 0, 0);
-            accl[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, accl[j], 0, 0, 0);
-            accl[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, accl[j], 0, 0, 0);
-            accl[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, accl[j], 0, 0, 0);
-            accl[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, accl[j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            a[p] = an[p];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) bv[j][p] = bn[j][p];
-        }
-    }
-}
 
 // One layer of the tile.  The (row block, column block) units go round-robin over the 4 waves; a wave works NJ <= 2 column blocks of
 // one row block at a time.  C/D layout: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
@@ -408,7 +330,7 @@ int launch_bn_fold(const float *w, int Cin, const float *b, const float *gamma, 
     return PNPP_OK;
 }
 
-static int launch_bn_fold_split(const float *w, int Cin, const float *b, const float *gamma, const float *beta, const float *rm, const float *rv,
+int launch_bn_fold_split(const float *w, int Cin, const float *b, const float *gamma, const float *beta, const float *rm, const float *rv,
                                 float eps, int C, int ld, unsigned short *wout, float *bout, hipStream_t st) {
     ProfScope ps(st, "bn_fold_split_kernel C=%d Cin=%d", C, Cin);
     hipLaunchKernelGGL(bn_fold_split_kernel, dim3(C), dim3(256), 0, st, w, Cin, b, gamma, beta, rm, rv, eps, ld, wout, bout);

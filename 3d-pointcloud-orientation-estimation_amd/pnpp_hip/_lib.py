@@ -44,6 +44,16 @@ class SaInferArgs(C.Structure):
                 ("new_xyz", _fp), ("out", _fp)]
 
 
+class PnInferDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("D", C.c_int), ("L", C.c_int), ("C", C.c_int * PNPP_MAX_LAYERS),
+                ("input_transform", C.c_int), ("transform_after", C.c_int), ("relu_last", C.c_int), ("eps", C.c_float)]
+
+
+class PnInferArgs(C.Structure):
+    _fields_ = [("x", _fp), ("stride_b", C.c_int64), ("stride_n", C.c_int64), ("stride_c", C.c_int64), ("trans", _fp), ("trans_feat", _fp),
+                ("weights", _fp), ("scratch", _fp), ("out", _fp), ("feat_out", _fp), ("feat_layer", C.c_int)]
+
+
 class FcDesc(C.Structure):
     _fields_ = [("M", C.c_int), ("K", C.c_int), ("N", C.c_int), ("norm", C.c_int), ("relu", C.c_int),
                 ("training", C.c_int), ("eps", C.c_float), ("momentum", C.c_float), ("drop_scale", C.c_float)]
@@ -109,6 +119,12 @@ SIGNATURES = {
     "pnpp_sa_infer": (_i, [C.POINTER(SaDesc), C.POINTER(SaInferArgs), _fp]),
     "pnpp_sa_infer_group_pair": (_i, [C.POINTER(SaDesc), C.POINTER(SaDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnpp_fc_infer_fold": (_i, [_i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _f, _fp, _fp, _fp]),
+    "pnpp_pn_infer_supported": (_i, [C.POINTER(PnInferDesc)]),
+    "pnpp_pn_infer_weights_bytes": (_sz, [C.POINTER(PnInferDesc)]),
+    "pnpp_pn_infer_weights_layout": (_i, [C.POINTER(PnInferDesc), _i, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_sz)]),
+    "pnpp_pn_infer_scratch_bytes": (_sz, [C.POINTER(PnInferDesc)]),
+    "pnpp_pn_infer_fold": (_i, [C.POINTER(PnInferDesc), C.POINTER(SaFwdArgs), _fp, _fp]),
+    "pnpp_pn_infer": (_i, [C.POINTER(PnInferDesc), C.POINTER(PnInferArgs), _fp]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

@@ -45,6 +45,7 @@ SOURCES = {
     "transformer_kernels.hip": [],
     "pointnet_kernels.hip": [],
     "pointnet_api.hip": [],
+    "pointnet_infer_kernels.hip": [],
 }
 
 

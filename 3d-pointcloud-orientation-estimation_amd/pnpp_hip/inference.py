@@ -15,6 +15,9 @@ private copies of the levels and of every other submodule for whatever runs the 
 The copies hold the fused levels' parameters a second time beside their folded planes (about 7 MB for the BASELINE models): the price
 of a level staying a snapshot when a call's sizes send it to the eval path.
 It is not differentiable (model.eval() remains the path with a backward pass), keeps nothing between calls but the folded weights and reusable index / activation buffers, and never writes to the model.
+
+Predictor(model) of a vanilla PointNet / PointNetEncoder (models/pointnet.py) builds the Predictor of pnpp_hip.pointnet_inference:
+the same contract, one launch per trunk (pnpp_pn_infer).
 """
 from __future__ import annotations
 
@@ -79,11 +82,19 @@ class Predictor:
     PointNetPPXYZ, PointNetPPXYZ_Schedmit) or of PointNetPPMvM: predictor(xyz, centres=None) == model.eval()(xyz, centres=centres)
     under no_grad -- same tuple structure, shapes and dtypes, same sampler / grouper per level, same draws from the host generator."""
 
+    def __new__(cls, model=None, *args, **kwargs):
+        if cls is Predictor:
+            from models.pointnet import PointNet, PointNetEncoder
+            if isinstance(model, (PointNet, PointNetEncoder)):   # the vanilla PointNet family has a Predictor of its own
+                from .pointnet_inference import PointNetPredictor
+                return object.__new__(PointNetPredictor)
+        return object.__new__(cls)
+
     def __init__(self, model: nn.Module):
         from models.pointnet_pp_8dir import BackboneBNHead
         from models.pointnet_pp_mvM import PointNetPPMvM
         if not isinstance(model, (BackboneBNHead, PointNetPPMvM)):
-            raise TypeError(f"Predictor takes a PointNet++ set-abstraction model, not {type(model).__name__}")
+            raise TypeError(f"Predictor takes a PointNet++ set-abstraction model, a PointNet or a PointNetEncoder, not {type(model).__name__}")
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError(f"the model is on '{p.device}': the pnpp HIP operators run on an AMD GPU only "

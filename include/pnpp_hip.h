@@ -541,6 +541,55 @@ int pnpp_fc_infer_fold(int N, int K, const float *w, const float *b, const float
                        const float *rv, float eps, float *w_out, float *b_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Forward-only (inference) path of a vanilla PointNet trunk (additive to ABI 5; csrc/pointnet_infer_kernels.hip).
+ * A trunk of models/pointnet.py in eval mode is a chain of per-point layers (1x1 convolution + BatchNorm, folded as above) followed
+ * by a max over the cloud's N points.  ONE launch runs the chain on row tiles that stay in LDS / registers and takes the max on the
+ * last layer's accumulators; a small second launch finishes the max over a cloud's row slices, adds b' and applies the ReLU
+ * (monotone, so after the max).  Nothing of size B*N x C is written for C > 64.
+ *   rows        x[b, n, :D] read through element strides (either input layout), zero-padded to a multiple of 16 columns;
+ *   input_transform: the first three columns are multiplied by the cloud's 3 x 3 matrix `trans` while the operand is built;
+ *   layers      L = 2 .. 4, widths C[l] multiples of 32 up to 1024, ReLU after every layer but the last, where relu_last decides;
+ *   transform_after = l >= 0: layer l's output (C[l] == 64) is multiplied by the cloud's 64 x 64 matrix `trans_feat` before layer
+ *                 l + 1 (a product layer of its own inside the kernel; its planes are split per call by a small launch); -1: none.
+ * Products, planes and the blob layout are those of pnpp_sa_infer (ld_0 = D rounded up to 16, ld_l = C[l-1]); any B >= 1, N >= 1.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int B, N;                 /* clouds, points per cloud                                                             */
+    int D;                    /* input columns per point (the first layer's input channels)                           */
+    int L;                    /* layers, 2 .. PNPP_MAX_LAYERS                                                         */
+    int C[PNPP_MAX_LAYERS];   /* their widths                                                                         */
+    int input_transform;      /* 1: x[..., :3] @ trans[b] while the layer-0 operand is built (D >= 3)                 */
+    int transform_after;      /* layer whose output is multiplied by trans_feat[b] (C[l] == 64, l < L - 1), or -1     */
+    int relu_last;            /* ReLU on the pooled layer (the T-Nets) or not (the encoder)                           */
+    float eps;                /* of the BatchNorms (pnpp_pn_infer_fold)                                               */
+} pnpp_pn_infer_desc;
+
+typedef struct {
+    const float *x;               /* element (b, n, c) at x[b * stride_b + n * stride_n + c * stride_c]                */
+    int64_t stride_b, stride_n, stride_c;
+    const float *trans;           /* (B,3,3), with input_transform                                                     */
+    const float *trans_feat;      /* (B,64,64), with transform_after >= 0                                              */
+    const void *weights;          /* blob written by pnpp_pn_infer_fold for the same layers                            */
+    void *scratch;                /* pnpp_pn_infer_scratch_bytes: partial maxima, the planes of trans_feat             */
+    float *out;                   /* out (B, C[L-1])                                                                   */
+    float *feat_out;              /* optional out (B*N, C[feat_layer]): layer feat_layer's output rows (after trans_feat when it
+                                     applies there); only for a 64-wide layer (PointNetEncoder(global_feat=False))     */
+    int feat_layer;
+} pnpp_pn_infer_args;
+
+/* 1: the fused kernel takes the trunk.  0: it does not, pnpp_last_error() names the reason */
+int pnpp_pn_infer_supported(const pnpp_pn_infer_desc *d);
+/* bytes of the folded-parameter blob (independent of B and N); 0 for a refused descriptor */
+size_t pnpp_pn_infer_weights_bytes(const pnpp_pn_infer_desc *d);
+int pnpp_pn_infer_weights_layout(const pnpp_pn_infer_desc *d, int layer, size_t *w_offset_host, int *w_ld_host, size_t *b_offset_host);
+/* bytes of the per-call workspace at the descriptor's B and N: O(B * slices * C[L-1]) partial maxima + B * 24 KiB of planes with
+ * transform_after; 0 for a refused descriptor */
+size_t pnpp_pn_infer_scratch_bytes(const pnpp_pn_infer_desc *d);
+/* reads conv_w / conv_b / bn_w / bn_b / bn_rm / bn_rv [0 .. L) of `params` (every other member is ignored) and writes the blob */
+int pnpp_pn_infer_fold(const pnpp_pn_infer_desc *d, const pnpp_sa_fwd_args *params, void *weights, void *stream);
+int pnpp_pn_infer(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Step glue on one flat parameter / gradient buffer
  * (train_single_peak_vonMises_KL.py:80,85; train_multi_peaks_vonMises_KL.py:221,235-236)
  * ---------------------------------------------------------------------------------------- */
