@@ -1,5 +1,6 @@
-// split_infer.h -- device routines shared by the forward-only kernels (sa_infer_kernels.hip, pointnet_infer_kernels.hip): the exact
-// three-way split of float32 into bfloat16 pieces and the split-product tile loop over fragment-major weight planes.
+// split_infer.h -- device routines shared by the forward-only kernels (sa_infer_kernels.hip, pointnet_infer_kernels.hip,
+// transformer_infer_kernels.hip): the exact three-way split of float32 into bfloat16 pieces and the split-product tile loop over
+// fragment-major weight planes.
 #pragma once
 #include "common.h"
 

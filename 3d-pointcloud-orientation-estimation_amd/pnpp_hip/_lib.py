@@ -54,6 +54,19 @@ class PnInferArgs(C.Structure):
                 ("weights", _fp), ("scratch", _fp), ("out", _fp), ("feat_out", _fp), ("feat_layer", C.c_int)]
 
 
+class PtInferDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("N", C.c_int), ("n_valid", C.c_int), ("in_dim", C.c_int), ("E", C.c_int), ("H", C.c_int), ("F", C.c_int),
+                ("depth", C.c_int), ("eps", C.c_float)]
+
+
+class PtInferLayerParams(C.Structure):
+    _fields_ = [(n, _fp) for n in ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b",
+                                   "norm1_w", "norm1_b", "norm2_w", "norm2_b")]
+
+
+PT_IN_PROJ, PT_OUT_PROJ, PT_LINEAR1, PT_LINEAR2, PT_NORM1, PT_NORM2, PT_INPUT_PROJ = range(7)
+
+
 class FcDesc(C.Structure):
     _fields_ = [("M", C.c_int), ("K", C.c_int), ("N", C.c_int), ("norm", C.c_int), ("relu", C.c_int),
                 ("training", C.c_int), ("eps", C.c_float), ("momentum", C.c_float), ("drop_scale", C.c_float)]
@@ -125,6 +138,14 @@ SIGNATURES = {
     "pnpp_pn_infer_scratch_bytes": (_sz, [C.POINTER(PnInferDesc)]),
     "pnpp_pn_infer_fold": (_i, [C.POINTER(PnInferDesc), C.POINTER(SaFwdArgs), _fp, _fp]),
     "pnpp_pn_infer": (_i, [C.POINTER(PnInferDesc), C.POINTER(PnInferArgs), _fp]),
+    "pnpp_pt_infer_supported": (_i, [C.POINTER(PtInferDesc)]),
+    "pnpp_pt_infer_weights_bytes": (_sz, [C.POINTER(PtInferDesc)]),
+    "pnpp_pt_infer_weights_layout": (_i, [C.POINTER(PtInferDesc), _i, _i, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_sz)]),
+    "pnpp_pt_infer_fold": (_i, [C.POINTER(PtInferDesc), _i, C.POINTER(PtInferLayerParams), _fp, _fp, _fp, _fp]),
+    "pnpp_pt_infer_scratch_bytes": (_sz, [C.POINTER(PtInferDesc)]),
+    "pnpp_pt_infer_head": (_i, [C.POINTER(PtInferDesc), _fp, _fp, _fp, _fp, _fp]),
+    "pnpp_pt_infer_tail": (_i, [C.POINTER(PtInferDesc), _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "pnpp_pt_infer_pool": (_i, [C.POINTER(PtInferDesc), _fp, _fp, _fp, _i, _fp, _fp]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

@@ -46,6 +46,7 @@ SOURCES = {
     "pointnet_kernels.hip": [],
     "pointnet_api.hip": [],
     "pointnet_infer_kernels.hip": [],
+    "transformer_infer_kernels.hip": _NOSLP,
 }
 
 

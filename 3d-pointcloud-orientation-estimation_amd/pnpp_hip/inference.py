@@ -17,7 +17,8 @@ of a level staying a snapshot when a call's sizes send it to the eval path.
 It is not differentiable (model.eval() remains the path with a backward pass), keeps nothing between calls but the folded weights and reusable index / activation buffers, and never writes to the model.
 
 Predictor(model) of a vanilla PointNet / PointNetEncoder (models/pointnet.py) builds the Predictor of pnpp_hip.pointnet_inference:
-the same contract, one launch per trunk (pnpp_pn_infer).
+the same contract, one launch per trunk (pnpp_pn_infer).  Predictor(model) of a PointTransformer (models/point_transformer.py) builds
+the TransformerPredictor of pnpp_hip.transformer_inference: one launch per encoder layer beside its attention (pnpp_pt_infer_tail).
 """
 from __future__ import annotations
 
@@ -88,13 +89,18 @@ class Predictor:
             if isinstance(model, (PointNet, PointNetEncoder)):   # the vanilla PointNet family has a Predictor of its own
                 from .pointnet_inference import PointNetPredictor
                 return object.__new__(PointNetPredictor)
+            from models.point_transformer import PointTransformer
+            if isinstance(model, PointTransformer):   # and so has the point transformer
+                from .transformer_inference import TransformerPredictor
+                return object.__new__(TransformerPredictor)
         return object.__new__(cls)
 
     def __init__(self, model: nn.Module):
         from models.pointnet_pp_8dir import BackboneBNHead
         from models.pointnet_pp_mvM import PointNetPPMvM
         if not isinstance(model, (BackboneBNHead, PointNetPPMvM)):
-            raise TypeError(f"Predictor takes a PointNet++ set-abstraction model, a PointNet or a PointNetEncoder, not {type(model).__name__}")
+            raise TypeError(f"Predictor takes a PointNet++ set-abstraction model, a PointNet, a PointNetEncoder or a PointTransformer, "
+                            f"not {type(model).__name__}")
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError(f"the model is on '{p.device}': the pnpp HIP operators run on an AMD GPU only "

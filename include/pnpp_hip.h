@@ -590,6 +590,74 @@ int pnpp_pn_infer_fold(const pnpp_pn_infer_desc *d, const pnpp_sa_fwd_args *para
 int pnpp_pn_infer(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Forward-only (inference) path of the point transformer (additive to ABI 5; csrc/transformer_infer_kernels.hip).
+ * models/point_transformer.py in eval mode: everything of an encoder layer behind the attention is row-local, so a forward is
+ *     pnpp_pt_infer_head                         x0 = xyz W_p^T + b_p,  qkv_0 = x0 W_in^T + b_in
+ *     depth x ( pnpp_attention_fwd (lse = NULL), pnpp_pt_infer_tail )
+ *     pnpp_pt_infer_pool                         mean over the cloud's n_valid points, fc_out
+ * = 2 + 2 * depth launches.  A tail launch computes, per 32-row tile,
+ *     u = LN1(x + o W_out^T + b_out);  y = LN2(u + relu(u W_1^T + b_1) W_2^T + b_2) -> x_next;
+ *     qkv_next = y W_in'^T + b_in' (the next layer's in_proj), or in the last layer the tile's column sums over its rows < n_valid;
+ * the F-wide hidden activation is produced and consumed 64 columns at a time and never leaves the chip.  Products, planes and the
+ * fragment-major layout [3][C/32][ld/16][2][32][8] are those of pnpp_sa_infer.
+ * Shapes taken (pnpp_pt_infer_supported): E == 64, H == 4 (head dimension 16), F a multiple of 64, 1 <= in_dim <= 8, N (rows per cloud)
+ * a multiple of 128 with 1 <= n_valid <= N points (the caller pads: rows >= n_valid are computed as zero points and never pooled);
+ * the post-norm, ReLU, packed in_proj, batch_first encoder layer with biases.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int B, N;                 /* clouds, rows per cloud (a multiple of 128)                                           */
+    int n_valid;              /* points per cloud, 1 .. N                                                             */
+    int in_dim;               /* input columns per point, 1 .. 8                                                      */
+    int E, H, F;              /* embedding, heads, dim_feedforward                                                    */
+    int depth;                /* encoder layers                                                                       */
+    float eps;                /* of the LayerNorms                                                                    */
+} pnpp_pt_infer_desc;
+
+/* device pointers to one encoder layer's float32 parameters, as nn.TransformerEncoderLayer stores them */
+typedef struct {
+    const float *in_proj_w, *in_proj_b;       /* (3E, E), (3E)  */
+    const float *out_proj_w, *out_proj_b;     /* (E, E), (E)    */
+    const float *linear1_w, *linear1_b;       /* (F, E), (F)    */
+    const float *linear2_w, *linear2_b;       /* (E, F), (E)    */
+    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;   /* (E) each */
+} pnpp_pt_infer_layer_params;
+
+/* matrix index of pnpp_pt_infer_weights_layout */
+#define PNPP_PT_IN_PROJ 0
+#define PNPP_PT_OUT_PROJ 1
+#define PNPP_PT_LINEAR1 2
+#define PNPP_PT_LINEAR2 3
+#define PNPP_PT_NORM1 4
+#define PNPP_PT_NORM2 5
+#define PNPP_PT_INPUT_PROJ 6
+
+/* 1: the fused kernels take the shape.  0: they do not, pnpp_last_error() names the field */
+int pnpp_pt_infer_supported(const pnpp_pt_infer_desc *d);
+/* bytes of ONE LAYER's folded-parameter blob (independent of B, N, n_valid and the layer): a caller holds `depth` of them, so that none
+ * of its allocations is larger than a layer's planes; 0 for a refused descriptor */
+size_t pnpp_pt_infer_weights_bytes(const pnpp_pt_infer_desc *d);
+/* byte offsets inside layer `layer`'s blob (the same for every layer).  matrix 0 .. 3: three bfloat16 planes of rows x ld at w_offset
+ * (fragment-major), float32 bias at b_offset.  matrix 4 / 5: norm1 / norm2, float32 weight at w_offset and bias at b_offset, ld = E.
+ * matrix 6: input_proj as float32 (E, ld = 8) row-major, zero beyond in_dim, bias at b_offset (written to layer 0's blob only). */
+int pnpp_pt_infer_weights_layout(const pnpp_pt_infer_desc *d, int layer, int matrix, size_t *w_offset_host, int *w_ld_host,
+                                 size_t *b_offset_host);
+/* writes layer `layer`'s blob from `params` (host struct of device pointers); layer 0 also takes input_proj (E, in_dim), (E) */
+int pnpp_pt_infer_fold(const pnpp_pt_infer_desc *d, int layer, const pnpp_pt_infer_layer_params *params, const float *input_w,
+                       const float *input_b, void *weights, void *stream);
+/* bytes of the last layer's partial sums (B, N/32, E) float32; 0 for a refused descriptor */
+size_t pnpp_pt_infer_scratch_bytes(const pnpp_pt_infer_desc *d);
+/* xyz (B, n_valid, in_dim) contiguous, unpadded -> x0 (B*N, E), qkv0 (B*N, 3E); weights0: layer 0's blob */
+int pnpp_pt_infer_head(const pnpp_pt_infer_desc *d, const float *xyz, const void *weights0, float *x0, float *qkv0, void *stream);
+/* layer `layer` (blob `weights`): x, o (B*N, E) -> x_next (B*N, E, not x or o) and qkv_next (B*N, 3E) through the in_proj of the next
+ * layer's blob `weights_next`, or for layer == depth - 1 the partial sums in `scratch` (qkv_next and weights_next are ignored there,
+ * scratch elsewhere) */
+int pnpp_pt_infer_tail(const pnpp_pt_infer_desc *d, int layer, const float *x, const float *o, const void *weights, const void *weights_next,
+                       float *x_next, float *qkv_next, void *scratch, void *stream);
+/* out (B, n_out) = (sum of the cloud's partial sums / n_valid) fc_w^T + fc_b, fc_w (n_out, E) float32; fixed summation order */
+int pnpp_pt_infer_pool(const pnpp_pt_infer_desc *d, const void *scratch, const float *fc_w, const float *fc_b, int n_out, float *out,
+                       void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Step glue on one flat parameter / gradient buffer
  * (train_single_peak_vonMises_KL.py:80,85; train_multi_peaks_vonMises_KL.py:221,235-236)
  * ---------------------------------------------------------------------------------------- */
