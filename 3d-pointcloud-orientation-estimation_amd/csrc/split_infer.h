@@ -26,6 +26,11 @@ __device__ __forceinline__ void i3_split2(float v0, float v1, unsigned &h, unsig
     r0 -= i3_lo(m), r1 -= i3_hi(m);
     l = i3_pk(r0, r1);
 }
+// four packed pairs of one plane, as i3_split2 leaves them, as the eight-element MFMA fragment (element 2 i = low half of p[i])
+__device__ __forceinline__ bf16x8 i3_frag(const unsigned (&p)[4]) {
+    const uint4 v = make_uint4(p[0], p[1], p[2], p[3]);
+    return __builtin_bit_cast(bf16x8, v);
+}
 
 // acc[j] + accl[j] += act[32 rows][0 .. Kd) * W[col_j .. +32][0 .. Kd)^T for NJ column blocks `colstep` apart, float32 products formed
 // on v_mfma_f32_32x32x16_bf16 from the three-way splits of both operands: a b = a_h b_h + (a_l b_h + a_h b_l + a_m b_m + a_m b_h +

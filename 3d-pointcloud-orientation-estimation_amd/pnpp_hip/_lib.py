@@ -146,6 +146,8 @@ SIGNATURES = {
     "pnpp_pt_infer_head": (_i, [C.POINTER(PtInferDesc), _fp, _fp, _fp, _fp, _fp]),
     "pnpp_pt_infer_tail": (_i, [C.POINTER(PtInferDesc), _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnpp_pt_infer_pool": (_i, [C.POINTER(PtInferDesc), _fp, _fp, _fp, _i, _fp, _fp]),
+    "pnpp_attention_infer": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _fp]),
+    "pnpp_attention_infer_supported": (_i, [_i, _i, _i, _i, _i]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

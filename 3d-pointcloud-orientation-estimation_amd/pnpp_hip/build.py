@@ -47,6 +47,7 @@ SOURCES = {
     "pointnet_api.hip": [],
     "pointnet_infer_kernels.hip": [],
     "transformer_infer_kernels.hip": _NOSLP,
+    "attention_infer_kernels.hip": _NOSLP,
 }
 
 

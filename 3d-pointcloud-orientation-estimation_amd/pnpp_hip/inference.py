@@ -18,7 +18,8 @@ It is not differentiable (model.eval() remains the path with a backward pass), k
 
 Predictor(model) of a vanilla PointNet / PointNetEncoder (models/pointnet.py) builds the Predictor of pnpp_hip.pointnet_inference:
 the same contract, one launch per trunk (pnpp_pn_infer).  Predictor(model) of a PointTransformer (models/point_transformer.py) builds
-the TransformerPredictor of pnpp_hip.transformer_inference: one launch per encoder layer beside its attention (pnpp_pt_infer_tail).
+the TransformerPredictor of pnpp_hip.transformer_inference: one launch per encoder layer beside its attention (pnpp_pt_infer_tail);
+Predictor(model, attention="split" | "float32") chooses the attention kernel there.
 """
 from __future__ import annotations
 

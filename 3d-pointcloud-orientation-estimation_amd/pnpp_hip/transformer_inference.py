@@ -6,10 +6,17 @@
 Everything of an encoder layer behind its attention is row-local (out_proj, residual, LayerNorm, the feed-forward block, residual,
 LayerNorm, the next layer's in_proj) and runs as ONE launch (pnpp_pt_infer_tail): the dim_feedforward-wide hidden activation is
 produced and consumed on the chip and no tensor with that many columns is allocated.  A forward is pnpp_pt_infer_head, then per
-layer pnpp_attention_fwd + pnpp_pt_infer_tail, then pnpp_pt_infer_pool: 2 + 2 * depth launches.  The stages are "head",
+layer the attention + pnpp_pt_infer_tail, then pnpp_pt_infer_pool: 2 + 2 * depth launches.  The stages are "head",
 "layers.0" ... "layers.{depth-1}" and "pool"; `plan` says for each whether it runs "fused" or on the "eval-path", `last_plan` what
-the latest call ran.  A model the kernels refuse (pnpp_pt_infer_supported: another width, head count or feed-forward size that is no
-multiple of 64, pre-norm, GELU, ...) runs transformer.point_transformer_forward on a private eval-mode copy.
+the latest call ran.
+
+The attention has two forms, chosen by Predictor(model, attention=...): "split" is pnpp_attention_infer, both products on the bf16
+matrix instruction from exact three-way splits of the float32 operands (no log-sum-exp, no dropout mask, no workspace); "float32" is
+the training kernel pnpp_attention_fwd with lse = NULL and mask = NULL.  `attention` says which one the Predictor was built with,
+`last_attention` which one the latest fused call ran: a call whose sizes pnpp_attention_infer_supported refuses runs the float32
+kernel.  Without the keyword the form is DEFAULT_ATTENTION below.  A model the kernels refuse (pnpp_pt_infer_supported: another
+width, head count or feed-forward size that is no multiple of 64, pre-norm, GELU, ...) runs transformer.point_transformer_forward
+on a private eval-mode copy.
 
 Same contract as the other Predictors: a snapshot (refresh() folds again), not differentiable, nothing written to the model,
 evaluated in eval mode whatever model.training says, any n_pts >= 1 (padded to a multiple of 128 inside), no CPU fallback.
@@ -26,6 +33,10 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .inference import Predictor
+
+# the form Predictor(model) runs: per launch at 8 x 4096 pnpp_attention_infer takes 318 us against 553 us for pnpp_attention_fwd
+# (kernel trace), far outside the spread of the timing windows
+DEFAULT_ATTENTION = "split"
 
 _MATRICES = {"in_proj": L.PT_IN_PROJ, "out_proj": L.PT_OUT_PROJ, "linear1": L.PT_LINEAR1, "linear2": L.PT_LINEAR2,
              "norm1": L.PT_NORM1, "norm2": L.PT_NORM2, "input_proj": L.PT_INPUT_PROJ}
@@ -48,10 +59,16 @@ def _is_relu(layer) -> bool:
 class TransformerPredictor(Predictor):
     """Forward-only evaluation of models.point_transformer.PointTransformer; built by Predictor(model)."""
 
-    def __init__(self, model: nn.Module):
+    ATTENTION_FORMS = ("split", "float32")
+
+    def __init__(self, model: nn.Module, attention: str = DEFAULT_ATTENTION):
         from models.point_transformer import PointTransformer
         if not isinstance(model, PointTransformer):
             raise TypeError(f"TransformerPredictor takes a PointTransformer, not {type(model).__name__}")
+        if attention not in self.ATTENTION_FORMS:
+            raise ValueError(f"attention={attention!r}: the forms are {', '.join(repr(a) for a in self.ATTENTION_FORMS)}")
+        self.attention = attention
+        self.last_attention: Optional[str] = None   # what the latest fused call ran
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError(f"the model is on '{p.device}': the pnpp HIP operators run on an AMD GPU only "
@@ -187,8 +204,19 @@ class TransformerPredictor(Predictor):
         part = self._buf("partial", (L.lib().pnpp_pt_infer_scratch_bytes(C.byref(d)),), torch.uint8)
         return x, qkv, att, part
 
-    def _attention(self, d, qkv, att):
-        L.check(L.lib().pnpp_attention_fwd(qkv.data_ptr(), d.B, d.N, d.n_valid, d.H, d.E // d.H, None, 0.0, att.data_ptr(), None, ops._stream()))
+    def _split_supported(self, d) -> bool:
+        return bool(L.lib().pnpp_attention_infer_supported(d.B, d.N, d.n_valid, d.H, d.E // d.H))
+
+    def _attention_form(self, d) -> str:
+        """the form this call runs: the Predictor's own, or "float32" where the split kernel does not take the call's sizes"""
+        return "split" if self.attention == "split" and self._split_supported(d) else "float32"
+
+    def _attention(self, d, qkv, att, form):
+        if form == "split":
+            L.check(L.lib().pnpp_attention_infer(qkv.data_ptr(), d.B, d.N, d.n_valid, d.H, d.E // d.H, att.data_ptr(), ops._stream()))
+        else:
+            L.check(L.lib().pnpp_attention_fwd(qkv.data_ptr(), d.B, d.N, d.n_valid, d.H, d.E // d.H, None, 0.0, att.data_ptr(), None, ops._stream()))
+        self.last_attention = form
 
     def _pool(self, d, part, w, b):
         out = torch.empty(d.B, w.shape[0], device=self.device, dtype=torch.float32)
@@ -207,9 +235,10 @@ class TransformerPredictor(Predictor):
             lib, st = L.lib(), ops._stream()
             blobs = [b.data_ptr() for b in self._blobs] + [None]
             x, qkv, att, part = self._buffers(d)
+            form = self._attention_form(d)
             L.check(lib.pnpp_pt_infer_head(C.byref(d), xyz.data_ptr(), blobs[0], x[0].data_ptr(), qkv.data_ptr(), st))
             for l in range(self.depth):
-                self._attention(d, qkv, att)
+                self._attention(d, qkv, att, form)
                 L.check(lib.pnpp_pt_infer_tail(C.byref(d), l, x[l & 1].data_ptr(), att.data_ptr(), blobs[l], blobs[l + 1], x[(l + 1) & 1].data_ptr(),
                                                qkv.data_ptr(), part.data_ptr(), st))
             fc = self._snap.fc_out
@@ -226,6 +255,27 @@ class TransformerPredictor(Predictor):
             x, qkv, _, _ = self._buffers(d)
             L.check(L.lib().pnpp_pt_infer_head(C.byref(d), xyz.data_ptr(), self._blobs[0].data_ptr(), x[0].data_ptr(), qkv.data_ptr(), ops._stream()))
             return x[0].view(B, N, d.E), qkv.view(B, N, 3 * d.E)
+
+    @torch.no_grad()
+    def attend(self, qkv_in: torch.Tensor):
+        """the attention alone on qkv_in (B, n_pts, 3E) float32, a layer's in_proj output: -> (B, N, E) with N = n_pts rounded up to 128,
+        a view of a reused buffer.  Rows beyond n_pts are padded with zeros here; the output's rows beyond n_pts are finite and mean
+        nothing.  Runs the form a call of these sizes runs (`last_attention`)."""
+        with torch.cuda.device(self.device):
+            if qkv_in.dim() != 3 or qkv_in.shape[1] < 1:
+                raise ValueError(f"expected a (B, n_pts, 3E) input with n_pts >= 1, got {tuple(qkv_in.shape)}")
+            B, n_pts, E3 = qkv_in.shape
+            N = (n_pts + 127) // 128 * 128
+            d = self._desc(B, N, n_pts) if self._blobs else None
+            if d is None or not L.lib().pnpp_pt_infer_supported(C.byref(d)):
+                raise RuntimeError(f"the fused kernels do not take this model or call: {self.refused or L.last_error()}")
+            if E3 != 3 * d.E:
+                raise ValueError(f"the model's qkv rows have {3 * d.E} columns, got {E3}")
+            _, qkv, att, _ = self._buffers(d)
+            qkv.zero_()
+            qkv.view(B, N, E3)[:, :n_pts] = ops._f32(qkv_in, "qkv")
+            self._attention(d, qkv, att, self._attention_form(d))
+            return att.view(B, N, d.E)
 
     @torch.no_grad()
     def tail(self, layer: int, x_in: torch.Tensor, o_in: torch.Tensor):

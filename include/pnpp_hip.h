@@ -593,7 +593,7 @@ int pnpp_pn_infer(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, void
  * Forward-only (inference) path of the point transformer (additive to ABI 5; csrc/transformer_infer_kernels.hip).
  * models/point_transformer.py in eval mode: everything of an encoder layer behind the attention is row-local, so a forward is
  *     pnpp_pt_infer_head                         x0 = xyz W_p^T + b_p,  qkv_0 = x0 W_in^T + b_in
- *     depth x ( pnpp_attention_fwd (lse = NULL), pnpp_pt_infer_tail )
+ *     depth x ( pnpp_attention_infer or pnpp_attention_fwd (lse = NULL), pnpp_pt_infer_tail )
  *     pnpp_pt_infer_pool                         mean over the cloud's n_valid points, fc_out
  * = 2 + 2 * depth launches.  A tail launch computes, per 32-row tile,
  *     u = LN1(x + o W_out^T + b_out);  y = LN2(u + relu(u W_1^T + b_1) W_2^T + b_2) -> x_next;
@@ -656,6 +656,14 @@ int pnpp_pt_infer_tail(const pnpp_pt_infer_desc *d, int layer, const float *x, c
 /* out (B, n_out) = (sum of the cloud's partial sums / n_valid) fc_w^T + fc_b, fc_w (n_out, E) float32; fixed summation order */
 int pnpp_pt_infer_pool(const pnpp_pt_infer_desc *d, const void *scratch, const float *fc_w, const float *fc_b, int n_out, float *out,
                        void *stream);
+/* The attention of that path (additive to ABI 5; csrc/attention_infer_kernels.hip): what pnpp_attention_fwd computes with mask == NULL
+ * and lse == NULL, on the same qkv (B, N, 3E) and out (B, N, E) buffers and with the same padding contract, both products formed on
+ * v_mfma_f32_32x32x16_bf16 from the exact three-way bfloat16 splits of their float32 operands.  No workspace, one launch.
+ * Shapes taken: head_dim == 16, N a multiple of 128, 1 <= n_valid <= N, B and H >= 1 (at most 65535 each).  Arguments are validated
+ * before anything is launched; for a refused shape pnpp_last_error() names the field. */
+int pnpp_attention_infer(const float *qkv, int B, int N, int n_valid, int H, int head_dim, float *out, void *stream);
+/* 1: pnpp_attention_infer takes the shape.  0: it does not, pnpp_last_error() names the field */
+int pnpp_attention_infer_supported(int B, int N, int n_valid, int H, int head_dim);
 
 /* ------------------------------------------------------------------------------------------
  * Step glue on one flat parameter / gradient buffer

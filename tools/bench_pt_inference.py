@@ -1,15 +1,23 @@
 #!/usr/bin/env python
-"""Forward-only throughput of the point transformer: model.eval() under no_grad against pnpp_hip.Predictor, timed alternately in one
-process (window() / launches() of tools/bench_inference.py).
+"""Forward-only throughput of the point transformer: model.eval() under no_grad against pnpp_hip.Predictor with each of its two attention
+forms ("split": pnpp_attention_infer, "float32": pnpp_attention_fwd), the three paths timed alternately in one process (window() /
+launches() of tools/bench_inference.py).
 
     python tools/bench_pt_inference.py                  # PointTransformer() at 8 x 4096 (the configs[4] per-GPU shard) and 32 x 1024
-    python tools/bench_pt_inference.py --out profiles/pt_inference_forward.json
+    python tools/bench_pt_inference.py --out profiles/pt_attention_inference.json
     python tools/bench_pt_inference.py --trace-only 10  # ~10 forwards of EACH path at 8 x 4096 and nothing else (for a kernel trace)
 
-One JSON line per shape in the format of profiles/pointnet_inference_forward.json: ms per forward and clouds/s of both paths (median
-over the windows), each path's min / max, library launches per forward, the Predictor's algorithmic FLOPs and compulsory HBM bytes per
-forward (from the shapes), the max-abs difference of the two paths' outputs, and `faster`: the acceptance condition
-median(eval) - median(predictor) > spread(eval) + spread(predictor)."""
+--trace-only is what a `rocprofv3 --kernel-trace --stats -- python tools/bench_pt_inference.py --trace-only 10` run of its own traces:
+the two attention kernels have different names (attention_infer_kernel, attention_fwd_kernel), so the per-launch times of both come
+from the same run; its kernel_stats.csv is what profiles/pt_attention_kernel_stats.csv holds.
+
+One JSON line per shape in the format of profiles/pointnet_inference_forward.json: ms per forward and clouds/s of the paths (median
+over the windows; `predictor_*` is the Predictor as it is built by default, `attention` its form, `predictor_<other form>_*` the other),
+each path's min / max, library launches per forward, the Predictor's algorithmic FLOPs and compulsory HBM bytes per forward (from the
+shapes), the max-abs difference of the paths' outputs, `faster`: the acceptance condition median(eval) - median(predictor) >
+spread(eval) + spread(predictor), `attention_speedup` / `attention_faster`: float32 over split and the same condition between the two attention forms, and
+`attention_err_split` / `attention_err_float32`: max |attend(qkv_0) - float64| over cloud 0, float64 softmax attention on the float32
+qkv of layer 0."""
 import argparse
 import datetime
 import json
@@ -49,42 +57,60 @@ def cloud(B, N):
     return torch.randn(B, N, 3, generator=torch.Generator().manual_seed(1234)).cuda()
 
 
+def attention_errors(preds, x):
+    """max |attend(qkv_0) - float64| over cloud 0 for each form: float64 softmax attention on the float32 qkv of layer 0"""
+    E = preds["split"].model.input_proj.out_features
+    heads = preds["split"].model.transformer.layers[0].self_attn.num_heads
+    n = x.shape[1]
+    qkv = preds["split"].head(x)[1][:1, :n].clone()
+    q, k, v = (t.reshape(n, heads, E // heads).transpose(0, 1) for t in qkv[0].cpu().double().split(E, dim=-1))
+    ref = (torch.softmax((q * (E // heads) ** -0.5) @ k.transpose(-1, -2), dim=-1) @ v).transpose(0, 1).reshape(n, E)
+    return {form: float((p.attend(qkv)[0, :n].cpu().double() - ref).abs().max()) for form, p in preds.items()}
+
+
 def case(B, N, windows, seconds):
     from pnpp_hip import Predictor
     model = make()
-    pred = Predictor(model)
+    default = Predictor(model).attention   # the form Predictor(model) runs: `predictor_*` below are that form's figures
+    preds = {"split": Predictor(model, attention="split"), "float32": Predictor(model, attention="float32")}
     x = cloud(B, N)
 
     def run_eval():
         with torch.no_grad():
             return model(x)
 
-    def run_pred():
-        return pred(x)
-
-    diff = float((run_eval() - run_pred()).abs().max())
+    runs = {"eval": run_eval, "split": lambda: preds["split"](x), "float32": lambda: preds["float32"](x)}
+    diff = {form: float((run_eval() - runs[form]()).abs().max()) for form in preds}
+    errs = attention_errors(preds, x)
     for _ in range(3):
-        run_eval(), run_pred()
+        for fn in runs.values():
+            fn()
     torch.cuda.synchronize()
-    n_eval, n_pred = launches(run_eval), launches(run_pred)
-    t_eval, t_pred, r_eval, r_pred = [], [], 4, 4
-    for _ in range(windows):   # alternately: drift of the clocks hits both paths alike
-        ms, r_eval = window(run_eval, seconds, r_eval)
-        t_eval.append(ms)
-        ms, r_pred = window(run_pred, seconds, r_pred)
-        t_pred.append(ms)
+    n = {k: launches(fn) for k, fn in runs.items()}
+    t, reps = {k: [] for k in runs}, {k: 4 for k in runs}
+    for _ in range(windows):   # alternately: drift of the clocks hits every path alike
+        for k, fn in runs.items():
+            ms, reps[k] = window(fn, seconds, reps[k])
+            t[k].append(ms)
     flops, nbytes = algorithmic(model, B, N)
-    me, mp = statistics.median(t_eval), statistics.median(t_pred)
-    se, sp = max(t_eval) - min(t_eval), max(t_pred) - min(t_pred)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    spread = {k: max(v) - min(v) for k, v in t.items()}
+    me, mp, other = med["eval"], med[default], "float32" if default == "split" else "split"
     return {
         "model": "PointTransformer()", "B": B, "N": N, "date": datetime.date.today().isoformat(),
         "device": torch.cuda.get_device_name(0), "windows": windows, "window_s": seconds,
-        "eval_ms": round(me, 4), "eval_ms_min": round(min(t_eval), 4), "eval_ms_max": round(max(t_eval), 4),
-        "eval_clouds_per_s": round(1e3 * B / me, 1), "eval_launches": n_eval,
-        "predictor_ms": round(mp, 4), "predictor_ms_min": round(min(t_pred), 4), "predictor_ms_max": round(max(t_pred), 4),
-        "predictor_clouds_per_s": round(1e3 * B / mp, 1), "predictor_launches": n_pred,
-        "predictor_flops": flops, "predictor_hbm_bytes": nbytes, "plan": pred.last_plan,
-        "max_abs_diff": diff, "speedup": round(me / mp, 3), "faster": bool(me - mp > se + sp),
+        "eval_ms": round(me, 4), "eval_ms_min": round(min(t["eval"]), 4), "eval_ms_max": round(max(t["eval"]), 4),
+        "eval_clouds_per_s": round(1e3 * B / me, 1), "eval_launches": n["eval"],
+        "attention": default,
+        "predictor_ms": round(mp, 4), "predictor_ms_min": round(min(t[default]), 4), "predictor_ms_max": round(max(t[default]), 4),
+        "predictor_clouds_per_s": round(1e3 * B / mp, 1), "predictor_launches": n[default],
+        "predictor_flops": flops, "predictor_hbm_bytes": nbytes, "plan": preds[default].last_plan,
+        "max_abs_diff": diff[default], "speedup": round(me / mp, 3), "faster": bool(me - mp > spread["eval"] + spread[default]),
+        f"predictor_{other}_ms": round(med[other], 4), f"predictor_{other}_ms_min": round(min(t[other]), 4),
+        f"predictor_{other}_ms_max": round(max(t[other]), 4), f"predictor_{other}_launches": n[other], f"max_abs_diff_{other}": diff[other],
+        "attention_speedup": round(med["float32"] / med["split"], 3),
+        "attention_faster": bool(med["float32"] - med["split"] > spread["float32"] + spread["split"]),
+        "attention_err_split": errs["split"], "attention_err_float32": errs["float32"],
     }
 
 
@@ -99,10 +125,11 @@ def main():
     if args.trace_only:
         from pnpp_hip import Predictor
         model = make()
-        pred = Predictor(model)
+        pred, pred32 = Predictor(model, attention="split"), Predictor(model, attention="float32")
         x = cloud(8, 4096)
         for _ in range(args.trace_only):
             pred(x)
+            pred32(x)
             with torch.no_grad():
                 model(x)
         torch.cuda.synchronize()
