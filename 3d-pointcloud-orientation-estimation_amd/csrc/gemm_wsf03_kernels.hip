@@ -71,11 +71,26 @@ gemm_wsf03_kernel(const Wsf0Args P) {
     double mpart = 0.0;
     const int mq = tid & 15, mqc = mq < 9 ? mq : 8;
     if (P.training) {
+        // more than kMomSlabs partials (the pair search writes one per search workgroup): the same sixteen slab lanes, 32 loads of a
+        // thread in flight per chunk of 512 partials, summed in slab order
+        if (P.nmom > kMomSlabs) {
+            for (int base = 0; base < P.nmom; base += 512) {
+                double v[32];
 #pragma unroll
-        for (int it = 0; it < kMomSlabs / 16; ++it) {
-            const int s = (tid >> 4) + 16 * it;
-            const double v = P.mom[(size_t)(s < P.nmom ? s : 0) * kMomPitch + mqc];
-            mpart += s < P.nmom ? v : 0.0;
+                for (int it = 0; it < 32; ++it) {
+                    const int s = base + (tid >> 4) + 16 * it;
+                    v[it] = P.mom[(size_t)(s < P.nmom ? s : 0) * kMomPitch + mqc];
+                }
+#pragma unroll
+                for (int it = 0; it < 32; ++it) mpart += base + (tid >> 4) + 16 * it < P.nmom ? v[it] : 0.0;
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < kMomSlabs / 16; ++it) {
+                const int s = (tid >> 4) + 16 * it;
+                const double v = P.mom[(size_t)(s < P.nmom ? s : 0) * kMomPitch + mqc];
+                mpart += s < P.nmom ? v : 0.0;
+            }
         }
     }
     float w0[3] = {0.f, 0.f, 0.f}, p_g = 1.f, p_b = 0.f, p_bias = 0.f, p_rm = 0.f, p_rv = 0.f;

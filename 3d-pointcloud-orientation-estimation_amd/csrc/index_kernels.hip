@@ -9,6 +9,7 @@
 // compiled with -ffp-contract=off and uses explicit fmaf where -- and only where -- ATen fuses.
 #include "common.h"
 #include "sampler_device.h"
+#include "wsf0_args.h"
 
 #pragma clang fp contract(off)
 
@@ -72,9 +73,11 @@ __global__ void __launch_bounds__(256) square_distance_kernel(const float *__res
 // Output: neighbours in ascending (distance, index).
 // ---------------------------------------------------------------------------------------------
 constexpr int KNN_TILE = 1024;
-constexpr int KNN_CPL = KNN_TILE / 64;  // candidates per lane per tile
+constexpr int KNN_TILE_SMALL = 128;   // a cloud of at most this many candidates (a stacked level's centres): two keys per lane, not sixteen
 constexpr int KNN_KMAX = 128;
 constexpr int KNN_POOL = 256;
+constexpr int KNN_PAIR_QPW = 2;
+constexpr int KNN_MOM_PITCH = 16;     // == kMomPitch (wsf0_args.h): one moment partial per workgroup
 constexpr unsigned long long KEY_MAX = ~0ull;
 
 __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
@@ -86,11 +89,26 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
     return v;
 }
 
+// k-th smallest (1-based, with multiplicity) of the 64 lanes' values, wave-uniform: built bit by bit from the top -- a bit is set when
+// fewer than k lanes lie at or below the candidate with that bit clear and every lower bit set.  32 compare + ballot + popcount steps
+// on the scalar unit instead of a 64-step readlane / compare / add chain on the vector unit.
+__device__ __forceinline__ unsigned wave_kth_smallest_u32(unsigned v, int k) {
+    unsigned t = 0u;
+#pragma unroll
+    for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = t | ((1u << bit) - 1u);
+        if (__popcll(__ballot(v <= cand)) < k) t |= 1u << bit;
+    }
+    return t;
+}
+
 // centre != nullptr: the query of (b, q) is xyz[b, centre[b, q]] and the kernel also writes it to out_a / out_b (the
 // caller's new_xyz and the copy kept for backward) -- the set-abstraction forward then needs no separate gather launch.
 // gather != nullptr: the "cloud" of (b) is itself a gathered subset of xyz -- candidate p is xyz[b, gather[b, p]] (the centres
 // of the level below, xyz holding Nsrc points per cloud): the neighbour search of a stacked level then needs neither the level
 // below's output nor a launch of its own (knn_pair_kernel).
+// mom != nullptr: the workgroup also sums the nine moments of rel = neighbour - centre over its queries' neighbourhoods (what
+// rel_moments_kernel computes from idx in a launch of its own) and writes them as partial [b * gridDim-of-the-level + bx].
 struct KnnJob {
     const float *new_xyz;      // explicit queries, or nullptr with `centre`
     const float *xyz;
@@ -100,16 +118,21 @@ struct KnnJob {
     int32_t *idx;
     const int32_t *centre;
     float *out_a, *out_b;
+    double *mom;               // [B * nblocks][KNN_MOM_PITCH] or nullptr
+    int qpw;                   // queries per wave: 1, or 2 on a cloud of one tile (the tile is then staged once for eight queries)
+    int nblocks;               // workgroups per cloud of this job
 };
 
-struct KnnLds {   // one copy per workgroup, shared by the two instantiations of the body a pair kernel contains
+struct alignas(16) KnnLds {   // one copy per workgroup, shared by the two instantiations of the body a pair kernel contains
     float sx[KNN_TILE], sy[KNN_TILE], sz[KNN_TILE], sn[KNN_TILE];
     unsigned long long best[4][2][KNN_KMAX];
     unsigned long long pool[4][KNN_POOL];
 };
 
-template <bool GATHER>
+template <bool GATHER, int TILE, bool MOM>
 __device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const int b, KnnLds &L) {
+    constexpr int CPL = TILE / 64;              // candidates per lane per tile
+    constexpr int SPT = (TILE + 255) / 256;     // staged points per thread per tile
     const float *__restrict__ new_xyz = J.new_xyz;
     const float *__restrict__ xyz = J.xyz;
     const int32_t *__restrict__ centre = J.centre;
@@ -122,135 +145,188 @@ __device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const in
     unsigned long long(&pool)[4][KNN_POOL] = L.pool;
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int q = bx * 4 + wave;
-    const bool active = q < S;  // wave-uniform
-    float ax = 0.f, ay = 0.f, az = 0.f, sa = 0.f;
-    if (active) {
-        const float *a = new_xyz + ((size_t)b * S + q) * 3;
-        if (centre) {
-            const int c = centre[(size_t)b * S + q];
-            a = xyz + ((size_t)b * J.Nsrc + (GATHER ? gather[c] : c)) * 3;
-        }
-        ax = a[0], ay = a[1], az = a[2];
-        sa = sq3_exact(ax, ay, az);
-        if (centre && lane < 3) {
-            const float v = lane == 0 ? ax : (lane == 1 ? ay : az);
-            out_a[((size_t)b * S + q) * 3 + lane] = v;
-            if (out_b) out_b[((size_t)b * S + q) * 3 + lane] = v;
-        }
-    }
-    int cur = 0;         // which half of best[] holds the current list
-    bool have = false;   // best[cur][0..k) is valid (wave-uniform)
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
-
     const float *cloud = xyz + (size_t)b * J.Nsrc * 3;
-    for (int t0 = 0; t0 < N; t0 += KNN_TILE) {
-        __syncthreads();  // previous tile fully consumed
-        const int cnt = min(KNN_TILE, N - t0);
-        // coalesced stage: 3*cnt consecutive floats, de-interleaved into SoA (gathered clouds: three floats per listed row)
-        for (int i = threadIdx.x; i < cnt * 3; i += 256) {
-            int p = i / 3, c = i - p * 3;
-            float v;
-            if constexpr (GATHER) v = cloud[(size_t)gather[t0 + p] * 3 + c];
-            else v = cloud[(size_t)t0 * 3 + i];
-            (c == 0 ? sx : c == 1 ? sy : sz)[p] = v;
-        }
-        __syncthreads();
-        for (int p = threadIdx.x; p < cnt; p += 256) sn[p] = sq3_exact(sx[p], sy[p], sz[p]);
-        __syncthreads();
-        if (!active) continue;
+    const int qpw = J.qpw;   // > 1 only with N <= TILE: the one tile staged in the first pass serves every pass
 
-        unsigned long long key[KNN_CPL + 2];
-        unsigned long long lmin = KEY_MAX;
-#pragma unroll
-        for (int j = 0; j < KNN_CPL; ++j) {
-            const int p = j * 64 + lane;
-            key[j] = KEY_MAX;
-            if (p < cnt) {
-                float d = pair_dist_exact(ax, ay, az, sx[p], sy[p], sz[p], sa, sn[p]);
-                key[j] = ((unsigned long long)f32_sortable(d) << 32) | (unsigned)(t0 + p);
+    for (int pass = 0; pass < qpw; ++pass) {
+        const int q = (bx * qpw + pass) * 4 + wave;
+        const bool active = q < S;  // wave-uniform
+        float ax = 0.f, ay = 0.f, az = 0.f, sa = 0.f;
+        if (active) {
+            const float *a = new_xyz + ((size_t)b * S + q) * 3;
+            if (centre) {
+                const int c = centre[(size_t)b * S + q];
+                a = xyz + ((size_t)b * J.Nsrc + (GATHER ? gather[c] : c)) * 3;
             }
-            lmin = key[j] < lmin ? key[j] : lmin;
+            ax = a[0], ay = a[1], az = a[2];
+            sa = sq3_exact(ax, ay, az);
+            if (centre && lane < 3) {
+                const float v = lane == 0 ? ax : (lane == 1 ? ay : az);
+                out_a[((size_t)b * S + q) * 3 + lane] = v;
+                if (out_b) out_b[((size_t)b * S + q) * 3 + lane] = v;
+            }
         }
-        // previous best list rides along as up to two more candidates per lane
-        key[KNN_CPL] = (have && lane < k) ? best[wave][cur][lane] : KEY_MAX;
-        key[KNN_CPL + 1] = (have && lane + 64 < k) ? best[wave][cur][lane + 64] : KEY_MAX;
+        int cur = pass & 1;  // which half of best[] holds the current list (alternating, so a pass leaves the previous pass's result alone)
+        bool have = false;   // best[cur][0..k) is valid (wave-uniform)
 
-        // ---- pruning bound on the distance word ----
-        unsigned long long T = KEY_MAX;
-        if (k <= 64) {
-            const unsigned hi = (unsigned)(lmin >> 32);
-            int cnt_le = 0;
+        for (int t0 = 0; t0 < N; t0 += TILE) {
+            const int cnt = min(TILE, N - t0);
+            if (pass == 0) {
+                if (t0 > 0) __syncthreads();  // previous tile fully consumed
+                // stage: one point per thread and step (three floats of a row; gathered clouds: of the listed row), every load of
+                // the thread requested before the first is used; |p|^2 comes from the registers, so the tile needs one barrier
+                float px[SPT], py[SPT], pz[SPT];
 #pragma unroll
-            for (int i = 0; i < 64; ++i) cnt_le += ((unsigned)__builtin_amdgcn_readlane((int)hi, i) <= hi) ? 1 : 0;
-            const unsigned thi = wave_min_u32(cnt_le >= k ? hi : 0xffffffffu);
-            T = ((unsigned long long)thi << 32) | 0xffffffffull;
-        }
-        if (have) {
-            const unsigned long long last = best[wave][cur][k - 1];
-            T = last < T ? last : T;
-        }
-        // ---- compaction of the survivors into the LDS pool ----
-        int P = 0;  // wave-uniform
+                for (int i = 0; i < SPT; ++i) {
+                    const int p = min((int)threadIdx.x + 256 * i, cnt - 1);
+                    const float *s = cloud + (size_t)(GATHER ? gather[t0 + p] : t0 + p) * 3;
+                    px[i] = s[0], py[i] = s[1], pz[i] = s[2];
+                }
 #pragma unroll
-        for (int j = 0; j < KNN_CPL + 2; ++j) {
-            const bool in = key[j] <= T && key[j] != KEY_MAX;
-            const unsigned long long m = __ballot(in);
-            const int pos = P + __popcll(m & lt_mask);
-            if (in && pos < KNN_POOL) pool[wave][pos] = key[j];
-            P += __popcll(m);
-        }
-        if (P <= KNN_POOL) {
-            // ---- rank selection inside the pool ----
-            for (int e0 = 0; e0 < P; e0 += 64) {
-                const int e = e0 + lane;
-                const unsigned long long mine = e < P ? pool[wave][e] : KEY_MAX;
-                int r = 0;
-                for (int j = 0; j < P; ++j) r += pool[wave][j] < mine ? 1 : 0;
-                if (e < P && r < k) best[wave][cur ^ 1][r] = mine;
+                for (int i = 0; i < SPT; ++i) {
+                    const int p = threadIdx.x + 256 * i;
+                    if (p < cnt) sx[p] = px[i], sy[p] = py[i], sz[p] = pz[i], sn[p] = sq3_exact(px[i], py[i], pz[i]);
+                }
+                __syncthreads();
             }
-        } else {
-            // ---- fallback: k rounds of wave-min extraction over everything this lane holds ----
-            unsigned long long fmin = KEY_MAX;
+            if (!active) continue;
+
+            unsigned long long key[CPL + 2];
+            unsigned long long lmin = KEY_MAX;
 #pragma unroll
-            for (int j = 0; j < KNN_CPL + 2; ++j) fmin = key[j] < fmin ? key[j] : fmin;
-            for (int it = 0; it < k; ++it) {
-                const unsigned long long w = wave_min_u64(fmin);
-                if (lane == 0) best[wave][cur ^ 1][it] = w;
-                if (fmin == w && w != KEY_MAX) {  // keys are unique: exactly one owner
-                    unsigned long long m2 = KEY_MAX;
+            for (int j = 0; j < CPL; ++j) {
+                const int p = j * 64 + lane;
+                key[j] = KEY_MAX;
+                if (p < cnt) {
+                    float d = pair_dist_exact(ax, ay, az, sx[p], sy[p], sz[p], sa, sn[p]);
+                    key[j] = ((unsigned long long)f32_sortable(d) << 32) | (unsigned)(t0 + p);
+                }
+                lmin = key[j] < lmin ? key[j] : lmin;
+            }
+            // previous best list rides along as up to two more candidates per lane
+            key[CPL] = (have && lane < k) ? best[wave][cur][lane] : KEY_MAX;
+            key[CPL + 1] = (have && lane + 64 < k) ? best[wave][cur][lane + 64] : KEY_MAX;
+
+            // ---- pruning bound on the distance word ----
+            unsigned long long T = KEY_MAX;
+            if (k <= 64) T = ((unsigned long long)wave_kth_smallest_u32((unsigned)(lmin >> 32), k) << 32) | 0xffffffffull;
+            if (have) {
+                const unsigned long long last = best[wave][cur][k - 1];
+                T = last < T ? last : T;
+            }
+            // ---- compaction of the survivors into the LDS pool ----
+            int P = 0;  // wave-uniform
 #pragma unroll
-                    for (int j = 0; j < KNN_CPL + 2; ++j) {
-                        if (key[j] == w) key[j] = KEY_MAX;
-                        m2 = key[j] < m2 ? key[j] : m2;
+            for (int j = 0; j < CPL + 2; ++j) {
+                const bool in = key[j] <= T && key[j] != KEY_MAX;
+                const unsigned long long mb = __ballot(in);
+                const int pos = P + __popcll(mb & lt_mask);
+                if (in && pos < KNN_POOL) pool[wave][pos] = key[j];
+                P += __popcll(mb);
+            }
+            if (P <= KNN_POOL) {
+                // ---- rank selection inside the pool: the list is padded with KEY_MAX (never below a pooled key) to a multiple of
+                // four entries, and a step reads four of them with two 16-byte broadcasts that are in flight together ----
+                if (lane < 3 && P + lane < ((P + 3) & ~3)) pool[wave][P + lane] = KEY_MAX;
+                const ulonglong2 *pool2 = reinterpret_cast<const ulonglong2 *>(pool[wave]);
+                const int P2 = (P + 3) >> 2 << 1;
+                for (int e0 = 0; e0 < P; e0 += 64) {
+                    const int e = e0 + lane;
+                    const unsigned long long mine = e < P ? pool[wave][e] : KEY_MAX;
+                    int r = 0;
+#pragma unroll 2
+                    for (int j = 0; j < P2; j += 2) {
+                        const ulonglong2 u = pool2[j], v = pool2[j + 1];
+                        r += (u.x < mine ? 1 : 0) + (u.y < mine ? 1 : 0) + (v.x < mine ? 1 : 0) + (v.y < mine ? 1 : 0);
                     }
-                    fmin = m2;
+                    if (e < P && r < k) best[wave][cur ^ 1][r] = mine;
+                }
+            } else {
+                // ---- fallback: k rounds of wave-min extraction over everything this lane holds ----
+                unsigned long long fmin = KEY_MAX;
+#pragma unroll
+                for (int j = 0; j < CPL + 2; ++j) fmin = key[j] < fmin ? key[j] : fmin;
+                for (int it = 0; it < k; ++it) {
+                    const unsigned long long w = wave_min_u64(fmin);
+                    if (lane == 0) best[wave][cur ^ 1][it] = w;
+                    if (fmin == w && w != KEY_MAX) {  // keys are unique: exactly one owner
+                        unsigned long long m2 = KEY_MAX;
+#pragma unroll
+                        for (int j = 0; j < CPL + 2; ++j) {
+                            if (key[j] == w) key[j] = KEY_MAX;
+                            m2 = key[j] < m2 ? key[j] : m2;
+                        }
+                        fmin = m2;
+                    }
                 }
             }
+            cur ^= 1;
+            have = true;
         }
-        cur ^= 1;
-        have = true;
+        if (active) {
+            int32_t *o = idx + ((size_t)b * S + q) * k;
+            for (int j = lane; j < k; j += 64) o[j] = (int32_t)(unsigned)(best[wave][cur][j] & 0xffffffffu);
+        }
     }
-    if (active) {
-        int32_t *o = idx + ((size_t)b * S + q) * k;
-        for (int j = lane; j < k; j += 64) o[j] = (int32_t)(unsigned)(best[wave][cur][j] & 0xffffffffu);
+    if constexpr (MOM) {
+        if (J.mom) {
+            // rel = neighbour - centre over the wave's neighbourhoods: the same float32 terms rel_moments_kernel forms from idx, summed
+            // in float64.  Pass p began on half p & 1 of best[] and flipped once per tile, so every pass's list is still there.
+            double m[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            const int ntiles = (N + TILE - 1) / TILE;
+            for (int pass = 0; pass < qpw; ++pass) {
+                const int q = (bx * qpw + pass) * 4 + wave;
+                if (q >= S) continue;
+                const float *a = centre ? xyz + ((size_t)b * J.Nsrc + centre[(size_t)b * S + q]) * 3 : new_xyz + ((size_t)b * S + q) * 3;
+                const float ax = a[0], ay = a[1], az = a[2];
+                const unsigned long long *list = best[wave][(pass ^ ntiles) & 1];
+                for (int j = lane; j < k; j += 64) {
+                    const unsigned n = (unsigned)(list[j] & 0xffffffffu);
+                    float nx, ny, nz;
+                    if (N <= TILE) nx = sx[n], ny = sy[n], nz = sz[n];   // the one tile is still staged
+                    else nx = cloud[(size_t)n * 3], ny = cloud[(size_t)n * 3 + 1], nz = cloud[(size_t)n * 3 + 2];
+                    const float x = __fsub_rn(nx, ax), y = __fsub_rn(ny, ay), z = __fsub_rn(nz, az);
+                    m[0] += (double)x, m[1] += (double)y, m[2] += (double)z;
+                    m[3] += (double)__fmul_rn(x, x), m[4] += (double)__fmul_rn(x, y), m[5] += (double)__fmul_rn(x, z);
+                    m[6] += (double)__fmul_rn(y, y), m[7] += (double)__fmul_rn(y, z), m[8] += (double)__fmul_rn(z, z);
+                }
+            }
+            // fixed order: lanes (butterfly), then the four waves in wave order; a wave's pool is free by now
+            double *red = reinterpret_cast<double *>(pool[wave]);
+#pragma unroll
+            for (int c = 0; c < 9; ++c) {
+                double v = m[c];
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) v += shfl_xor_f64(v, o);
+                if (lane == 0) red[c] = v;
+            }
+            __syncthreads();
+            if (threadIdx.x < 9) {
+                const double *r0 = reinterpret_cast<const double *>(pool[0]), *r1 = reinterpret_cast<const double *>(pool[1]);
+                const double *r2 = reinterpret_cast<const double *>(pool[2]), *r3 = reinterpret_cast<const double *>(pool[3]);
+                J.mom[((size_t)b * J.nblocks + bx) * KNN_MOM_PITCH + threadIdx.x] =
+                    (r0[threadIdx.x] + r1[threadIdx.x]) + (r2[threadIdx.x] + r3[threadIdx.x]);
+            }
+        }
     }
 }
 
 __global__ void __launch_bounds__(256) knn_kernel(const KnnJob J) {
     __shared__ KnnLds L;
-    knn_body<false>(J, blockIdx.x, blockIdx.y, L);
+    knn_body<false, KNN_TILE, false>(J, blockIdx.x, blockIdx.y, L);
 }
 
 // The neighbour searches of two stacked levels in ONE launch (they are independent once both levels' centre indices are drawn:
-// level 2 searches among level 1's centres, which are rows of the same cloud).  blockIdx.x < nb1: level 1, else level 2.
+// level 2 searches among level 1's centres, which are rows of the same cloud).  blockIdx.x < nb2: level 2, else level 1.
 // 5 workgroups per CU (<= 96 registers): 32 clouds x (32 + 8) workgroups = 1,280 are then all resident at once on 256 CUs -- at 4 per
 // CU the last 256 start only when a slot frees up and the launch takes a round and a half (measured: 21.1 us against 12.6 + 7.0 for
-// the two separate launches).  The short level-2 workgroups come first.
+// the two separate launches).  The short level-2 workgroups come first.  TILE2: level 2's tile (KNN_TILE_SMALL when its cloud fits).
+template <int TILE2>
 __global__ void __launch_bounds__(256, 5) knn_pair_kernel(const KnnJob J1, const KnnJob J2, int nb2) {
     __shared__ KnnLds L;
-    if ((int)blockIdx.x < nb2) knn_body<true>(J2, blockIdx.x, blockIdx.y, L);
-    else knn_body<false>(J1, blockIdx.x - nb2, blockIdx.y, L);
+    if ((int)blockIdx.x < nb2) knn_body<true, TILE2, false>(J2, blockIdx.x, blockIdx.y, L);
+    else knn_body<false, KNN_TILE, true>(J1, blockIdx.x - nb2, blockIdx.y, L);
 }
 
 // Wave-wide maximum of a 64-bit key, result in every lane.  Six dependent ds_bpermute round trips (what __shfl_xor compiles
@@ -621,7 +697,7 @@ int launch_knn(const float *new_xyz, const float *xyz, int B, int S, int N, int 
     PNPP_REQUIRE(k <= KNN_KMAX, PNPP_ERR_ARG, "knn: nsample=%d exceeds the supported maximum %d", k, KNN_KMAX);
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "knn: batch %d exceeds grid limit", B);
     ProfScope ps(st, "knn_kernel B=%d S=%d N=%d k=%d", B, S, N, k);
-    const KnnJob J{new_xyz, xyz, nullptr, N, S, N, k, idx, nullptr, nullptr, nullptr};
+    const KnnJob J{new_xyz, xyz, nullptr, N, S, N, k, idx, nullptr, nullptr, nullptr, nullptr, 1, cdiv(S, 4)};
     hipLaunchKernelGGL(knn_kernel, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
     PNPP_CHECK_LAUNCH("knn");
     return PNPP_OK;
@@ -636,27 +712,39 @@ int launch_knn_centres(const float *xyz, const int32_t *centre, int B, int S, in
     PNPP_REQUIRE(k <= KNN_KMAX, PNPP_ERR_ARG, "knn: nsample=%d exceeds the supported maximum %d", k, KNN_KMAX);
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "knn: batch %d exceeds grid limit", B);
     ProfScope ps(st, "knn_kernel B=%d S=%d N=%d k=%d", B, S, N, k);
-    const KnnJob J{nullptr, xyz, nullptr, N, S, N, k, idx, centre, out_a, out_b};
+    const KnnJob J{nullptr, xyz, nullptr, N, S, N, k, idx, centre, out_a, out_b, nullptr, 1, cdiv(S, 4)};
     hipLaunchKernelGGL(knn_kernel, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
     PNPP_CHECK_LAUNCH("knn");
     return PNPP_OK;
 }
 
+// queries per wave of level 1 in the pair kernel: two when the cloud is one tile -- a workgroup then stages the cloud once for eight
+// queries and writes one moment partial for them (measured at B=32, N=1024, S=128: 16.8 us against 20.6 us with one query per wave,
+// and half the partials for the consumer's prologue to read)
+static int knn_pair_qpw(int N) { return N <= KNN_TILE ? KNN_PAIR_QPW : 1; }
+int knn_pair_moment_partials(int B, int S1, int N) { return B * cdiv(S1, 4 * knn_pair_qpw(N)); }
+size_t knn_pair_moment_doubles(int B, int S1, int N) { return (size_t)knn_pair_moment_partials(B, S1, N) * kMomPitch; }
+
 // Both levels' searches in one launch: level 1 = S1 centres (rows centre1 of the N-point cloud), k1 neighbours among the N
 // points; level 2 = S2 of those centres (positions centre2 in 0..S1-1), k2 neighbours among the S1 centres.
+// mom != nullptr: level 1 also writes knn_pair_moment_partials(B, S1, N) moment partials of its relative coordinates.
 int launch_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int S1, int k1, int32_t *idx1, float *a1, float *b1,
-                    const int32_t *centre2, int S2, int k2, int32_t *idx2, float *a2, float *b2, hipStream_t st) {
+                    const int32_t *centre2, int S2, int k2, int32_t *idx2, float *a2, float *b2, double *mom, hipStream_t st) {
     PNPP_REQUIRE(xyz && centre1 && centre2 && idx1 && idx2 && a1 && a2, PNPP_ERR_ARG, "knn_pair: null pointer");
     PNPP_REQUIRE(B > 0 && N > 0 && S1 > 0 && S2 > 0 && k1 > 0 && k2 > 0, PNPP_ERR_ARG, "knn_pair: non-positive size");
     PNPP_REQUIRE(k1 <= N && k2 <= S1, PNPP_ERR_RANGE, "selected index k out of range (k=%d > N=%d)", k1 <= N ? k2 : k1, k1 <= N ? S1 : N);
     PNPP_REQUIRE(S1 <= N && S2 <= S1, PNPP_ERR_RANGE, "knn_pair: more centres than points");
     PNPP_REQUIRE(k1 <= KNN_KMAX && k2 <= KNN_KMAX, PNPP_ERR_ARG, "knn: nsample exceeds the supported maximum %d", KNN_KMAX);
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "knn: batch %d exceeds grid limit", B);
-    ProfScope ps(st, "knn_pair_kernel B=%d | S=%d N=%d k=%d | S=%d N=%d k=%d", B, S1, N, k1, S2, S1, k2);
-    const KnnJob J1{nullptr, xyz, nullptr, N, S1, N, k1, idx1, centre1, a1, b1};
-    const KnnJob J2{nullptr, xyz, centre1, N, S2, S1, k2, idx2, centre2, a2, b2};
-    const int nb2 = cdiv(S2, 4);
-    hipLaunchKernelGGL(knn_pair_kernel, dim3(cdiv(S1, 4) + nb2, B), dim3(256), 0, st, J1, J2, nb2);
+    static_assert(KNN_MOM_PITCH == kMomPitch, "moment partial pitch");
+    const int qpw = knn_pair_qpw(N), nb1 = cdiv(S1, 4 * qpw), nb2 = cdiv(S2, 4);
+    ProfScope ps(st, "knn_pair_kernel B=%d | S=%d N=%d k=%d | S=%d N=%d k=%d%s", B, S1, N, k1, S2, S1, k2, mom ? " +moments" : "");
+    const KnnJob J1{nullptr, xyz, nullptr, N, S1, N, k1, idx1, centre1, a1, b1, mom, qpw, nb1};
+    const KnnJob J2{nullptr, xyz, centre1, N, S2, S1, k2, idx2, centre2, a2, b2, nullptr, 1, nb2};
+    if (S1 <= KNN_TILE_SMALL)
+        hipLaunchKernelGGL(knn_pair_kernel<KNN_TILE_SMALL>, dim3(nb1 + nb2, B), dim3(256), 0, st, J1, J2, nb2);
+    else
+        hipLaunchKernelGGL(knn_pair_kernel<KNN_TILE>, dim3(nb1 + nb2, B), dim3(256), 0, st, J1, J2, nb2);
     PNPP_CHECK_LAUNCH("knn_pair");
     return PNPP_OK;
 }
@@ -696,6 +784,14 @@ extern "C" int pnpp_square_distance(const float *src, const float *dst, int B, i
 
 extern "C" int pnpp_knn(const float *new_xyz, const float *xyz, int B, int S, int N, int k, int32_t *idx, void *stream) {
     return launch_knn(new_xyz, xyz, B, S, N, k, idx, as_stream(stream));
+}
+
+extern "C" int pnpp_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int S1, int k1, int32_t *idx1, float *new_xyz1,
+                             const int32_t *centre2, int S2, int k2, int32_t *idx2, float *new_xyz2, double *mom, void *stream) {
+    return launch_knn_pair(xyz, B, N, centre1, S1, k1, idx1, new_xyz1, nullptr, centre2, S2, k2, idx2, new_xyz2, nullptr, mom, as_stream(stream));
+}
+extern "C" int pnpp_knn_pair_partials(int B, int S1, int N) {
+    return (B > 0 && S1 > 0 && N > 0) ? knn_pair_moment_partials(B, S1, N) : 0;
 }
 
 extern "C" int pnpp_fps(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out, void *stream) {

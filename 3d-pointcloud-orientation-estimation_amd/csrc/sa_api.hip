@@ -140,12 +140,20 @@ struct SaSaved {
     float *z[PNPP_MAX_LAYERS];
     float *mean[PNPP_MAX_LAYERS], *istd[PNPP_MAX_LAYERS], *scale[PNPP_MAX_LAYERS], *shift[PNPP_MAX_LAYERS];
     int32_t *arg;
+    double *mom;   // a level on raw coordinates grouped by pnpp_sa_group_pair: the moment partials its search wrote (sa_pair_moments)
     float *zmax;   // (G, C_last): the pre-BN value each pooled output came from (the backward pass's ReLU gate and xhat need it)
     size_t bytes;
 };
 
 // whole-cloud pooling in K chunks (pool_fwd_split / merge) does not produce the selected pre-BN values; backward gathers them there
 static bool sa_keeps_zmax(const pnpp_sa_desc *d, const SaGeom &g) { return pool_fwd_splits(g.G, d->K, d->C[d->L - 1]) <= 1; }
+
+// The pair search (pnpp_sa_group_pair) also sums the moments of this level's relative coordinates, one partial per search workgroup,
+// into the level's kept workspace: the forward pass that finds its neighbours already in place (they can only come from that search)
+// then needs no rel_moments launch.  Decided from the descriptor's geometry alone, so both calls agree without passing anything.
+static bool sa_pair_moments(const pnpp_sa_desc *d, const SaGeom &g) {
+    return xyz0_applies(g.M, d->D, d->K, d->group_all, d->L, d->C);
+}
 
 static SaSaved sa_saved_layout(const pnpp_sa_desc *d, const SaGeom &g, void *base) {
     Carver cv(base);
@@ -161,6 +169,7 @@ static SaSaved sa_saved_layout(const pnpp_sa_desc *d, const SaGeom &g, void *bas
     }
     s.arg = cv.take<int32_t>((size_t)g.G * d->C[d->L - 1]);
     s.zmax = cv.take<float>(sa_keeps_zmax(d, g) ? (size_t)g.G * d->C[d->L - 1] : 0);
+    s.mom = cv.take<double>(sa_pair_moments(d, g) ? knn_pair_moment_doubles(d->B, d->S, d->N) : 0);
     s.bytes = cv.bytes();
     return s;
 }
@@ -281,10 +290,12 @@ static int sa_forward_impl(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, hip
     // coordinates, layer 1's product builds its operand from the coordinates (gemm_wsx_kernels.hip); the backward pass does the same
     const bool xyz0 = xyz0_applies(g.M, d->D, d->K, d->group_all, d->L, d->C);
     int nmom = 0;
+    const double *mom = sc.mom;
     for (int l = 0; l < d->L; ++l) {
         if (xyz0 && l == 0) {
             if (d->training) {
-                PNPP_TRY(launch_rel_moments(layer0_operand(d, a->xyz, a->points, sv), g.M, sc.mom, &nmom, st));
+                if (a->neighbour_idx == sv.idx && sa_pair_moments(d, g)) mom = sv.mom, nmom = knn_pair_moment_partials(d->B, d->S, d->N);
+                else PNPP_TRY(launch_rel_moments(layer0_operand(d, a->xyz, a->points, sv), g.M, sc.mom, &nmom, st));
             } else {
                 PNPP_TRY(launch_bn_finalize_fwd(nullptr, 0, d->C[0], (double)g.M, a->conv_b[0], a->bn_w[0], a->bn_b[0], a->bn_rm[0],
                                                 a->bn_rv[0], nullptr, d->momentum, d->eps, 0, sv.mean[0], sv.istd[0], sv.scale[0],
@@ -295,7 +306,7 @@ static int sa_forward_impl(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, hip
         // layer 1 of such a level: the product that also finishes layer 0's BatchNorm
         auto gemm_l = [&](const AOperand &Aop, const BOperand &Wop, const Epilogue &Eop, int *ns) -> int {
             if (xyz0 && l == 1)
-                return launch_wsf0(layer0_operand(d, a->xyz, a->points, sv), g.M, a->conv_w[0], g.Cin[0], sc.mom, nmom, d->training ? 1 : 0,
+                return launch_wsf0(layer0_operand(d, a->xyz, a->points, sv), g.M, a->conv_w[0], g.Cin[0], mom, nmom, d->training ? 1 : 0,
                                    a->conv_b[0], a->bn_w[0], a->bn_b[0], a->bn_rm[0], a->bn_rv[0],
                                    d->training ? (long long *)a->bn_nbt[0] : nullptr, d->momentum, d->eps, sv.mean[0], sv.istd[0],
                                    sv.scale[0], sv.shift[0], a->conv_w[1], g.Cin[1], Eop, ns, st);
@@ -716,7 +727,7 @@ extern "C" int pnpp_sa_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2
     PNPP_REQUIRE(xyz && centre1 && centre2 && saved1 && saved2 && new_xyz1 && new_xyz2, PNPP_ERR_ARG, "sa_group_pair: null pointer");
     const SaSaved s1 = sa_saved_layout(d1, g1, saved1), s2 = sa_saved_layout(d2, g2, saved2);
     return launch_knn_pair(xyz, d1->B, d1->N, centre1, d1->S, d1->K, s1.idx, new_xyz1, s1.new_xyz, centre2, d2->S, d2->K, s2.idx,
-                           new_xyz2, s2.new_xyz, as_stream(stream));
+                           new_xyz2, s2.new_xyz, sa_pair_moments(d1, g1) ? s1.mom : nullptr, as_stream(stream));
 }
 
 extern "C" int pnpp_sa_forward(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, void *stream) {

@@ -426,7 +426,7 @@ extern "C" int pnpp_sa_infer_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_de
     PNPP_REQUIRE(d1->B == d2->B && d2->N == d1->S, PNPP_ERR_ARG, "sa_infer_group_pair: level 2 must take level 1's %d centres (got N=%d)", d1->S,
                  d2->N);
     PNPP_REQUIRE(xyz && centre1 && centre2 && idx1 && idx2 && new_xyz1 && new_xyz2, PNPP_ERR_ARG, "sa_infer_group_pair: null pointer");
-    return launch_knn_pair(xyz, d1->B, d1->N, centre1, d1->S, d1->K, idx1, new_xyz1, nullptr, centre2, d2->S, d2->K, idx2, new_xyz2, nullptr,
+    return launch_knn_pair(xyz, d1->B, d1->N, centre1, d1->S, d1->K, idx1, new_xyz1, nullptr, centre2, d2->S, d2->K, idx2, new_xyz2, nullptr, nullptr,
                            as_stream(stream));
 }
 extern "C" int pnpp_fc_infer_fold(int N, int K, const float *w, const float *b, const float *gamma, const float *beta, const float *rm,

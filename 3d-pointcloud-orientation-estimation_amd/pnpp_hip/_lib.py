@@ -122,6 +122,8 @@ SIGNATURES = {
     "pnpp_sa_forward": (_i, [C.POINTER(SaDesc), C.POINTER(SaFwdArgs), _fp]),
     "pnpp_sa_backward": (_i, [C.POINTER(SaDesc), C.POINTER(SaBwdArgs), _fp]),
     "pnpp_sa_saved_neighbours": (_fp, [C.POINTER(SaDesc), _fp]),
+    "pnpp_knn_pair": (_i, [_fp, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp]),
+    "pnpp_knn_pair_partials": (_i, [_i, _i, _i]),
     "pnpp_sa_group_pair": (_i, [C.POINTER(SaDesc), C.POINTER(SaDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnpp_sa_saved_argmax": (_fp, [C.POINTER(SaDesc), _fp]),
     "pnpp_sa_saved_relu_mask": (_i, [C.POINTER(SaDesc), _fp, _fp, _fp, _i, _fp, _fp]),

@@ -168,6 +168,13 @@ int pnpp_sa_backward(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, void *str
  * takes them as already grouped when its neighbour_idx argument IS pnpp_sa_saved_neighbours(d, saved) (and new_xyz is that buffer). */
 int pnpp_sa_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *centre1,
                        const int32_t *centre2, void *saved1, float *new_xyz1, void *saved2, float *new_xyz2, void *stream);
+/* The search of pnpp_sa_group_pair on plain buffers, with the moment partials its level-1 side can sum on the way: idx1 (B,S1,k1),
+ * new_xyz1 (B,S1,3), idx2 (B,S2,k2), new_xyz2 (B,S2,3).  mom (optional) receives pnpp_knn_pair_partials(B,S1,N) partials of 16 doubles,
+ * the first nine of each being sum rel (x,y,z) and sum rel rel^T (xx,xy,xz,yy,yz,zz) of rel = neighbour - centre over the workgroup's
+ * level-1 neighbourhoods (float32 terms, float64 sums, fixed order). */
+int pnpp_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int S1, int k1, int32_t *idx1, float *new_xyz1,
+                  const int32_t *centre2, int S2, int k2, int32_t *idx2, float *new_xyz2, double *mom, void *stream);
+int pnpp_knn_pair_partials(int B, int S1, int N);
 /* read-only view of the neighbour indices kept in `saved` ((B,S,K) int32; NULL when group_all) */
 const int32_t *pnpp_sa_saved_neighbours(const pnpp_sa_desc *d, const void *saved);
 /* read-only view of the max-pool routing kept in `saved`: (B*S, C_last) int32, the position 0..K-1 inside its group of the
