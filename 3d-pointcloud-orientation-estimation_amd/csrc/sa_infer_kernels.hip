@@ -18,8 +18,15 @@
 // No M x C tensor is written to global memory.  When the level has fewer row tiles than the chip has CUs (group_all levels), the
 // columns of the LAST layer are split over blockIdx.y and every such workgroup recomputes layers 0 and 1 of its tile.
 //
-// Shapes taken (pnpp_sa_infer_supported): L == 3; C[l] multiples of 32, <= 1024; K in {16, 32} (group_all: N in {16, 32});
-// D + 3 <= 1024; the two LDS tiles (three bf16 planes each) of a 32-row workgroup fit 160 KiB.
+//
+// sa_infer_wide_kernel: neighbourhoods larger than a row tile, K = 32 m rows (m = 2 .. 8).  A workgroup owns ONE neighbourhood and walks
+// it in 32-row tiles: per tile it builds the layer-0 operand and runs the same three products; the column maxima of layer 2's
+// accumulators are folded into a running maximum that stays in registers (a lane keeps one column of each of its wave's <= 8 column
+// blocks), and (B, S, C_2) is written once, after the last tile.  Same LDS tiles, same weight blob, same column split of the last
+// layer over blockIdx.y when there are fewer neighbourhoods than CUs (group_all levels over 64 .. 256 rows).
+//
+// Shapes taken (pnpp_sa_infer_supported): L == 3; C[l] multiples of 32, <= 1024; K = 16 or a multiple of 32 up to 256 (group_all: N
+// likewise); D + 3 <= 1024; the two LDS tiles (three bf16 planes each) of a 32-row workgroup fit 160 KiB.
 #include "kernels.h"
 #include "split_infer.h"
 
@@ -42,9 +49,11 @@ namespace {
 
 constexpr int kInferThreads = 256;
 constexpr int kInferMaxLds = 160 * 1024;
+constexpr int kInferMaxK = 256;   // rows of a neighbourhood the wide kernel walks (8 tiles)
 
 struct InferPlan {
     int TM;        // rows per workgroup (32 or 64)
+    bool wide;     // K > 32: one neighbourhood per workgroup, walked in 32-row tiles (sa_infer_wide_kernel)
     int Kd0;       // layer 0's reduction length, padded to a multiple of 16
     int ldA, ldB;  // row strides of the two LDS tiles (bf16 elements)
     int nsplit;    // column split of the last layer over blockIdx.y
@@ -66,7 +75,8 @@ static int infer_plan(const pnpp_sa_desc *d, InferPlan *p) {
                  d->B, d->N, d->S, d->K, d->D);
     if (d->group_all) PNPP_REQUIRE(d->S == 1 && d->K == d->N, PNPP_ERR_ARG, "sa_infer: group_all needs S == 1 and K == N");
     PNPP_REQUIRE(d->L == 3, PNPP_ERR_ARG, "sa_infer: the fused kernel takes 3 layers, not %d", d->L);
-    PNPP_REQUIRE(d->K == 16 || d->K == 32, PNPP_ERR_ARG, "sa_infer: the fused kernel takes neighbourhoods of K = 16 or 32 rows, not K=%d", d->K);
+    PNPP_REQUIRE(d->K == 16 || (d->K % 32 == 0 && d->K <= kInferMaxK), PNPP_ERR_ARG,
+                 "sa_infer: the fused kernel takes neighbourhoods of K = 16 or a multiple of 32 up to %d rows, not K=%d", kInferMaxK, d->K);
     for (int l = 0; l < 3; ++l)
         PNPP_REQUIRE(d->C[l] > 0 && d->C[l] % 32 == 0 && d->C[l] <= 1024, PNPP_ERR_ARG,
                      "sa_infer: mlp channel %d (=%d) must be a multiple of 32 up to 1024", l, d->C[l]);
@@ -79,14 +89,15 @@ static int infer_plan(const pnpp_sa_desc *d, InferPlan *p) {
     p->ldB = d->C[0] + 8;
     const size_t per_row = (size_t)(p->ldA + p->ldB) * 3 * sizeof(unsigned short);   // three bf16 planes per tile
     const long long M = (long long)d->B * d->S * d->K;
-    if (64 * per_row <= 80 * 1024 && M > 32)
+    p->wide = d->K > 32;
+    if (64 * per_row <= 80 * 1024 && M > 32 && !p->wide)
         p->TM = 64;   // two workgroups per CU still fit
     else
         p->TM = 32;
     p->lds = p->TM * per_row;
     PNPP_REQUIRE(p->lds <= (size_t)kInferMaxLds, PNPP_ERR_ARG, "sa_infer: a 32-row tile of widths %d and %d needs %zu bytes of LDS (> %d)", wideA,
                  d->C[0], p->lds, kInferMaxLds);
-    p->ntiles = (int)((M + p->TM - 1) / p->TM);
+    p->ntiles = p->wide ? d->B * d->S : (int)((M + p->TM - 1) / p->TM);   // workgroups along x
     int ns = 1;
     const int ncb = d->C[2] / 32;
     const int target = infer_target_wgs();
@@ -231,34 +242,13 @@ __device__ __forceinline__ void infer_layer(const unsigned short *__restrict__ a
     }
 }
 
-template <int TM>
-__global__ __launch_bounds__(kInferThreads) void sa_infer_kernel(const InferArgs P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
-    const size_t planeA = (size_t)TM * P.ldA, planeB = (size_t)TM * P.ldB;
-    unsigned short *bufA = lds;               // three planes of the layer-0 operand, later of layer 1's output (row stride ldA)
-    unsigned short *bufB = lds + 3 * planeA;  // three planes of layer 0's output (row stride ldB)
+// Rows [m0, m0 + nrows) of the level's G * K grouped rows as the layer-0 operand [xyz[nbr] - xyz[centre] | points[nbr] | 0], split
+// as it is written into the three planes of bufA: 16 lanes per row.  Rows past M are zeros.
+__device__ __forceinline__ void infer_stage_rows(const InferArgs &P, unsigned short *__restrict__ bufA, size_t planeA, int nrows, long long m0,
+                                                 long long M) {
     const int t = threadIdx.x;
-    const long long M = (long long)P.G * P.K;
-    const long long tile0 = (long long)blockIdx.x * TM;
-
-    // centres of this tile's groups (pointnet_pp_8dir.py:24 / :29): zeros for group_all, the gathered rows otherwise
-    if (blockIdx.y == 0 && t < (TM / 16) * 3) {
-        const int ngrp = TM / P.K;
-        const long long g = tile0 / P.K + t / 3;
-        if (t / 3 < ngrp && g < P.G) {
-            float v = 0.f;
-            if (!P.group_all) {
-                const int b = (int)(g / P.S);
-                const int c = min(max(P.centre[g], 0), P.N - 1);
-                v = P.xyz[((size_t)b * P.N + c) * 3 + t % 3];
-            }
-            P.new_xyz[g * 3 + t % 3] = v;
-        }
-    }
-
-    // 1. layer-0 operand, split as it is written: 16 lanes per row
-    for (int row = t >> 4; row < TM; row += kInferThreads / 16) {
-        const long long m = tile0 + row;
+    for (int row = t >> 4; row < nrows; row += kInferThreads / 16) {
+        const long long m = m0 + row;
         unsigned short *dst = bufA + (size_t)row * P.ldA;
         const int lane = t & 15;
         const bool valid = m < M;
@@ -288,6 +278,35 @@ __global__ __launch_bounds__(kInferThreads) void sa_infer_kernel(const InferArgs
             dst[c] = (unsigned short)ph, dst[planeA + c] = (unsigned short)pm, dst[2 * planeA + c] = (unsigned short)pl;
         }
     }
+}
+
+template <int TM>
+__global__ __launch_bounds__(kInferThreads) void sa_infer_kernel(const InferArgs P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
+    const size_t planeA = (size_t)TM * P.ldA, planeB = (size_t)TM * P.ldB;
+    unsigned short *bufA = lds;               // three planes of the layer-0 operand, later of layer 1's output (row stride ldA)
+    unsigned short *bufB = lds + 3 * planeA;  // three planes of layer 0's output (row stride ldB)
+    const int t = threadIdx.x;
+    const long long M = (long long)P.G * P.K;
+    const long long tile0 = (long long)blockIdx.x * TM;
+
+    // centres of this tile's groups (pointnet_pp_8dir.py:24 / :29): zeros for group_all, the gathered rows otherwise
+    if (blockIdx.y == 0 && t < (TM / 16) * 3) {
+        const int ngrp = TM / P.K;
+        const long long g = tile0 / P.K + t / 3;
+        if (t / 3 < ngrp && g < P.G) {
+            float v = 0.f;
+            if (!P.group_all) {
+                const int b = (int)(g / P.S);
+                const int c = min(max(P.centre[g], 0), P.N - 1);
+                v = P.xyz[((size_t)b * P.N + c) * 3 + t % 3];
+            }
+            P.new_xyz[g * 3 + t % 3] = v;
+        }
+    }
+
+    // 1. layer-0 operand, split as it is written
+    infer_stage_rows(P, bufA, planeA, TM, tile0, M);
     __syncthreads();
     // 2. the three products
     infer_layer<TM, false>(bufA, P.ldA, planeA, P.Kd0, P.w[0], P.C0, P.b[0], 0, P.C0 / 32, bufB, P.ldB, planeB, P);
@@ -295,6 +314,94 @@ __global__ __launch_bounds__(kInferThreads) void sa_infer_kernel(const InferArgs
     infer_layer<TM, false>(bufB, P.ldB, planeB, P.C0, P.w[1], P.C1, P.b[1], 0, P.C1 / 32, bufA, P.ldA, planeA, P);
     __syncthreads();
     infer_layer<TM, true>(bufA, P.ldA, planeA, P.C1, P.w[2], P.C2, P.b[2], blockIdx.y * P.c2_per_wg, P.c2_per_wg / 32, nullptr, 0, 0, P);
+}
+
+// The last layer of one 32-row tile for the wide kernel: the tile's column maxima of z = act W^T (bias and ReLU come after the max over
+// the whole neighbourhood, x -> relu(x + b') being monotone) folded into mx[j], the running maxima of NJ column blocks.
+template <int NJ>
+__device__ __forceinline__ void infer_unit_max(const unsigned short *__restrict__ actIn, int ldin, size_t inplane, int Kd,
+                                               const unsigned short *__restrict__ W, size_t wplane, int col0, int colstep, float (&mx)[NJ]) {
+    f32x16 acc[NJ], accl[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f, accl[j][i] = 0.f;
+    infer_chunk<NJ>(actIn, ldin, inplane, Kd, W, wplane, col0, colstep, acc, accl);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        float m = acc[j][0] + accl[j][0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) m = fmaxf(m, acc[j][i] + accl[j][i]);
+        mx[j] = fmaxf(mx[j], fmaxf(m, __shfl_xor(m, 32, 64)));   // the other half-wave holds the column's other 16 rows
+    }
+}
+
+// K = 32 m rows per neighbourhood: workgroup blockIdx.x owns neighbourhood g = blockIdx.x, every tile is full.  The column blocks of
+// the last layer go round-robin over the 4 waves as in infer_layer<32, true> (a wave works blocks jb and jb + 4 together, then
+// jb + 8 ...): at most 32 / 4 = 8 blocks per wave, so a lane's running maxima are 8 registers, indexed statically.
+__global__ __launch_bounds__(kInferThreads) void sa_infer_wide_kernel(const InferArgs P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
+    const size_t planeA = (size_t)32 * P.ldA, planeB = (size_t)32 * P.ldB;
+    unsigned short *bufA = lds;
+    unsigned short *bufB = lds + 3 * planeA;
+    const int t = threadIdx.x, wave = t >> 6;
+    const long long g = blockIdx.x;
+    const long long M = (long long)P.G * P.K;
+
+    if (blockIdx.y == 0 && t < 3) {   // the centre (zeros for group_all)
+        float v = 0.f;
+        if (!P.group_all) {
+            const int b = (int)(g / P.S);
+            const int c = min(max(P.centre[g], 0), P.N - 1);
+            v = P.xyz[((size_t)b * P.N + c) * 3 + t];
+        }
+        P.new_xyz[g * 3 + t] = v;
+    }
+
+    const int colbeg = blockIdx.y * P.c2_per_wg, ncb = P.c2_per_wg / 32;
+    const size_t wplane2 = (size_t)P.C2 * P.C1;
+    float runmax[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) runmax[i] = -INFINITY;
+
+    for (int tile = 0; tile < P.K / 32; ++tile) {
+        infer_stage_rows(P, bufA, planeA, 32, g * P.K + tile * 32, M);
+        __syncthreads();
+        infer_layer<32, false>(bufA, P.ldA, planeA, P.Kd0, P.w[0], P.C0, P.b[0], 0, P.C0 / 32, bufB, P.ldB, planeB, P);
+        __syncthreads();
+        infer_layer<32, false>(bufB, P.ldB, planeB, P.C0, P.w[1], P.C1, P.b[1], 0, P.C1 / 32, bufA, P.ldA, planeA, P);
+        __syncthreads();
+        // one copy of the product code: the loop is not unrolled, the unit at hand is always runmax[0 .. 1] and the array is rotated
+        // by two per step (four steps bring it back), so no register is indexed dynamically
+#pragma unroll 1
+        for (int u = 0; u < 4; ++u) {
+            const int jb = wave + 8 * u;   // wave-uniform
+            float mx[2] = {runmax[0], runmax[1]};
+            if (jb + 4 < ncb) {
+                infer_unit_max<2>(bufA, P.ldA, planeA, P.C1, P.w[2], wplane2, colbeg + jb * 32, 128, mx);
+            } else if (jb < ncb) {
+                float m1[1] = {mx[0]};
+                infer_unit_max<1>(bufA, P.ldA, planeA, P.C1, P.w[2], wplane2, colbeg + jb * 32, 128, m1);
+                mx[0] = m1[0];
+            }
+#pragma unroll
+            for (int i = 0; i < 6; ++i) runmax[i] = runmax[i + 2];
+            runmax[6] = mx[0], runmax[7] = mx[1];
+        }
+        __syncthreads();   // the next tile's operand overwrites bufA
+    }
+
+    if (((t >> 5) & 1) == 0) {
+        const int r = t & 31;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int jb = wave + 8 * u;
+            if (jb >= ncb) continue;
+            const int col = colbeg + jb * 32 + r;
+            P.out[(size_t)g * P.C2 + col] = fmaxf(runmax[2 * u] + P.b[2][col], 0.f);
+            if (jb + 4 < ncb) P.out[(size_t)g * P.C2 + col + 128] = fmaxf(runmax[2 * u + 1] + P.b[2][col + 128], 0.f);
+        }
+    }
 }
 
 }  // namespace
@@ -384,18 +491,21 @@ int sa_infer(const pnpp_sa_desc *d, const pnpp_sa_infer_args *a, hipStream_t st)
     P.ldA = p.ldA, P.ldB = p.ldB;
     P.group_all = d->group_all;
     P.c2_per_wg = d->C[2] / p.nsplit;
-    ProfScope ps(st, "sa_infer_kernel TM=%d G=%d K=%d D=%d C=%d,%d,%d split=%d", p.TM, P.G, d->K, d->D, d->C[0], d->C[1], d->C[2], p.nsplit);
+    ProfScope ps(st, "%s TM=%d G=%d K=%d D=%d C=%d,%d,%d split=%d", p.wide ? "sa_infer_wide_kernel" : "sa_infer_kernel", p.TM, P.G, d->K, d->D,
+                 d->C[0], d->C[1], d->C[2], p.nsplit);
     const dim3 grid(p.ntiles, p.nsplit);
     // dynamic LDS above 48 KiB has to be allowed once per kernel (process-wide flag, not per device: one process drives one GPU)
-    static bool granted[2] = {false, false};
-    const int ki = p.TM == 64 ? 0 : 1;
+    static bool granted[3] = {false, false, false};
+    const int ki = p.wide ? 2 : p.TM == 64 ? 0 : 1;
     if (p.lds > 48 * 1024 && !granted[ki]) {
-        const void *fn = ki == 0 ? (const void *)sa_infer_kernel<64> : (const void *)sa_infer_kernel<32>;
+        const void *fn = ki == 2 ? (const void *)sa_infer_wide_kernel : ki == 0 ? (const void *)sa_infer_kernel<64> : (const void *)sa_infer_kernel<32>;
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kInferMaxLds);
         PNPP_REQUIRE(e == hipSuccess, PNPP_ERR_LAUNCH, "sa_infer: cannot allow %d bytes of dynamic LDS: %s", kInferMaxLds, hipGetErrorString(e));
         granted[ki] = true;
     }
-    if (p.TM == 64)
+    if (p.wide)
+        hipLaunchKernelGGL(sa_infer_wide_kernel, grid, dim3(kInferThreads), p.lds, st, P);
+    else if (p.TM == 64)
         hipLaunchKernelGGL(sa_infer_kernel<64>, grid, dim3(kInferThreads), p.lds, st, P);
     else
         hipLaunchKernelGGL(sa_infer_kernel<32>, grid, dim3(kInferThreads), p.lds, st, P);

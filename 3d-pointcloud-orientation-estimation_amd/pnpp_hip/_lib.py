@@ -168,6 +168,11 @@ SIGNATURES = {
     "pnpp_mvm_head": (_i, [_fp, _fp, _fp, _i, _i, _f, _f, _fp, _fp, _fp, _fp]),
     "pnpp_mvm_head_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _f, _f, _fp, _fp, _fp, _fp]),
     "pnpp_soft_ce": (_i, [_fp, _fp, _i, _i, _fp, _fp, _fp]),
+    "pnpp_log_softmax": (_i, [_fp, _i, _i, _fp, _fp]),
+    "pnpp_log_softmax_bwd": (_i, [_fp, _fp, _i, _i, _fp, _fp]),
+    "pnpp_linear_log_softmax": (_i, [_fp, _fp, _fp, _i, _i, _i, _fp, _fp]),
+    "pnpp_nll_loss": (_i, [_fp, _fp, _i, _i, _fp, _fp, _i, _fp]),
+    "pnpp_nll_loss_bwd": (_i, [_fp, _fp, _i, _i, _fp, _fp]),
     "pnpp_l2_normalize": (_i, [_fp, _i, _i, _f, _fp, _fp]),
     "pnpp_l2_normalize_bwd": (_i, [_fp, _fp, _i, _i, _f, _fp, _fp]),
     "pnpp_mse": (_i, [_fp, _fp, _sz, _fp, _fp, _fp]),

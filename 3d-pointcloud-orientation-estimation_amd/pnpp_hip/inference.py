@@ -5,7 +5,7 @@
 
 A level runs as ONE launch (pnpp_sa_infer: gather -> 3 x (product + bias + ReLU) -> max, nothing of size M x C leaves the
 chip); the BatchNorm head blocks run as a plain linear + ReLU on folded parameters.  Whatever the fused kernel does not take
-(pnpp_sa_infer_supported: K outside {16, 32}, other layer counts, the LayerNorm head of PointNetPPMvM, the output maps) goes
+(pnpp_sa_infer_supported: K other than 16 or a multiple of 32 up to 256, other layer counts, the LayerNorm head of PointNetPPMvM, the output maps) goes
 through the library's existing eval-mode entry points, unchanged.  `predictor.plan` says which is which at the sizes the model's
 constructor arguments imply; the choice is made again from each call's sizes (a level planned "fused" whose input a call makes
 unsupported runs the eval path for that call), and `predictor.last_plan` says what the latest call ran.
@@ -19,7 +19,9 @@ It is not differentiable (model.eval() remains the path with a backward pass), k
 Predictor(model) of a vanilla PointNet / PointNetEncoder (models/pointnet.py) builds the Predictor of pnpp_hip.pointnet_inference:
 the same contract, one launch per trunk (pnpp_pn_infer).  Predictor(model) of a PointTransformer (models/point_transformer.py) builds
 the TransformerPredictor of pnpp_hip.transformer_inference: one launch per encoder layer beside its attention (pnpp_pt_infer_tail);
-Predictor(model, attention="split" | "float32") chooses the attention kernel there.
+Predictor(model, attention="split" | "float32") chooses the attention kernel there.  Predictor(model) of a PointNetPlusPlusCls
+(models/pointnet_pp_cls.py) builds the ClsPredictor below: the same levels and head blocks, farthest-point sampling + radius query
+in front of each level's launch, and fc3 + log_softmax as one launch (pnpp_linear_log_softmax).
 """
 from __future__ import annotations
 
@@ -94,21 +96,28 @@ class Predictor:
             if isinstance(model, PointTransformer):   # and so has the point transformer
                 from .transformer_inference import TransformerPredictor
                 return object.__new__(TransformerPredictor)
+            from models.pointnet_pp_cls import PointNetPlusPlusCls
+            if isinstance(model, PointNetPlusPlusCls):   # the textbook classifier: other samplers, other head tail
+                return object.__new__(ClsPredictor)
         return object.__new__(cls)
 
-    def __init__(self, model: nn.Module):
+    @staticmethod
+    def _check_model(model) -> None:
         from models.pointnet_pp_8dir import BackboneBNHead
         from models.pointnet_pp_mvM import PointNetPPMvM
         if not isinstance(model, (BackboneBNHead, PointNetPPMvM)):
-            raise TypeError(f"Predictor takes a PointNet++ set-abstraction model, a PointNet, a PointNetEncoder or a PointTransformer, "
-                            f"not {type(model).__name__}")
+            raise TypeError(f"Predictor takes a PointNet++ set-abstraction model, a PointNetPlusPlusCls, a PointNet, a PointNetEncoder or "
+                            f"a PointTransformer, not {type(model).__name__}")
+        # the model class's own forward() is run on a proxy whose backbone entry is the Predictor's: it must have one
+        if not any(callable(getattr(type(model), n, None)) for n in ("trunk", "_global_feat")):
+            raise TypeError(f"{type(model).__name__} reaches its backbone through neither trunk() nor _global_feat()")
+
+    def __init__(self, model: nn.Module):
+        self._check_model(model)
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError(f"the model is on '{p.device}': the pnpp HIP operators run on an AMD GPU only "
                                "(no CPU fallback exists in this package)")
-        # the model class's own forward() is run on a proxy whose backbone entry is the Predictor's: it must have one
-        if not any(callable(getattr(type(model), n, None)) for n in ("trunk", "_global_feat")):
-            raise TypeError(f"{type(model).__name__} reaches its backbone through neither trunk() nor _global_feat()")
         self.model = model
         self.device = p.device
         self._levels = [model.sa1, model.sa2, model.sa3]
@@ -337,3 +346,38 @@ class Predictor:
         ops._need_gpu(xyz, "xyz")
         with torch.cuda.device(self.device):
             return type(self.model).forward(_Proxy(self), xyz, centres=centres)
+
+
+class ClsPredictor(Predictor):
+    """Forward-only evaluation of PointNetPlusPlusCls: predictor(x, start=None) == model.eval()(x, start=start) under no_grad.
+    Each level is farthest-point sampling, the radius query and one pnpp_sa_infer launch on the neighbour lists; fc1 / bn1 and
+    fc2 / bn2 are folded; fc3 + log_softmax is one launch on the snapshot's fc3 (plan["fc3"]).  Same draws from the host generator as
+    the model: one torch.randint per level unless `start` injects them."""
+
+    @staticmethod
+    def _check_model(model) -> None:
+        from models.pointnet_pp_cls import PointNetPlusPlusCls
+        if not isinstance(model, PointNetPlusPlusCls):
+            raise TypeError(f"ClsPredictor takes a PointNetPlusPlusCls, not {type(model).__name__}")
+
+    def __init__(self, model: nn.Module):
+        super().__init__(model)
+        self.plan["fc3"] = self.last_plan["fc3"] = "fused"
+
+    @torch.no_grad()
+    def __call__(self, x: torch.Tensor, start=None):
+        ops._need_gpu(x, "x")
+        with torch.cuda.device(self.device):
+            xyz, points = self.model.split_input(x)
+            s1, s2 = start if start is not None else (None, None)
+            sa1, sa2 = self._levels[0], self._levels[1]
+            l1_xyz, l1_pts = self._level(0, xyz, points, sa1._centres(xyz, s1))
+            l2_xyz, l2_pts = self._level(1, l1_xyz, l1_pts, sa2._centres(l1_xyz, s2))
+            h = self._level(2, l2_xyz, l2_pts)[1].reshape(xyz.size(0), -1)
+            for i in (1, 2):
+                f = self._heads.get(f"fc{i}")
+                if f is not None:
+                    h = ops.fc_block(h, f, None, relu=True, training=False)
+                else:
+                    h = ops.fc_block(h, self._snap[f"fc{i}"], self._snap[f"bn{i}"], relu=True, training=False)
+            return ops.linear_log_softmax(h, self._snap["fc3"])

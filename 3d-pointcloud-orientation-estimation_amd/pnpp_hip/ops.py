@@ -845,6 +845,73 @@ def soft_ce(logits, p_target):
     return _SoftCE.apply(logits, p_target)
 
 
+class _LogSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _f32(x, "x")
+        if x.dim() != 2:
+            raise ValueError(f"log_softmax takes (M, C) rows, got {tuple(x.shape)}")
+        M, Cc = x.shape
+        y = torch.empty_like(x)
+        L.check(L.lib().pnpp_log_softmax(x.data_ptr(), M, Cc, y.data_ptr(), _stream()))
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        dy = _f32(dy, "dy")
+        dx = torch.empty_like(y)
+        L.check(L.lib().pnpp_log_softmax_bwd(y.data_ptr(), dy.data_ptr(), y.shape[0], y.shape[1], dx.data_ptr(), _stream()))
+        return dx
+
+
+def log_softmax(x):
+    """F.log_softmax(x, dim=1) of (M, C) rows (PointNet++Demo.py:234)."""
+    return _LogSoftmax.apply(x)
+
+
+class _NllLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logp, target, check):
+        logp = _f32(logp, "logp")
+        target = _i32(target, "target")
+        if logp.dim() != 2 or target.shape != (logp.shape[0],):
+            raise ValueError(f"nll_loss takes logp (M, C) and target (M,), got {tuple(logp.shape)} and {tuple(target.shape)}")
+        M, Cc = logp.shape
+        loss = torch.empty((), device=logp.device, dtype=torch.float32)
+        bad = torch.empty(1, device=logp.device, dtype=torch.int32)
+        L.check(L.lib().pnpp_nll_loss(logp.data_ptr(), target.data_ptr(), M, Cc, loss.data_ptr(), bad.data_ptr(), int(check), _stream()))
+        ctx.save_for_backward(target)
+        ctx.C = Cc
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (target,) = ctx.saved_tensors
+        g = _f32(g, "grad")
+        M = target.shape[0]
+        dlogp = torch.empty(M, ctx.C, device=target.device, dtype=torch.float32)
+        L.check(L.lib().pnpp_nll_loss_bwd(target.data_ptr(), g.data_ptr(), M, ctx.C, dlogp.data_ptr(), _stream()))
+        return dlogp, None, None
+
+
+def nll_loss(logp, target, check: bool = True):
+    """F.nll_loss(logp, target) with the default mean reduction (PointNet++Demo.py:244); there is no ignore_index.  A target outside
+    [0, C) raises RuntimeError (PNPP_ERR_RANGE): the targets live on the device, so the call waits for the stream to read the kernel's
+    count.  check=False skips the wait (stream capture); such a target then adds nothing to the sum and gets no gradient."""
+    return _NllLoss.apply(logp, target, check)
+
+
+def linear_log_softmax(x, linear):
+    """log_softmax(linear(x), dim=1) as one launch, forward only (the tail of the classifier's Predictor)."""
+    x, w, b = _f32(x, "x"), _f32(linear.weight, "weight"), _f32(linear.bias, "bias")
+    M, K = x.shape
+    y = torch.empty(M, w.shape[0], device=x.device, dtype=torch.float32)
+    L.check(L.lib().pnpp_linear_log_softmax(x.data_ptr(), w.data_ptr(), b.data_ptr(), M, K, w.shape[0], y.data_ptr(), _stream()))
+    return y
+
+
 # ------------------------------------------------------------------------------------------------
 # direction-vector heads and losses of the other set-abstraction models (SURVEY section 8 f-3)
 # ------------------------------------------------------------------------------------------------

@@ -313,6 +313,21 @@ int pnpp_mvm_head_bwd(const float *pi_raw, const float *mu_raw, const float *kap
 /* train_8dir_KL.py:60-68: loss_vec[b] = -sum p * log_softmax(logits); dlogits = softmax*sum(p) - p. */
 int pnpp_soft_ce(const float *logits, const float *p, int B, int C, float *loss_vec, float *dlogits, void *stream);
 
+/* Classification head of PointNet++Demo.py (csrc/cls_loss_kernels.hip; additive to ABI 5).  One wave per row, any C; the row maximum
+ * and the sums are wave reductions, sums in float64.
+ * PointNet++Demo.py:234 F.log_softmax(x, dim=1): y (M,C) = x - logsumexp(x, 1);  backward dx = dy - exp(y) * sum_c dy. */
+int pnpp_log_softmax(const float *x, int M, int C, float *y, void *stream);
+int pnpp_log_softmax_bwd(const float *y, const float *dy, int M, int C, float *dx, void *stream);
+/* forward-only tail of the classifier's Predictor, one launch: y (M,C) = log_softmax(x (M,K) w (C,K)^T + b), C <= 1024 */
+int pnpp_linear_log_softmax(const float *x, const float *w, const float *b, int M, int K, int C, float *y, void *stream);
+/* PointNet++Demo.py:244 F.nll_loss(pred, target) with its default mean reduction: loss_mean[0] = -(1/M) sum_m logp[m, target[m]].
+ * target (M) int32 on the device.  A target outside [0, C) adds nothing to the sum and is counted in bad_targets[0] (device int32,
+ * always written); there is no ignore_index.  check != 0: the call waits for the stream, reads the count and returns PNPP_ERR_RANGE
+ * when it is not zero; check == 0 leaves reading it to the caller (stream capture).  Nothing in the kernel can abort the process.
+ * Backward: dlogp (M,C) = -grad_loss[0] / M at the target's column, 0 elsewhere; grad_loss is a device scalar. */
+int pnpp_nll_loss(const float *logp, const int32_t *target, int M, int C, float *loss_mean, int32_t *bad_targets, int check, void *stream);
+int pnpp_nll_loss_bwd(const int32_t *target, const float *grad_loss, int M, int C, float *dlogp, void *stream);
+
 /* Heads and losses of the other set-abstraction models.
  * models/pointnet_pp_Fwd.py:98, models/Pointnet_pp_xyz.py:84-85, models/Pointnet_pp_xyz_Schedmit.py:87-88:
  * F.normalize(x, p=2, dim=1, eps): y[m,:] = x[m,:] / max(||x[m,:]||, eps); x, y (M,C), C <= 64. */
@@ -502,7 +517,8 @@ int pnpp_pn_bn_relu_bwd(const float *x, const float *y, const float *dy, int M, 
  * `saved` and no `scratch`: pnpp_sa_forward with training = 0 remains the differentiable eval path and the path for every other shape.
  *
  * Shapes the fused kernel takes (pnpp_sa_infer_supported answers for a descriptor; d->training and d->momentum are ignored):
- *   L == 3;  every C[l] a multiple of 32, at most 1024;  K == 16 or K == 32 (group_all: N == 16 or N == 32);  D <= 1021;
+ *   L == 3;  every C[l] a multiple of 32, at most 1024;  K == 16 or a multiple of 32 up to 256 (group_all: N likewise);  D <= 1021;
+ *   (K > 32: a workgroup owns one neighbourhood and walks it in 32-row tiles, the running column maximum stays in registers);
  *   a 32-row tile of widths max(round16(D+3), C[1]) + 8 and C[0] + 8, three bfloat16 planes each, must fit 160 KiB of LDS;  any B, N, S within int32 sizes.
  * float32 products formed on the bf16 matrix pipe from exact three-way operand splits (the arithmetic pnpp_set_split_products(1)
  * describes: float32 results to float32 rounding, same parity gates) whatever pnpp_set_matmul_precision / pnpp_set_split_products say;
