@@ -64,11 +64,11 @@ attention_infer_kernel(const float *__restrict__ qkv, int N, int Nv, int H, floa
         const float4 *qp = reinterpret_cast<const float4 *>(base + (size_t)q * ld + h * AI_DH + 8 * lh);
         const float4 a = qp[0], c = qp[1];
         unsigned ph[4], pm[4], pl[4];
-        i3_split2(a.x * 0.25f, a.y * 0.25f, ph[0], pm[0], pl[0]);
-        i3_split2(a.z * 0.25f, a.w * 0.25f, ph[1], pm[1], pl[1]);
-        i3_split2(c.x * 0.25f, c.y * 0.25f, ph[2], pm[2], pl[2]);
-        i3_split2(c.z * 0.25f, c.w * 0.25f, ph[3], pm[3], pl[3]);
-        qh = i3_frag(ph), qm = i3_frag(pm), ql = i3_frag(pl);
+        sp_split2(a.x * 0.25f, a.y * 0.25f, ph[0], pm[0], pl[0]);
+        sp_split2(a.z * 0.25f, a.w * 0.25f, ph[1], pm[1], pl[1]);
+        sp_split2(c.x * 0.25f, c.y * 0.25f, ph[2], pm[2], pl[2]);
+        sp_split2(c.z * 0.25f, c.w * 0.25f, ph[3], pm[3], pl[3]);
+        qh = sp_frag(ph), qm = sp_frag(pm), ql = sp_frag(pl);
     }
 
     // staging map.  K: thread = (key, four dims), one float4.  V: thread = (dim, four consecutive keys), so that the split leaves a
@@ -89,12 +89,12 @@ attention_infer_kernel(const float *__restrict__ qkv, int N, int Nv, int H, floa
     };
     auto put = [&](int buf) {
         unsigned a[3], c[3];
-        i3_split2(kf.x, kf.y, a[0], a[1], a[2]);
-        i3_split2(kf.z, kf.w, c[0], c[1], c[2]);
+        sp_split2(kf.x, kf.y, a[0], a[1], a[2]);
+        sp_split2(kf.z, kf.w, c[0], c[1], c[2]);
 #pragma unroll
         for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2 *>(&Ks[buf][p][k_dst]) = make_uint2(a[p], c[p]);
-        i3_split2(vf[0], vf[1], a[0], a[1], a[2]);
-        i3_split2(vf[2], vf[3], c[0], c[1], c[2]);
+        sp_split2(vf[0], vf[1], a[0], a[1], a[2]);
+        sp_split2(vf[2], vf[3], c[0], c[1], c[2]);
 #pragma unroll
         for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2 *>(&Vs[buf][p][v_dst]) = make_uint2(a[p], c[p]);
     };
@@ -152,8 +152,8 @@ attention_infer_kernel(const float *__restrict__ qkv, int N, int Nv, int H, floa
             for (int u = 0; u < 2; ++u) {
                 unsigned ph[4], pm[4], pl[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) i3_split2(s[8 * u + 2 * i], s[8 * u + 2 * i + 1], ph[i], pm[i], pl[i]);
-                const bf16x8 bh = i3_frag(ph), bm = i3_frag(pm), bl = i3_frag(pl);
+                for (int i = 0; i < 4; ++i) sp_split2(s[8 * u + 2 * i], s[8 * u + 2 * i + 1], ph[i], pm[i], pl[i]);
+                const bf16x8 bh = sp_frag(ph), bm = sp_frag(pm), bl = sp_frag(pl);
                 const unsigned short *vp = &Vs[buf][0][l31 * AI_VP + (2 * t + u) * 16 + lh * 8];
                 const bf16x8 vh = *reinterpret_cast<const bf16x8 *>(vp), vm = *reinterpret_cast<const bf16x8 *>(vp + AI_VPLANE),
                              vl = *reinterpret_cast<const bf16x8 *>(vp + 2 * AI_VPLANE);

@@ -24,6 +24,7 @@
 // each) into a small [64 k][8 chunks] image of the same form, so that every wave can contract over all 64 rows of the
 // tile and a wave owns whole dW tiles (half as many accumulators as with per-half partial sums, one partial per worker).
 #include "kernels.h"
+#include "split_prims.h"
 
 namespace pnpp {
 
@@ -38,16 +39,7 @@ int matmul_precision() {
 }
 void set_matmul_precision(int bf16) { g_matmul_bf16 = bf16 ? 1 : 0; }
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pk_bf16(float lo, float hi) {  // two floats -> one dword of two bf16, round to nearest even
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ uint2 pk4_bf16(float a, float b, float c, float d) { return make_uint2(pk_bf16(a, b), pk_bf16(c, d)); }
-__device__ __forceinline__ bf16x8 as_bf16x8(uint4 v) { return __builtin_bit_cast(bf16x8, v); }
+__device__ __forceinline__ uint2 pk4_bf16(float a, float b, float c, float d) { return make_uint2(sp_pk(a, b), sp_pk(c, d)); }
 
 template <int KD, int AMODE, int EMODE, bool FDW>
 __global__ void __launch_bounds__(256, (KD >= 256 ? 1 : 2))  // K = 256: the three images fill the LDS, one workgroup per CU anyway
@@ -249,17 +241,17 @@ gemm_wsb_kernel(const AOperand A, const BOperand B, int M, int Nout, int ncol, c
                 if constexpr (KD == 256) {
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const uint4 pk = make_uint4(pk_bf16(v[8 * h + 0][e], v[8 * h + 1][e]), pk_bf16(v[8 * h + 2][e], v[8 * h + 3][e]),
-                                                    pk_bf16(v[8 * h + 4][e], v[8 * h + 5][e]), pk_bf16(v[8 * h + 6][e], v[8 * h + 7][e]));
+                        const uint4 pk = make_uint4(sp_pk(v[8 * h + 0][e], v[8 * h + 1][e]), sp_pk(v[8 * h + 2][e], v[8 * h + 3][e]),
+                                                    sp_pk(v[8 * h + 4][e], v[8 * h + 5][e]), sp_pk(v[8 * h + 6][e], v[8 * h + 7][e]));
                         *reinterpret_cast<uint4 *>(crow + 16 * ((4 * h + rho) ^ swzT(c))) = pk;
                     }
                 } else if constexpr (KD == 128) {
-                    const uint4 pk = make_uint4(pk_bf16(v[0][e], v[1][e]), pk_bf16(v[2][e], v[3][e]), pk_bf16(v[4][e], v[5][e]),
-                                                pk_bf16(v[6][e], v[7][e]));
+                    const uint4 pk = make_uint4(sp_pk(v[0][e], v[1][e]), sp_pk(v[2][e], v[3][e]), sp_pk(v[4][e], v[5][e]),
+                                                sp_pk(v[6][e], v[7][e]));
                     *reinterpret_cast<uint4 *>(crow + 16 * ((4 * hq + rho) ^ swzT(c))) = pk;
                 } else {  // four rows = half a chunk
                     *reinterpret_cast<uint2 *>(crow + 16 * ((4 * hq + rho) ^ swzT(c)) + 2 * j0) =
-                        make_uint2(pk_bf16(v[0][e], v[1][e]), pk_bf16(v[2][e], v[3][e]));
+                        make_uint2(sp_pk(v[0][e], v[1][e]), sp_pk(v[2][e], v[3][e]));
                 }
             }
         }
@@ -280,7 +272,7 @@ gemm_wsb_kernel(const AOperand A, const BOperand B, int M, int Nout, int ncol, c
 #pragma unroll
             for (int st = 0; st < KD / 16; ++st) {
                 if (st + 1 < KD / 16) ld((st + 1) & 1, st + 1);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ra[st & 1]), as_bf16x8(rb[st & 1]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_op(ra[st & 1]), sp_op(rb[st & 1]), acc, 0, 0, 0);
             }
         }
 
@@ -319,8 +311,8 @@ gemm_wsb_kernel(const AOperand A, const BOperand B, int M, int Nout, int ncol, c
 #pragma unroll
                 for (int s = 0; s < 2; ++s)
                     *reinterpret_cast<uint4 *>(krow + 16 * ((4 * wm + 2 * s + lh) ^ kx)) =
-                        make_uint4(pk_bf16(av[8 * s + 0], av[8 * s + 1]), pk_bf16(av[8 * s + 2], av[8 * s + 3]),
-                                   pk_bf16(av[8 * s + 4], av[8 * s + 5]), pk_bf16(av[8 * s + 6], av[8 * s + 7]));
+                        make_uint4(sp_pk(av[8 * s + 0], av[8 * s + 1]), sp_pk(av[8 * s + 2], av[8 * s + 3]),
+                                   sp_pk(av[8 * s + 4], av[8 * s + 5]), sp_pk(av[8 * s + 6], av[8 * s + 7]));
             }
             __syncthreads();
             // dW[c][k] += sum over the tile's 64 rows of dZ[row][c] a[row][k]: step p = 2 h + s contracts the 16 rows
@@ -341,7 +333,7 @@ gemm_wsb_kernel(const AOperand A, const BOperand B, int M, int Nout, int ncol, c
 #pragma unroll
                 for (int p2 = 0; p2 < 4; ++p2) {
                     const uint4 aop = *reinterpret_cast<const uint4 *>(crow + 16 * ((4 * (p2 >> 1) + 2 * (p2 & 1) + lh) ^ cx));
-                    dwacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(aop), as_bf16x8(bop[p2]), dwacc[t], 0, 0, 0);
+                    dwacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_op(aop), sp_op(bop[p2]), dwacc[t], 0, 0, 0);
                 }
             }
         }

@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "kernels.h"
+#include "split_prims.h"
 
 namespace pnpp {
 
@@ -377,22 +378,6 @@ __device__ unsigned long long g_mid3_stamps[2][4];   // [stager, multiplier][pro
 constexpr int MID3_PLANE = MID_T * 128, MID3_IMG = 3 * MID3_PLANE, MID3_STAGE = 2 * MID3_IMG;   // bytes: plane, image (A or W), stage
 constexpr size_t MID3_LDS_BYTES = (size_t)2 * MID3_STAGE;                                    // two stages: 98,304 bytes
 
-typedef __bf16 mid3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 mid3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float mid3_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned mid3_pk(float lo, float hi) {
-    const mid3_f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, mid3_bf16x2));
-}
-__device__ __forceinline__ void mid3_split4(const f32x4 v, uint2 &h, uint2 &m, uint2 &l) {
-    h.x = mid3_pk(v[0], v[1]), h.y = mid3_pk(v[2], v[3]);
-    float r0 = v[0] - __uint_as_float(h.x << 16), r1 = v[1] - __uint_as_float(h.x & 0xffff0000u);
-    float r2 = v[2] - __uint_as_float(h.y << 16), r3 = v[3] - __uint_as_float(h.y & 0xffff0000u);
-    m.x = mid3_pk(r0, r1), m.y = mid3_pk(r2, r3);
-    r0 -= __uint_as_float(m.x << 16), r1 -= __uint_as_float(m.x & 0xffff0000u), r2 -= __uint_as_float(m.y << 16), r3 -= __uint_as_float(m.y & 0xffff0000u);
-    l.x = mid3_pk(r0, r1), l.y = mid3_pk(r2, r3);
-}
-__device__ __forceinline__ mid3_bf16x8 mid3_op(uint4 v) { return __builtin_bit_cast(mid3_bf16x8, v); }
 __device__ __forceinline__ void mid3_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }   // LDS only: no vmcnt wait
 
 template <int AX, int EM>
@@ -404,7 +389,6 @@ __global__ void __launch_bounds__(512, 1) gemm_mid3_kernel(const MidGemm G, int 
     const int l31 = lane & 31, lh = lane >> 5;
     const int m0 = tm * MID_T, n0 = tn * MID_T, nc = G.K / MID_T;
     const Epilogue &E = G.E;
-    auto xs = [](int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); };   // group XOR of image row r (bits 1-3 of r)
     const bool stager = wave >= 4;
     const int wm = (wave >> 1) & 1, wn = wave & 1;   // multipliers: the wave's 32 x 32 tile
     f32x16 acc, accs;
@@ -420,7 +404,7 @@ __global__ void __launch_bounds__(512, 1) gemm_mid3_kernel(const MidGemm G, int 
         const int t2 = tid - 256, q = t2 & 15, q4 = 4 * q, rb = t2 >> 4;   // k group 4 q .. + 3 of the chunk, rows rb + 16 i
         const __amdgpu_buffer_rsrc_t resA = mid_rsrc(G.a + (size_t)m0 * G.lda), resW = mid_rsrc(G.b + (size_t)n0 * G.ldb);
         const unsigned oa = 4u * ((unsigned)rb * (unsigned)G.lda + (unsigned)q4), ow = 4u * ((unsigned)rb * (unsigned)G.ldb + (unsigned)q4);
-        const unsigned wofs = (unsigned)(rb * 128 + 16 * ((q >> 1) ^ xs(rb)) + 8 * (q & 1));   // row rb + 16 i: + 2048 i (x ignores bit 4)
+        const unsigned wofs = (unsigned)(rb * 128 + 16 * ((q >> 1) ^ sp_swz_row(rb)) + 8 * (q & 1));   // row rb + 16 i: + 2048 i (x ignores bit 4)
         // four register sets, by chunk index mod 4, named apart (a set indexed by c & 3 would live in private memory): a chunk is requested
         // four chunk times before it is staged -- with two sets the loop ran at the L2 round trip per chunk (13.8 us for 8 chunks)
         f32x4 ra0[4], rw0[4], ra1[4], rw1[4], ra2[4], rw2[4], ra3[4], rw3[4];
@@ -446,10 +430,10 @@ __global__ void __launch_bounds__(512, 1) gemm_mid3_kernel(const MidGemm G, int 
                     for (int u = 0; u < 4; ++u) v[u] = fmaxf(fmaf(v[u], sc[u], sh[u]), 0.f);
                 }
                 uint2 h, m, l;
-                mid3_split4(v, h, m, l);
+                sp_split4(v, h, m, l);
                 unsigned char *d = As + wofs + i * 2048;
                 *reinterpret_cast<uint2 *>(d) = h, *reinterpret_cast<uint2 *>(d + MID3_PLANE) = m, *reinterpret_cast<uint2 *>(d + 2 * MID3_PLANE) = l;
-                mid3_split4(rw[i], h, m, l);
+                sp_split4(rw[i], h, m, l);
                 d = Ws + wofs + i * 2048;
                 *reinterpret_cast<uint2 *>(d) = h, *reinterpret_cast<uint2 *>(d + MID3_PLANE) = m, *reinterpret_cast<uint2 *>(d + 2 * MID3_PLANE) = l;
             }
@@ -493,7 +477,7 @@ __global__ void __launch_bounds__(512, 1) gemm_mid3_kernel(const MidGemm G, int 
         pass(nc - 4, false, false);
     } else {
         const unsigned arow = (unsigned)((wm * 32 + l31) * 128), brow = (unsigned)((wn * 32 + l31) * 128);
-        const int ax = xs(l31);   // rows 32 wm + l31 and 32 wn + l31: x ignores bits 4, 5
+        const int ax = sp_swz_row(l31);   // rows 32 wm + l31 and 32 wn + l31: x ignores bits 4, 5
         M3_STAMP(0)
         mid3_barrier();   // stage 0 is complete
         M3_STAMP(2)
@@ -509,8 +493,8 @@ __global__ void __launch_bounds__(512, 1) gemm_mid3_kernel(const MidGemm G, int 
                 }
             };
             auto mm = [&](int buf) {
-                const mid3_bf16x8 ah = mid3_op(fa[buf][0]), am = mid3_op(fa[buf][1]), al = mid3_op(fa[buf][2]);
-                const mid3_bf16x8 bh = mid3_op(fb[buf][0]), bm = mid3_op(fb[buf][1]), bl = mid3_op(fb[buf][2]);
+                const bf16x8 ah = sp_op(fa[buf][0]), am = sp_op(fa[buf][1]), al = sp_op(fa[buf][2]);
+                const bf16x8 bh = sp_op(fb[buf][0]), bm = sp_op(fb[buf][1]), bl = sp_op(fb[buf][2]);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
                 accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, accs, 0, 0, 0);
                 accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, accs, 0, 0, 0);

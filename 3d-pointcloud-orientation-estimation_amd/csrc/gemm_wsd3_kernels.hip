@@ -1,5 +1,5 @@
 // gemm_wsd3_kernels.hip -- the fused backward products of the grouped levels (dA + ReLU mask + BatchNorm-backward sums + dW in one
-// launch) with the float32 products formed on the bf16 matrix pipe from exact three-way operand splits (gemm_wsf3_kernels.hip has the
+// launch) with the float32 products formed on the bf16 matrix pipe from exact three-way operand splits (split_prims.h has the
 // arithmetic), as a PAIR of waves per 32-row strip on one SIMD: a producer that builds dZ and a consumer that multiplies.
 //
 // Reference: the autograd backward of conv -> BatchNorm -> ReLU (-> max over the 32 neighbours) (models/pointnet_pp_8dir.py:40-42):
@@ -33,48 +33,16 @@
 //   K = 256 (SA2's last layer 256 -> 128): no LDS is left for the hand-off, both waves build the activation fragments.  Stamps: P 54 k
 //     ticks, C 57 k per launch -- balanced.  (A first arrangement for K = 256 had P multiply dA and run the epilogue and C hold all of
 //     dW: P was the critical path, C waited 48 %: 37.4 against 34.6 us on one box.)
-// Image layout: 16-byte group g of row r at g ^ x(r), x(r) = 4 bit1(r) + bits3:2(r): conflict-free for the row reads (the four
-// 16-lane groups of a ds_read_b128 see eight different x per row parity) and for the transposed reads (rows r and r + 2 of a block
-// differ in x's bit 2).  Addresses: ONE lane-offset register per stream, everything uniform in the instructions' scalar offsets -- a
+// Image layout: 16-byte group g of row r at g ^ sp_swz_row(r) (split_prims.h: conflict-free for the row reads and for the transposed
+// reads).  Addresses: ONE lane-offset register per stream, everything uniform in the instructions' scalar offsets -- a
 // spilled address register is reloaded behind s_waitcnt vmcnt(0) and serialises every load behind it (measured: 74 % of a wave's time).
 #include <stdlib.h>
 
 #include "kernels.h"
+#include "split_prims.h"
 
 namespace pnpp {
 
-typedef __bf16 wd3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wd3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float wd3_f32x2 __attribute__((ext_vector_type(2)));
-typedef short wd3_s16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned wd3_pk(float lo, float hi) {
-    const wd3_f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, wd3_bf16x2));
-}
-__device__ __forceinline__ float wd3_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float wd3_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ void wd3_split4(const f32x4 v, uint2 &h, uint2 &m, uint2 &l) {
-    h.x = wd3_pk(v[0], v[1]), h.y = wd3_pk(v[2], v[3]);
-    float r0 = v[0] - wd3_lo(h.x), r1 = v[1] - wd3_hi(h.x), r2 = v[2] - wd3_lo(h.y), r3 = v[3] - wd3_hi(h.y);
-    m.x = wd3_pk(r0, r1), m.y = wd3_pk(r2, r3);
-    r0 -= wd3_lo(m.x), r1 -= wd3_hi(m.x), r2 -= wd3_lo(m.y), r3 -= wd3_hi(m.y);
-    l.x = wd3_pk(r0, r1), l.y = wd3_pk(r2, r3);
-}
-__device__ __forceinline__ wd3_bf16x8 wd3_op(uint4 v) { return __builtin_bit_cast(wd3_bf16x8, v); }
-__device__ __forceinline__ uint2 wd3_tr(const unsigned char *p) {   // ds_read_b64_tr_b16: 4 rows x 16 columns per 16 lanes, transposed
-    const wd3_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wd3_s16x4 *)(p));
-    return __builtin_bit_cast(uint2, v);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wd3_rsrc(const void *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, 0xfffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 wd3_load4(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, (int)s_off, 0));
-}
-__device__ __forceinline__ float wd3_load1(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)lane_off, (int)s_off, 0));
-}
 typedef __attribute__((address_space(3))) volatile unsigned wd3_flag;   // a counter in LDS (ds_read_b32 / ds_write_b32, never flat)
 __device__ int g_wsd3_timeouts;   // set by a poll that gave up (pnpp_debug_wsd3_timeouts)
 // waits until *f >= target (f: an LDS counter that only grows); false after 2^16 polls (a few milliseconds: a legitimate wait is
@@ -149,7 +117,6 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
     uint4 *Bf = reinterpret_cast<uint4 *>(lds3 + OFF_BFR + pair * BFR) + lane;   // this lane's slots: Bf[(2 step + piece... ) * 64]
     wd3_flag *f_ready = (wd3_flag *)(lds3 + OFF_FLG) + 2 * pair, *f_done = f_ready + 1;
     const int l31 = lane & 31, lh = lane >> 5;
-    auto xs = [](int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); };   // chunk XOR of image row r
     auto xw = [](int n) { return n & 15; };                                  // chunk XOR of panel row n
 
     const int nworkers = gridDim.x / ncol;
@@ -161,8 +128,8 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
     const int n0 = col_blk * BN;
     const int nstrips = M / 32, stride = nworkers * 4;
     int strip = worker * 4 + pair;
-    const __amdgpu_buffer_rsrc_t resNull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A.z), (short)0, 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t resP = wd3_rsrc(E.zp);
+    const __amdgpu_buffer_rsrc_t resNull = sp_buf_rsrc_null(A.z);
+    const __amdgpu_buffer_rsrc_t resP = sp_buf_rsrc(E.zp);
     // accumulator positions of a strip of layer l-1 (z_{l-1} in, dY_{l-1} out): row 4 lh + (r & 3) + 8 (r >> 2), column n0 + l31; the
     // lane part is ONE register, the register part is uniform and rides in the instruction's scalar offset
     const unsigned oq = 4u * ((unsigned)(4 * lh) * (unsigned)Nout + (unsigned)(n0 + l31));
@@ -177,7 +144,7 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             const int r = 8 * b + 4 * lh + qq, ch = 2 * g1 + (pp >> 1);
-            tbase[b] = (unsigned)(r * 128 + 16 * (ch ^ xs(r)) + 8 * (pp & 1));
+            tbase[b] = (unsigned)(r * 128 + 16 * (ch ^ sp_swz_row(r)) + 8 * (pp & 1));
         }
     }
     auto tofs = [&](int it, int s, int b) -> unsigned { return (tbase[b] ^ (unsigned)(it * 64)) + (unsigned)(s * 2048); };
@@ -193,8 +160,8 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
             v0[0] = act[8 * s + 0], v0[1] = act[8 * s + 1], v0[2] = act[8 * s + 2], v0[3] = act[8 * s + 3];
             v1[0] = act[8 * s + 4], v1[1] = act[8 * s + 5], v1[2] = act[8 * s + 6], v1[3] = act[8 * s + 7];
             uint2 h0, m0, l0, h1, m1, l1;
-            wd3_split4(v0, h0, m0, l0);
-            wd3_split4(v1, h1, m1, l1);
+            sp_split4(v0, h0, m0, l0);
+            sp_split4(v1, h1, m1, l1);
             bfr[s][0] = make_uint4(h0.x, h0.y, h1.x, h1.y);
             bfr[s][1] = make_uint4(m0.x, m0.y, m1.x, m1.y);
             bfr[s][2] = make_uint4(l0.x, l0.y, l1.x, l1.y);
@@ -207,12 +174,12 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
             uint4 ta[3];
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
-                const uint2 lo = wd3_tr(Ab + p * APLANE + tofs(it, s, 0)), hi = wd3_tr(Ab + p * APLANE + tofs(it, s, 1));
+                const uint2 lo = sp_tr_b64(Ab + p * APLANE + tofs(it, s, 0)), hi = sp_tr_b64(Ab + p * APLANE + tofs(it, s, 1));
                 ta[p] = make_uint4(lo.x, lo.y, hi.x, hi.y);
             }
             if (s == 1) last();
-            const wd3_bf16x8 ah = wd3_op(ta[0]), am = wd3_op(ta[1]), al = wd3_op(ta[2]);
-            const wd3_bf16x8 bh = wd3_op(bfr[s][0]), bm = wd3_op(bfr[s][1]), bl = wd3_op(bfr[s][2]);
+            const bf16x8 ah = sp_op(ta[0]), am = sp_op(ta[1]), al = sp_op(ta[2]);
+            const bf16x8 bh = sp_op(bfr[s][0]), bm = sp_op(bfr[s][1]), bl = sp_op(bfr[s][2]);
             f32x16 d = DW2 ? dwsm : dwl;   // the small products first, the leading one last
             d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, d, 0, 0, 0);
             d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, d, 0, 0, 0);
@@ -249,7 +216,7 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
         for (int j = 0; j < NWF; ++j) {
             const int f = tid + 512 * j, nl = f % BN, k4 = 4 * (f / BN);
             uint2 h, m, l;
-            wd3_split4(tw[j], h, m, l);
+            sp_split4(tw[j], h, m, l);
             unsigned char *dst = Wp + nl * WPITCH + 16 * ((k4 >> 3) ^ xw(nl)) + 2 * (k4 & 7);
             *reinterpret_cast<uint2 *>(dst) = h;
             *reinterpret_cast<uint2 *>(dst + WPLANE) = m;
@@ -271,7 +238,7 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
     if (producer) {
         // =========================== P: the dZ image, nothing else (vector work only) ===========================
         const int q = lane & 15, q4 = 4 * q, rb = lane >> 4;   // staging map: channels 64 c + 4 q .. + 3, rows rb + 4 i
-        const __amdgpu_buffer_rsrc_t resZ = wd3_rsrc(A.z), resY = wd3_rsrc(A.a), resI = wd3_rsrc(A.arg);
+        const __amdgpu_buffer_rsrc_t resZ = sp_buf_rsrc(A.z), resY = sp_buf_rsrc(A.a), resI = sp_buf_rsrc(A.arg);
         const unsigned oa0 = 4u * ((unsigned)rb * (unsigned)KD + (unsigned)q4);
         f32x4 rz[2][8], ry[AM == A_DZ ? 2 : 1][8], rdm[2];   // two chunk register sets in flight (A_DZ: the dense gradient beside Z)
         int4 rarg[2];
@@ -280,13 +247,13 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
             const unsigned so = (unsigned)s * (32u * KD * 4u) + 256u * (unsigned)c;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                rz[c & 1][i] = wd3_load4(rZ, oa0, so + (unsigned)i * (4u * KD * 4u));
-                if constexpr (AM == A_DZ) ry[c & 1][i] = wd3_load4(rY, oa0, so + (unsigned)i * (4u * KD * 4u));
+                rz[c & 1][i] = sp_buf_load4(rZ, oa0, so + (unsigned)i * (4u * KD * 4u));
+                if constexpr (AM == A_DZ) ry[c & 1][i] = sp_buf_load4(rY, oa0, so + (unsigned)i * (4u * KD * 4u));
             }
             if constexpr (AM == A_DZ_POOL) {
                 const unsigned sg = (unsigned)s * (KD * 4u) + 256u * (unsigned)c;   // one row of the pooled tables per strip
-                rdm[c & 1] = wd3_load4(rY, 4u * (unsigned)q4, sg);
-                rarg[c & 1] = __builtin_bit_cast(int4, wd3_load4(rI, 4u * (unsigned)q4, sg));
+                rdm[c & 1] = sp_buf_load4(rY, 4u * (unsigned)q4, sg);
+                rarg[c & 1] = __builtin_bit_cast(int4, sp_buf_load4(rI, 4u * (unsigned)q4, sg));
             }
         };
         float zn[16];   // z_{l-1} of the next strip at this lane's accumulator positions (the consumer's dW operand is built here)
@@ -296,12 +263,12 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
             fetch_chunk(have, strip, 1);
             const __amdgpu_buffer_rsrc_t rP = have ? resP : resNull;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) zn[r] = wd3_load1(rP, oq, (unsigned)strip * (32u * (unsigned)Nout * 4u) + quni(r));
+            for (int r = 0; r < 16; ++r) zn[r] = sp_buf_load1(rP, oq, (unsigned)strip * (32u * (unsigned)Nout * 4u) + quni(r));
         }
         // LDS offsets of this lane inside a chunk-image plane: row rb + 4 i: x(r) = 4 bit1(rb) + (i & 3)
         unsigned wofs[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) wofs[i] = (unsigned)(rb * 128 + 16 * ((q >> 1) ^ (((rb >> 1) & 1) << 2 | i)) + 8 * (q & 1));
+        for (int i = 0; i < 4; ++i) wofs[i] = (unsigned)(rb * 128 + 16 * ((q >> 1) ^ sp_swz_row(rb + 4 * i)) + 8 * (q & 1));
         if constexpr (SPLITDW) {
 #pragma unroll
             for (int i = 0; i < CTC; ++i)
@@ -327,7 +294,7 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
                 const __amdgpu_buffer_rsrc_t nP = more ? resP : resNull;
                 const unsigned sn_off = (unsigned)snext * (32u * (unsigned)Nout * 4u);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) zn[r] = wd3_load1(nP, oq, sn_off + quni(r));
+                for (int r = 0; r < 16; ++r) zn[r] = sp_buf_load1(nP, oq, sn_off + quni(r));
             }
             if constexpr (HANDOFF) {
                 if (kbase >= 2) timed_out = timed_out || !wd3_wait(f_done, kbase - 1);
@@ -365,7 +332,7 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
                 if constexpr (AM == A_DZ_POOL && !SPLITDW) {   // the split goes ahead of the wait for the buffer (48 registers the other forms lack)
                     uint2 ph[8], pm[8], pl[8];
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) wd3_split4(dz4(i), ph[i], pm[i], pl[i]);
+                    for (int i = 0; i < 8; ++i) sp_split4(dz4(i), ph[i], pm[i], pl[i]);
                     WD3_STAMP(0)   // dZ and its pieces
                     // this register set is free: the chunk two ahead goes out
                     if (c + 2 < NC) fetch_chunk(true, strip, c + 2);
@@ -385,7 +352,7 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         uint2 h, m, l;
-                        wd3_split4(dz4(i), h, m, l);
+                        sp_split4(dz4(i), h, m, l);
                         unsigned char *dst = Ab + wofs[i & 3] + i * 512;
                         *reinterpret_cast<uint2 *>(dst) = h;
                         *reinterpret_cast<uint2 *>(dst + APLANE) = m;
@@ -417,18 +384,18 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) dws[i][r] = 0.f;
         }
-        const __amdgpu_buffer_rsrc_t resC = wd3_rsrc(E.c);
+        const __amdgpu_buffer_rsrc_t resC = sp_buf_rsrc(E.c);
         const float e_mu = E.mu[n0 + l31], e_is = E.istd[n0 + l31];
         float zq[16];   // z_{l-1} of the strip: requested at its start, used in its epilogue (mask, sum v z)
         const unsigned arow = (unsigned)(l31 * 128);
-        const int ax = xs(l31);
+        const int ax = sp_swz_row(l31);
         const unsigned char *brow = Wp + l31 * WPITCH;
         const int bx = xw(l31);
         float zn[16];   // (!HANDOFF) the next strip's z_{l-1}: this wave builds its fragments itself
         if constexpr (!HANDOFF) {
             const __amdgpu_buffer_rsrc_t rP = strip < nstrips ? resP : resNull;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) zn[r] = wd3_load1(rP, oq, (unsigned)strip * (32u * (unsigned)Nout * 4u) + quni(r));
+            for (int r = 0; r < 16; ++r) zn[r] = sp_buf_load1(rP, oq, (unsigned)strip * (32u * (unsigned)Nout * 4u) + quni(r));
         }
         unsigned kbase = 0;
         for (; strip < nstrips; strip += stride, kbase += NC) {
@@ -437,14 +404,14 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
             if constexpr (HANDOFF) {   // z_{l-1} is only needed in the epilogue: requested now
                 const unsigned sq_off = (unsigned)strip * (32u * (unsigned)Nout * 4u);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) zq[r] = wd3_load1(resP, oq, sq_off + quni(r));
+                for (int r = 0; r < 16; ++r) zq[r] = sp_buf_load1(resP, oq, sq_off + quni(r));
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) zq[r] = zn[r];
                 const __amdgpu_buffer_rsrc_t nP = more ? resP : resNull;
                 const unsigned sn_off = (unsigned)(strip + stride) * (32u * (unsigned)Nout * 4u);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) zn[r] = wd3_load1(nP, oq, sn_off + quni(r));
+                for (int r = 0; r < 16; ++r) zn[r] = sp_buf_load1(nP, oq, sn_off + quni(r));
                 act_fragments(zq, bfr);
             }
             f32x16 acc, accs;   // dA: the leading products and (ACC2) the small ones, added in the epilogue
@@ -478,8 +445,8 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
                         fa[p] = *reinterpret_cast<const uint4 *>(Ab + p * APLANE + arow + 16 * (g ^ ax));
                         fb[p] = *reinterpret_cast<const uint4 *>(brow + p * WPLANE + 16 * ((8 * c + g) ^ bx));
                     }
-                    const wd3_bf16x8 ah = wd3_op(fa[0]), am = wd3_op(fa[1]), al = wd3_op(fa[2]);
-                    const wd3_bf16x8 bh = wd3_op(fb[0]), bm = wd3_op(fb[1]), bl = wd3_op(fb[2]);
+                    const bf16x8 ah = sp_op(fa[0]), am = sp_op(fa[1]), al = sp_op(fa[2]);
+                    const bf16x8 bh = sp_op(fb[0]), bm = sp_op(fb[1]), bl = sp_op(fb[2]);
                     f32x16 d = ACC2 ? accs : acc;   // the small products first, the leading one last
                     d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, d, 0, 0, 0);
                     d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, d, 0, 0, 0);

@@ -1,6 +1,6 @@
 // gemm_wsf03_kernels.hip -- gemm_wsf0_kernel (gemm_wsx_kernels.hip: layer 1's forward product of a grouped level whose layer 0 convolves
 // relative coordinates only, layer 0 rebuilt from the coordinates inside the kernel) with its 64 -> 64 product formed from exact three-way
-// bf16 splits on v_mfma_f32_32x32x16_bf16 (gemm_wsf3_kernels.hip has the arithmetic).
+// bf16 splits on v_mfma_f32_32x32x16_bf16 (split_prims.h has the arithmetic).
 //
 // Reference: models/pointnet_pp_8dir.py:31-41 (grouped_xyz - new_xyz, conv 3 -> 64, BatchNorm, ReLU, conv 64 -> 64).
 //
@@ -17,26 +17,10 @@
 #include <stdlib.h>
 
 #include "kernels.h"
+#include "split_prims.h"
 #include "wsf0_args.h"
 
 namespace pnpp {
-
-typedef __bf16 w03_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 w03_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float w03_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned w03_pk(float lo, float hi) {
-    const w03_f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, w03_bf16x2));
-}
-// two floats -> their three bf16 pieces, packed (lo in the low half)
-__device__ __forceinline__ void w03_split2(float v0, float v1, unsigned &h, unsigned &m, unsigned &l) {
-    h = w03_pk(v0, v1);
-    float r0 = v0 - __uint_as_float(h << 16), r1 = v1 - __uint_as_float(h & 0xffff0000u);
-    m = w03_pk(r0, r1);
-    r0 -= __uint_as_float(m << 16), r1 -= __uint_as_float(m & 0xffff0000u);
-    l = w03_pk(r0, r1);
-}
-__device__ __forceinline__ w03_bf16x8 w03_op(uint4 v) { return __builtin_bit_cast(w03_bf16x8, v); }
 
 constexpr int W03_PLANE = 64 * 128;   // bytes: [64 output channels][64 k] bf16
 
@@ -50,20 +34,19 @@ gemm_wsf03_kernel(const Wsf0Args P) {
     double *Rm = reinterpret_cast<double *>(Tc + 128);                   // [4][16]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
-    auto xs = [](int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); };   // group XOR of image row r (conflict-free ds_read_b128 row reads)
     const int worker = blockIdx.x, nworkers = gridDim.x;
     const int nstrips = P.M / 32, stride = nworkers * 4;
     int strip = worker * 4 + wave;
-    const __amdgpu_buffer_rsrc_t resI = wsx_rsrc(P.idx), resX = wsx_rsrc(P.xyz), resC = wsx_rsrc(P.centres);
-    const __amdgpu_buffer_rsrc_t resNull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.xyz), (short)0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t resI = sp_buf_rsrc(P.idx), resX = sp_buf_rsrc(P.xyz), resC = sp_buf_rsrc(P.centres);
+    const __amdgpu_buffer_rsrc_t resNull = sp_buf_rsrc_null(P.xyz);
     int nidx;
     float px, py, pz, cx, cy, cz;
-    auto fetch_idx = [&](__amdgpu_buffer_rsrc_t rI, int s) { nidx = __builtin_bit_cast(int, wsx_load1(rI, 4u * (unsigned)l31, (unsigned)s * 128u)); };
+    auto fetch_idx = [&](__amdgpu_buffer_rsrc_t rI, int s) { nidx = __builtin_bit_cast(int, sp_buf_load1(rI, 4u * (unsigned)l31, (unsigned)s * 128u)); };
     auto fetch_geo = [&](__amdgpu_buffer_rsrc_t rX, __amdgpu_buffer_rsrc_t rCn, int s) {
         const unsigned cloud = (unsigned)(s / P.S) * (unsigned)P.N * 12u, po = 12u * (unsigned)nidx;
-        px = wsx_load1(rX, po, cloud), py = wsx_load1(rX, po + 4u, cloud), pz = wsx_load1(rX, po + 8u, cloud);
+        px = sp_buf_load1(rX, po, cloud), py = sp_buf_load1(rX, po + 4u, cloud), pz = sp_buf_load1(rX, po + 8u, cloud);
         const unsigned co = (unsigned)s * 12u;
-        cx = wsx_load1(rCn, 0u, co), cy = wsx_load1(rCn, 4u, co), cz = wsx_load1(rCn, 8u, co);
+        cx = sp_buf_load1(rCn, 0u, co), cy = sp_buf_load1(rCn, 4u, co), cz = sp_buf_load1(rCn, 8u, co);
     };
     // ---- prologue: as gemm_wsf0_kernel (everything it reads is requested before its first wait) ----
     const bool have = strip < nstrips;
@@ -131,9 +114,9 @@ gemm_wsf03_kernel(const Wsf0Args P) {
         const int f = tid + 256 * j, nl = f >> 4, kq = f & 15;   // kq = k4 / 4
         const int g = 2 * (kq >> 2) + (kq & 1), sub = (kq >> 1) & 1;
         unsigned h0, m0, l0, h1, m1, l1;
-        w03_split2(tw[j][0], tw[j][1], h0, m0, l0);
-        w03_split2(tw[j][2], tw[j][3], h1, m1, l1);
-        unsigned char *d = Wp + nl * 128 + 16 * (g ^ xs(nl)) + 8 * sub;
+        sp_split2(tw[j][0], tw[j][1], h0, m0, l0);
+        sp_split2(tw[j][2], tw[j][3], h1, m1, l1);
+        unsigned char *d = Wp + nl * 128 + 16 * (g ^ sp_swz_row(nl)) + 8 * sub;
         *reinterpret_cast<uint2 *>(d) = make_uint2(h0, h1);
         *reinterpret_cast<uint2 *>(d + W03_PLANE) = make_uint2(m0, m1);
         *reinterpret_cast<uint2 *>(d + 2 * W03_PLANE) = make_uint2(l0, l1);
@@ -177,7 +160,7 @@ gemm_wsf03_kernel(const Wsf0Args P) {
     }
     double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
     const unsigned char *brow = Wp + l31 * 128;   // output channel 32 jn + l31: + 4096 jn (x ignores bit 5)
-    const int bx = xs(l31);
+    const int bx = sp_swz_row(l31);
     for (; strip < nstrips; strip += stride) {
         const bool more = strip + stride < nstrips;
         const int snext = more ? strip + stride : 0;
@@ -213,13 +196,13 @@ gemm_wsf03_kernel(const Wsf0Args P) {
                     unsigned h[4], m[4], l[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        w03_split2(fmaxf(zt[j][8 * s + 2 * e], 0.f), fmaxf(zt[j][8 * s + 2 * e + 1], 0.f), h[e], m[e], l[e]);
+                        sp_split2(fmaxf(zt[j][8 * s + 2 * e], 0.f), fmaxf(zt[j][8 * s + 2 * e + 1], 0.f), h[e], m[e], l[e]);
                     ah = make_uint4(h[0], h[1], h[2], h[3]), am = make_uint4(m[0], m[1], m[2], m[3]), al = make_uint4(l[0], l[1], l[2], l[3]);
                 }
-                const w03_bf16x8 a_h = w03_op(ah), a_m = w03_op(am), a_l = w03_op(al);
+                const bf16x8 a_h = sp_op(ah), a_m = sp_op(am), a_l = sp_op(al);
 #pragma unroll
                 for (int jn = 0; jn < 2; ++jn) {
-                    const w03_bf16x8 b_h = w03_op(fb[jn][0]), b_m = w03_op(fb[jn][1]), b_l = w03_op(fb[jn][2]);
+                    const bf16x8 b_h = sp_op(fb[jn][0]), b_m = sp_op(fb[jn][1]), b_l = sp_op(fb[jn][2]);
                     acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_h, acc[jn], 0, 0, 0);
                     accs[jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, b_h, accs[jn], 0, 0, 0);
                     accs[jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_l, accs[jn], 0, 0, 0);

@@ -3,20 +3,7 @@
 //
 // Reference: models/pointnet_pp_8dir.py:40-42 (conv -> BatchNorm -> ReLU), float32.
 //
-// Why.  gfx950 has no reduced-width float32 MFMA: v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate (64 FLOP/clk/SIMD), and on the
-// float32 forward kernels the MFMA time and the HBM time ADD.  A float32 number is the exact sum of three
-// bfloat16 numbers (24 significand bits = 8 + 8 + 8; bf16 has float32's exponent range):
-//     a = a_h + a_m + a_l,   a_h = bf16(a),  a_m = bf16(a - a_h),  a_l = a - a_h - a_m   (every subtraction exact, a_l exact in bf16)
-// so  a b = a_h b_h + (a_h b_m + a_m b_h) + (a_h b_l + a_l b_h + a_m b_m) + [a_m b_l + a_l b_m + a_l b_l].
-// The bracket is at most 2^-25 |a b| -- below the rounding of the float32 accumulation itself (2^-24 per addition) -- and is dropped; the
-// six products kept are exact in float32 (8 x 8 significand bits) and are accumulated in float32 by v_mfma_f32_32x32x16_bf16: six
-// instructions of 32 cycles for 16 reduction steps against eight of 64 cycles = 2.67 x the float32 MFMA rate.  The leading products go
-// to one accumulator and the five small ones to a second, added once per strip, so the rounding of the sum is that of a float32
-// accumulation of the leading products.  (Why two accumulators: v_mfma_f32_32x32x16_bf16 aligns its 16 products and the accumulator to
-// the largest exponent among them and drops what lies 2^-26 below it -- tools/mfma_round.hip -- so small addends must not meet the
-// large sum inside the instruction.)  Not a reduced-precision mode: tests/test_gpu_levels_routed.py holds it to the same gates as the
-// float32 MFMA form, and tests/test_gpu_split_products.py measures both against float64.  (Infinities do not survive the split:
-// inf - inf; the float32 form gives inf where this one gives NaN.  Operands below 2^-110 lose their low pieces to underflow.)
+// The arithmetic of the split (why three pieces, which six products, why two accumulators): split_prims.h.
 //
 // Layout.  Per wave 3 planes [32 rows][64 k] bf16 of its strip chunk (128-byte rows, 16-byte groups XOR-swizzled by x(r) = 4 bit1(r) +
 // bits3:2(r): the four 16-lane groups of a ds_read_b128 then touch all 64 banks once); per workgroup 3 planes [64 n][KD] bf16 of the weight panel.
@@ -26,35 +13,9 @@
 #include <stdlib.h>
 
 #include "kernels.h"
+#include "split_prims.h"
 
 namespace pnpp {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned x3_pk(float lo, float hi) {   // two floats -> two bf16 in one dword, round to nearest even
-    const f32x2v v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
-}
-__device__ __forceinline__ float x3_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float x3_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-// four floats -> their three bf16 pieces, four per 8-byte word
-__device__ __forceinline__ void x3_split4(const f32x4 v, uint2 &h, uint2 &m, uint2 &l) {
-    h.x = x3_pk(v[0], v[1]), h.y = x3_pk(v[2], v[3]);
-    float r0 = v[0] - x3_lo(h.x), r1 = v[1] - x3_hi(h.x), r2 = v[2] - x3_lo(h.y), r3 = v[3] - x3_hi(h.y);
-    m.x = x3_pk(r0, r1), m.y = x3_pk(r2, r3);
-    r0 -= x3_lo(m.x), r1 -= x3_hi(m.x), r2 -= x3_lo(m.y), r3 -= x3_hi(m.y);
-    l.x = x3_pk(r0, r1), l.y = x3_pk(r2, r3);
-}
-__device__ __forceinline__ bf16x8 x3_op(uint4 v) { return __builtin_bit_cast(bf16x8, v); }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wsf3_rsrc(const float *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), (short)0, 0xfffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 wsf3_load4(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, (int)s_off, 0));
-}
 
 // KD in {64, 128}; NW waves per workgroup; NT column tiles of 32 per wave; AX = A_PLAIN or A_BNRELU; EM = E_STORE or E_STORE_STATS
 template <int KD, int NW, int NT, int AX, int EM>
@@ -70,8 +31,6 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned char *Ap = lds3 + 3 * WPLANE + wave * ASTRIP;
     const int l31 = lane & 31, lh = lane >> 5;
-    auto swzA = [](int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); };   // x(r) = 4 bit1(r) + bits3:2(r): conflict-free row reads, and row
-                                                                                 // rb + 4 i of the staging map is one register ^ ((i & 3) << 4) + 512 i
     auto swzW = [](int n) { return WCH >= 16 ? (n & 15) : ((n >> 1) & 7); };
 
     // XCD-aware map (as gemm_wsf_kernel): the column blocks of one worker sit on one XCD and share its L2
@@ -107,7 +66,7 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
         for (int j = 0; j < NWF; ++j) {
             const int f = tid + NTHR * j, nl = f / (KD / 4), k4 = 4 * (f % (KD / 4));
             uint2 h, m, l;
-            x3_split4(tw[j], h, m, l);
+            sp_split4(tw[j], h, m, l);
             unsigned char *dst = Wp + nl * WPITCH + 16 * ((k4 >> 3) ^ swzW(nl)) + 2 * (k4 & 7);
             *reinterpret_cast<uint2 *>(dst) = h;
             *reinterpret_cast<uint2 *>(dst + WPLANE) = m;
@@ -118,7 +77,7 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
     // strips: this wave takes strip (worker * NW + wave) + i * (nworkers * NW)
     const int nstrips = M / 32, stride = nworkers * NW;
     int strip = worker * NW + wave;
-    const __amdgpu_buffer_rsrc_t resA = wsf3_rsrc(A);
+    const __amdgpu_buffer_rsrc_t resA = sp_buf_rsrc(A);
     const unsigned oa0 = 4u * ((unsigned)rb * (unsigned)lda + (unsigned)q4);   // rows rb + 4 i: the i part rides in the scalar offset
     f32x4 ra[NC][8];
     auto fetch = [&](int s) {
@@ -126,7 +85,7 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
 #pragma unroll
         for (int c = 0; c < NC; ++c)
 #pragma unroll
-            for (int i = 0; i < 8; ++i) ra[c][i] = wsf3_load4(resA, oa0, so + 256u * (unsigned)c + (unsigned)i * (16u * (unsigned)lda));
+            for (int i = 0; i < 8; ++i) ra[c][i] = sp_buf_load4(resA, oa0, so + 256u * (unsigned)c + (unsigned)i * (16u * (unsigned)lda));
     };
     if (strip < nstrips) fetch(strip);
 
@@ -142,10 +101,11 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
     }
     __syncthreads();   // the weight panel is complete; from here on the waves run on their own
 
-    // this lane's staging slot in a strip plane: row rb + 4 i, 8 bytes at k = q4 (half q & 1 of group q >> 1)
-    const unsigned wofs0 = (unsigned)(rb * 128 + 16 * ((q >> 1) ^ (((rb >> 1) & 1) << 2)) + 8 * (q & 1));   // row rb + 4 i: ^ ((i & 3) << 4), + 512 i
+    // this lane's staging slot in a strip plane: row rb + 4 i, 8 bytes at k = q4 (half q & 1 of group q >> 1).  sp_swz_row(rb + 4 i) =
+    // 4 bit1(rb) | (i & 3) as rb < 4: the i part is applied per store (^ ((i & 3) << 4), + 512 i), the rb part is spelled out here
+    const unsigned wofs0 = (unsigned)(rb * 128 + 16 * ((q >> 1) ^ (((rb >> 1) & 1) << 2)) + 8 * (q & 1));
     const unsigned char *arow = Ap + l31 * 128;
-    const int ax = swzA(l31);
+    const int ax = sp_swz_row(l31);
     const unsigned char *brow[NT];
     int bx[NT];
 #pragma unroll
@@ -169,7 +129,7 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
                 v[2] = fmaxf(fmaf(v[2], sc[c].z, sh[c].z), 0.f), v[3] = fmaxf(fmaf(v[3], sc[c].w, sh[c].w), 0.f);
             }
             uint2 h, m, l;
-            x3_split4(v, h, m, l);
+            sp_split4(v, h, m, l);
             unsigned char *dst = Ap + (wofs0 ^ (unsigned)((i & 3) << 4)) + i * 512;
             *reinterpret_cast<uint2 *>(dst) = h;
             *reinterpret_cast<uint2 *>(dst + APLANE) = m;
@@ -193,8 +153,8 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
         auto mm = [&](int buf) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const bf16x8 ah = x3_op(fa[buf][0]), am = x3_op(fa[buf][1]), al = x3_op(fa[buf][2]);
-                const bf16x8 bh = x3_op(fb[buf][j][0]), bm = x3_op(fb[buf][j][1]), bl = x3_op(fb[buf][j][2]);
+                const bf16x8 ah = sp_op(fa[buf][0]), am = sp_op(fa[buf][1]), al = sp_op(fa[buf][2]);
+                const bf16x8 bh = sp_op(fb[buf][j][0]), bm = sp_op(fb[buf][j][1]), bl = sp_op(fb[buf][j][2]);
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[j], 0, 0, 0);
                 accl[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, accl[j], 0, 0, 0);
                 accl[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, accl[j], 0, 0, 0);

@@ -18,17 +18,11 @@
 #include <stdlib.h>
 
 #include "kernels.h"
+#include "split_prims.h"
 
 namespace pnpp {
 
 typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wsf_rsrc(const float *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), (short)0, 0xfffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 wsf_load4(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, (int)s_off, 0));
-}
 
 #ifndef WSF_EXP   // timing experiments (wrong results): 1 no output stores, 2 no MFMA loop, 4 no operand transform (copy), 8 no statistics / pooling arithmetic
 #define WSF_EXP 0
@@ -102,7 +96,7 @@ gemm_wsf_kernel(const float *__restrict__ A, int lda, const float *__restrict__ 
     // strips: this wave takes strip (worker * 4 + wave) + i * (nworkers * 4)
     const int nstrips = M / 32, stride = nworkers * 4;
     int strip = worker * 4 + wave;
-    const __amdgpu_buffer_rsrc_t resA = wsf_rsrc(A);
+    const __amdgpu_buffer_rsrc_t resA = sp_buf_rsrc(A);
     unsigned oa[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) oa[i] = 4u * ((unsigned)(rb + 4 * i) * (unsigned)lda + (unsigned)q4);
@@ -112,7 +106,7 @@ gemm_wsf_kernel(const float *__restrict__ A, int lda, const float *__restrict__ 
 #pragma unroll
         for (int c = 0; c < NC; ++c)
 #pragma unroll
-            for (int i = 0; i < 8; ++i) ra[c][i] = wsf_load4(resA, oa[i] + 256u * (unsigned)c, so);
+            for (int i = 0; i < 8; ++i) ra[c][i] = sp_buf_load4(resA, oa[i] + 256u * (unsigned)c, so);
     };
     if (strip < nstrips) fetch(strip);
 

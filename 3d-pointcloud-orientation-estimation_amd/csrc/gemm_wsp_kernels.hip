@@ -22,18 +22,9 @@
 #include <stdlib.h>
 
 #include "kernels.h"
+#include "split_prims.h"
 
 namespace pnpp {
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wsp_rsrc(const void *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, 0xfffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 wsp_load4(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, (int)s_off, 0));
-}
-__device__ __forceinline__ float wsp_load1(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)lane_off, (int)s_off, 0));
-}
 
 #ifndef WSP_EXP   // timing experiments (wrong results): 1 no output stores, 2 no dW loop, 4 no dA loop, 8 no epilogue, 16 no staging, 32 no re-fetch
 #define WSP_EXP 0
@@ -97,9 +88,9 @@ gemm_wsp_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, c
     const int q4 = 4 * (lane & 15), rb = lane >> 4;
     const int nstrips = M / 32, stride = nworkers * 4;
     int strip = worker * 4 + wave;
-    const __amdgpu_buffer_rsrc_t resZ = wsp_rsrc(A.z), resY = wsp_rsrc(A.a), resP = wsp_rsrc(E.zp), resI = wsp_rsrc(A.arg);
-    const __amdgpu_buffer_rsrc_t resC = wsp_rsrc(E.c);
-    const __amdgpu_buffer_rsrc_t resNull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A.z), (short)0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t resZ = sp_buf_rsrc(A.z), resY = sp_buf_rsrc(A.a), resP = sp_buf_rsrc(E.zp), resI = sp_buf_rsrc(A.arg);
+    const __amdgpu_buffer_rsrc_t resC = sp_buf_rsrc(E.c);
+    const __amdgpu_buffer_rsrc_t resNull = sp_buf_rsrc_null(A.z);
     unsigned oa[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) oa[i] = 4u * ((unsigned)(rb + 4 * i) * (unsigned)KD + (unsigned)q4);
@@ -115,15 +106,15 @@ gemm_wsp_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, c
     int rarg[NC];
     auto fetch_z = [&](__amdgpu_buffer_rsrc_t rZ, __amdgpu_buffer_rsrc_t rY, int s, int c, int i) {
         const unsigned so = (unsigned)s * (32u * KD * 4u);
-        rz[c][i] = wsp_load4(rZ, oa[i] + 256u * (unsigned)c, so);
-        if constexpr (AM == A_DZ) ry[c][i] = wsp_load4(rY, oa[i] + 256u * (unsigned)c, so);
+        rz[c][i] = sp_buf_load4(rZ, oa[i] + 256u * (unsigned)c, so);
+        if constexpr (AM == A_DZ) ry[c][i] = sp_buf_load4(rY, oa[i] + 256u * (unsigned)c, so);
     };
-    auto fetch_p = [&](__amdgpu_buffer_rsrc_t rP, int s, int j, int r) { zq[j][r] = wsp_load1(rP, qoff(j, r), (unsigned)s * (32u * BN * 4u)); };
+    auto fetch_p = [&](__amdgpu_buffer_rsrc_t rP, int s, int j, int r) { zq[j][r] = sp_buf_load1(rP, qoff(j, r), (unsigned)s * (32u * BN * 4u)); };
     auto fetch_g = [&](__amdgpu_buffer_rsrc_t rY, __amdgpu_buffer_rsrc_t rI, int s, int c) {   // one row of the pooled tables per strip
         if constexpr (AM == A_DZ_POOL) {
             const unsigned sg = (unsigned)s * (KD * 4u);
-            rdm[c] = wsp_load1(rY, 4u * (unsigned)lane + 256u * (unsigned)c, sg);
-            rarg[c] = __builtin_bit_cast(int, wsp_load1(rI, 4u * (unsigned)lane + 256u * (unsigned)c, sg));
+            rdm[c] = sp_buf_load1(rY, 4u * (unsigned)lane + 256u * (unsigned)c, sg);
+            rarg[c] = __builtin_bit_cast(int, sp_buf_load1(rI, 4u * (unsigned)lane + 256u * (unsigned)c, sg));
         }
     };
     // the first strip's loads go out before anything else of the prologue (chunk 0 first: the MFMAs start on it)

@@ -25,21 +25,13 @@
 #include <stdlib.h>
 
 #include "kernels.h"
+#include "split_prims.h"
 
 namespace pnpp {
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wsq_rsrc(const void *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, 0xfffffffe, 0x00020000);
-}
-__device__ __forceinline__ f32x4 wsq_load4(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, (int)s_off, 0));
-}
 typedef int i32x4q __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ i32x4q wsq_load4i(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
     return __builtin_bit_cast(i32x4q, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, (int)s_off, 0));
-}
-__device__ __forceinline__ float wsq_load1(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)lane_off, (int)s_off, 0));
 }
 
 #ifndef WSQ_PLAIN
@@ -94,8 +86,8 @@ gemm_wsq_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, i
 
     // staging map of a tile: column group lane (16 bytes), rows wave + 4 i -- a row's stager is the wave (row mod 4)
     const int q4 = 4 * lane;
-    const __amdgpu_buffer_rsrc_t resZ = wsq_rsrc(A.z), resD = wsq_rsrc(A.a), resI = wsq_rsrc(A.arg), resP = wsq_rsrc(E.zp), resC = wsq_rsrc(E.c);
-    const __amdgpu_buffer_rsrc_t resNull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A.z), (short)0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t resZ = sp_buf_rsrc(A.z), resD = sp_buf_rsrc(A.a), resI = sp_buf_rsrc(A.arg), resP = sp_buf_rsrc(E.zp), resC = sp_buf_rsrc(E.c);
+    const __amdgpu_buffer_rsrc_t resNull = sp_buf_rsrc_null(A.z);
     unsigned oa[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) oa[i] = 4u * ((unsigned)(wave + 4 * i) * (unsigned)KD + (unsigned)q4);
@@ -112,15 +104,15 @@ gemm_wsq_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, i
     float vh[16];      // this tile's outputs, stored during the NEXT tile's dA product (see the tile loop)
     f32x4 gdm[2];      // pooled gradient / arg-max rows of the tile's two neighbourhoods at this lane's column group
     i32x4q garg[2];
-    auto fetch_z = [&](__amdgpu_buffer_rsrc_t rZ, int t, int i) { rz[i] = wsq_load4(rZ, oa[i], (unsigned)t * (BM * KD * 4u)); };
+    auto fetch_z = [&](__amdgpu_buffer_rsrc_t rZ, int t, int i) { rz[i] = sp_buf_load4(rZ, oa[i], (unsigned)t * (BM * KD * 4u)); };
     auto fetch_p = [&](__amdgpu_buffer_rsrc_t rP, int t, int r) {
-        zn[r] = wsq_load1(rP, oq[r >> 2] + (unsigned)(r & 3) * rowp, (unsigned)t * (unsigned)BM * rowp);
+        zn[r] = sp_buf_load1(rP, oq[r >> 2] + (unsigned)(r & 3) * rowp, (unsigned)t * (unsigned)BM * rowp);
     };
     auto fetch_g = [&](__amdgpu_buffer_rsrc_t rD, __amdgpu_buffer_rsrc_t rI, int t) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const unsigned so = (unsigned)(2 * t + h) * (KD * 4u);
-            gdm[h] = wsq_load4(rD, 4u * (unsigned)q4, so);
+            gdm[h] = sp_buf_load4(rD, 4u * (unsigned)q4, so);
             garg[h] = wsq_load4i(rI, 4u * (unsigned)q4, so);
         }
     };
@@ -458,8 +450,8 @@ gemm_wsq2_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
 #endif
 
     const int q4 = 4 * lane;
-    const __amdgpu_buffer_rsrc_t resZ = wsq_rsrc(A.z), resD = wsq_rsrc(A.a), resI = wsq_rsrc(A.arg), resP = wsq_rsrc(E.zp), resC = wsq_rsrc(E.c);
-    const __amdgpu_buffer_rsrc_t resNull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A.z), (short)0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t resZ = sp_buf_rsrc(A.z), resD = sp_buf_rsrc(A.a), resI = sp_buf_rsrc(A.arg), resP = sp_buf_rsrc(E.zp), resC = sp_buf_rsrc(E.c);
+    const __amdgpu_buffer_rsrc_t resNull = sp_buf_rsrc_null(A.z);
     unsigned oq[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) oq[g] = 4u * ((unsigned)(32 * wm + 4 * lh + 8 * g) * (unsigned)Nout + (unsigned)(n0 + 32 * wn + l31));
@@ -493,13 +485,13 @@ gemm_wsq2_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
     };
     const u32x4q dmaZ = dma_desc(A.z, true), dmaNull = dma_desc(A.z, false);
     auto fetch_p = [&](__amdgpu_buffer_rsrc_t rP, int t, int r) {
-        zn[r] = wsq_load1(rP, oq[r >> 2] + (unsigned)(r & 3) * rowp, (unsigned)t * (unsigned)BM * rowp);
+        zn[r] = sp_buf_load1(rP, oq[r >> 2] + (unsigned)(r & 3) * rowp, (unsigned)t * (unsigned)BM * rowp);
     };
     auto fetch_g = [&](__amdgpu_buffer_rsrc_t rD, __amdgpu_buffer_rsrc_t rI, int t) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const unsigned so = (unsigned)(2 * t + h) * (KD * 4u);
-            gdm[h] = wsq_load4(rD, 4u * (unsigned)q4, so);
+            gdm[h] = sp_buf_load4(rD, 4u * (unsigned)q4, so);
             garg[h] = wsq_load4i(rI, 4u * (unsigned)q4, so);
         }
     };

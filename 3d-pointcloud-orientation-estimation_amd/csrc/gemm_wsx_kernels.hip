@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "kernels.h"
+#include "split_prims.h"
 #include "wsf0_args.h"
 
 namespace pnpp {
@@ -42,47 +43,22 @@ struct WsxArgs {
     double *xslab;               // [workers][kWsxSlab]
 };
 
-__device__ __forceinline__ f32x4 wsx_load4(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, (int)s_off, 0));
-}
-
 #ifndef WSX_EXP   // timing experiments (wrong results): 2 no dW loop, 4 no dA loop, 8 no epilogue arithmetic
 #define WSX_EXP 0
 #endif
 
 // KD = C_1 (64); C_0 = 64.  One workgroup per CU or two (launch bounds 256 x WPC); a wave owns strips of 32 rows end to end.
-// S3: the dA product (X W', 64 -> 64 per strip) from exact three-way bf16 splits on v_mfma_f32_32x32x16_bf16 (gemm_wsf3_kernels.hip has the
+// S3: the dA product (X W', 64 -> 64 per strip) from exact three-way bf16 splits on v_mfma_f32_32x32x16_bf16 (split_prims.h has the
 // arithmetic): the weight panel is split once in the prologue (three bf16 planes, the k order of a 16-group laid out as the operand reads
 // it, as in gemm_wsf03_kernels.hip), a lane splits the 8 values of its row it multiplies per step in registers -- 48 MFMAs of 32 cycles per
 // strip instead of 64 of 64 for 2,048 split elements.  dW_1 stays on the float32 instruction: its operands would be 4,096 split elements per
 // strip for the same 2,560 cycles (a split element has to feed three tiles to earn its 29 cycles: DESIGN.md section 9).
-typedef __bf16 wsx_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wsx_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float wsx_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned wsx_pk(float lo, float hi) {
-    const wsx_f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, wsx_bf16x2));
-}
-__device__ __forceinline__ void wsx_split2(float v0, float v1, unsigned &h, unsigned &m, unsigned &l) {
-    h = wsx_pk(v0, v1);
-    float r0 = v0 - __uint_as_float(h << 16), r1 = v1 - __uint_as_float(h & 0xffff0000u);
-    m = wsx_pk(r0, r1);
-    r0 -= __uint_as_float(m << 16), r1 -= __uint_as_float(m & 0xffff0000u);
-    l = wsx_pk(r0, r1);
-}
-__device__ __forceinline__ wsx_bf16x8 wsx_op(uint4 v) { return __builtin_bit_cast(wsx_bf16x8, v); }
 constexpr int WSX3_PLANE = 64 * 128;   // bytes: [64 columns n][64 k] bf16
 
 // D3 (with S3): the dW_1 product on the bf16 pipe too.  dZ_1 is split ONCE, when the strip is staged: the strip image is three bf16 planes
-// ([32 rows][64 channels], 128-byte rows, 16-byte group g of row r at g ^ x(r) as in gemm_wsd3_kernels.hip), read back by rows for dA
+// ([32 rows][64 channels], 128-byte rows, 16-byte group g of row r at g ^ sp_swz_row(r) as in gemm_wsd3_kernels.hip), read back by rows for dA
 // (ds_read_b128) and transposed for dW (ds_read_b64_tr_b16: lane = channel, eight rows per lane half); the activation operand of dW is the
 // layer-0 tile's accumulator registers (eight consecutive ones = one 32x32x16 operand), ReLU'd and split in registers.
-typedef short wsx_s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 wsx_tr(const unsigned char *p) {   // ds_read_b64_tr_b16: 4 rows x 16 columns per 16 lanes, transposed
-    const wsx_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wsx_s16x4 *)(p));
-    return __builtin_bit_cast(uint2, v);
-}
-
 template <int KD, int WPC, bool S3, bool D3>
 __global__ void __launch_bounds__(256, WPC)
 gemm_wsx_kernel(const WsxArgs P) {
@@ -104,15 +80,14 @@ gemm_wsx_kernel(const WsxArgs P) {
     float *Rl = RlAll + wave * 128;
     const int l31 = lane & 31, lh = lane >> 5;
     auto swz = [](int r) { return (r & 15) << 2; };
-    auto xs3 = [](int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); };   // group XOR of a plane row (conflict-free ds_read_b128 row reads)
     const int worker = blockIdx.x, nworkers = gridDim.x;
 
     const int q4 = 4 * (lane & 15), rb = lane >> 4;        // staging map of a strip: column group lane % 16, rows lane / 16 + 4 i
     const int nstrips = P.M / 32, stride = nworkers * 4;
     int strip = worker * 4 + wave;
-    const __amdgpu_buffer_rsrc_t resZ = wsx_rsrc(P.z), resY = wsx_rsrc(P.dy), resI = wsx_rsrc(P.idx), resX = wsx_rsrc(P.xyz),
-                                 resC = wsx_rsrc(P.centres);
-    const __amdgpu_buffer_rsrc_t resNull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.z), (short)0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t resZ = sp_buf_rsrc(P.z), resY = sp_buf_rsrc(P.dy), resI = sp_buf_rsrc(P.idx), resX = sp_buf_rsrc(P.xyz),
+                                 resC = sp_buf_rsrc(P.centres);
+    const __amdgpu_buffer_rsrc_t resNull = sp_buf_rsrc_null(P.z);
     unsigned oa[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) oa[i] = 4u * ((unsigned)(rb + 4 * i) * (unsigned)KD + (unsigned)q4);
@@ -121,18 +96,18 @@ gemm_wsx_kernel(const WsxArgs P) {
     f32x4 rz[NC][8], ry[NC][8];
     auto fetch_z = [&](__amdgpu_buffer_rsrc_t rZ, __amdgpu_buffer_rsrc_t rY, int s, int c, int i) {
         const unsigned so = (unsigned)s * (32u * KD * 4u);
-        rz[c][i] = wsx_load4(rZ, oa[i] + 256u * (unsigned)c, so);
-        ry[c][i] = wsx_load4(rY, oa[i] + 256u * (unsigned)c, so);
+        rz[c][i] = sp_buf_load4(rZ, oa[i] + 256u * (unsigned)c, so);
+        ry[c][i] = sp_buf_load4(rY, oa[i] + 256u * (unsigned)c, so);
     };
     // geometry of a strip = one neighbourhood: row l31's neighbour index, then its coordinates and the centre's
     int nidx;
     float px, py, pz, cx, cy, cz;
-    auto fetch_idx = [&](__amdgpu_buffer_rsrc_t rI, int s) { nidx = __builtin_bit_cast(int, wsx_load1(rI, 4u * (unsigned)l31, (unsigned)s * 128u)); };
+    auto fetch_idx = [&](__amdgpu_buffer_rsrc_t rI, int s) { nidx = __builtin_bit_cast(int, sp_buf_load1(rI, 4u * (unsigned)l31, (unsigned)s * 128u)); };
     auto fetch_geo = [&](__amdgpu_buffer_rsrc_t rX, __amdgpu_buffer_rsrc_t rCn, int s) {
         const unsigned cloud = (unsigned)(s / P.S) * (unsigned)P.N * 12u, po = 12u * (unsigned)nidx;
-        px = wsx_load1(rX, po, cloud), py = wsx_load1(rX, po + 4u, cloud), pz = wsx_load1(rX, po + 8u, cloud);
+        px = sp_buf_load1(rX, po, cloud), py = sp_buf_load1(rX, po + 4u, cloud), pz = sp_buf_load1(rX, po + 8u, cloud);
         const unsigned co = (unsigned)s * 12u;
-        cx = wsx_load1(rCn, 0u, co), cy = wsx_load1(rCn, 4u, co), cz = wsx_load1(rCn, 8u, co);
+        cx = sp_buf_load1(rCn, 0u, co), cy = sp_buf_load1(rCn, 4u, co), cz = sp_buf_load1(rCn, 8u, co);
     };
     // ---- everything the prologue reads is requested before its first wait: first strip, constants, weight panel ----
     const bool have = strip < nstrips;
@@ -190,9 +165,9 @@ gemm_wsx_kernel(const WsxArgs P) {
                 const int kq = k4 >> 2;   // D3: plain k order (the strip rows come from the planes); else the order a register-split row has
                 const int g = D3 ? (kq >> 1) : 2 * (kq >> 2) + (kq & 1), sub = D3 ? (kq & 1) : (kq >> 1) & 1;
                 unsigned h0, m0, l0, h1, m1, l1;
-                wsx_split2(t[0], t[1], h0, m0, l0);
-                wsx_split2(t[2], t[3], h1, m1, l1);
-                unsigned char *d = reinterpret_cast<unsigned char *>(Ws) + nl * 128 + 16 * (g ^ xs3(nl)) + 8 * sub;
+                sp_split2(t[0], t[1], h0, m0, l0);
+                sp_split2(t[2], t[3], h1, m1, l1);
+                unsigned char *d = reinterpret_cast<unsigned char *>(Ws) + nl * 128 + 16 * (g ^ sp_swz_row(nl)) + 8 * sub;
                 *reinterpret_cast<uint2 *>(d) = make_uint2(h0, h1);
                 *reinterpret_cast<uint2 *>(d + WSX3_PLANE) = make_uint2(m0, m1);
                 *reinterpret_cast<uint2 *>(d + 2 * WSX3_PLANE) = make_uint2(l0, l1);
@@ -229,9 +204,9 @@ gemm_wsx_kernel(const WsxArgs P) {
         if constexpr (D3) {   // the strip is split here, once for both products
             const int r = rb + 4 * i, q = q4 >> 2;
             unsigned h0, m0, l0, h1, m1, l1;
-            wsx_split2(v[0], v[1], h0, m0, l0);
-            wsx_split2(v[2], v[3], h1, m1, l1);
-            unsigned char *d = Dzp + r * 128 + 16 * ((q >> 1) ^ xs3(r)) + 8 * (q & 1);
+            sp_split2(v[0], v[1], h0, m0, l0);
+            sp_split2(v[2], v[3], h1, m1, l1);
+            unsigned char *d = Dzp + r * 128 + 16 * ((q >> 1) ^ sp_swz_row(r)) + 8 * (q & 1);
             *reinterpret_cast<uint2 *>(d) = make_uint2(h0, h1);
             *reinterpret_cast<uint2 *>(d + SPLANE) = make_uint2(m0, m1);
             *reinterpret_cast<uint2 *>(d + 2 * SPLANE) = make_uint2(l0, l1);
@@ -246,7 +221,7 @@ gemm_wsx_kernel(const WsxArgs P) {
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             const int r = 8 * b + 4 * lh + qq, ch = 2 * g1 + (pp >> 1);
-            tbase[b] = (unsigned)(r * 128 + 16 * (ch ^ xs3(r)) + 8 * (pp & 1));
+            tbase[b] = (unsigned)(r * 128 + 16 * (ch ^ sp_swz_row(r)) + 8 * (pp & 1));
         }
     }
     auto tofs = [&](int it, int st, int b) -> unsigned { return (tbase[b] ^ (unsigned)(it * 64)) + (unsigned)(st * 2048); };
@@ -301,7 +276,7 @@ gemm_wsx_kernel(const WsxArgs P) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) accs[0][r] = 0.f, accs[1][r] = 0.f;
                 const unsigned char *bpl = reinterpret_cast<const unsigned char *>(Ws) + l31 * 128;   // column 32 j + l31: + 4096 j
-                const int bx = xs3(l31);
+                const int bx = sp_swz_row(l31);
                 float4 fa[2][2];
                 uint4 fap[2][3];
                 uint4 fb[2][2][3];
@@ -321,21 +296,21 @@ gemm_wsx_kernel(const WsxArgs P) {
                         for (int p = 0; p < 3; ++p) fb[buf][j][p] = *reinterpret_cast<const uint4 *>(bpl + j * 4096 + p * WSX3_PLANE + 16 * g);
                 };
                 auto mm = [&](int buf) {
-                    wsx_bf16x8 a_h, a_m, a_l;
+                    bf16x8 a_h, a_m, a_l;
                     if constexpr (D3) {
-                        a_h = wsx_op(fap[buf][0]), a_m = wsx_op(fap[buf][1]), a_l = wsx_op(fap[buf][2]);
+                        a_h = sp_op(fap[buf][0]), a_m = sp_op(fap[buf][1]), a_l = sp_op(fap[buf][2]);
                     } else {
                         unsigned h[4], m[4], l[4];
-                        wsx_split2(fa[buf][0].x, fa[buf][0].y, h[0], m[0], l[0]);
-                        wsx_split2(fa[buf][0].z, fa[buf][0].w, h[1], m[1], l[1]);
-                        wsx_split2(fa[buf][1].x, fa[buf][1].y, h[2], m[2], l[2]);
-                        wsx_split2(fa[buf][1].z, fa[buf][1].w, h[3], m[3], l[3]);
-                        a_h = wsx_op(make_uint4(h[0], h[1], h[2], h[3])), a_m = wsx_op(make_uint4(m[0], m[1], m[2], m[3]));
-                        a_l = wsx_op(make_uint4(l[0], l[1], l[2], l[3]));
+                        sp_split2(fa[buf][0].x, fa[buf][0].y, h[0], m[0], l[0]);
+                        sp_split2(fa[buf][0].z, fa[buf][0].w, h[1], m[1], l[1]);
+                        sp_split2(fa[buf][1].x, fa[buf][1].y, h[2], m[2], l[2]);
+                        sp_split2(fa[buf][1].z, fa[buf][1].w, h[3], m[3], l[3]);
+                        a_h = sp_op(make_uint4(h[0], h[1], h[2], h[3])), a_m = sp_op(make_uint4(m[0], m[1], m[2], m[3]));
+                        a_l = sp_op(make_uint4(l[0], l[1], l[2], l[3]));
                     }
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        const wsx_bf16x8 b_h = wsx_op(fb[buf][j][0]), b_m = wsx_op(fb[buf][j][1]), b_l = wsx_op(fb[buf][j][2]);
+                        const bf16x8 b_h = sp_op(fb[buf][j][0]), b_m = sp_op(fb[buf][j][1]), b_l = sp_op(fb[buf][j][2]);
                         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_h, acc[j], 0, 0, 0);
                         accs[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, b_h, accs[j], 0, 0, 0);
                         accs[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_l, accs[j], 0, 0, 0);
@@ -403,7 +378,7 @@ gemm_wsx_kernel(const WsxArgs P) {
                         unsigned h[4], m[4], l[4];
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
-                            wsx_split2(fmaxf(zt[j][8 * u + 2 * e], 0.f), fmaxf(zt[j][8 * u + 2 * e + 1], 0.f), h[e], m[e], l[e]);
+                            sp_split2(fmaxf(zt[j][8 * u + 2 * e], 0.f), fmaxf(zt[j][8 * u + 2 * e + 1], 0.f), h[e], m[e], l[e]);
                         bfr[j][u][0] = make_uint4(h[0], h[1], h[2], h[3]), bfr[j][u][1] = make_uint4(m[0], m[1], m[2], m[3]);
                         bfr[j][u][2] = make_uint4(l[0], l[1], l[2], l[3]);
                     }
@@ -414,13 +389,13 @@ gemm_wsx_kernel(const WsxArgs P) {
                         uint4 ta[3];
 #pragma unroll
                         for (int p = 0; p < 3; ++p) {
-                            const uint2 lo = wsx_tr(Dzp + p * SPLANE + tofs(i, u, 0)), hi = wsx_tr(Dzp + p * SPLANE + tofs(i, u, 1));
+                            const uint2 lo = sp_tr_b64(Dzp + p * SPLANE + tofs(i, u, 0)), hi = sp_tr_b64(Dzp + p * SPLANE + tofs(i, u, 1));
                             ta[p] = make_uint4(lo.x, lo.y, hi.x, hi.y);
                         }
-                        const wsx_bf16x8 a_h = wsx_op(ta[0]), a_m = wsx_op(ta[1]), a_l = wsx_op(ta[2]);
+                        const bf16x8 a_h = sp_op(ta[0]), a_m = sp_op(ta[1]), a_l = sp_op(ta[2]);
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
-                            const wsx_bf16x8 b_h = wsx_op(bfr[j][u][0]), b_m = wsx_op(bfr[j][u][1]), b_l = wsx_op(bfr[j][u][2]);
+                            const bf16x8 b_h = sp_op(bfr[j][u][0]), b_m = sp_op(bfr[j][u][1]), b_l = sp_op(bfr[j][u][2]);
                             dw[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_h, dw[i][j], 0, 0, 0);
                             dws[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, b_h, dws[i][j], 0, 0, 0);
                             dws[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_l, dws[i][j], 0, 0, 0);
@@ -768,16 +743,16 @@ gemm_wsf0_kernel(const Wsf0Args P) {
     const int worker = blockIdx.x, nworkers = gridDim.x;
     const int nstrips = P.M / 32, stride = nworkers * 4;
     int strip = worker * 4 + wave;
-    const __amdgpu_buffer_rsrc_t resI = wsx_rsrc(P.idx), resX = wsx_rsrc(P.xyz), resC = wsx_rsrc(P.centres);
-    const __amdgpu_buffer_rsrc_t resNull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.xyz), (short)0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t resI = sp_buf_rsrc(P.idx), resX = sp_buf_rsrc(P.xyz), resC = sp_buf_rsrc(P.centres);
+    const __amdgpu_buffer_rsrc_t resNull = sp_buf_rsrc_null(P.xyz);
     int nidx;
     float px, py, pz, cx, cy, cz;
-    auto fetch_idx = [&](__amdgpu_buffer_rsrc_t rI, int s) { nidx = __builtin_bit_cast(int, wsx_load1(rI, 4u * (unsigned)l31, (unsigned)s * 128u)); };
+    auto fetch_idx = [&](__amdgpu_buffer_rsrc_t rI, int s) { nidx = __builtin_bit_cast(int, sp_buf_load1(rI, 4u * (unsigned)l31, (unsigned)s * 128u)); };
     auto fetch_geo = [&](__amdgpu_buffer_rsrc_t rX, __amdgpu_buffer_rsrc_t rCn, int s) {
         const unsigned cloud = (unsigned)(s / P.S) * (unsigned)P.N * 12u, po = 12u * (unsigned)nidx;
-        px = wsx_load1(rX, po, cloud), py = wsx_load1(rX, po + 4u, cloud), pz = wsx_load1(rX, po + 8u, cloud);
+        px = sp_buf_load1(rX, po, cloud), py = sp_buf_load1(rX, po + 4u, cloud), pz = sp_buf_load1(rX, po + 8u, cloud);
         const unsigned co = (unsigned)s * 12u;
-        cx = wsx_load1(rCn, 0u, co), cy = wsx_load1(rCn, 4u, co), cz = wsx_load1(rCn, 8u, co);
+        cx = sp_buf_load1(rCn, 0u, co), cy = sp_buf_load1(rCn, 4u, co), cz = sp_buf_load1(rCn, 8u, co);
     };
     // ---- everything the prologue reads is requested before its first wait ----
     const bool have = strip < nstrips;

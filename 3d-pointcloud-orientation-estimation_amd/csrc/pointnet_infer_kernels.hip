@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void pn_split_transform_kernel(const float *__
     for (int e = threadIdx.x; e < k * k; e += blockDim.x) {
         const int j = e / k, n = e % k;
         unsigned h, m, l;
-        i3_split2(t[e], 0.f, h, m, l);
+        sp_split2(t[e], 0.f, h, m, l);
         const size_t at = ((((size_t)(n >> 5) * (k >> 4) + (j >> 4)) * 64 + (((j & 15) >> 3) << 5) + (n & 31)) << 3) + (j & 7);
         o[at] = (unsigned short)h, o[plane + at] = (unsigned short)m, o[2 * plane + at] = (unsigned short)l;
     }
@@ -185,7 +185,7 @@ __device__ __forceinline__ void pn_unit(const unsigned short *__restrict__ actIn
                 float v0 = acc[j][i] + bc, v1 = acc[j][i + 1] + bc;
                 if (S.relu) v0 = fmaxf(v0, 0.f), v1 = fmaxf(v1, 0.f);
                 unsigned ph, pm, pl;
-                i3_split2(v0, v1, ph, pm, pl);
+                sp_split2(v0, v1, ph, pm, pl);
                 unsigned short *o = actOut + (size_t)row * ldout + col;
                 o[0] = (unsigned short)ph, o[ldout] = (unsigned short)(ph >> 16);
                 o[outplane] = (unsigned short)pm, o[outplane + ldout] = (unsigned short)(pm >> 16);
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(kPnThreads) void pn_infer_kernel(const PnArgs P) {
                 v = xr[(long long)c * P.sc];
         }
         unsigned ph, pm, pl;
-        i3_split2(v, 0.f, ph, pm, pl);
+        sp_split2(v, 0.f, ph, pm, pl);
         unsigned short *dst = bufA + (size_t)row * P.ldA + c;
         dst[0] = (unsigned short)ph, dst[planeA] = (unsigned short)pm, dst[2 * planeA] = (unsigned short)pl;
     }

@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void bn_fold_split_kernel(const float *__restr
     for (int k = threadIdx.x; k < ld; k += blockDim.x) {
         const float v = k < Cin ? (float)(a * (double)w[(size_t)n * Cin + k]) : 0.f;
         unsigned h, m, l;
-        i3_split2(v, 0.f, h, m, l);
+        sp_split2(v, 0.f, h, m, l);
         const size_t at = ((((size_t)(n >> 5) * (ld >> 4) + (k >> 4)) * 64 + (((k & 15) >> 3) << 5) + (n & 31)) << 3) + (k & 7);
         wout[at] = (unsigned short)h, wout[plane + at] = (unsigned short)m, wout[2 * plane + at] = (unsigned short)l;
     }
@@ -193,7 +193,7 @@ __device__ __forceinline__ void infer_unit(const unsigned short *__restrict__ ac
             for (int i = 0; i < 16; i += 2) {   // registers i and i + 1 are rows `row` and `row + 1`
                 const int row = rb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
                 unsigned ph, pm, pl;
-                i3_split2(fmaxf(acc[j][i] + bc, 0.f), fmaxf(acc[j][i + 1] + bc, 0.f), ph, pm, pl);
+                sp_split2(fmaxf(acc[j][i] + bc, 0.f), fmaxf(acc[j][i + 1] + bc, 0.f), ph, pm, pl);
                 unsigned short *o = actOut + (size_t)row * ldout + col;
                 o[0] = (unsigned short)ph, o[ldout] = (unsigned short)(ph >> 16);
                 o[outplane] = (unsigned short)pm, o[outplane + ldout] = (unsigned short)(pm >> 16);
@@ -274,7 +274,7 @@ __device__ __forceinline__ void infer_stage_rows(const InferArgs &P, unsigned sh
                 }
             }
             unsigned ph, pm, pl;
-            i3_split2(v, 0.f, ph, pm, pl);
+            sp_split2(v, 0.f, ph, pm, pl);
             dst[c] = (unsigned short)ph, dst[planeA + c] = (unsigned short)pm, dst[2 * planeA + c] = (unsigned short)pl;
         }
     }

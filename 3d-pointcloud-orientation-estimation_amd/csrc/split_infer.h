@@ -1,36 +1,11 @@
-// split_infer.h -- device routines shared by the forward-only kernels (sa_infer_kernels.hip, pointnet_infer_kernels.hip,
-// transformer_infer_kernels.hip): the exact three-way split of float32 into bfloat16 pieces and the split-product tile loop over
-// fragment-major weight planes.
+// split_infer.h -- device routine shared by the forward-only kernels (sa_infer_kernels.hip, pointnet_infer_kernels.hip,
+// transformer_infer_kernels.hip): the split-product tile loop over fragment-major weight planes.  The exact three-way split of float32
+// into bfloat16 pieces that feeds it is in split_prims.h.
 #pragma once
-#include "common.h"
+#include "split_prims.h"
 
 namespace pnpp {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-
-// Exact three-way split of float32 into bfloat16 pieces (24 significand bits = 8 + 8 + 8), as csrc/gemm_wsf3_kernels.hip:
-// v = h + m + l with h = bf16(v), m = bf16(v - h), l = v - h - m (exact in bf16); two values at a time, packed low / high.
-__device__ __forceinline__ unsigned i3_pk(float lo, float hi) {
-    const f32x2v v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
-}
-__device__ __forceinline__ float i3_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float i3_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ void i3_split2(float v0, float v1, unsigned &h, unsigned &m, unsigned &l) {
-    h = i3_pk(v0, v1);
-    float r0 = v0 - i3_lo(h), r1 = v1 - i3_hi(h);
-    m = i3_pk(r0, r1);
-    r0 -= i3_lo(m), r1 -= i3_hi(m);
-    l = i3_pk(r0, r1);
-}
-// four packed pairs of one plane, as i3_split2 leaves them, as the eight-element MFMA fragment (element 2 i = low half of p[i])
-__device__ __forceinline__ bf16x8 i3_frag(const unsigned (&p)[4]) {
-    const uint4 v = make_uint4(p[0], p[1], p[2], p[3]);
-    return __builtin_bit_cast(bf16x8, v);
-}
 
 // acc[j] + accl[j] += act[32 rows][0 .. Kd) * W[col_j .. +32][0 .. Kd)^T for NJ column blocks `colstep` apart, float32 products formed
 // on v_mfma_f32_32x32x16_bf16 from the three-way splits of both operands: a b = a_h b_h + (a_l b_h + a_h b_l + a_m b_m + a_m b_h +

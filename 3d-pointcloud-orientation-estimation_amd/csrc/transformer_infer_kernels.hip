@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void pt_split_weight_kernel(const float *__res
     const size_t plane = (size_t)gridDim.x * ld;
     for (int k = threadIdx.x; k < ld; k += blockDim.x) {
         unsigned h, m, l;
-        i3_split2(w[(size_t)n * ld + k], 0.f, h, m, l);
+        sp_split2(w[(size_t)n * ld + k], 0.f, h, m, l);
         const size_t at = ((((size_t)(n >> 5) * (ld >> 4) + (k >> 4)) * 64 + (((k & 15) >> 3) << 5) + (n & 31)) << 3) + (k & 7);
         out[at] = (unsigned short)h, out[plane + at] = (unsigned short)m, out[2 * plane + at] = (unsigned short)l;
     }
@@ -150,7 +150,7 @@ __device__ __forceinline__ void pt_store_split(const float (&v)[2][16], unsigned
 #pragma unroll
         for (int i = 0; i < 16; i += 2) {   // registers i and i + 1 are rows `row` and `row + 1`
             unsigned ph, pm, pl;
-            i3_split2(v[j][i], v[j][i + 1], ph, pm, pl);
+            sp_split2(v[j][i], v[j][i + 1], ph, pm, pl);
             unsigned short *o = tile + pt_row(i, h) * kPtLd + 32 * j + r;
             o[0] = (unsigned short)ph, o[kPtLd] = (unsigned short)(ph >> 16);
             o[kPtPlane] = (unsigned short)pm, o[kPtPlane + kPtLd] = (unsigned short)(pm >> 16);

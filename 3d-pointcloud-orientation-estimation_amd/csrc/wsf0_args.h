@@ -1,5 +1,5 @@
 // wsf0_args.h -- what gemm_wsf0_kernel (gemm_wsx_kernels.hip) and its split-product form gemm_wsf03_kernel (gemm_wsf03_kernels.hip) share:
-// the argument block, the moment-partial layout and the buffer-load helpers.
+// the argument block and the moment-partial layout.
 #pragma once
 #include "kernels.h"
 
@@ -26,13 +26,6 @@ struct Wsf0Args {
     float *z1;         // M x 64
     double *slab;      // [workers][2][64] (EM == E_STORE_STATS)
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wsx_rsrc(const void *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, 0xfffffffe, 0x00020000);
-}
-__device__ __forceinline__ float wsx_load1(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)lane_off, (int)s_off, 0));
-}
 
 // the split-product form (float32 products from exact three-way bf16 splits; on with split_products() unless PNPP_WSF03=0)
 bool wsf03_enabled();
