@@ -16,19 +16,22 @@ The copies hold the fused levels' parameters a second time beside their folded p
 of a level staying a snapshot when a call's sizes send it to the eval path.
 It is not differentiable (model.eval() remains the path with a backward pass), keeps nothing between calls but the folded weights and reusable index / activation buffers, and never writes to the model.
 
-Predictor(model) of a vanilla PointNet / PointNetEncoder (models/pointnet.py) builds the Predictor of pnpp_hip.pointnet_inference:
-the same contract, one launch per trunk (pnpp_pn_infer).  Predictor(model) of a PointTransformer (models/point_transformer.py) builds
-the TransformerPredictor of pnpp_hip.transformer_inference: one launch per encoder layer beside its attention (pnpp_pt_infer_tail);
-Predictor(model, attention="split" | "float32") chooses the attention kernel there.  Predictor(model) of a PointNetPlusPlusCls
-(models/pointnet_pp_cls.py) builds the ClsPredictor below: the same levels and head blocks, farthest-point sampling + radius query
-in front of each level's launch, and fc3 + log_softmax as one launch (pnpp_linear_log_softmax).
+`Predictor` itself is the base class and the factory: it holds what every model family shares (the device check, the reusable
+buffers, held_tensors() / persistent_bytes(), the fold of a conv + BatchNorm chain and of a head block, the bf16-plane view) and
+Predictor(model) builds the family's subclass.  The set-abstraction models get the SetAbstractionPredictor below; a PointNetPlusPlusCls
+(models/pointnet_pp_cls.py) the ClsPredictor below: the same levels and head blocks, farthest-point sampling + radius query in
+front of each level's launch, and fc3 + log_softmax as one launch (pnpp_linear_log_softmax).  A vanilla PointNet / PointNetEncoder
+(models/pointnet.py) gets the PointNetPredictor of pnpp_hip.pointnet_inference: the same contract, one launch per trunk
+(pnpp_pn_infer).  A PointTransformer (models/point_transformer.py) gets the TransformerPredictor of pnpp_hip.transformer_inference:
+one launch per encoder layer beside its attention (pnpp_pt_infer_tail); Predictor(model, attention="split" | "float32") chooses the
+attention kernel there.
 """
 from __future__ import annotations
 
 import copy
 import ctypes as C
 import types
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 import torch.nn as nn
@@ -81,52 +84,143 @@ def _ball(grouper):
     return float(radius)
 
 
+def _tracked(*bns) -> bool:
+    return all(isinstance(b, nn.BatchNorm1d) and b.track_running_stats and b.affine for b in bns)
+
+
+def planes_to_float32(blob: torch.Tensor, offset: int, rows: int, ld: int) -> torch.Tensor:
+    """the (rows, ld) float32 matrix that the three bf16 planes at `offset` of a uint8 blob sum to"""
+    # three bf16 planes (W' = high + middle + low, exactly), each fragment-major [rows/32][ld/16][2][32][8]:
+    # rows n = 32 cb + r, columns k = 16 ks + 8 h + j
+    w = blob[offset:offset + 6 * rows * ld].view(torch.bfloat16).view(3, rows // 32, ld // 16, 2, 32, 8)
+    w = w.permute(0, 1, 4, 2, 3, 5).reshape(3, rows, ld).float()
+    return (w[0] + w[1]) + w[2]
+
+
 class Predictor:
-    """Forward-only evaluation of a BackboneBNHead model (PointNetPPVonMises, PointNetPP8Dir, PointNetPP, PointNetPPFwd,
-    PointNetPPXYZ, PointNetPPXYZ_Schedmit) or of PointNetPPMvM: predictor(xyz, centres=None) == model.eval()(xyz, centres=centres)
-    under no_grad -- same tuple structure, shapes and dtypes, same sampler / grouper per level, same draws from the host generator."""
+    """What the forward-only Predictors of every model family share, and their factory: Predictor(model, ...) builds the
+    SetAbstractionPredictor, ClsPredictor, PointNetPredictor or TransformerPredictor that takes the model.  A subclass checks its
+    model type, calls _bind(), plans (`plan`, `_blobs`, `_heads`) and folds in refresh() into `_blobs`, `_heads` and `_snap`."""
 
     def __new__(cls, model=None, *args, **kwargs):
-        if cls is Predictor:
-            from models.pointnet import PointNet, PointNetEncoder
-            if isinstance(model, (PointNet, PointNetEncoder)):   # the vanilla PointNet family has a Predictor of its own
-                from .pointnet_inference import PointNetPredictor
-                return object.__new__(PointNetPredictor)
-            from models.point_transformer import PointTransformer
-            if isinstance(model, PointTransformer):   # and so has the point transformer
-                from .transformer_inference import TransformerPredictor
-                return object.__new__(TransformerPredictor)
-            from models.pointnet_pp_cls import PointNetPlusPlusCls
-            if isinstance(model, PointNetPlusPlusCls):   # the textbook classifier: other samplers, other head tail
-                return object.__new__(ClsPredictor)
-        return object.__new__(cls)
-
-    @staticmethod
-    def _check_model(model) -> None:
+        if cls is not Predictor:
+            return object.__new__(cls)
+        from models.pointnet import PointNet, PointNetEncoder
+        if isinstance(model, (PointNet, PointNetEncoder)):
+            from .pointnet_inference import PointNetPredictor
+            return object.__new__(PointNetPredictor)
+        from models.point_transformer import PointTransformer
+        if isinstance(model, PointTransformer):
+            from .transformer_inference import TransformerPredictor
+            return object.__new__(TransformerPredictor)
+        from models.pointnet_pp_cls import PointNetPlusPlusCls
+        if isinstance(model, PointNetPlusPlusCls):   # the textbook classifier: other samplers, other head tail
+            return object.__new__(ClsPredictor)
         from models.pointnet_pp_8dir import BackboneBNHead
         from models.pointnet_pp_mvM import PointNetPPMvM
-        if not isinstance(model, (BackboneBNHead, PointNetPPMvM)):
-            raise TypeError(f"Predictor takes a PointNet++ set-abstraction model, a PointNetPlusPlusCls, a PointNet, a PointNetEncoder or "
-                            f"a PointTransformer, not {type(model).__name__}")
-        # the model class's own forward() is run on a proxy whose backbone entry is the Predictor's: it must have one
-        if not any(callable(getattr(type(model), n, None)) for n in ("trunk", "_global_feat")):
-            raise TypeError(f"{type(model).__name__} reaches its backbone through neither trunk() nor _global_feat()")
+        if isinstance(model, (BackboneBNHead, PointNetPPMvM)):
+            return object.__new__(SetAbstractionPredictor)
+        raise TypeError(f"Predictor takes a PointNet++ set-abstraction model, a PointNetPlusPlusCls, a PointNet, a PointNetEncoder or "
+                        f"a PointTransformer, not {type(model).__name__}")
 
-    def __init__(self, model: nn.Module):
-        self._check_model(model)
+    # ---- construction ----------------------------------------------------------------------------------------------------
+    def _bind(self, model: nn.Module) -> None:
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError(f"the model is on '{p.device}': the pnpp HIP operators run on an AMD GPU only "
                                "(no CPU fallback exists in this package)")
         self.model = model
         self.device = p.device
+        self._bufs: Dict[tuple, torch.Tensor] = {}
+        self._heads: Dict[str, _Folded] = {}
+        self.plan: Dict[str, str] = {}
+        self.last_plan: Dict[str, str] = {}   # what the latest call ran (a call's sizes can refuse what was planned "fused")
+
+    def _plan_head(self, name: str, fc, bn) -> None:
+        if _tracked(bn) and isinstance(fc, nn.Linear) and fc.bias is not None:
+            self._heads[name] = _Folded(fc.weight.shape[0], fc.weight.shape[1], self.device)
+            self.plan[name] = "fused"
+        else:
+            self.plan[name] = "eval-path"
+
+    @staticmethod
+    def _fold_chain(entry, desc, convs, bns, blob: torch.Tensor) -> None:
+        """pnpp_sa_infer_fold / pnpp_pn_infer_fold (`entry`) of a conv + BatchNorm chain into its blob"""
+        a = L.SaFwdArgs()
+        keep = []   # the contiguous float32 tensors whose pointers the call reads
+        for field, ts in (("conv_w", [c.weight for c in convs]), ("conv_b", [c.bias for c in convs]),
+                          ("bn_w", [b.weight for b in bns]), ("bn_b", [b.bias for b in bns]),
+                          ("bn_rm", [b.running_mean for b in bns]), ("bn_rv", [b.running_var for b in bns])):
+            ts = [ops._f32(t.detach(), field) for t in ts]
+            keep += ts
+            setattr(a, field, ops._ptr_array(ts))
+        L.check(entry(C.byref(desc), C.byref(a), blob.data_ptr(), ops._stream()))
+
+    @staticmethod
+    def _fold_head(f: _Folded, fc, bn) -> None:
+        ts = [ops._f32(t.detach(), "head parameter") for t in (fc.weight, fc.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+        L.check(L.lib().pnpp_fc_infer_fold(f.weight.shape[0], f.weight.shape[1], *[t.data_ptr() for t in ts], float(bn.eps),
+                                           f.weight.data_ptr(), f.bias.data_ptr(), ops._stream()))
+
+    def _blob_tensors(self) -> List[torch.Tensor]:
+        return list(self._blobs.values())
+
+    def _snap_modules(self) -> List[nn.Module]:
+        return [self._snap]
+
+    def held_tensors(self) -> List[torch.Tensor]:
+        """the device tensors the Predictor holds between calls: folded weights, the reusable index / activation buffers, the
+        folded head blocks, the snapshot's parameters and buffers"""
+        ts = self._blob_tensors() + list(self._bufs.values())
+        for f in self._heads.values():
+            ts += [f.weight, f.bias]
+        for m in self._snap_modules():
+            ts += list(m.parameters()) + list(m.buffers())
+        return ts
+
+    def persistent_bytes(self) -> int:
+        """device memory the Predictor holds between calls"""
+        return sum(t.numel() * t.element_size() for t in self.held_tensors())
+
+    # ---- one call --------------------------------------------------------------------------------------------------------
+    def _buf(self, tag: str, shape, dtype) -> torch.Tensor:
+        key = (tag, tuple(shape), dtype)
+        t = self._bufs.get(key)
+        if t is None:
+            for k in [k for k in self._bufs if k[0] == tag]:   # one buffer per role: a new shape replaces the old one
+                del self._bufs[k]
+            t = torch.empty(*shape, dtype=dtype, device=self.device)
+            self._bufs[key] = t
+        return t
+
+    def _run_head(self, name: str, x, eval_block):
+        f = self._heads.get(name)
+        if f is not None:     # folded linear + BatchNorm1d: y = relu(x W'^T + b'); eval-mode dropout is the identity
+            return ops.fc_block(x, f, None, relu=True, training=False)
+        return eval_block(name, x)
+
+
+class SetAbstractionPredictor(Predictor):
+    """Forward-only evaluation of a BackboneBNHead model (PointNetPPVonMises, PointNetPP8Dir, PointNetPP, PointNetPPFwd,
+    PointNetPPXYZ, PointNetPPXYZ_Schedmit) or of PointNetPPMvM: predictor(xyz, centres=None) == model.eval()(xyz, centres=centres)
+    under no_grad -- same tuple structure, shapes and dtypes, same sampler / grouper per level, same draws from the host generator."""
+
+    def __init__(self, model: nn.Module):
+        from models.pointnet_pp_8dir import BackboneBNHead
+        from models.pointnet_pp_mvM import PointNetPPMvM
+        if not isinstance(model, (BackboneBNHead, PointNetPPMvM)):
+            raise TypeError(f"SetAbstractionPredictor takes a PointNet++ set-abstraction model, not {type(model).__name__}")
+        # the model class's own forward() is run on a proxy whose backbone entry is the Predictor's: it must have one
+        if not any(callable(getattr(type(model), n, None)) for n in ("trunk", "_global_feat")):
+            raise TypeError(f"{type(model).__name__} reaches its backbone through neither trunk() nor _global_feat()")
+        self._build(model)
+
+    def _build(self, model: nn.Module) -> None:
+        self._bind(model)
         self._levels = [model.sa1, model.sa2, model.sa3]
         self._names = ["sa1", "sa2", "sa3"]
         self._blobs: Dict[str, torch.Tensor] = {}
-        self._heads: Dict[str, _Folded] = {}
         self._snap: Dict[str, nn.Module] = {}   # private copies of the submodules that are not folded (refresh())
-        self._bufs: Dict[tuple, torch.Tensor] = {}
-        self.plan: Dict[str, str] = {}
         lib = L.lib()
         prev_npoint = None
         for name, sa in zip(self._names, self._levels):
@@ -139,13 +233,8 @@ class Predictor:
                 self.plan[name] = "eval-path"
             prev_npoint = sa.npoint
         for i in (1, 2):
-            fc, bn = getattr(model, f"fc{i}"), getattr(model, f"bn{i}", None)
-            if isinstance(bn, nn.BatchNorm1d) and bn.track_running_stats:
-                self._heads[f"fc{i}"] = _Folded(fc.weight.shape[0], fc.weight.shape[1], self.device)
-                self.plan[f"fc{i}"] = "fused"
-            else:
-                self.plan[f"fc{i}"] = "eval-path"
-        self.last_plan: Dict[str, str] = dict(self.plan)   # what the latest call ran (a call's sizes can refuse a planned level)
+            self._plan_head(f"fc{i}", getattr(model, f"fc{i}"), getattr(model, f"bn{i}", None))
+        self.last_plan.update(self.plan)
         self.refresh()
 
     # ---- construction ----------------------------------------------------------------------------------------------------
@@ -179,25 +268,10 @@ class Predictor:
         with torch.cuda.device(self.device):
             for name, sa in zip(self._names, self._levels):
                 if name in self._blobs:
-                    d = self._nominal_desc(sa, prev_npoint)
-                    a = L.SaFwdArgs()
-                    keep = []   # the contiguous float32 tensors whose pointers the call reads
-                    for field, ts in (("conv_w", [c.weight for c in sa.convs]), ("conv_b", [c.bias for c in sa.convs]),
-                                      ("bn_w", [b.weight for b in sa.bns]), ("bn_b", [b.bias for b in sa.bns]),
-                                      ("bn_rm", [b.running_mean for b in sa.bns]), ("bn_rv", [b.running_var for b in sa.bns])):
-                        ts = [ops._f32(t.detach(), field) for t in ts]
-                        keep += ts
-                        setattr(a, field, ops._ptr_array(ts))
-                    L.check(lib.pnpp_sa_infer_fold(C.byref(d), C.byref(a), self._blobs[name].data_ptr(), ops._stream()))
+                    self._fold_chain(lib.pnpp_sa_infer_fold, self._nominal_desc(sa, prev_npoint), sa.convs, sa.bns, self._blobs[name])
                 prev_npoint = sa.npoint
-            for i in (1, 2):
-                f = self._heads.get(f"fc{i}")
-                if f is None:
-                    continue
-                fc, bn = getattr(self.model, f"fc{i}"), getattr(self.model, f"bn{i}")
-                ts = [ops._f32(t.detach(), "head parameter") for t in (fc.weight, fc.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-                L.check(lib.pnpp_fc_infer_fold(f.weight.shape[0], f.weight.shape[1], *[t.data_ptr() for t in ts], float(bn.eps),
-                                               f.weight.data_ptr(), f.bias.data_ptr(), ops._stream()))
+            for name, f in self._heads.items():
+                self._fold_head(f, getattr(self.model, name), getattr(self.model, "bn" + name[2:]))
 
     def folded_layer(self, level: str, layer: int):
         """(W' (C_l, Cin_l), b' (C_l)) of a fused level as float32 tensors: the documented view of its blob (pnpp_sa_infer_weights_layout)."""
@@ -209,34 +283,14 @@ class Predictor:
         blob = self._blobs[level]
         c = self._channels(sa)[layer]
         cin = sa.convs[layer].weight.shape[1]
-        # three bf16 planes (W' = high + middle + low, exactly), each fragment-major [C/32][ld/16][2][32][8]:
-        # rows n = 32 cb + r, columns k = 16 ks + 8 h + j
-        w = blob[woff.value:woff.value + 6 * c * ld.value].view(torch.bfloat16).view(3, c // 32, ld.value // 16, 2, 32, 8)
-        w = w.permute(0, 1, 4, 2, 3, 5).reshape(3, c, ld.value).float()
-        w = (w[0] + w[1]) + w[2]
+        w = planes_to_float32(blob, woff.value, c, ld.value)
         b = blob[boff.value:boff.value + 4 * c].view(torch.float32)
         return w[:, :cin].clone(), b.clone(), w[:, cin:].clone()
 
-    def persistent_bytes(self) -> int:
-        """device memory the Predictor holds between calls: folded weights + the reusable index / activation buffers"""
-        ts = list(self._blobs.values()) + list(self._bufs.values())
-        for f in self._heads.values():
-            ts += [f.weight, f.bias]
-        for m in self._snap.values():
-            ts += list(m.parameters()) + list(m.buffers())
-        return sum(t.numel() * t.element_size() for t in ts)
+    def _snap_modules(self):
+        return list(self._snap.values())
 
     # ---- one call --------------------------------------------------------------------------------------------------------
-    def _buf(self, tag: str, shape, dtype) -> torch.Tensor:
-        key = (tag, tuple(shape), dtype)
-        t = self._bufs.get(key)
-        if t is None:
-            for k in [k for k in self._bufs if k[0] == tag]:   # one buffer per role: a new shape replaces the old one
-                del self._bufs[k]
-            t = torch.empty(*shape, dtype=dtype, device=self.device)
-            self._bufs[key] = t
-        return t
-
     def _takes(self, i: int, B: int, N: int) -> Optional[L.SaDesc]:
         """the level's descriptor at this call's sizes when the fused kernel takes it, else None"""
         name, sa = self._names[i], self._levels[i]
@@ -326,19 +380,18 @@ class Predictor:
         l1_xyz, l1_pts = self._level(0, xyz, None, c1)
         return self._level(1, l1_xyz, l1_pts, c2)
 
-    def _trunk(self, xyz, centres):
+    def _eval_head(self, name, x):
         m = _Proxy(self)   # unfolded head blocks come from the snapshot
+        norm = getattr(m, "bn" + name[2:], None) or getattr(m, "ln" + name[2:], None)
+        return ops.fc_block(x, getattr(m, name), norm, relu=True, dropout=m.drop, training=False)
+
+    def _trunk(self, xyz, centres):
         xyz = ops._f32(xyz, "xyz")
         B = xyz.size(0)
         l2_xyz, l2_pts = self._levels12(xyz, centres)
         x = self._level(2, l2_xyz, l2_pts)[1].reshape(B, -1)
-        for i in (1, 2):
-            f = self._heads.get(f"fc{i}")
-            if f is not None:     # folded linear + BatchNorm1d: y = relu(x W'^T + b'); eval-mode dropout is the identity
-                x = ops.fc_block(x, f, None, relu=True, training=False)
-            else:
-                norm = getattr(m, f"bn{i}", None) or getattr(m, f"ln{i}", None)
-                x = ops.fc_block(x, getattr(m, f"fc{i}"), norm, relu=True, dropout=m.drop, training=False)
+        for name in ("fc1", "fc2"):
+            x = self._run_head(name, x, self._eval_head)
         return x
 
     @torch.no_grad()
@@ -348,21 +401,21 @@ class Predictor:
             return type(self.model).forward(_Proxy(self), xyz, centres=centres)
 
 
-class ClsPredictor(Predictor):
+class ClsPredictor(SetAbstractionPredictor):
     """Forward-only evaluation of PointNetPlusPlusCls: predictor(x, start=None) == model.eval()(x, start=start) under no_grad.
     Each level is farthest-point sampling, the radius query and one pnpp_sa_infer launch on the neighbour lists; fc1 / bn1 and
     fc2 / bn2 are folded; fc3 + log_softmax is one launch on the snapshot's fc3 (plan["fc3"]).  Same draws from the host generator as
     the model: one torch.randint per level unless `start` injects them."""
 
-    @staticmethod
-    def _check_model(model) -> None:
+    def __init__(self, model: nn.Module):
         from models.pointnet_pp_cls import PointNetPlusPlusCls
         if not isinstance(model, PointNetPlusPlusCls):
             raise TypeError(f"ClsPredictor takes a PointNetPlusPlusCls, not {type(model).__name__}")
-
-    def __init__(self, model: nn.Module):
-        super().__init__(model)
+        self._build(model)
         self.plan["fc3"] = self.last_plan["fc3"] = "fused"
+
+    def _eval_head(self, name, x):
+        return ops.fc_block(x, self._snap[name], self._snap["bn" + name[2:]], relu=True, training=False)
 
     @torch.no_grad()
     def __call__(self, x: torch.Tensor, start=None):
@@ -374,10 +427,6 @@ class ClsPredictor(Predictor):
             l1_xyz, l1_pts = self._level(0, xyz, points, sa1._centres(xyz, s1))
             l2_xyz, l2_pts = self._level(1, l1_xyz, l1_pts, sa2._centres(l1_xyz, s2))
             h = self._level(2, l2_xyz, l2_pts)[1].reshape(xyz.size(0), -1)
-            for i in (1, 2):
-                f = self._heads.get(f"fc{i}")
-                if f is not None:
-                    h = ops.fc_block(h, f, None, relu=True, training=False)
-                else:
-                    h = ops.fc_block(h, self._snap[f"fc{i}"], self._snap[f"bn{i}"], relu=True, training=False)
+            for name in ("fc1", "fc2"):
+                h = self._run_head(name, h, self._eval_head)
             return ops.linear_log_softmax(h, self._snap["fc3"])

@@ -32,11 +32,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .inference import Predictor, _Folded
-
-
-def _tracked(*bns) -> bool:
-    return all(isinstance(b, nn.BatchNorm1d) and b.track_running_stats and b.affine for b in bns)
+from .inference import Predictor, _tracked, planes_to_float32
 
 
 class PointNetPredictor(Predictor):
@@ -47,18 +43,10 @@ class PointNetPredictor(Predictor):
         from models.pointnet import PointNet, PointNetEncoder
         if not isinstance(model, (PointNet, PointNetEncoder)):
             raise TypeError(f"PointNetPredictor takes a PointNet or a PointNetEncoder, not {type(model).__name__}")
-        p = next(model.parameters())
-        if not p.is_cuda:
-            raise RuntimeError(f"the model is on '{p.device}': the pnpp HIP operators run on an AMD GPU only "
-                               "(no CPU fallback exists in this package)")
-        self.model = model
-        self.device = p.device
+        self._bind(model)
         self._whole = isinstance(model, PointNet)
         self._blobs: Dict[str, torch.Tensor] = {}
-        self._heads: Dict[str, _Folded] = {}
-        self._bufs: Dict[tuple, torch.Tensor] = {}
         self._snap: Optional[nn.Module] = None
-        self.plan: Dict[str, str] = {}
         lib = L.lib()
         enc = self._enc(model)
         for name in self._trunk_names(enc):
@@ -75,7 +63,7 @@ class PointNetPredictor(Predictor):
         if self._whole:
             self._plan_head("fc1", model.fc1, model.bn1)
             self._plan_head("fc2", model.fc2, model.bn2)
-        self.last_plan: Dict[str, str] = dict(self.plan)
+        self.last_plan.update(self.plan)
         self.refresh()
 
     # ---- construction ----------------------------------------------------------------------------------------------------
@@ -85,13 +73,6 @@ class PointNetPredictor(Predictor):
     @staticmethod
     def _trunk_names(enc) -> List[str]:
         return ["stn"] + (["fstn"] if enc.feature_transform else []) + ["encoder"]
-
-    def _plan_head(self, name, fc, bn):
-        if _tracked(bn) and isinstance(fc, nn.Linear) and fc.bias is not None:
-            self._heads[name] = _Folded(fc.weight.shape[0], fc.weight.shape[1], self.device)
-            self.plan[name] = "fused"
-        else:
-            self.plan[name] = "eval-path"
 
     @staticmethod
     def _trunk_layers(enc, name) -> List[Tuple[nn.Module, nn.Module]]:
@@ -133,22 +114,10 @@ class PointNetPredictor(Predictor):
         enc = self._enc(self.model)
         with torch.cuda.device(self.device):
             for name, blob in self._blobs.items():
-                layers = self._trunk_layers(enc, name)
-                d = self._trunk_desc(enc, name, 1, 1)
-                a = L.SaFwdArgs()
-                keep = []   # the contiguous float32 tensors whose pointers the call reads
-                for field, ts in (("conv_w", [c.weight for c, _ in layers]), ("conv_b", [c.bias for c, _ in layers]),
-                                  ("bn_w", [b.weight for _, b in layers]), ("bn_b", [b.bias for _, b in layers]),
-                                  ("bn_rm", [b.running_mean for _, b in layers]), ("bn_rv", [b.running_var for _, b in layers])):
-                    ts = [ops._f32(t.detach(), field) for t in ts]
-                    keep += ts
-                    setattr(a, field, ops._ptr_array(ts))
-                L.check(lib.pnpp_pn_infer_fold(C.byref(d), C.byref(a), blob.data_ptr(), ops._stream()))
+                convs, bns = zip(*self._trunk_layers(enc, name))
+                self._fold_chain(lib.pnpp_pn_infer_fold, self._trunk_desc(enc, name, 1, 1), convs, bns, blob)
             for name, f in self._heads.items():
-                fc, bn = self._head_modules(self.model, name)
-                ts = [ops._f32(t.detach(), "head parameter") for t in (fc.weight, fc.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-                L.check(lib.pnpp_fc_infer_fold(f.weight.shape[0], f.weight.shape[1], *[t.data_ptr() for t in ts], float(bn.eps),
-                                               f.weight.data_ptr(), f.bias.data_ptr(), ops._stream()))
+                self._fold_head(f, *self._head_modules(self.model, name))
 
     def _head_modules(self, model, name):
         if "." in name:
@@ -167,22 +136,9 @@ class PointNetPredictor(Predictor):
         L.check(L.lib().pnpp_pn_infer_weights_layout(C.byref(d), layer, C.byref(woff), C.byref(ld), C.byref(boff)))
         blob = self._blobs[trunk]
         c, cin = conv.weight.shape[0], conv.weight.shape[1]
-        w = blob[woff.value:woff.value + 6 * c * ld.value].view(torch.bfloat16).view(3, c // 32, ld.value // 16, 2, 32, 8)
-        w = w.permute(0, 1, 4, 2, 3, 5).reshape(3, c, ld.value).float()
-        w = (w[0] + w[1]) + w[2]
+        w = planes_to_float32(blob, woff.value, c, ld.value)
         b = blob[boff.value:boff.value + 4 * c].view(torch.float32)
         return w[:, :cin].clone(), b.clone(), w[:, cin:].clone()
-
-    def persistent_bytes(self) -> int:
-        """device memory the Predictor holds between calls: folded weights, the model copy, the reusable buffers"""
-        return sum(t.numel() * t.element_size() for t in self.held_tensors())
-
-    def held_tensors(self) -> List[torch.Tensor]:
-        ts = list(self._blobs.values()) + list(self._bufs.values())
-        for f in self._heads.values():
-            ts += [f.weight, f.bias]
-        ts += list(self._snap.parameters()) + list(self._snap.buffers())
-        return ts
 
     # ---- one call --------------------------------------------------------------------------------------------------------
     def _fused_trunk(self, name, d, xr, trans, trans_feat, want_feat, fresh_out):
@@ -233,15 +189,15 @@ class PointNetPredictor(Predictor):
             return self._eval_trunk(name, xr, trans, trans_feat)
         return self._fused_trunk(name, d, xr, trans, trans_feat, want_feat, fresh_out)
 
-    def _head(self, name, x):
-        f = self._heads.get(name)
-        self.last_plan[name] = self.plan[name]
-        if f is not None:   # folded linear + BatchNorm1d: y = relu(x W'^T + b')
-            return ops.fc_block(x, f, None, relu=True, training=False)
+    def _eval_head(self, name, x):
         fc, bn = self._head_modules(self._snap, name)
         if name == "fc2":   # the model head's relu(bn2(dropout(fc2(x)))), dropout the identity
             return ops.pn_bn_relu(ops.fc_block(x, fc, None, relu=False, training=False), bn, training=False)
         return ops.fc_block(x, fc, bn, relu=True, training=False)
+
+    def _head(self, name, x):
+        self.last_plan[name] = self.plan[name]
+        return self._run_head(name, x, self._eval_head)
 
     def _tnet(self, name, xr, trans, k):
         g, _ = self._trunk(name, xr, trans)

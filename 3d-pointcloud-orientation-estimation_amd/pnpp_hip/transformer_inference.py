@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .inference import Predictor
+from .inference import Predictor, planes_to_float32
 
 # the form Predictor(model) runs: per launch at 8 x 4096 pnpp_attention_infer takes 318 us against 553 us for pnpp_attention_fwd
 # (kernel trace), far outside the spread of the timing windows
@@ -69,15 +69,9 @@ class TransformerPredictor(Predictor):
             raise ValueError(f"attention={attention!r}: the forms are {', '.join(repr(a) for a in self.ATTENTION_FORMS)}")
         self.attention = attention
         self.last_attention: Optional[str] = None   # what the latest fused call ran
-        p = next(model.parameters())
-        if not p.is_cuda:
-            raise RuntimeError(f"the model is on '{p.device}': the pnpp HIP operators run on an AMD GPU only "
-                               "(no CPU fallback exists in this package)")
-        self.model = model
-        self.device = p.device
+        self._bind(model)
         self.depth = len(model.transformer.layers)
         self.stages = ["head"] + [f"layers.{l}" for l in range(self.depth)] + ["pool"]
-        self._bufs: Dict[tuple, torch.Tensor] = {}
         self._snap: Optional[nn.Module] = None
         self._blobs: List[torch.Tensor] = []   # one per layer: no allocation larger than a layer's planes
         d = self._desc(1, 128, 1)
@@ -85,8 +79,8 @@ class TransformerPredictor(Predictor):
         self.refused = None if nbytes else (self._why or L.last_error())   # why the kernels do not take the model
         if nbytes:
             self._blobs = [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
-        self.plan: Dict[str, str] = {s: "fused" if nbytes else "eval-path" for s in self.stages}
-        self.last_plan: Dict[str, str] = dict(self.plan)
+        self.plan.update({s: "fused" if nbytes else "eval-path" for s in self.stages})
+        self.last_plan.update(self.plan)
         self.refresh()
 
     # ---- construction ----------------------------------------------------------------------------------------------------
@@ -168,18 +162,10 @@ class TransformerPredictor(Predictor):
         if name == "input_proj":
             return f32(woff.value, E * ld.value).view(E, ld.value), f32(boff.value, E)
         rows = {"in_proj": 3 * E, "linear1": d.F}.get(name, E)
-        # three bf16 planes (W = high + middle + low, exactly), each fragment-major [rows/32][ld/16][2][32][8]
-        w = blob[woff.value:woff.value + 6 * rows * ld.value].view(torch.bfloat16).view(3, rows // 32, ld.value // 16, 2, 32, 8)
-        w = w.permute(0, 1, 4, 2, 3, 5).reshape(3, rows, ld.value).float()
-        return (w[0] + w[1]) + w[2], f32(boff.value, rows)
+        return planes_to_float32(blob, woff.value, rows, ld.value), f32(boff.value, rows)
 
-    def persistent_bytes(self) -> int:
-        """device memory the Predictor holds between calls: the planes, the model copy, the reusable buffers"""
-        return sum(t.numel() * t.element_size() for t in self.held_tensors())
-
-    def held_tensors(self) -> List[torch.Tensor]:
-        ts = list(self._blobs) + list(self._bufs.values())
-        return ts + list(self._snap.parameters()) + list(self._snap.buffers())
+    def _blob_tensors(self):
+        return list(self._blobs)
 
     # ---- one call --------------------------------------------------------------------------------------------------------
     def _sizes(self, xyz):
