@@ -4,9 +4,7 @@
 // The matrix products run on the same fused MFMA GEMM / dW kernels as the set-abstraction layers;
 // the row/column normalisation passes here touch only M x N elements (M = batch), so they are plain
 // wave-per-row / lane-per-column kernels with float64 accumulation.
-#include <stdlib.h>
-
-#include "kernels.h"
+#include "launch.h"
 
 namespace pnpp {
 
@@ -803,7 +801,7 @@ static int fc_backward_impl(const pnpp_fc_desc *d, const pnpp_fc_bwd_args *a, hi
         const int bn = d->norm == PNPP_NORM_BATCH;
         // head blocks of at most 32 rows with a gradient to pass on: dz is never written (fc_bwd_fused_kernel); PNPP_NO_FC_FUSED=1 keeps
         // the two launches
-        static const bool fused_on = !(getenv("PNPP_NO_FC_FUSED") && atoi(getenv("PNPP_NO_FC_FUSED")) != 0);
+        static const bool fused_on = env_int("PNPP_NO_FC_FUSED", 0) == 0;
         if (fused_on && a->dx && d->M <= 32 && d->N >= 256 && d->N % 2 == 0 && !(bn && d->training && stats_sync_on())) {
             FcFusedArgs P;
             P.dy = a->dy, P.z = sv.z, P.mask = a->mask, P.drop_scale = d->drop_scale, P.relu = d->relu, P.bn = bn, P.training = d->training;
@@ -817,18 +815,15 @@ static int fc_backward_impl(const pnpp_fc_desc *d, const pnpp_fc_bwd_args *a, hi
             const size_t lds_dx = (img > part ? img : part) * sizeof(float), lds_dw = (size_t)(32 * 32 + 32 * 128 + 2 * 32 * 32) * sizeof(float);
             const size_t lds = lds_dx > lds_dw ? lds_dx : lds_dw;
             if (lds <= 160 * 1024) {
-                static size_t granted[3] = {0, 0, 0};
-                auto go = [&](auto kfn, int slot) {
-                    if (lds > 48 * 1024 && lds > granted[slot]) {
-                        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                        granted[slot] = lds;
-                    }
+                auto go = [&](auto tc) {
+                    constexpr auto kfn = fc_bwd_fused_kernel<tc()>;
+                    grant_lds<kfn>(lds);
                     hipLaunchKernelGGL(kfn, dim3(P.g1 + P.gx2 * gy2), dim3(1024), lds, st, P);
                 };
                 ProfScope ps(st, "fc_bwd_fused_kernel M=%d N=%d K=%d grid=%d+%d", d->M, d->N, d->K, P.g1, P.gx2 * gy2);
-                if (tpc == 4) go(fc_bwd_fused_kernel<4>, 0);
-                else if (tpc == 2) go(fc_bwd_fused_kernel<2>, 1);
-                else go(fc_bwd_fused_kernel<1>, 2);
+                if (tpc == 4) go(mode_c<4>{});
+                else if (tpc == 2) go(mode_c<2>{});
+                else go(mode_c<1>{});
                 PNPP_CHECK_LAUNCH("fc_backward(fused)");
                 return PNPP_OK;
             }

@@ -23,7 +23,7 @@
 // relu(bn(z_{l-1})), is 8 consecutive epilogue registers per MFMA operand: each lane stores its two operands (16 bytes
 // each) into a small [64 k][8 chunks] image of the same form, so that every wave can contract over all 64 rows of the
 // tile and a wave owns whole dW tiles (half as many accumulators as with per-half partial sums, one partial per worker).
-#include "kernels.h"
+#include "launch.h"
 #include "split_prims.h"
 
 namespace pnpp {
@@ -376,20 +376,13 @@ static int launch_wsb_one(const AOperand &A, const BOperand &B, int M, int Nout,
     int per_cu = (int)((160 * 1024) / lds);
     const int cap_cu = FDW ? 2 : 4;          // __launch_bounds__(256, 2): the fused kernels need ~200 registers, the others < 128
     if (per_cu > cap_cu) per_cu = cap_cu;
-    int workers = (256 * per_cu) / ncol;
-    if (workers > tiles) workers = tiles;
-    if (workers > kMaxStatBlocks) workers = kMaxStatBlocks;
-    if (workers < 1) workers = 1;
+    const int workers = worker_count((256 * per_cu) / ncol, tiles, 1);
     if (nslab) *nslab = workers;
     if (dw_slabs) *dw_slabs = FDW ? workers : 0;
     ProfScope ps(st, "gemm_wsb_kernel<%d,64,64,A%d,E%d%s> M=%d N=%d K=%d grid=%dx1", KD, AM, EM, FDW ? ",dW" : "", M, Nout, KD,
                  workers * ncol);
-    auto kfn = gemm_wsb_kernel<KD, AM, EM, FDW>;
-    static size_t lds_granted = 0;
-    if (lds > 48 * 1024 && lds > lds_granted) {
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        lds_granted = lds;
-    }
+    constexpr auto kfn = gemm_wsb_kernel<KD, AM, EM, FDW>;
+    grant_lds<kfn>(lds);
     hipLaunchKernelGGL(kfn, dim3(workers * ncol), dim3(256), lds, st, A, B, M, Nout, ncol, E);
     PNPP_CHECK_LAUNCH("gemm_wsb");
     return PNPP_OK;

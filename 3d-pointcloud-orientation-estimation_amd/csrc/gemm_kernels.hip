@@ -13,20 +13,14 @@
 // MFMA operand maps (wave64, 32x32x2 f32):  A: lane l holds A[i=l&31][k=l>>5]
 //                                           B: lane l holds B[k=l>>5][j=l&31]
 //                                           D: lane l, reg r: col j=l&31, row i=(r&3)+8*(r>>2)+4*(l>>5)
-#include <stdlib.h>
-
-#include "kernels.h"
+#include "launch.h"
 
 namespace pnpp {
 
 // A/B switch read once per process (PNPP_NO_MID=1: the group_all level stays on the 32 x 32 split-K kernels)
 static bool mid_tiles_on() {
-    static int cached = -1;
-    if (cached < 0) {
-        const char *v = getenv("PNPP_NO_MID");
-        cached = (v && atoi(v) != 0) ? 0 : 1;
-    }
-    return cached != 0;
+    static const bool on = env_int("PNPP_NO_MID", 0) == 0;
+    return on;
 }
 
 constexpr int KC = 32;       // reduction-dim chunk staged in LDS per step
@@ -1435,20 +1429,13 @@ static int launch_ws_one(const AOperand &A, const BOperand &B, int M, int Nout, 
     int per_cu = (int)((160 * 1024) / lds);
     if (per_cu > 3) per_cu = 3;
     if (per_cu < 1) per_cu = 1;
-    int workers = (256 * per_cu) / ncol;
-    if (workers > tiles) workers = tiles;
-    if (workers > kMaxStatBlocks) workers = kMaxStatBlocks;
-    if (workers < 1) workers = 1;
+    const int workers = worker_count((256 * per_cu) / ncol, tiles, 1);
     if (nslab) *nslab = workers;
     if (dw_slabs) *dw_slabs = FDW ? workers : 0;
     ProfScope ps(st, "gemm_ws_kernel<%d,%d,%d,A%d,E%d%s> M=%d N=%d K=%d grid=%dx1", KD, BM, BN, AM, EM, FDW ? ",dW" : "", M, Nout,
                  KD, workers * ncol);
-    auto kfn = gemm_ws_kernel<KD, BM, BN, WM, WN, AM, EM, FDW>;
-    static size_t lds_granted = 0;  // per instantiation; the attribute call is a host-side setting, made once per size
-    if (lds > 48 * 1024 && lds > lds_granted) {
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        lds_granted = lds;
-    }
+    constexpr auto kfn = gemm_ws_kernel<KD, BM, BN, WM, WN, AM, EM, FDW>;
+    grant_lds<kfn>(lds);
     hipLaunchKernelGGL(kfn, dim3(workers * ncol), dim3(256), lds, st, A, B, M, Nout, ncol, E);
     PNPP_CHECK_LAUNCH("gemm_ws");
     return PNPP_OK;
@@ -2528,10 +2515,7 @@ bool try_launch_fc_dx_dw(const float *dz, const float *w, const float *x, int M,
     const int g1 = cdiv(K, 32), gx2 = cdiv(K, 128), gy2 = cdiv(N, 32);
     ProfScope ps(st, "fc_dx_dw_kernel M=%d N=%d K=%d grid=%d+%d", M, N, K, g1, gx2 * gy2);
     hipLaunchKernelGGL(fc_dx_dw_kernel, dim3(g1 + gx2 * gy2), dim3(1024), 0, st, A, B, M, K, N, E, g1, x, N, K, gx2, dw);
-    if (hipGetLastError() != hipSuccess) {
-        set_error("fc_dx_dw: launch failed");
-        *rc = PNPP_ERR_LAUNCH;
-    }
+    check_launch("fc_dx_dw", rc);
     return true;
 }
 
@@ -2572,10 +2556,7 @@ bool try_launch_da_dw(const AOperand &dz, const BOperand &Win, int M, int Nout, 
         else PNPP_DADW(E_MASK_STATS, A_CONCAT);
     }
 #undef PNPP_DADW
-    if (hipGetLastError() != hipSuccess) {
-        set_error("da_dw: launch failed");
-        *rc = PNPP_ERR_LAUNCH;
-    }
+    check_launch("da_dw", rc);
     return true;
 }
 
@@ -3336,11 +3317,6 @@ int launch_fill_zero(void *p, size_t bytes, hipStream_t st) {
     return PNPP_OK;
 }
 
-#ifdef PNPP_STAMPS
-#define PNPP_STAMPS_BIT 64u
-#else
-#define PNPP_STAMPS_BIT 0u
-#endif
-unsigned gemm_build_flags() { return ((PNPP_WS_EXP_NO_MFMA != 0) ? 1u : 0u) | PNPP_STAMPS_BIT; }
+unsigned gemm_build_flags() { return ((PNPP_WS_EXP_NO_MFMA != 0) ? 1u : 0u) | stamps_bit(); }
 
 }  // namespace pnpp

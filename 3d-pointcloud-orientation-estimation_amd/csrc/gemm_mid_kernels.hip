@@ -24,9 +24,7 @@
 // forward  Z = a W^T : a row operand, W [n][k] row operand.     dA = dZ W : dZ row operand, W [k][n] column operand.
 // dW = dZ^T a        : both column operands (reduction over rows).
 // Both operands of an MFMA step must carry the same reduction index in the same lane half; k(t, lh, u) = 8 t + 4 lh + u for all.
-#include <stdlib.h>
-
-#include "kernels.h"
+#include "launch.h"
 #include "split_prims.h"
 
 namespace pnpp {
@@ -575,14 +573,7 @@ __global__ void __launch_bounds__(512, 1) gemm_mid3_kernel(const MidGemm G, int 
 
 static bool mid_ptr_ok(const float *p, int ld) { return p && (ld & 3) == 0 && ((uintptr_t)p & 15) == 0; }
 
-template <typename K>
-static void mid_grant_lds(K kfn) {
-    static bool done = false;   // per instantiation
-    if (!done) {
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MID_LDS_BYTES);
-        done = true;
-    }
-}
+static_assert(MID_LDS_BYTES > 48 * 1024 && MID3_LDS_BYTES > 48 * 1024, "always above what a launch gets unasked");
 
 static bool mid_gemm_shape_ok(int M, int Nout, int Kd) {
     if (M < 512 || M > 8192 || M % MID_T || Nout % MID_T || Kd % MID_T) return false;
@@ -605,44 +596,25 @@ bool try_launch_mid_gemm(const AOperand &A, const BOperand &B, int M, int Nout, 
     MidGemm G{A.a, A.lda, A.scale, A.shift, B.b, B.ldb, M, Nout, Kd, E};
     if (nslab) *nslab = M / MID_T;
     const int tn = Nout / MID_T, grid = (M / MID_T) * tn;
-    static const bool mid3_on = !(getenv("PNPP_MID3") && atoi(getenv("PNPP_MID3")) == 0);   // PNPP_MID3=0: the float32-MFMA tile kernel (A/B runs)
+    static const bool mid3_on = env_int("PNPP_MID3", 1) != 0;   // PNPP_MID3=0: the float32-MFMA tile kernel (A/B runs)
     if (mid3_on && split_products() && matmul_precision() == 0 && E.mode == E_STORE_STATS && Kd >= 512 && (Kd & 255) == 0 && (unsigned long long)M * (unsigned)A.lda * 4ull < 0x7ffffff0ull &&
         (unsigned long long)Nout * (unsigned)B.ldb * 4ull < 0x7ffffff0ull) {   // float32 products from exact bf16 splits (the default)
         ProfScope ps(st, "gemm_mid3_kernel<A%d,E%d> M=%d N=%d K=%d grid=%d", A.mode, E.mode, M, Nout, Kd, grid);
-#define PNPP_MID3(AX, EMV)                                                                                                       \
-    {                                                                                                                            \
-        static bool granted = false;                                                                                             \
-        if (!granted) {                                                                                                          \
-            (void)hipFuncSetAttribute((const void *)gemm_mid3_kernel<AX, EMV>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                      (int)MID3_LDS_BYTES);                                                                      \
-            granted = true;                                                                                                      \
-        }                                                                                                                        \
-        hipLaunchKernelGGL((gemm_mid3_kernel<AX, EMV>), dim3(grid), dim3(512), MID3_LDS_BYTES, st, G, tn);                       \
-    }
-        if (A.mode == A_BNRELU) PNPP_MID3(A_BNRELU, E_STORE_STATS) else PNPP_MID3(A_PLAIN, E_STORE_STATS)
-#undef PNPP_MID3
-        if (hipGetLastError() != hipSuccess) {
-            set_error("gemm_mid3: launch failed");
-            *rc = PNPP_ERR_LAUNCH;
-        }
+        dispatch_mode<A_BNRELU, A_PLAIN>(A.mode, [&](auto am) {
+            constexpr auto kfn = gemm_mid3_kernel<am(), E_STORE_STATS>;
+            grant_lds<kfn>(MID3_LDS_BYTES);
+            hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), MID3_LDS_BYTES, st, G, tn);
+        });
+        check_launch("gemm_mid3", rc);
         return true;
     }
     ProfScope ps(st, "gemm_mid_kernel<A%d,E%d,T1> M=%d N=%d K=%d grid=%d", A.mode, E.mode, M, Nout, Kd, grid);
-#define PNPP_MID(AX, EMV)                                                                              \
-    {                                                                                                  \
-        mid_grant_lds(gemm_mid_kernel<AX, true, EMV>);                                                 \
-        hipLaunchKernelGGL((gemm_mid_kernel<AX, true, EMV>), dim3(grid), dim3(256), MID_LDS_BYTES, st, G, tn); \
-    }
-    if (A.mode == A_BNRELU) {
-        if (E.mode == E_STORE_STATS) PNPP_MID(A_BNRELU, E_STORE_STATS) else PNPP_MID(A_BNRELU, E_STORE)
-    } else {
-        if (E.mode == E_STORE_STATS) PNPP_MID(A_PLAIN, E_STORE_STATS) else PNPP_MID(A_PLAIN, E_STORE)
-    }
-#undef PNPP_MID
-    if (hipGetLastError() != hipSuccess) {
-        set_error("gemm_mid: launch failed");
-        *rc = PNPP_ERR_LAUNCH;
-    }
+    dispatch_ae(A.mode, E.mode, [&](auto am, auto em) {
+        constexpr auto kfn = gemm_mid_kernel<am(), true, em()>;
+        grant_lds<kfn>(MID_LDS_BYTES);
+        hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), MID_LDS_BYTES, st, G, tn);
+    });
+    check_launch("gemm_mid", rc);
     return true;
 }
 
@@ -678,21 +650,14 @@ bool try_launch_mid_da_dw(const AOperand &dz, const BOperand &W, int M, int Nout
     const int tn = Nout / MID_T, g1 = (M / MID_T) * tn, tc = Nc / MID_T, tk = Kp / MID_T, g2 = tc * tk * nsplit;
     ProfScope ps(st, "da_dw_mid_kernel<E%d,A%d> M=%d | dA N=%d K=%d grid=%d | dW N=%d K=%d split=%d grid=%d", E.mode, a2.mode, M, Nout, Kd, g1,
                  Nc, Kp, nsplit, g2);
-#define PNPP_MIDP(EMV, AX)                                                                                         \
-    {                                                                                                              \
-        mid_grant_lds(da_dw_mid_kernel<EMV, AX>);                                                                  \
-        hipLaunchKernelGGL((da_dw_mid_kernel<EMV, AX>), dim3(g1 + g2), dim3(256), MID_LDS_BYTES, st, G, tn, g1, D, tc, tk); \
-    }
-    if (E.mode == E_STORE) {
-        if (a2.mode == A_BNRELU) PNPP_MIDP(E_STORE, A_BNRELU) else PNPP_MIDP(E_STORE, A_PLAIN)
-    } else {
-        if (a2.mode == A_BNRELU) PNPP_MIDP(E_MASK_STATS, A_BNRELU) else PNPP_MIDP(E_MASK_STATS, A_PLAIN)
-    }
-#undef PNPP_MIDP
-    if (hipGetLastError() != hipSuccess) {
-        set_error("da_dw_mid: launch failed");
-        *rc = PNPP_ERR_LAUNCH;
-    }
+    dispatch_mode<E_STORE, E_MASK_STATS>(E.mode, [&](auto em) {
+        dispatch_mode<A_BNRELU, A_PLAIN>(a2.mode, [&](auto am) {
+            constexpr auto kfn = da_dw_mid_kernel<em(), am()>;
+            grant_lds<kfn>(MID_LDS_BYTES);
+            hipLaunchKernelGGL(kfn, dim3(g1 + g2), dim3(256), MID_LDS_BYTES, st, G, tn, g1, D, tc, tk);
+        });
+    });
+    check_launch("da_dw_mid", rc);
     return true;
 }
 
@@ -705,12 +670,6 @@ unsigned mid3_build_flags() { return 0u; }
 }  // namespace pnpp
 
 #ifdef MID3_STAMPS
-extern "C" int pnpp_debug_mid3_stamps(unsigned long long *out8, int reset) {
-    if (reset) {
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(pnpp::g_mid3_stamps), z, sizeof(z));
-    }
-    if (out8) (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(pnpp::g_mid3_stamps), 8 * sizeof(unsigned long long));
-    return 0;
-}
+// (tools/mid3_stamps.py resets with a null buffer and reads after a device synchronisation: the common read-out serves it)
+extern "C" int pnpp_debug_mid3_stamps(unsigned long long *out8, int reset) { return pnpp::stamps_io<8>(&pnpp::g_mid3_stamps, out8, reset); }
 #endif

@@ -36,9 +36,7 @@
 // Image layout: 16-byte group g of row r at g ^ sp_swz_row(r) (split_prims.h: conflict-free for the row reads and for the transposed
 // reads).  Addresses: ONE lane-offset register per stream, everything uniform in the instructions' scalar offsets -- a
 // spilled address register is reloaded behind s_waitcnt vmcnt(0) and serialises every load behind it (measured: 74 % of a wave's time).
-#include <stdlib.h>
-
-#include "kernels.h"
+#include "launch.h"
 #include "split_prims.h"
 
 namespace pnpp {
@@ -547,13 +545,9 @@ static void wsd3_launch(const AOperand &A, const BOperand &B, int M, int Nout, c
     constexpr size_t main_b = Wsd3Lds<KD, BN, KD != 256>::END;   // (the hand-off area exists for K = 128 only)
     constexpr size_t red_b = (size_t)(KD / 32) * (BN / 32) * 4 * 4 * 64 * 16 + (size_t)4 * 2 * BN * 8;
     constexpr size_t lds = main_b > red_b ? main_b : red_b;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kfn = gemm_wsd3_kernel<KD, BN, AM>;
-    static bool granted = false;
-    if (!granted) {
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        granted = true;
-    }
+    static_assert(lds > 48 * 1024 && lds <= 160 * 1024, "LDS budget (always above what a launch gets unasked)");
+    constexpr auto kfn = gemm_wsd3_kernel<KD, BN, AM>;
+    grant_lds<kfn>(lds);
     hipLaunchKernelGGL(kfn, dim3(workers * ncol), dim3(512), lds, st, A, B.b, B.ldb, M, Nout, ncol, E);
 }
 
@@ -577,33 +571,23 @@ bool try_launch_wsd3(const AOperand &A, const BOperand &B, int M, int Nout, int 
     *rc = PNPP_OK;
     if (!dw_slabs || !wsd3_applies(A, B, M, Nout, Kd, E)) return false;
     const int nstrips = M / 32, ncol = Nout / 32;
-    int workers = 256 / ncol;   // one workgroup of eight waves per CU
-    if (workers * 4 > nstrips) workers = (nstrips + 3) / 4;
-    if (workers > kMaxStatBlocks) workers = kMaxStatBlocks;
+    const int workers = worker_count(256 / ncol, nstrips, 4);   // one workgroup of eight waves per CU
     if (nslab) *nslab = workers;
     *dw_slabs = workers;
     ProfScope ps(st, "gemm_wsd3_kernel<%d,32,A%d> M=%d N=%d K=%d grid=%dx1", Kd, A.mode, M, Nout, Kd, workers * ncol);
     if (Kd == 256) wsd3_launch<256, 32, A_DZ_POOL>(A, B, M, Nout, E, workers, ncol, st);
     else if (A.mode == A_DZ_POOL) wsd3_launch<128, 32, A_DZ_POOL>(A, B, M, Nout, E, workers, ncol, st);
     else wsd3_launch<128, 32, A_DZ>(A, B, M, Nout, E, workers, ncol, st);
-    if (hipGetLastError() != hipSuccess) {
-        set_error("gemm_wsd3: launch failed");
-        *rc = PNPP_ERR_LAUNCH;
-    }
+    check_launch("gemm_wsd3", rc);
     return true;
 }
 
-#ifdef PNPP_STAMPS
-#define WD3_STAMPS_BIT 64u
-#else
-#define WD3_STAMPS_BIT 0u
-#endif
 #ifdef WD3_PRIO
 #define WD3_PRIO_BIT 256u
 #else
 #define WD3_PRIO_BIT 0u
 #endif
-unsigned wsd3_build_flags() { return WD3_STAMPS_BIT | WD3_PRIO_BIT; }
+unsigned wsd3_build_flags() { return stamps_bit() | WD3_PRIO_BIT; }
 
 int wsd3_timeouts() {
     int v = 0;
@@ -615,14 +599,5 @@ int wsd3_timeouts() {
 
 extern "C" int pnpp_debug_wsd3_timeouts(void) { return pnpp::wsd3_timeouts(); }
 #ifdef PNPP_STAMPS
-extern "C" int pnpp_debug_wsd3_stamps(unsigned long long *out32, int reset) {
-    if (reset) {
-        unsigned long long z[32] = {0};
-        hipMemcpyToSymbol(HIP_SYMBOL(pnpp::g_wsd3_stamps), z, sizeof(z));
-    } else {
-        hipDeviceSynchronize();
-        hipMemcpyFromSymbol(out32, HIP_SYMBOL(pnpp::g_wsd3_stamps), 32 * sizeof(unsigned long long));
-    }
-    return 0;
-}
+extern "C" int pnpp_debug_wsd3_stamps(unsigned long long *out32, int reset) { return pnpp::stamps_io<32>(&pnpp::g_wsd3_stamps, out32, reset); }
 #endif

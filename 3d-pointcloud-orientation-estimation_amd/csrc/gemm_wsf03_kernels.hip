@@ -14,9 +14,7 @@
 // (channel order 16 s + 8 (e >> 2) + 4 lh + (e & 3), e = 0 .. 7; the weight image is laid out in the same order): ReLU, split into three
 // bf16 pieces in registers, six MFMAs of 32 cycles per 16 channels and 32 output columns -- 48 per strip, no strip image, and the
 // weight fragments are the only LDS reads of the loop.
-#include <stdlib.h>
-
-#include "kernels.h"
+#include "launch.h"
 #include "split_prims.h"
 #include "wsf0_args.h"
 
@@ -245,7 +243,7 @@ gemm_wsf03_kernel(const Wsf0Args P) {
 }
 
 bool wsf03_enabled() {
-    static const bool on = !(getenv("PNPP_WSF03") && atoi(getenv("PNPP_WSF03")) == 0);   // PNPP_WSF03=0: gemm_wsf0_kernel (float32 MFMA; A/B runs)
+    static const bool on = env_int("PNPP_WSF03", 1) != 0;   // PNPP_WSF03=0: gemm_wsf0_kernel (float32 MFMA; A/B runs)
     return on && split_products();
 }
 void launch_wsf03(const Wsf0Args &P, int workers, int epilogue_mode, hipStream_t st) {

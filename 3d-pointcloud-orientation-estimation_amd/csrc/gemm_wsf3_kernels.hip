@@ -10,9 +10,7 @@
 // K = 64: 4 waves, 24 + 48 = 72 KB, two workgroups per CU; K = 128: 8 waves, 48 + 96 = 144 KB, one workgroup per CU -- eight waves per
 // CU either way: while one wave of a SIMD splits and stages (VALU), the other multiplies (an MFMA holds the vector issue for 8 of its
 // 32 cycles only).
-#include <stdlib.h>
-
-#include "kernels.h"
+#include "launch.h"
 #include "split_prims.h"
 
 namespace pnpp {
@@ -261,10 +259,7 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
 // (this file, gemm_wsd3_kernels.hip); 0: on v_mfma_f32_32x32x2_f32 (PNPP_SPLIT_PRODUCTS=0 / pnpp_set_split_products)
 static int g_split_products = -1;
 int split_products() {
-    if (g_split_products < 0) {
-        const char *v = getenv("PNPP_SPLIT_PRODUCTS");
-        g_split_products = (v && atoi(v) == 0) ? 0 : 1;
-    }
+    if (g_split_products < 0) g_split_products = env_int("PNPP_SPLIT_PRODUCTS", 1) != 0;
     return g_split_products;
 }
 void set_split_products(int on) { g_split_products = on ? 1 : 0; }
@@ -273,12 +268,8 @@ template <int KD, int NW, int NT, int AX, int EM>
 static void wsf3_launch(const AOperand &A, const BOperand &B, int M, int Nout, const Epilogue &E, int workers, int ncol, hipStream_t st) {
     constexpr size_t lds = (size_t)3 * (NT * 32) * KD * 2 + (size_t)NW * 3 * 32 * 128;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kfn = gemm_wsf3_kernel<KD, NW, NT, AX, EM>;
-    static bool granted = false;
-    if (lds > 48 * 1024 && !granted) {
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        granted = true;
-    }
+    constexpr auto kfn = gemm_wsf3_kernel<KD, NW, NT, AX, EM>;
+    grant_lds<kfn>(lds);
     hipLaunchKernelGGL(kfn, dim3(workers * ncol), dim3(NW * 64), lds, st, A.a, A.lda, A.scale, A.shift, B.b, B.ldb, M, Nout, ncol, E);
 }
 
@@ -289,34 +280,17 @@ bool try_launch_wsf3(const AOperand &A, const BOperand &B, int M, int Nout, int 
     // two column tiles per wave.  (PNPP_WSF3_NT4=1: four tiles per wave for K = 64 with 128 or more columns -- the strip is read, transformed
     // and split once for 128 columns, eight waves in one workgroup per CU -- measured 23.2 - 23.6 us against 22.6 us on the sa1 launch: the
     // launch is bound by its 67 MB of stores and by latency, not by the vector work the form saves)
-    static const bool nt4_on = getenv("PNPP_WSF3_NT4") && atoi(getenv("PNPP_WSF3_NT4")) != 0;
+    static const bool nt4_on = env_int("PNPP_WSF3_NT4", 0) != 0;
     const bool nt4 = nt4_on && Kd == 64 && Nout % 128 == 0;
     const int BNsel = nt4 ? 128 : 64, ncol = Nout / BNsel, nstrips = M / 32;
     const int NW = (Kd == 64 && !nt4) ? 4 : 8;
-    int workers = (NW == 4 ? 512 : 256) / ncol;   // eight waves per CU either way
-    if (workers * NW > nstrips) workers = (nstrips + NW - 1) / NW;
-    if (workers > kMaxStatBlocks) workers = kMaxStatBlocks;
-    if (workers < 1) workers = 1;
+    const int workers = worker_count((NW == 4 ? 512 : 256) / ncol, nstrips, NW);   // eight waves per CU either way
     if (nslab) *nslab = workers;
     ProfScope ps(st, "gemm_wsf3_kernel<%d,A%d,E%d> M=%d N=%d K=%d grid=%dx1", Kd, A.mode, E.mode, M, Nout, Kd, workers * ncol);
-#define PNPP_WSF3(KDV, NWV, NTV)                                                                                                    \
-    {                                                                                                                               \
-        if (A.mode == A_BNRELU) {                                                                                                   \
-            if (E.mode == E_STORE_STATS) wsf3_launch<KDV, NWV, NTV, A_BNRELU, E_STORE_STATS>(A, B, M, Nout, E, workers, ncol, st);  \
-            else wsf3_launch<KDV, NWV, NTV, A_BNRELU, E_STORE>(A, B, M, Nout, E, workers, ncol, st);                                \
-        } else {                                                                                                                    \
-            if (E.mode == E_STORE_STATS) wsf3_launch<KDV, NWV, NTV, A_PLAIN, E_STORE_STATS>(A, B, M, Nout, E, workers, ncol, st);   \
-            else wsf3_launch<KDV, NWV, NTV, A_PLAIN, E_STORE>(A, B, M, Nout, E, workers, ncol, st);                                 \
-        }                                                                                                                           \
-    }
-    if (Kd == 64 && nt4) PNPP_WSF3(64, 8, 4)
-    else if (Kd == 64) PNPP_WSF3(64, 4, 2)
-    else PNPP_WSF3(128, 8, 2)
-#undef PNPP_WSF3
-    if (hipGetLastError() != hipSuccess) {
-        set_error("gemm_wsf3: launch failed");
-        *rc = PNPP_ERR_LAUNCH;
-    }
+    if (Kd == 64 && nt4) dispatch_ae(A.mode, E.mode, [&](auto am, auto em) { wsf3_launch<64, 8, 4, am(), em()>(A, B, M, Nout, E, workers, ncol, st); });
+    else if (Kd == 64) dispatch_ae(A.mode, E.mode, [&](auto am, auto em) { wsf3_launch<64, 4, 2, am(), em()>(A, B, M, Nout, E, workers, ncol, st); });
+    else dispatch_ae(A.mode, E.mode, [&](auto am, auto em) { wsf3_launch<128, 8, 2, am(), em()>(A, B, M, Nout, E, workers, ncol, st); });
+    check_launch("gemm_wsf3", rc);
     return true;
 }
 

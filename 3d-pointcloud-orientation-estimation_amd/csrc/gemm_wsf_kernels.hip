@@ -15,9 +15,7 @@
 // reads; the only barriers of the kernel are the one behind the weight panel and the one in front of the final statistics reduction.
 // The operand transform is done once per strip for ALL NT x 32 columns (the 64 x 64 form redoes it per 64-column block), and a strip
 // IS a neighbourhood (nsample = 32), so the pooled extreme of a column is a reduction over one accumulator tile.
-#include <stdlib.h>
-
-#include "kernels.h"
+#include "launch.h"
 #include "split_prims.h"
 
 namespace pnpp {
@@ -247,23 +245,15 @@ gemm_wsf_kernel(const float *__restrict__ A, int lda, const float *__restrict__ 
 
 // A/B switch: PNPP_NO_WSF=1 keeps the forward products on gemm_ws_kernel
 static bool wsf_on() {
-    static int cached = -1;
-    if (cached < 0) {
-        const char *v = getenv("PNPP_NO_WSF");
-        cached = (v && atoi(v) != 0) ? 0 : 1;
-    }
-    return cached != 0;
+    static const bool on = env_int("PNPP_NO_WSF", 0) == 0;
+    return on;
 }
 
 template <int KD, int NT, int AX, int EM>
 static void wsf_launch(const AOperand &A, const BOperand &B, int M, int Nout, const Epilogue &E, int workers, int ncol, hipStream_t st) {
     constexpr size_t lds = ((size_t)NT * 32 * KD + 4 * 32 * 64) * sizeof(float);
-    auto kfn = gemm_wsf_kernel<KD, NT, AX, EM>;
-    static bool granted = false;
-    if (lds > 48 * 1024 && !granted) {
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        granted = true;
-    }
+    constexpr auto kfn = gemm_wsf_kernel<KD, NT, AX, EM>;
+    grant_lds<kfn>(lds);
     hipLaunchKernelGGL(kfn, dim3(workers * ncol), dim3(256), lds, st, A.a, A.lda, A.scale, A.shift, B.b, B.ldb, M, Nout, ncol, E);
 }
 
@@ -284,54 +274,23 @@ bool try_launch_wsf(const AOperand &A, const BOperand &B, int M, int Nout, int K
     // column tiles per wave: 4 (128 columns) for K = 64 when the width allows it, else 2; two workgroups per CU either way (64 KB)
     // (NT = 4 for K = 64, N = 128 -- the operand transform done once for all 128 columns -- measured 32.8 us against 31.1 us for the
     //  64 x 64 kernel: 233 registers and a 64-store epilogue per strip; PNPP_WSF_NT4=1 selects it)
-    static const bool nt4 = getenv("PNPP_WSF_NT4") && atoi(getenv("PNPP_WSF_NT4")) != 0;
+    static const bool nt4 = env_int("PNPP_WSF_NT4", 0) != 0;
     const int NTsel = (nt4 && Kd == 64 && Nout % 128 == 0) ? 4 : 2;
     const int ncol = Nout / (NTsel * 32), nstrips = M / 32;
-    int workers = 512 / ncol;
-    if (workers * 4 > nstrips) workers = (nstrips + 3) / 4;
-    if (workers > kMaxStatBlocks) workers = kMaxStatBlocks;
-    if (workers < 1) workers = 1;
+    const int workers = worker_count(512 / ncol, nstrips, 4);
     if (nslab) *nslab = workers;
     ProfScope ps(st, "gemm_wsf_kernel<%d,%d,A%d,E%d> M=%d N=%d K=%d grid=%dx1", Kd, NTsel, A.mode, E.mode, M, Nout, Kd, workers * ncol);
-#define PNPP_WSF(KDV, NTV)                                                                                                   \
-    {                                                                                                                        \
-        if (A.mode == A_BNRELU) {                                                                                            \
-            if (E.mode == E_STORE_STATS) wsf_launch<KDV, NTV, A_BNRELU, E_STORE_STATS>(A, B, M, Nout, E, workers, ncol, st); \
-            else wsf_launch<KDV, NTV, A_BNRELU, E_STORE>(A, B, M, Nout, E, workers, ncol, st);                               \
-        } else {                                                                                                             \
-            if (E.mode == E_STORE_STATS) wsf_launch<KDV, NTV, A_PLAIN, E_STORE_STATS>(A, B, M, Nout, E, workers, ncol, st);  \
-            else wsf_launch<KDV, NTV, A_PLAIN, E_STORE>(A, B, M, Nout, E, workers, ncol, st);                                \
-        }                                                                                                                    \
-    }
-    if (Kd == 64 && NTsel == 4) PNPP_WSF(64, 4)
-    else if (Kd == 64) PNPP_WSF(64, 2)
-    else PNPP_WSF(128, 2)
-#undef PNPP_WSF
-    if (hipGetLastError() != hipSuccess) {
-        set_error("gemm_wsf: launch failed");
-        *rc = PNPP_ERR_LAUNCH;
-    }
+    if (Kd == 64 && NTsel == 4) dispatch_ae(A.mode, E.mode, [&](auto am, auto em) { wsf_launch<64, 4, am(), em()>(A, B, M, Nout, E, workers, ncol, st); });
+    else if (Kd == 64) dispatch_ae(A.mode, E.mode, [&](auto am, auto em) { wsf_launch<64, 2, am(), em()>(A, B, M, Nout, E, workers, ncol, st); });
+    else dispatch_ae(A.mode, E.mode, [&](auto am, auto em) { wsf_launch<128, 2, am(), em()>(A, B, M, Nout, E, workers, ncol, st); });
+    check_launch("gemm_wsf", rc);
     return true;
 }
 
-#ifdef PNPP_STAMPS
-#define PNPP_WSF_STAMPS_BIT 64u
-#else
-#define PNPP_WSF_STAMPS_BIT 0u
-#endif
-unsigned wsf_build_flags() { return ((WSF_EXP != 0) ? 128u : 0u) | PNPP_WSF_STAMPS_BIT; }
+unsigned wsf_build_flags() { return ((WSF_EXP != 0) ? 128u : 0u) | stamps_bit(); }
 
 }  // namespace pnpp
 
 #ifdef PNPP_STAMPS
-extern "C" int pnpp_debug_wsf_stamps(unsigned long long *out32, int reset) {
-    if (reset) {
-        unsigned long long z[32] = {0};
-        hipMemcpyToSymbol(HIP_SYMBOL(pnpp::g_wsf_stamps), z, sizeof(z));
-    } else {
-        hipDeviceSynchronize();
-        hipMemcpyFromSymbol(out32, HIP_SYMBOL(pnpp::g_wsf_stamps), 32 * sizeof(unsigned long long));
-    }
-    return 0;
-}
+extern "C" int pnpp_debug_wsf_stamps(unsigned long long *out32, int reset) { return pnpp::stamps_io<32>(&pnpp::g_wsf_stamps, out32, reset); }
 #endif

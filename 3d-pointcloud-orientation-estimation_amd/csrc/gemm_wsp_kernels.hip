@@ -19,9 +19,7 @@
 // FMA per element.
 //
 // LDS of one wave executes in order, so the strip images need no barrier between their writes and their reads.
-#include <stdlib.h>
-
-#include "kernels.h"
+#include "launch.h"
 #include "split_prims.h"
 
 namespace pnpp {
@@ -416,12 +414,8 @@ gemm_wsp_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, c
 
 // A/B switch: PNPP_NO_WSP=1 keeps these launches on gemm_ws_kernel<..., dW>
 static bool wsp_on() {
-    static int cached = -1;
-    if (cached < 0) {
-        const char *v = getenv("PNPP_NO_WSP");
-        cached = (v && atoi(v) != 0) ? 0 : 1;
-    }
-    return cached != 0;
+    static const bool on = env_int("PNPP_NO_WSP", 0) == 0;
+    return on;
 }
 
 template <int KD, int AM>
@@ -430,12 +424,8 @@ static void wsp_launch(const AOperand &A, const BOperand &B, int M, const Epilog
     // tables behind the larger of the two: scale[KD], b[KD], (b W)[64], scratch [4][64] floats reused as [4][64] doubles
     constexpr size_t lds = ((main_f > red_f ? main_f : red_f) + 2 * KD + 64 + 2 * 4 * 64) * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kfn = gemm_wsp_kernel<KD, AM>;
-    static bool granted = false;
-    if (lds > 48 * 1024 && !granted) {
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        granted = true;
-    }
+    constexpr auto kfn = gemm_wsp_kernel<KD, AM>;
+    grant_lds<kfn>(lds);
     hipLaunchKernelGGL(kfn, dim3(workers), dim3(256), lds, st, A, B.b, B.ldb, M, E);
 }
 
@@ -459,37 +449,19 @@ bool try_launch_wsp(const AOperand &A, const BOperand &B, int M, int Nout, int K
     *rc = PNPP_OK;
     if (!dw_slabs || !wsp_applies(A, B, M, Nout, Kd, E)) return false;
     const int nstrips = M / 32;
-    int workers = 256;   // one workgroup per CU, one wave per SIMD
-    if (workers * 4 > nstrips) workers = (nstrips + 3) / 4;
+    const int workers = worker_count(256, nstrips, 4);   // one workgroup per CU, one wave per SIMD
     if (nslab) *nslab = workers;
     *dw_slabs = workers;
     ProfScope ps(st, "gemm_wsp_kernel<%d,A%d> M=%d N=%d K=%d grid=%dx1", Kd, A.mode, M, Nout, Kd, workers);
     wsp_launch<128, A_DZ_POOL>(A, B, M, E, workers, st);
-    if (hipGetLastError() != hipSuccess) {
-        set_error("gemm_wsp: launch failed");
-        *rc = PNPP_ERR_LAUNCH;
-    }
+    check_launch("gemm_wsp", rc);
     return true;
 }
 
-#ifdef PNPP_STAMPS
-#define PNPP_STAMPS_BIT 64u
-#else
-#define PNPP_STAMPS_BIT 0u
-#endif
-unsigned wsp_build_flags() { return ((WSP_EXP != 0) ? 2u : 0u) | PNPP_STAMPS_BIT; }
+unsigned wsp_build_flags() { return ((WSP_EXP != 0) ? 2u : 0u) | stamps_bit(); }
 
 }  // namespace pnpp
 
 #ifdef PNPP_STAMPS
-extern "C" int pnpp_debug_wsp_stamps(unsigned long long *out32, int reset) {
-    if (reset) {
-        unsigned long long z[32] = {0};
-        hipMemcpyToSymbol(HIP_SYMBOL(pnpp::g_wsp_stamps), z, sizeof(z));
-    } else {
-        hipDeviceSynchronize();
-        hipMemcpyFromSymbol(out32, HIP_SYMBOL(pnpp::g_wsp_stamps), 32 * sizeof(unsigned long long));
-    }
-    return 0;
-}
+extern "C" int pnpp_debug_wsp_stamps(unsigned long long *out32, int reset) { return pnpp::stamps_io<32>(&pnpp::g_wsp_stamps, out32, reset); }
 #endif

@@ -22,9 +22,7 @@
 //     activation image in LDS and no staging pass for it;
 //   * every operand register is re-loaded for the next tile right behind its last use (the dense stream one 16-byte group per two
 //     steps of the dA product, a z_{l-1} value behind its step of the dW product).
-#include <stdlib.h>
-
-#include "kernels.h"
+#include "launch.h"
 #include "split_prims.h"
 
 namespace pnpp {
@@ -727,12 +725,8 @@ gemm_wsq2_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
 
 // A/B switch: PNPP_NO_WSQ=1 keeps this launch on gemm_ws_kernel<256, ..., dW>
 static bool wsq_on() {
-    static int cached = -1;
-    if (cached < 0) {
-        const char *v = getenv("PNPP_NO_WSQ");
-        cached = (v && atoi(v) != 0) ? 0 : 1;
-    }
-    return cached != 0;
+    static const bool on = env_int("PNPP_NO_WSQ", 0) == 0;
+    return on;
 }
 
 bool wsq_applies(const AOperand &A, const BOperand &B, int M, int Nout, int Kd, const Epilogue &E) {
@@ -752,63 +746,35 @@ bool try_launch_wsq(const AOperand &A, const BOperand &B, int M, int Nout, int K
     if (!dw_slabs || !wsq_applies(A, B, M, Nout, Kd, E)) return false;
     constexpr int KD = 256;
     const int ncol = Nout / 64, tiles = M / 64;
-    int workers = 256 / ncol;   // one workgroup per CU
-    if (workers > tiles) workers = tiles;
-    if (workers > kMaxStatBlocks) workers = kMaxStatBlocks;
-    if (workers < 1) workers = 1;
+    const int workers = worker_count(256 / ncol, tiles, 1);   // one workgroup per CU
     if (nslab) *nslab = workers;
     *dw_slabs = workers;
     constexpr size_t lds = ((size_t)64 * KD + 64 * (KD + 4) + 2 * KD + 64 + 2 * 4 * 64) * sizeof(float);
-    static_assert(lds <= 160 * 1024, "LDS budget");
+    static_assert(lds > 48 * 1024 && lds <= 160 * 1024, "LDS budget (always above what a launch gets unasked)");
     // 1: weight panel in LDS, one image (default); 2: panel in registers, two images filled by LDS-DMA.  Form 2's stamped wave ends
     // 1.6 us earlier inside the step (5 - 7 % fewer shader cycles at a 1 - 2 % lower clock) and the launch takes the same time at every
     // batch size (49.3 / 49.8 us at 32 clouds, 93.3 k / 93.4 k clouds/s at 512): DESIGN section 9
-    static const int form = getenv("PNPP_WSQ_FORM") ? atoi(getenv("PNPP_WSQ_FORM")) : 1;
+    static const int form = env_int("PNPP_WSQ_FORM", 1);
     ProfScope ps(st, "gemm_wsq_kernel<%d,A%d%s> M=%d N=%d K=%d grid=%dx1", Kd, A.mode, form == 2 ? ",F2" : "", M, Nout, Kd, workers * ncol);
     if (form == 2) {
         constexpr size_t lds2 = ((size_t)2 * 64 * (KD + 4) + 2 * KD + 2 * 4 * 64) * sizeof(float);
-        static_assert(lds2 <= 160 * 1024, "LDS budget");
-        auto kfn2 = gemm_wsq2_kernel<KD, 128>;
-        static bool granted2 = false;
-        if (!granted2) {
-            (void)hipFuncSetAttribute((const void *)kfn2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            granted2 = true;
-        }
+        static_assert(lds2 > 48 * 1024 && lds2 <= 160 * 1024, "LDS budget");
+        constexpr auto kfn2 = gemm_wsq2_kernel<KD, 128>;
+        grant_lds<kfn2>(lds2);
         hipLaunchKernelGGL(kfn2, dim3(workers * ncol), dim3(256), lds2, st, A, B.b, B.ldb, M, ncol, E);
     } else {
-    auto kfn = gemm_wsq_kernel<KD, 128>;
-    static bool granted = false;
-    if (!granted) {
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        granted = true;
+        constexpr auto kfn = gemm_wsq_kernel<KD, 128>;
+        grant_lds<kfn>(lds);
+        hipLaunchKernelGGL(kfn, dim3(workers * ncol), dim3(256), lds, st, A, B.b, B.ldb, M, ncol, E);
     }
-    hipLaunchKernelGGL(kfn, dim3(workers * ncol), dim3(256), lds, st, A, B.b, B.ldb, M, ncol, E);
-    }
-    if (hipGetLastError() != hipSuccess) {
-        set_error("gemm_wsq: launch failed");
-        *rc = PNPP_ERR_LAUNCH;
-    }
+    check_launch("gemm_wsq", rc);
     return true;
 }
 
-#ifdef PNPP_STAMPS
-#define PNPP_STAMPS_BIT 64u
-#else
-#define PNPP_STAMPS_BIT 0u
-#endif
-unsigned wsq_build_flags() { return ((WSQ_EXP != 0) ? 8u : 0u) | ((WSQ_PLAIN != 0) ? 16u : 0u) | PNPP_STAMPS_BIT; }
+unsigned wsq_build_flags() { return ((WSQ_EXP != 0) ? 8u : 0u) | ((WSQ_PLAIN != 0) ? 16u : 0u) | stamps_bit(); }
 
 }  // namespace pnpp
 
 #ifdef PNPP_STAMPS
-extern "C" int pnpp_debug_wsq_stamps(unsigned long long *out16, int reset) {
-    if (reset) {
-        unsigned long long z[16] = {0};
-        hipMemcpyToSymbol(HIP_SYMBOL(pnpp::g_wsq_stamps), z, sizeof(z));
-    } else {
-        hipDeviceSynchronize();
-        hipMemcpyFromSymbol(out16, HIP_SYMBOL(pnpp::g_wsq_stamps), 16 * sizeof(unsigned long long));
-    }
-    return 0;
-}
+extern "C" int pnpp_debug_wsq_stamps(unsigned long long *out16, int reset) { return pnpp::stamps_io<16>(&pnpp::g_wsq_stamps, out16, reset); }
 #endif

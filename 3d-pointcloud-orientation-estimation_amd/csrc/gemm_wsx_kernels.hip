@@ -19,9 +19,7 @@
 //     moments R1 = sum rel, R2 = sum rel rel^T of the relative coordinates (nine numbers, collected here too).  xyz0_post_kernel turns
 //     those sums into dW_0, dgamma_0, dbeta_0 in float64 and reduces dW_1's partials in the same launch.
 // Four launches (fused GEMM, post_gemm, dw_xyz, slab_reduce: 61 us at 131,072 rows) become two.
-#include <stdlib.h>
-
-#include "kernels.h"
+#include "launch.h"
 #include "split_prims.h"
 #include "wsf0_args.h"
 
@@ -949,18 +947,11 @@ gemm_wsf0_kernel(const Wsf0Args P) {
 
 // A/B switch: PNPP_NO_WSX=1 keeps the level on the generic path
 static bool wsx_on() {
-    static int cached = -1;
-    if (cached < 0) {
-        const char *v = getenv("PNPP_NO_WSX");
-        cached = (v && atoi(v) != 0) ? 0 : 1;
-    }
-    return cached != 0;
+    static const bool on = env_int("PNPP_NO_WSX", 0) == 0;
+    return on;
 }
 
-size_t wsx_stat_doubles(int M) {   // what try_launch_wsx writes to its statistics workspace, at most
-    (void)M;
-    return (size_t)512 * kWsxSlab;
-}
+size_t wsx_stat_doubles() { return (size_t)kMaxStatBlocks * kWsxSlab; }   // what try_launch_wsx writes to its statistics workspace, at most
 
 bool wsx_applies(const AOperand &dz, const BOperand &W, int M, int C1, int C0, const AOperand &geo) {
     if (!wsx_on() || matmul_precision() != 0 || stats_sync_on()) return false;
@@ -1009,11 +1000,12 @@ int launch_wsf0(const AOperand &geo, int M, const float *W0, int ldw0, const dou
     P.nbt0 = nbt0, P.momentum = momentum, P.eps = eps, P.mean0 = mean0, P.istd0 = istd0, P.scale0 = scale0, P.shift0 = shift0;
     P.W1 = W1, P.ldw1 = ldw1, P.z1 = E.c, P.slab = E.slab;
     const int nstrips = M / 32;
-    static const int wmax = getenv("PNPP_WSF0_WORKERS") ? atoi(getenv("PNPP_WSF0_WORKERS")) : 512;   // (256 measured: see DESIGN section 9)
-    int workers = wmax > 0 ? wmax : 512;
-    if (workers * 4 > nstrips) workers = (nstrips + 3) / 4;
+    // PNPP_WSF0_WORKERS (256 measured: see DESIGN section 9); 0 or less: the default.  worker_count keeps it inside the statistics slab
+    static const int wmax = env_int("PNPP_WSF0_WORKERS", kMaxStatBlocks);
+    const int workers = worker_count(wmax > 0 ? wmax : kMaxStatBlocks, nstrips, 4);
     if (nslab) *nslab = workers;
     constexpr size_t lds = ((size_t)64 * 64 + 4 * 32 * 68 + 128) * sizeof(float) + (64 + 16) * sizeof(double);
+    static_assert(lds > 48 * 1024, "always above what a launch gets unasked");
     {   // float32 products from exact bf16 splits (the default): gemm_wsf03_kernels.hip
         if (wsf03_enabled()) {
             ProfScope ps3(st, "gemm_wsf03_kernel<E%d> M=%d N=64 K=64 grid=%dx1", E.mode, M, workers);
@@ -1023,16 +1015,11 @@ int launch_wsf0(const AOperand &geo, int M, const float *W0, int ldw0, const dou
         }
     }
     ProfScope ps(st, "gemm_wsf0_kernel<E%d> M=%d N=64 K=64 grid=%dx1", E.mode, M, workers);
-    static bool granted[2] = {false, false};
-    if (E.mode == E_STORE_STATS) {
-        auto kfn = gemm_wsf0_kernel<E_STORE_STATS>;
-        if (!granted[0]) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), granted[0] = true;
+    dispatch_mode<E_STORE_STATS, E_STORE>(E.mode, [&](auto em) {
+        constexpr auto kfn = gemm_wsf0_kernel<em()>;
+        grant_lds<kfn>(lds);
         hipLaunchKernelGGL(kfn, dim3(workers), dim3(256), lds, st, P);
-    } else {
-        auto kfn = gemm_wsf0_kernel<E_STORE>;
-        if (!granted[1]) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), granted[1] = true;
-        hipLaunchKernelGGL(kfn, dim3(workers), dim3(256), lds, st, P);
-    }
+    });
     PNPP_CHECK_LAUNCH("gemm_wsf0");
     return PNPP_OK;
 }
@@ -1043,12 +1030,8 @@ static void wsx_launch(const WsxArgs &P, int workers, hipStream_t st) {
                      red_f = (size_t)(KD / 32) * 2 * 4 * 4 * 64 * 4;
     constexpr size_t lds = ((main_f > red_f ? main_f : red_f) + 2 * KD + 64 + 512 + 512) * sizeof(float);
     static_assert(lds * WPC <= 160 * 1024, "LDS budget");
-    auto kfn = gemm_wsx_kernel<KD, WPC, S3, D3>;
-    static bool granted = false;
-    if (lds > 48 * 1024 && !granted) {
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        granted = true;
-    }
+    constexpr auto kfn = gemm_wsx_kernel<KD, WPC, S3, D3>;
+    grant_lds<kfn>(lds);
     hipLaunchKernelGGL(kfn, dim3(workers), dim3(256), lds, st, P);
 }
 
@@ -1058,19 +1041,18 @@ bool try_launch_wsx(const AOperand &dz, const BOperand &W, int M, int C1, int C0
                     const float *scale0, const float *shift0, float *dwslab, double *stat, int *workers_out, hipStream_t st, int *rc) {
     *rc = PNPP_OK;
     if (!wsx_applies(dz, W, M, C1, C0, geo)) return false;
-    static const int wpc = (getenv("PNPP_WSX_WPC") && atoi(getenv("PNPP_WSX_WPC")) == 2) ? 2 : 1;
+    static const int wpc = env_int("PNPP_WSX_WPC", 1) == 2 ? 2 : 1;
     const int nstrips = M / 32;
-    int workers = 256 * wpc;
-    if (workers * 4 > nstrips) workers = (nstrips + 3) / 4;
+    const int workers = worker_count(256 * wpc, nstrips, 4);
     *workers_out = workers;
     WsxArgs P;
     P.dy = dz.a, P.z = dz.z, P.cst = dz.cst, P.W = W.b, P.ldw = W.ldb, P.M = M;
     P.xyz = geo.xyz, P.centres = geo.new_xyz, P.idx = geo.idx, P.N = geo.N, P.S = geo.S;
     P.W0 = W0, P.ldw0 = ldw0, P.scale0 = scale0, P.shift0 = shift0, P.dwslab = dwslab, P.xslab = stat;
-    static const bool s3_on = !(getenv("PNPP_WSX3") && atoi(getenv("PNPP_WSX3")) == 0);   // PNPP_WSX3=0: the dA product on the float32 instruction (A/B runs)
-    const bool s3 = s3_on && split_products() && wpc == 1;   // (two workgroups per CU leave the split form 74 registers short)
-    static const bool d3_on = getenv("PNPP_WSX3") && atoi(getenv("PNPP_WSX3")) == 2;   // PNPP_WSX3=2: the dW_1 product on the bf16 pipe too
-    const bool d3 = s3 && d3_on;
+    // PNPP_WSX3=0: the dA product on the float32 instruction (A/B runs); 2: the dW_1 product on the bf16 pipe too
+    static const int wsx3 = env_int("PNPP_WSX3", 1);
+    const bool s3 = wsx3 != 0 && split_products() && wpc == 1;   // (two workgroups per CU leave the split form 74 registers short)
+    const bool d3 = s3 && wsx3 == 2;
     ProfScope ps(st, "gemm_wsx_kernel<%d,%d%s> M=%d N=%d K=%d grid=%dx1", C1, wpc, d3 ? ",S3,D3" : s3 ? ",S3" : "", M, C0, C1, workers);
     if (wpc == 2) {
         wsx_launch<64, 2, false, false>(P, workers, st);
@@ -1079,10 +1061,7 @@ bool try_launch_wsx(const AOperand &dz, const BOperand &W, int M, int C1, int C0
         else if (s3) wsx_launch<64, 1, true, false>(P, workers, st);
         else wsx_launch<64, 1, false, false>(P, workers, st);
     }
-    if (hipGetLastError() != hipSuccess) {
-        set_error("gemm_wsx: launch failed");
-        *rc = PNPP_ERR_LAUNCH;
-    }
+    check_launch("gemm_wsx", rc);
     return true;
 }
 

@@ -166,7 +166,7 @@ bool try_launch_wsq(const AOperand &A, const BOperand &B, int M, int Nout, int K
 // into dW_1 and layer 0's parameter gradients
 bool try_launch_wsx(const AOperand &dz, const BOperand &W, int M, int C1, int C0, const AOperand &geo, const float *W0, int ldw0,
                     const float *scale0, const float *shift0, float *dwslab, double *stat, int *workers_out, hipStream_t st, int *rc);
-size_t wsx_stat_doubles(int M);
+size_t wsx_stat_doubles();
 // the forward half: layer 0's statistics from the moments of the relative coordinates, layer 1's product with its operand built from
 // the coordinates -- Z_0 is never stored.  xyz0_applies decides for BOTH directions of a level (forward keeps no Z_0 for a generic backward)
 bool xyz0_applies(int M, int D, int K, int group_all, int L, const int *C);

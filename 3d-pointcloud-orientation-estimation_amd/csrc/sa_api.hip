@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "kernels.h"
+#include "launch.h"
 
 namespace pnpp {
 
@@ -176,12 +176,8 @@ static SaSaved sa_saved_layout(const pnpp_sa_desc *d, const SaGeom &g, void *bas
 
 // A/B switch (PNPP_NO_POOL_FUSION=1: pooling stays a pass of its own over Z)
 static bool pool_fused_on() {
-    static int cached = -1;
-    if (cached < 0) {
-        const char *v = getenv("PNPP_NO_POOL_FUSION");
-        cached = (v && atoi(v) != 0) ? 0 : 1;
-    }
-    return cached != 0;
+    static const bool on = env_int("PNPP_NO_POOL_FUSION", 0) == 0;
+    return on;
 }
 
 constexpr int kSmallM = 4096;  // at or below this many rows dZ is materialised once per layer (group_all layers)
@@ -209,7 +205,7 @@ static SaScratch sa_scratch_layout(const pnpp_sa_desc *d, const SaGeom &g, void 
     SaScratch s;
     {   // BatchNorm partial sums of one layer; a level on raw coordinates also parks layer 0's backward sums here (gemm_wsx_kernels.hip)
         size_t nd = (size_t)kMaxStatBlocks * 2 * g.maxC;
-        if (!d->group_all && d->D == 0 && wsx_stat_doubles(g.M) > nd) nd = wsx_stat_doubles(g.M);
+        if (!d->group_all && d->D == 0 && wsx_stat_doubles() > nd) nd = wsx_stat_doubles();
         s.slab = cv.take<double>(nd);
     }
     const int wide = g.maxC > d->D ? g.maxC : d->D;
@@ -405,7 +401,7 @@ static int sa_backward_impl(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, hi
     int cur = 0, nslab = 0, nslab_next = 0;
     // a level with few groups (group_all: one per cloud) whose dZ is materialised anyway: the finalisation launch takes the pooled
     // gradient as it is -- no pool_bwd launch, no dm tensor (PNPP_NO_POOL_BWD_FUSION=1 keeps the launch)
-    static const bool pool_bwd_fused = !(getenv("PNPP_NO_POOL_BWD_FUSION") && atoi(getenv("PNPP_NO_POOL_BWD_FUSION")) != 0);
+    static const bool pool_bwd_fused = env_int("PNPP_NO_POOL_BWD_FUSION", 0) == 0;
     const bool pooled_src = pool_bwd_fused && g.M <= kSmallM && g.G <= 64 && sa_keeps_zmax(d, g) && (d->C[Lm] & 3) == 0 &&
                             !(d->training && stats_sync_on());
     if (!pooled_src)

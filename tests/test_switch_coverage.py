@@ -1,4 +1,5 @@
-"""Every kernel-selection switch the library reads (getenv("PNPP_...") in csrc/) has a GPU test that runs the form it selects: a case of
+"""Every kernel-selection switch the library reads (env_int("PNPP_...") -- csrc/launch.h, the one parser -- or getenv("PNPP_...") in csrc/)
+has a GPU test that runs the form it selects: a case of
 tests/test_gpu_switch_forms.py, or an exemption below that names the test owning it.  A switch added without a test fails here, on
 the CPU."""
 import glob
@@ -21,13 +22,16 @@ def _switches_read_by_the_library():
     names = set()
     for path in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")):
         with open(path) as f:
-            names.update(re.findall(r'getenv\(\s*"(PNPP_[A-Z0-9_]+)"', f.read()))
+            names.update(re.findall(r'(?:getenv|env_int)\(\s*"(PNPP_[A-Z0-9_]+)"', f.read()))
     return names
 
 
 def test_the_scan_finds_the_switches():
     names = _switches_read_by_the_library()
     assert {"PNPP_NO_WSF", "PNPP_MID3", "PNPP_WSX3", "PNPP_NO_FC_FUSED", "PNPP_MATMUL"} <= names, sorted(names)
+    assert names == {"PNPP_NO_WSF", "PNPP_WSF_NT4", "PNPP_NO_WSP", "PNPP_NO_FC_FUSED", "PNPP_NO_POOL_FUSION", "PNPP_NO_POOL_BWD_FUSION",
+                     "PNPP_SPLIT_PRODUCTS", "PNPP_WSF3_NT4", "PNPP_WSF03", "PNPP_MID3", "PNPP_NO_WSQ", "PNPP_WSQ_FORM", "PNPP_NO_MID",
+                     "PNPP_NO_WSX", "PNPP_WSF0_WORKERS", "PNPP_WSX_WPC", "PNPP_WSX3", "PNPP_MATMUL"}, sorted(names)
 
 
 def test_every_switch_has_a_gpu_case_or_a_named_owner():

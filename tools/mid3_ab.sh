@@ -1,3 +1,4 @@
+#!/bin/bash
 set -e -o pipefail
 export OUT=${PNPP_AB_OUT:-ab/mid3}   # where the logs, tables and bench lines go
 mkdir -p $OUT
