@@ -29,6 +29,13 @@ void set_error(const char *fmt, ...);
         }                                                                               \
     } while (0)
 
+// a callee's status is the caller's: anything but PNPP_OK returns at once (the message is already set)
+#define PNPP_TRY(expr)                  \
+    do {                                \
+        int rc_ = (expr);               \
+        if (rc_ != PNPP_OK) return rc_; \
+    } while (0)
+
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

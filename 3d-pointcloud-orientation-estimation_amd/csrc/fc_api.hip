@@ -8,12 +8,6 @@
 
 namespace pnpp {
 
-#define PNPP_TRY(expr)                 \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != PNPP_OK) return rc_; \
-    } while (0)
-
 // y = dropout(relu(z*scale + shift))   (BatchNorm) or   y = dropout(relu(z + b))   (no norm)
 __global__ void __launch_bounds__(256) fc_apply_cols_kernel(const float *__restrict__ z, const float *__restrict__ scale,
                                                             const float *__restrict__ shift, const uint8_t *__restrict__ mask,
@@ -691,8 +685,10 @@ static int fc_forward_impl(const pnpp_fc_desc *d, const pnpp_fc_fwd_args *a, hip
         StatsView V;
         V.slab = sc.slab, V.nslab = nslab;
         if (d->training) PNPP_TRY(stats_exchange(sc.slab, nslab, d->N, (double)d->M, st, &V));
-        PNPP_TRY(launch_bn_finalize_fwd(V.slab, V.nslab, d->N, (double)d->M, a->b, a->nw, a->nb, a->rm, a->rv, (long long *)a->nbt, d->momentum, d->eps,
-                                        d->training, sv.mean, sv.istd, sv.scale, sv.shift, st, V.count_dev));
+        BnLayer bn;
+        bn.C = d->N, bn.bias = a->b, bn.gamma = a->nw, bn.beta = a->nb, bn.rm = a->rm, bn.rv = a->rv, bn.nbt = (long long *)a->nbt;
+        bn.mean = sv.mean, bn.istd = sv.istd, bn.scale = sv.scale, bn.shift = sv.shift;
+        PNPP_TRY(launch_bn_finalize_fwd(V, (double)d->M, bn, BnHyper{d->momentum, d->eps, d->training}, st));
         hipLaunchKernelGGL(fc_apply_cols_kernel, dim3(grid), dim3(256), 0, st, sv.z, sv.scale, sv.shift, a->mask, d->drop_scale,
                            d->relu, d->M, d->N, a->y);
     } else {

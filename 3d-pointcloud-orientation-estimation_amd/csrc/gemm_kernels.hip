@@ -2563,13 +2563,6 @@ bool try_launch_da_dw(const AOperand &dz, const BOperand &Win, int M, int Nout, 
 // out[c][perm(k)] = sum_s slab[s][c][k], fixed summation order: block = EPB outputs x (256/EPB) split lanes,
 // every lane strides the splits with four independent partial sums, the lanes are combined in lane order.
 // Small outputs (a 64 x 3 weight) take 16 outputs per block so that the splits, not the outputs, fill the chip.
-struct SlabReduceArgs {
-    const float *slab;
-    int nsplit, Nc, kp_pad, Kvalid, perm_D;
-    float *out;
-    int ldo;
-};
-
 template <int EPB>
 __device__ __forceinline__ void slab_reduce_block(const SlabReduceArgs &R, int bid) {
     constexpr int SL = 256 / EPB;
@@ -3013,59 +3006,56 @@ int launch_slab_sum(const double *slab, int nslab, int C, double count, double *
     return PNPP_OK;
 }
 
-int launch_bn_finalize_fwd(const double *slab, int nslab, int C, double count, const float *bias, const float *gamma,
-                           const float *beta, float *rm, float *rv, long long *nbt, float momentum, float eps, int training,
-                           float *mean, float *istd, float *scale, float *shift, hipStream_t st, const double *count_dev,
-                           const float *pool_ext, float *pool_out, int G, int32_t *pool_arg, float *origin_a, float *origin_b,
-                           int norigin) {
-    const bool pool = pool_ext && pool_out && G > 0 && training;
-    int gy = 1;
+int launch_bn_finalize_fwd(const StatsView &V, double count, const BnLayer &bn, const BnHyper &h, hipStream_t st, const PoolTail *tail) {
+    const PoolTail T = tail ? *tail : PoolTail();
+    const bool pool = T.pool_ext && T.pool_out && T.G > 0 && h.training;
+    int gy = 1, C = bn.C;
     if (pool) {   // enough row blocks to fill the chip, at least 64 rows each
         gy = cdiv(256, cdiv(C, FIN_COLS));
-        if (gy > cdiv(G, 64)) gy = cdiv(G, 64);
+        if (gy > cdiv(T.G, 64)) gy = cdiv(T.G, 64);
         if (gy < 1) gy = 1;
     }
     ProfScope ps(st, "bn_finalize_fwd_kernel C=%d%s", C, pool ? " +pool" : "");
-    hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(cdiv(C, FIN_COLS), gy), dim3(256), 0, st, slab, nslab, C, count, bias, gamma, beta,
-                       rm, rv, nbt, momentum, eps, training, mean, istd, scale, shift, count_dev, pool ? pool_ext : nullptr,
-                       pool ? pool_out : nullptr, G, pool ? pool_arg : nullptr, pool ? origin_a : nullptr, pool ? origin_b : nullptr,
-                       pool ? norigin : 0);
+    hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(cdiv(C, FIN_COLS), gy), dim3(256), 0, st, V.slab, V.nslab, C, count, bn.bias, bn.gamma,
+                       bn.beta, bn.rm, bn.rv, bn.nbt, h.momentum, h.eps, h.training, bn.mean, bn.istd, bn.scale, bn.shift, V.count_dev,
+                       pool ? T.pool_ext : nullptr, pool ? T.pool_out : nullptr, T.G, pool ? T.pool_arg : nullptr,
+                       pool ? T.origin_a : nullptr, pool ? T.origin_b : nullptr, pool ? T.norigin : 0);
     PNPP_CHECK_LAUNCH("bn_finalize_fwd");
     return PNPP_OK;
 }
 
-static DzJob make_dz_job(const AOperand *dz, int M, int C, float *out) {
+static DzJob make_dz_job(const DzSide &S, int C) {
     DzJob J;
-    if (dz && out && (C & 3) == 0 && dz->lda == C && (dz->mode == A_DZ || dz->mode == A_DZ_POOL)) {
-        J.dy = dz->a, J.z = dz->z, J.M = M, J.out = out;
+    const AOperand *dz = S.dz;
+    if (dz && S.out && (C & 3) == 0 && dz->lda == C && (dz->mode == A_DZ || dz->mode == A_DZ_POOL)) {
+        J.dy = dz->a, J.z = dz->z, J.M = S.M, J.out = S.out;
         if (dz->mode == A_DZ_POOL) J.arg = dz->arg, J.K = dz->K;
     }
     return J;
 }
+static BnFinalizeBwdArgs make_finalize_bwd(const StatsView &V, double count, int training, const BnLayer &bn, float *cst, const BnGrads &g) {
+    return BnFinalizeBwdArgs{V.slab, V.nslab, bn.C, count, training, bn.gamma, bn.mean, bn.istd, cst, g.dgamma, g.dbeta, g.dbias, V.count_dev, V.local};
+}
 
-int launch_bn_finalize_bwd(const double *slab, int nslab, int C, double count, int training, const float *gamma,
-                           const float *mean, const float *istd, float *cst, float *dgamma, float *dbeta, float *dbias,
-                           hipStream_t st, const AOperand *dz, int M, float *dz_out, const double *count_dev, const double *local,
-                           const PooledSource *pooled) {
-    BnFinalizeBwdArgs F{slab, nslab, C, count, training, gamma, mean, istd, cst, dgamma, dbeta, dbias, count_dev, local};
+int launch_bn_finalize_bwd(const StatsView &V, double count, int training, const BnLayer &bn, float *cst, const BnGrads &g, hipStream_t st,
+                           const DzSide &dz, const PooledSource *pooled) {
+    BnFinalizeBwdArgs F = make_finalize_bwd(V, count, training, bn, cst, g);
     if (pooled) F.p_dout = pooled->dout, F.p_zsel = pooled->zsel, F.p_scale = pooled->scale, F.p_shift = pooled->shift, F.p_G = pooled->G;
-    const DzJob J = make_dz_job(dz, M, C, dz_out);
-    const int nfin = cdiv(C, FIN_COLS), ndz = dz_job_blocks(J, C);
+    const DzJob J = make_dz_job(dz, bn.C);
+    const int C = bn.C, nfin = cdiv(C, FIN_COLS), ndz = dz_job_blocks(J, C);
     ProfScope ps(st, "bn_finalize_bwd_kernel C=%d%s%s", C, ndz ? " +dZ" : "", pooled ? " +pool" : "");
     hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(nfin + ndz), dim3(256), 0, st, F, nfin, J);
     PNPP_CHECK_LAUNCH("bn_finalize_bwd");
     return PNPP_OK;
 }
 
-int launch_post_gemm(const double *slab, int nslab, int C, double count, int training, const float *gamma, const float *mean,
-                     const float *istd, float *cst, float *dgamma, float *dbeta, float *dbias, const float *dwslab, int nsplit,
-                     int Nc, int kp_pad, int Kvalid, int perm_D, float *dw, int ldo, hipStream_t st, const AOperand *dz, int M,
-                     float *dz_out, const double *count_dev, const double *local) {
-    const BnFinalizeBwdArgs F{slab, nslab, C, count, training, gamma, mean, istd, cst, dgamma, dbeta, dbias, count_dev, local};
-    const SlabReduceArgs R{dwslab, nsplit, Nc, kp_pad, Kvalid, perm_D, dw, ldo};
-    const DzJob J = make_dz_job(dz, M, C, dz_out);
-    const int total = Nc * Kvalid, nfin = cdiv(C, FIN_COLS), ndz = dz_job_blocks(J, C), nf = nfin + ndz;
-    ProfScope ps(st, "post_gemm_kernel C=%d%s | N=%d K=%d split=%d", C, ndz ? " +dZ" : "", Nc, Kvalid, nsplit);
+int launch_post_gemm(const StatsView &V, double count, int training, const BnLayer &bn, float *cst, const BnGrads &g, const SlabReduceArgs &R,
+                     hipStream_t st, const DzSide &dz) {
+    const BnFinalizeBwdArgs F = make_finalize_bwd(V, count, training, bn, cst, g);
+    const int C = bn.C, nsplit = R.nsplit;
+    const DzJob J = make_dz_job(dz, C);
+    const int total = R.Nc * R.Kvalid, nfin = cdiv(C, FIN_COLS), ndz = dz_job_blocks(J, C), nf = nfin + ndz;
+    ProfScope ps(st, "post_gemm_kernel C=%d%s | N=%d K=%d split=%d", C, ndz ? " +dZ" : "", R.Nc, R.Kvalid, nsplit);
     if (nsplit == 0) {   // the weight gradient was written in place by its GEMM (one row range): nothing to reduce
         hipLaunchKernelGGL(post_gemm_kernel<64>, dim3(nf), dim3(256), 0, st, F, nfin, R, ndz, J);
     } else if (slab_reduce_vec4(R)) {

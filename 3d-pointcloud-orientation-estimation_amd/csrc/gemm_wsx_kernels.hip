@@ -989,16 +989,15 @@ int launch_rel_moments(const AOperand &geo, int M, double *mom, int *nmom, hipSt
 
 // layer 1's forward product with layer 0 built from the coordinates.  training: mom / nmom from launch_rel_moments, the kernel writes
 // mean0 / istd0 / scale0 / shift0 (and updates rm0 / rv0 / nbt0); eval: scale0 / shift0 are read.  E: E_STORE or E_STORE_STATS.
-int launch_wsf0(const AOperand &geo, int M, const float *W0, int ldw0, const double *mom, int nmom, int training, const float *bias0,
-                const float *gamma0, const float *beta0, float *rm0, float *rv0, long long *nbt0, float momentum, float eps, float *mean0,
-                float *istd0, float *scale0, float *shift0, const float *W1, int ldw1, const Epilogue &E, int *nslab, hipStream_t st) {
+int launch_wsf0(const AOperand &geo, int M, const BOperand &W0, const double *mom, int nmom, const BnLayer &bn0, const BnHyper &h,
+                const BOperand &W1, const Epilogue &E, int *nslab, hipStream_t st) {
     PNPP_REQUIRE(E.ldc == 64 && !E.pool_ext && (E.mode == E_STORE || E.mode == E_STORE_STATS), PNPP_ERR_ARG, "wsf0: unsupported epilogue");
-    PNPP_REQUIRE((ldw1 & 3) == 0 && ((uintptr_t)W1 & 15) == 0, PNPP_ERR_ARG, "wsf0: weight alignment");
+    PNPP_REQUIRE((W1.ldb & 3) == 0 && ((uintptr_t)W1.b & 15) == 0, PNPP_ERR_ARG, "wsf0: weight alignment");
     Wsf0Args P;
-    P.xyz = geo.xyz, P.centres = geo.new_xyz, P.idx = geo.idx, P.M = M, P.N = geo.N, P.S = geo.S, P.W0 = W0, P.ldw0 = ldw0;
-    P.mom = mom, P.nmom = nmom, P.training = training, P.bias0 = bias0, P.gamma0 = gamma0, P.beta0 = beta0, P.rm0 = rm0, P.rv0 = rv0;
-    P.nbt0 = nbt0, P.momentum = momentum, P.eps = eps, P.mean0 = mean0, P.istd0 = istd0, P.scale0 = scale0, P.shift0 = shift0;
-    P.W1 = W1, P.ldw1 = ldw1, P.z1 = E.c, P.slab = E.slab;
+    P.xyz = geo.xyz, P.centres = geo.new_xyz, P.idx = geo.idx, P.M = M, P.N = geo.N, P.S = geo.S, P.W0 = W0.b, P.ldw0 = W0.ldb;
+    P.mom = mom, P.nmom = nmom, P.training = h.training, P.bias0 = bn0.bias, P.gamma0 = bn0.gamma, P.beta0 = bn0.beta, P.rm0 = bn0.rm;
+    P.rv0 = bn0.rv, P.nbt0 = bn0.nbt, P.momentum = h.momentum, P.eps = h.eps, P.mean0 = bn0.mean, P.istd0 = bn0.istd, P.scale0 = bn0.scale, P.shift0 = bn0.shift;
+    P.W1 = W1.b, P.ldw1 = W1.ldb, P.z1 = E.c, P.slab = E.slab;
     const int nstrips = M / 32;
     // PNPP_WSF0_WORKERS (256 measured: see DESIGN section 9); 0 or less: the default.  worker_count keeps it inside the statistics slab
     static const int wmax = env_int("PNPP_WSF0_WORKERS", kMaxStatBlocks);
@@ -1065,13 +1064,13 @@ bool try_launch_wsx(const AOperand &dz, const BOperand &W, int M, int C1, int C0
     return true;
 }
 
-int launch_xyz0_post(const float *dwslab, int workers, int C1, float *dw1, int ld1, const double *stat, const float *W0, int ldw0,
-                     const float *gamma0, const float *mean0, const float *istd0, double count, int training, float *dW0, int ld0,
-                     float *dgamma0, float *dbeta0, float *dbias0, hipStream_t st) {
+int launch_xyz0_post(const SlabReduceArgs &R1, const double *stat, const BOperand &W0, const BnLayer &bn0, double count, int training,
+                     float *dW0, int ld0, const BnGrads &g0, hipStream_t st) {
+    const int workers = R1.nsplit, C1 = R1.Nc;
     Xyz0PostArgs P;
-    P.dwslab = dwslab, P.nslab = workers, P.KD = C1, P.dw1 = dw1, P.ld1 = ld1, P.xslab = stat, P.W0 = W0, P.ldw0 = ldw0;
-    P.gamma0 = gamma0, P.mean0 = mean0, P.istd0 = istd0, P.count = count, P.training = training;
-    P.dW0 = dW0, P.ld0 = ld0, P.dgamma0 = dgamma0, P.dbeta0 = dbeta0, P.dbias0 = dbias0;
+    P.dwslab = R1.slab, P.nslab = workers, P.KD = C1, P.dw1 = R1.out, P.ld1 = R1.ldo, P.xslab = stat, P.W0 = W0.b, P.ldw0 = W0.ldb;
+    P.gamma0 = bn0.gamma, P.mean0 = bn0.mean, P.istd0 = bn0.istd, P.count = count, P.training = training;
+    P.dW0 = dW0, P.ld0 = ld0, P.dgamma0 = g0.dgamma, P.dbeta0 = g0.dbeta, P.dbias0 = g0.dbias;
     const int nfin = 64 / 8, nred = cdiv(C1 * 16, 16);
     ProfScope ps(st, "xyz0_post_kernel C=64 | N=%d K=64 split=%d", C1, workers);
     hipLaunchKernelGGL(xyz0_post_kernel, dim3(nfin + nred), dim3(256), 0, st, P, nfin);

@@ -101,6 +101,41 @@ struct BOperand {
     int rows = 0;      // number of valid reduction rows (<= Kd; beyond it B is treated as zero)
 };
 
+// ---- a BatchNorm layer as a value: what the finalisation launchers take instead of loose pointers ----
+struct BnLayer {   // one layer's parameters and the statistics kept for the backward pass (forward writes mean .. shift, backward reads them)
+    int C = 0;
+    const float *bias = nullptr, *gamma = nullptr, *beta = nullptr;
+    float *rm = nullptr, *rv = nullptr, *mean = nullptr, *istd = nullptr, *scale = nullptr, *shift = nullptr;
+    long long *nbt = nullptr;
+};
+struct BnGrads { float *dgamma = nullptr, *dbeta = nullptr, *dbias = nullptr; };   // where its parameter gradients go
+struct BnHyper { float momentum = 0.1f, eps = 1e-5f; int training = 0; };
+// What a finalisation reads: this rank's partial slabs, or -- after stats_exchange (SyncBN) -- one slab of sums over all ranks, their row count and this rank's own sums
+struct StatsView {
+    const double *slab = nullptr;
+    int nslab = 0;
+    const double *count_dev = nullptr, *local = nullptr;
+};
+// forward, optional: the pooled output from the producer's extreme pre-BN values (Epilogue::pool_ext) and, for a group_all level,
+// the origin as every cloud's centre -- both ride in the finalisation launch
+struct PoolTail {
+    const float *pool_ext = nullptr;
+    float *pool_out = nullptr;
+    int32_t *pool_arg = nullptr;
+    float *origin_a = nullptr, *origin_b = nullptr;
+    int G = 0, norigin = 0;
+};
+// backward, optional: also materialise dZ = BN-backward(dz operand) of the layer being finalised, M x C (small-M levels)
+struct DzSide { const AOperand *dz = nullptr; int M = 0; float *out = nullptr; };
+// out[c][perm(k)] = sum_s slab[s][c][k] (gemm_kernels.hip: launch_slab_reduce, post_gemm_kernel); perm_D < 0: identity; else
+// feature-first -> xyz-first column order
+struct SlabReduceArgs {
+    const float *slab;
+    int nsplit, Nc, kp_pad, Kvalid, perm_D;
+    float *out;
+    int ldo;
+};
+
 // C[M x Nout] = A'[M x Kd] * B[Kd x Nout].  Returns the number of statistic slabs written (gridDim.x)
 // through *nslab when the epilogue collects statistics.
 // *dw_slabs (optional) receives the number of dW partial slabs written when E.dwslab was honoured, else 0.
@@ -131,7 +166,6 @@ int scatter_dz_splits(int rows);  // number of [C][4] dW_xyz partials launch_sca
 int launch_scatter_dz(const AOperand &dz, const AOperand &geo, int B, int Mc, int C, float *G, float *wslab, hipStream_t st);
 int dw_xyz_splits(int M);
 int launch_dw_xyz(const AOperand &dz, int Nc, const AOperand &a2, int M, float *slab, hipStream_t st);
-// out[c][perm(k)] = sum_s slab[s][c][k]; perm_D < 0: identity; else feature-first -> xyz-first column order.
 bool try_launch_fc_dx_dw(const float *dz, const float *w, const float *x, int M, int N, int K, float *dx, float *dw, hipStream_t st,
                          int *rc);
 // *nsplit / *kp_pad: in = what dw_plan chose (the slab is sized for it); out = the partial count and pitch actually written
@@ -172,12 +206,11 @@ size_t wsx_stat_doubles();
 bool xyz0_applies(int M, int D, int K, int group_all, int L, const int *C);
 size_t xyz0_moment_doubles();
 int launch_rel_moments(const AOperand &geo, int M, double *mom, int *nmom, hipStream_t st);
-int launch_wsf0(const AOperand &geo, int M, const float *W0, int ldw0, const double *mom, int nmom, int training, const float *bias0,
-                const float *gamma0, const float *beta0, float *rm0, float *rv0, long long *nbt0, float momentum, float eps, float *mean0,
-                float *istd0, float *scale0, float *shift0, const float *W1, int ldw1, const Epilogue &E, int *nslab, hipStream_t st);
-int launch_xyz0_post(const float *dwslab, int workers, int C1, float *dw1, int ld1, const double *stat, const float *W0, int ldw0,
-                     const float *gamma0, const float *mean0, const float *istd0, double count, int training, float *dW0, int ld0,
-                     float *dgamma0, float *dbeta0, float *dbias0, hipStream_t st);
+int launch_wsf0(const AOperand &geo, int M, const BOperand &W0, const double *mom, int nmom, const BnLayer &bn0, const BnHyper &h,
+                const BOperand &W1, const Epilogue &E, int *nslab, hipStream_t st);
+// W0 / W1: the conv weights as stored (b, ldb); R1: the reduction of dW_1's partials (slab, nsplit = workers, Nc = C_1, out, ldo; pitch 64)
+int launch_xyz0_post(const SlabReduceArgs &R1, const double *stat, const BOperand &W0, const BnLayer &bn0, double count, int training,
+                     float *dW0, int ld0, const BnGrads &g0, hipStream_t st);
 // diagnostics (pnpp_sa_saved_relu_mask): the ReLU decisions of a stored layer / of the rebuilt layer 0 of a level on raw coordinates
 int launch_relu_mask(const float *z, const float *scale, const float *shift, size_t n, int C, uint8_t *out, hipStream_t st);
 int launch_xyz0_mask(const AOperand &geo, int M, const float *W0, int ldw0, const float *scale0, const float *shift0, uint8_t *out,
@@ -199,11 +232,8 @@ int launch_slab_reduce2(const float *slab1, int nsplit1, int Nc1, int kp_pad1, i
 int launch_slab_reduce(const float *slab, int nsplit, int Nc, int kp_pad, int Kvalid, int perm_D, float *out, int ldo,
                        hipStream_t st);
 
-int launch_bn_finalize_fwd(const double *slab, int nslab, int C, double count, const float *bias, const float *gamma,
-                           const float *beta, float *rm, float *rv, long long *nbt, float momentum, float eps, int training,
-                           float *mean, float *istd, float *scale, float *shift, hipStream_t st, const double *count_dev = nullptr,
-                           const float *pool_ext = nullptr, float *pool_out = nullptr, int G = 0, int32_t *pool_arg = nullptr,
-                           float *origin_a = nullptr, float *origin_b = nullptr, int norigin = 0);
+int launch_bn_finalize_fwd(const StatsView &V, double count, const BnLayer &bn, const BnHyper &h, hipStream_t st,
+                           const PoolTail *tail = nullptr);
 // true when launch_gemm will honour Epilogue::pool_ext for this shape (the weights-stationary kernel, 32-row neighbourhoods)
 bool gemm_pools_in_epilogue(const AOperand &A, int M, int Nout, int Kd, int nsample);
 // pooled (optional): levels with few groups take the column sums (and, in the dZ job, the masked pooled gradient) straight from
@@ -212,26 +242,13 @@ struct PooledSource {
     const float *dout = nullptr, *zsel = nullptr, *scale = nullptr, *shift = nullptr;
     int G = 0;
 };
-int launch_bn_finalize_bwd(const double *slab, int nslab, int C, double count, int training, const float *gamma,
-                           const float *mean, const float *istd, float *cst, float *dgamma, float *dbeta, float *dbias,
-                           hipStream_t st, const AOperand *dz = nullptr, int M = 0, float *dz_out = nullptr,
-                           const double *count_dev = nullptr, const double *local = nullptr, const PooledSource *pooled = nullptr);
-
+int launch_bn_finalize_bwd(const StatsView &V, double count, int training, const BnLayer &bn, float *cst, const BnGrads &g, hipStream_t st,
+                           const DzSide &dz = DzSide(), const PooledSource *pooled = nullptr);
 // bn_finalize_bwd of one layer and the weight-gradient slab reduction of the layer above it, in one launch
-// dz / M / dz_out (optional): also materialise dZ = BN-backward(dz operand) of the layer being finalised (small-M levels)
-int launch_post_gemm(const double *slab, int nslab, int C, double count, int training, const float *gamma, const float *mean,
-                     const float *istd, float *cst, float *dgamma, float *dbeta, float *dbias, const float *dwslab, int nsplit,
-                     int Nc, int kp_pad, int Kvalid, int perm_D, float *dw, int ldo, hipStream_t st, const AOperand *dz = nullptr, int M = 0,
-                     float *dz_out = nullptr, const double *count_dev = nullptr, const double *local = nullptr);
+int launch_post_gemm(const StatsView &V, double count, int training, const BnLayer &bn, float *cst, const BnGrads &g, const SlabReduceArgs &R,
+                     hipStream_t st, const DzSide &dz = DzSide());
 
-// ---- SyncBN (off unless pnpp_set_stats_exchange has registered a callback; sa_api.hip) ----
-// What a BatchNorm finalisation reads: the partial slabs of this rank, or -- after stats_exchange -- one slab of sums over all
-// ranks with their row count in device memory, plus this rank's own sums for the parameter gradients.
-struct StatsView {
-    const double *slab = nullptr;
-    int nslab = 0;
-    const double *count_dev = nullptr, *local = nullptr;
-};
+// ---- SyncBN (off unless pnpp_set_stats_exchange has registered a callback; runtime.hip) ----
 bool stats_sync_on();
 int launch_slab_sum(const double *slab, int nslab, int C, double count, double *glob, double *local, hipStream_t st);
 // training-mode statistics of one BatchNorm layer: reduce, exchange over the ranks (stream-ordered), return the view to finalise from

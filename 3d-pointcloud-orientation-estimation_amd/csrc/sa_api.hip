@@ -1,113 +1,15 @@
-// sa_api.hip -- host-side orchestration of PointNetSetAbstraction forward / backward and of the
-// fully connected head blocks, on top of the fused kernels (gemm_kernels.hip, index_kernels.hip).
-//
-// Reference: models/pointnet_pp_8dir.py:21-43 (forward), its autograd graph and the
-// heads models/pointnet_pp_vonMises.py:32-35 / pointnet_pp_mvM.py:82-83.
+// sa_api.hip -- host-side orchestration of PointNetSetAbstraction forward / backward on top of the fused kernels
+// (gemm_*_kernels.hip, index_kernels.hip).  The library's runtime -- errors, launch timing, the SyncBN exchange -- is runtime.hip.
+// Reference: models/pointnet_pp_8dir.py:21-43 (forward) and its autograd graph.
 //
 // Everything is stream-ordered: these functions only enqueue work on `stream`; they never allocate,
 // free, copy to the host or synchronise (they can be captured into a hipGraph).
-#include <stdarg.h>
-#include <stdlib.h>
-
-#include <map>
-#include <string>
-#include <vector>
-
 #include "launch.h"
 
 namespace pnpp {
 
-static thread_local char g_err[512] = "";
-
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-// ---- opt-in launch timing ----------------------------------------------------------------------
-struct ProfRec {
-    std::string tag;
-    hipEvent_t a, b;
-};
-static bool g_prof = false;
-static std::vector<ProfRec> g_recs;
-static std::string g_open_tag;   // tag of the open ProfScope; every launch inside it gets its own record
-static bool g_scope_open = false;
-
-bool prof_on() { return g_prof; }
-void prof_begin(hipStream_t, const char *fmt, ...) {
-    char buf[160];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_open_tag = buf;
-    g_scope_open = true;
-}
-void prof_end(hipStream_t) { g_scope_open = false; }
-bool prof_take_events(hipEvent_t *a, hipEvent_t *b) {
-    if (!g_prof || !g_scope_open) return false;   // a launch outside any scope is not timed
-    ProfRec r;
-    r.tag = g_open_tag;
-    if (hipEventCreate(&r.a) != hipSuccess) return false;
-    if (hipEventCreate(&r.b) != hipSuccess) {
-        (void)hipEventDestroy(r.a);
-        return false;
-    }
-    g_recs.push_back(r);
-    *a = r.a, *b = r.b;
-    return true;
-}
-
-// ---- SyncBN: optional cross-rank exchange of the BatchNorm sums (off by default) ----------------------------
-// The callback sums a device buffer of doubles over the ranks, stream-ordered (RCCL: an all-reduce enqueued behind `stream`).
-// The buffer is the caller's (this library never allocates): [0, half) is exchanged, [half, 2 half) keeps this rank's sums.
-struct StatsExchange {
-    pnpp_stats_exchange_fn fn = nullptr;
-    void *user = nullptr;
-    double *buf = nullptr;
-    size_t half = 0;   // doubles per half
-};
-static StatsExchange g_sx;
-
-bool stats_sync_on() { return g_sx.fn != nullptr; }
-double *stats_buffer_global() { return g_sx.buf; }
-double *stats_buffer_local() { return g_sx.buf + g_sx.half; }
-
-int stats_exchange_inplace(int C, hipStream_t st, StatsView *out) {
-    PNPP_REQUIRE((size_t)(2 * C + 1) <= g_sx.half, PNPP_ERR_ARG, "stats exchange: buffer of %zu doubles per half is too small for C=%d",
-                 g_sx.half, C);
-    const int rc = g_sx.fn(g_sx.buf, (size_t)(2 * C + 1), (void *)st, g_sx.user);
-    PNPP_REQUIRE(rc == 0, PNPP_ERR_LAUNCH, "stats exchange: the registered callback returned %d", rc);
-    out->slab = g_sx.buf, out->nslab = 1, out->count_dev = g_sx.buf + 2 * C, out->local = g_sx.buf + g_sx.half;
-    return PNPP_OK;
-}
-
-int stats_exchange(const double *slab, int nslab, int C, double count, hipStream_t st, StatsView *out) {
-    if (!g_sx.fn) {
-        out->slab = slab, out->nslab = nslab, out->count_dev = nullptr, out->local = nullptr;
-        return PNPP_OK;
-    }
-    PNPP_REQUIRE((size_t)(2 * C + 1) <= g_sx.half, PNPP_ERR_ARG, "stats exchange: buffer of %zu doubles per half is too small for C=%d",
-                 g_sx.half, C);
-    int rc = launch_slab_sum(slab, nslab, C, count, g_sx.buf, g_sx.buf + g_sx.half, st);
-    if (rc != PNPP_OK) return rc;
-    return stats_exchange_inplace(C, st, out);
-}
-
-#define PNPP_TRY(expr)                 \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != PNPP_OK) return rc_; \
-    } while (0)
-
-// ---------------------------------------------------------------------------------------------
-// set abstraction
-// ---------------------------------------------------------------------------------------------
 struct SaGeom {
-    int M, G, Kd0, maxC, L;
+    int M, G, maxC;
     int Cin[PNPP_MAX_LAYERS];  // reduction dim of layer l in state_dict terms (D+3 for l = 0)
     int Kd[PNPP_MAX_LAYERS];   // padded reduction dim used by the kernels
 };
@@ -119,17 +21,15 @@ static int sa_geom(const pnpp_sa_desc *d, SaGeom *g) {
     PNPP_REQUIRE(d->L >= 1 && d->L <= PNPP_MAX_LAYERS, PNPP_ERR_ARG, "sa: unsupported layer count %d", d->L);
     if (d->group_all) PNPP_REQUIRE(d->S == 1 && d->K == d->N, PNPP_ERR_ARG, "sa: group_all needs S == 1 and K == N");
     PNPP_REQUIRE((long long)d->B * d->S * d->K < (1ll << 31), PNPP_ERR_ARG, "sa: B*S*K overflows int32");
-    g->L = d->L;
     g->M = d->B * d->S * d->K;
     g->G = d->B * d->S;
-    g->Kd0 = (d->D + 3 + 3) & ~3;
     g->maxC = 0;
     for (int l = 0; l < d->L; ++l) {
         PNPP_REQUIRE(d->C[l] > 0 && d->C[l] % 32 == 0, PNPP_ERR_ARG,
                      "sa: mlp channel %d (=%d) must be a positive multiple of 32 for the MFMA path", l, d->C[l]);
         g->maxC = d->C[l] > g->maxC ? d->C[l] : g->maxC;
         g->Cin[l] = l == 0 ? d->D + 3 : d->C[l - 1];
-        g->Kd[l] = l == 0 ? g->Kd0 : d->C[l - 1];
+        g->Kd[l] = l == 0 ? (d->D + 3 + 3) & ~3 : d->C[l - 1];
     }
     return PNPP_OK;
 }
@@ -140,22 +40,102 @@ struct SaSaved {
     float *z[PNPP_MAX_LAYERS];
     float *mean[PNPP_MAX_LAYERS], *istd[PNPP_MAX_LAYERS], *scale[PNPP_MAX_LAYERS], *shift[PNPP_MAX_LAYERS];
     int32_t *arg;
-    double *mom;   // a level on raw coordinates grouped by pnpp_sa_group_pair: the moment partials its search wrote (sa_pair_moments)
+    double *mom;   // a level on raw coordinates grouped by pnpp_sa_group_pair: the moment partials its search wrote (SaLevel::pair_moments)
     float *zmax;   // (G, C_last): the pre-BN value each pooled output came from (the backward pass's ReLU gate and xhat need it)
     size_t bytes;
 };
 
-// whole-cloud pooling in K chunks (pool_fwd_split / merge) does not produce the selected pre-BN values; backward gathers them there
-static bool sa_keeps_zmax(const pnpp_sa_desc *d, const SaGeom &g) { return pool_fwd_splits(g.G, d->K, d->C[d->L - 1]) <= 1; }
+struct SaScratch {
+    double *slab;
+    float *dy[2];
+    float *dzbuf;  // small-M layers only: materialised dZ
+    float *dm;
+    float *cst;    // the BatchNorm-backward constants of the layer being processed (written by the finalisation that precedes it)
+    float *dwslab;
+    float *src;  // convolve-then-gather layer 0: one C_0-wide row per source point (P forward, G backward)
+    float *xslab;  // ... and the [C_0][4] dW_xyz partials of its backward scatter
+    double *mom;   // a level on raw coordinates: moment partials of the relative coordinates (gemm_wsx_kernels.hip)
+    size_t bytes;
+};
 
-// The pair search (pnpp_sa_group_pair) also sums the moments of this level's relative coordinates, one partial per search workgroup,
-// into the level's kept workspace: the forward pass that finds its neighbours already in place (they can only come from that search)
-// then needs no rel_moments launch.  Decided from the descriptor's geometry alone, so both calls agree without passing anything.
-static bool sa_pair_moments(const pnpp_sa_desc *d, const SaGeom &g) {
-    return xyz0_applies(g.M, d->D, d->K, d->group_all, d->L, d->C);
+constexpr int kSmallM = 4096;  // at or below this many rows dZ is materialised once per layer (group_all layers)
+static Epilogue store_to(float *c, int ldc) {
+    Epilogue E;
+    E.mode = E_STORE, E.c = c, E.ldc = ldc;
+    return E;
 }
 
-static SaSaved sa_saved_layout(const pnpp_sa_desc *d, const SaGeom &g, void *base) {
+// ---- one call's view of a level, built once on the stack: geometry, routing facts, workspaces, the layers as values ----
+struct SaLevel {
+    const pnpp_sa_desc *d = nullptr;
+    hipStream_t st = nullptr;
+    SaGeom g;
+    // the routing facts: functions of the geometry (and the process-wide modes) alone, so both passes, the size queries and the pair search agree
+    bool xyz0 = false;          // on raw coordinates (SA1): no Z_0 -- statistics from the coordinate moments, layer 1 builds its operand (gemm_wsx_kernels.hip)
+    bool delayed = false;       // layer 0 is convolved on the B*N source points and gathered afterwards (a level grouping points WITH features)
+    bool keeps_zmax = false;    // false: whole-cloud pooling in K chunks (pool_fwd_split / merge) produces no selected pre-BN values
+    bool small = false;         // M <= kSmallM: dZ is materialised once per layer, in the launch that finalises the layer's sums
+    bool pair_moments = false;  // the pair search also sums this level's coordinate moments into sv.mom: no rel_moments launch then
+    SaSaved sv;
+    SaScratch sc;
+    const float *xyz = nullptr, *points = nullptr;
+    const float *const *conv_w = nullptr;
+    BnLayer bn[PNPP_MAX_LAYERS];    // gamma always; bias / beta / running statistics in a forward call
+    BnGrads dbn[PNPP_MAX_LAYERS];   // backward calls
+    BnHyper hyper;
+    bool want_dpoints = false;      // backward calls
+
+    double count() const { return (double)g.M; }
+    AOperand layer0_operand() const {
+        AOperand A;
+        A.mode = d->group_all ? A_CONCAT : A_GATHER;
+        A.a = points, A.xyz = xyz, A.new_xyz = sv.new_xyz, A.idx = sv.idx;
+        A.D = d->D, A.N = d->N, A.S = d->S, A.K = d->K;
+        return A;
+    }
+    AOperand input_of(int l) const {   // what layer l multiplies: the grouped input, or relu(bn(Z_{l-1})) applied by the operand loader
+        if (l == 0) return layer0_operand();
+        AOperand A;
+        A.mode = A_BNRELU;
+        A.a = sv.z[l - 1], A.lda = d->C[l - 1], A.scale = sv.scale[l - 1], A.shift = sv.shift[l - 1];
+        return A;
+    }
+    BOperand weight(int l, int rows) const {   // W_l (C_l x Cin_l) row-major as stored, `rows` valid reduction rows
+        BOperand W;
+        W.b = conv_w[l], W.ldb = g.Cin[l], W.rows = rows;
+        return W;
+    }
+    BOperand w0_features() const {   // feature columns of W_0: (C_0 x (3+D)) row-major, skip the three xyz columns
+        BOperand W = weight(0, d->C[0]);
+        W.b += 3;
+        return W;
+    }
+    // dZ_l as the kernels rebuild it; the top layer's dense gradient is never materialised (A_DZ_POOL rebuilds it from dm / arg)
+    AOperand dz_operand(int l, int buf) const {
+        const bool top = l == d->L - 1;
+        AOperand dz;
+        dz.mode = top ? A_DZ_POOL : A_DZ, dz.a = top ? sc.dm : sc.dy[buf];
+        dz.arg = sv.arg, dz.K = d->K, dz.lda = dz.C = d->C[l], dz.z = sv.z[l], dz.cst = sc.cst;
+        return dz;
+    }
+    DzSide dz_side(const AOperand *dz) const { return small ? DzSide{dz, g.M, sc.dzbuf} : DzSide(); }
+};
+
+static int sa_level_plan(const pnpp_sa_desc *d, SaLevel *L) {
+    PNPP_TRY(sa_geom(d, &L->g));
+    const SaGeom &g = L->g;
+    L->d = d;
+    L->xyz0 = xyz0_applies(g.M, d->D, d->K, d->group_all, d->L, d->C);
+    L->delayed = !d->group_all && d->D > 0 && d->D % 4 == 0 && delayed_layer0_ok(d->C[0]) && d->S * d->K > d->N;
+    L->keeps_zmax = pool_fwd_splits(g.G, d->K, d->C[d->L - 1]) <= 1;
+    L->small = g.M <= kSmallM;
+    L->pair_moments = L->xyz0;
+    return PNPP_OK;
+}
+
+static SaSaved sa_saved_layout(const SaLevel &L, void *base) {
+    const pnpp_sa_desc *d = L.d;
+    const SaGeom &g = L.g;
     Carver cv(base);
     SaSaved s;
     s.idx = cv.take<int32_t>(d->group_all ? 0 : (size_t)g.M);
@@ -168,39 +148,15 @@ static SaSaved sa_saved_layout(const pnpp_sa_desc *d, const SaGeom &g, void *bas
         s.shift[l] = cv.take<float>(d->C[l]);
     }
     s.arg = cv.take<int32_t>((size_t)g.G * d->C[d->L - 1]);
-    s.zmax = cv.take<float>(sa_keeps_zmax(d, g) ? (size_t)g.G * d->C[d->L - 1] : 0);
-    s.mom = cv.take<double>(sa_pair_moments(d, g) ? knn_pair_moment_doubles(d->B, d->S, d->N) : 0);
+    s.zmax = cv.take<float>(L.keeps_zmax ? (size_t)g.G * d->C[d->L - 1] : 0);
+    s.mom = cv.take<double>(L.pair_moments ? knn_pair_moment_doubles(d->B, d->S, d->N) : 0);
     s.bytes = cv.bytes();
     return s;
 }
 
-// A/B switch (PNPP_NO_POOL_FUSION=1: pooling stays a pass of its own over Z)
-static bool pool_fused_on() {
-    static const bool on = env_int("PNPP_NO_POOL_FUSION", 0) == 0;
-    return on;
-}
-
-constexpr int kSmallM = 4096;  // at or below this many rows dZ is materialised once per layer (group_all layers)
-
-struct SaScratch {
-    double *slab;
-    float *dy[2];
-    float *dzbuf;  // small-M layers only: materialised dZ
-    float *dm;
-    float *cst;
-    float *dwslab;
-    float *src;  // convolve-then-gather layer 0: one C_0-wide row per source point (P forward, G backward)
-    float *xslab;  // ... and the [C_0][4] dW_xyz partials of its backward scatter
-    double *mom;   // a level on raw coordinates: moment partials of the relative coordinates (gemm_wsx_kernels.hip)
-    size_t bytes;
-};
-
-// layer 0 is convolved on the B*N source points and gathered afterwards when the level groups points WITH features
-static bool sa_delayed(const pnpp_sa_desc *d) {
-    return !d->group_all && d->D > 0 && d->D % 4 == 0 && delayed_layer0_ok(d->C[0]) && d->S * d->K > d->N;
-}
-
-static SaScratch sa_scratch_layout(const pnpp_sa_desc *d, const SaGeom &g, void *base) {
+static SaScratch sa_scratch_layout(const SaLevel &L, void *base) {
+    const pnpp_sa_desc *d = L.d;
+    const SaGeom &g = L.g;
     Carver cv(base);
     SaScratch s;
     {   // BatchNorm partial sums of one layer; a level on raw coordinates also parks layer 0's backward sums here (gemm_wsx_kernels.hip)
@@ -211,7 +167,7 @@ static SaScratch sa_scratch_layout(const pnpp_sa_desc *d, const SaGeom &g, void 
     const int wide = g.maxC > d->D ? g.maxC : d->D;
     s.dy[0] = cv.take<float>((size_t)g.M * wide);
     s.dy[1] = cv.take<float>((size_t)g.M * wide);
-    s.dzbuf = cv.take<float>(g.M <= kSmallM ? (size_t)g.M * g.maxC : 0);
+    s.dzbuf = cv.take<float>(L.small ? (size_t)g.M * g.maxC : 0);
     s.dm = cv.take<float>((size_t)g.G * d->C[d->L - 1]);
     s.cst = cv.take<float>((size_t)5 * g.maxC);
     size_t dwmax = 0;
@@ -224,399 +180,345 @@ static SaScratch sa_scratch_layout(const pnpp_sa_desc *d, const SaGeom &g, void 
         need = fused > need ? fused : need;
         dwmax = need > dwmax ? need : dwmax;
     }
-    if (sa_delayed(d)) {  // the per-source-point dW_f partials
+    if (L.delayed) {  // the per-source-point dW_f partials
         int nsplit, kp_pad;
         dw_plan(d->B * d->N, d->C[0], d->D, &nsplit, &kp_pad);
         const size_t a = (size_t)nsplit * d->C[0] * kp_pad;
         dwmax = a > dwmax ? a : dwmax;
     }
     s.dwslab = cv.take<float>(dwmax);
-    s.src = cv.take<float>(sa_delayed(d) ? (size_t)d->B * d->N * d->C[0] : 0);
-    s.xslab = cv.take<float>(sa_delayed(d) ? (size_t)scatter_dz_splits(d->B * d->N) * d->C[0] * 4 : 0);
+    s.src = cv.take<float>(L.delayed ? (size_t)d->B * d->N * d->C[0] : 0);
+    s.xslab = cv.take<float>(L.delayed ? (size_t)scatter_dz_splits(d->B * d->N) * d->C[0] * 4 : 0);
     s.mom = cv.take<double>((!d->group_all && d->D == 0) ? xyz0_moment_doubles() : 0);
     s.bytes = cv.bytes();
     return s;
 }
 
-static AOperand layer0_operand(const pnpp_sa_desc *d, const float *xyz, const float *points, const SaSaved &sv) {
-    AOperand A;
-    A.mode = d->group_all ? A_CONCAT : A_GATHER;
-    A.a = points;
-    A.xyz = xyz;
-    A.new_xyz = sv.new_xyz;
-    A.idx = sv.idx;
-    A.D = d->D;
-    A.N = d->N;
-    A.S = d->S;
-    A.K = d->K;
-    return A;
+// the call's workspaces and tensors; the statistics every layer keeps live in `saved`
+static void sa_level_bind(SaLevel *L, void *saved, void *scratch, const float *xyz, const float *points, const float *const *conv_w,
+                          const float *const *gamma, hipStream_t st) {
+    L->sv = sa_saved_layout(*L, saved);
+    L->sc = sa_scratch_layout(*L, scratch);
+    L->xyz = xyz, L->points = points, L->conv_w = conv_w, L->st = st;
+    for (int l = 0; l < L->d->L; ++l) {
+        BnLayer &b = L->bn[l];
+        b.C = L->d->C[l], b.gamma = gamma[l];
+        b.mean = L->sv.mean[l], b.istd = L->sv.istd[l], b.scale = L->sv.scale[l], b.shift = L->sv.shift[l];
+    }
 }
 
-static int sa_forward_impl(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, hipStream_t st) {
-    SaGeom g;
-    PNPP_TRY(sa_geom(d, &g));
+// A/B switches (PNPP_NO_POOL_FUSION=1: pooling stays a pass of its own over Z; PNPP_NO_POOL_BWD_FUSION=1: so does its backward)
+static bool pool_fused_on() { static const bool on = env_int("PNPP_NO_POOL_FUSION", 0) == 0; return on; }
+static bool pool_bwd_fused_on() { static const bool on = env_int("PNPP_NO_POOL_BWD_FUSION", 0) == 0; return on; }
+
+// ---- forward ----
+static int sa_level_fwd(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, hipStream_t st, SaLevel *L) {
+    PNPP_TRY(sa_level_plan(d, L));
     PNPP_REQUIRE(a && a->xyz && a->new_xyz && a->out && a->saved && a->scratch, PNPP_ERR_ARG, "sa_forward: null pointer");
     PNPP_REQUIRE(d->D == 0 || a->points, PNPP_ERR_ARG, "sa_forward: D=%d but points is null", d->D);
     PNPP_REQUIRE(d->group_all || a->centre_idx, PNPP_ERR_ARG, "sa_forward: centre_idx is null");
-    for (int l = 0; l < d->L; ++l)
+    for (int l = 0; l < d->L; ++l) {
         PNPP_REQUIRE(a->conv_w[l] && a->conv_b[l] && a->bn_w[l] && a->bn_b[l] && a->bn_rm[l] && a->bn_rv[l], PNPP_ERR_ARG,
                      "sa_forward: null parameter pointer in layer %d", l);
-    const SaSaved sv = sa_saved_layout(d, g, a->saved);
-    const SaScratch sc = sa_scratch_layout(d, g, a->scratch);
-
-    // 1. centres and neighbours (pointnet_pp_8dir.py:23-31)
-    if (d->group_all) {
-        // the centres are the origin: written by the pooling launch that ends this forward (nothing in between reads them)
-    } else {
-        PNPP_REQUIRE(d->S <= d->N, PNPP_ERR_RANGE, "sa_forward: npoint=%d > N=%d", d->S, d->N);
-        if (a->neighbour_idx == sv.idx) {
-            // grouped ahead of time by pnpp_sa_group_pair: neighbours, saved centres and new_xyz are already in place
-        } else if (a->neighbour_idx) {
-            PNPP_TRY(launch_gather_centres(a->xyz, a->centre_idx, d->B, d->N, d->S, a->new_xyz, sv.new_xyz, st));
-            hipError_t e = hipMemcpyAsync(sv.idx, a->neighbour_idx, (size_t)g.M * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
-            PNPP_REQUIRE(e == hipSuccess, PNPP_ERR_LAUNCH, "sa_forward: neighbour copy failed: %s", hipGetErrorString(e));
-        } else {  // the neighbour search gathers its own queries and writes the centre coordinates on the way
-            PNPP_TRY(launch_knn_centres(a->xyz, a->centre_idx, d->B, d->S, d->N, d->K, sv.idx, a->new_xyz, sv.new_xyz, st));
-        }
+        BnLayer &b = L->bn[l];
+        b.bias = a->conv_b[l], b.beta = a->bn_b[l], b.rm = a->bn_rm[l], b.rv = a->bn_rv[l];
+        b.nbt = d->training ? (long long *)a->bn_nbt[l] : nullptr;
     }
-
-    // 2. conv -> BN -> ReLU chain; BN apply + ReLU of layer l-1 happen inside layer l's operand loader
-    bool pooled = false;
-    // a level on raw coordinates (SA1): layer 0 never exists as a tensor -- its statistics come from the moments of the relative
-    // coordinates, layer 1's product builds its operand from the coordinates (gemm_wsx_kernels.hip); the backward pass does the same
-    const bool xyz0 = xyz0_applies(g.M, d->D, d->K, d->group_all, d->L, d->C);
-    int nmom = 0;
-    const double *mom = sc.mom;
-    for (int l = 0; l < d->L; ++l) {
-        if (xyz0 && l == 0) {
-            if (d->training) {
-                if (a->neighbour_idx == sv.idx && sa_pair_moments(d, g)) mom = sv.mom, nmom = knn_pair_moment_partials(d->B, d->S, d->N);
-                else PNPP_TRY(launch_rel_moments(layer0_operand(d, a->xyz, a->points, sv), g.M, sc.mom, &nmom, st));
-            } else {
-                PNPP_TRY(launch_bn_finalize_fwd(nullptr, 0, d->C[0], (double)g.M, a->conv_b[0], a->bn_w[0], a->bn_b[0], a->bn_rm[0],
-                                                a->bn_rv[0], nullptr, d->momentum, d->eps, 0, sv.mean[0], sv.istd[0], sv.scale[0],
-                                                sv.shift[0], st));
-            }
-            continue;
-        }
-        // layer 1 of such a level: the product that also finishes layer 0's BatchNorm
-        auto gemm_l = [&](const AOperand &Aop, const BOperand &Wop, const Epilogue &Eop, int *ns) -> int {
-            if (xyz0 && l == 1)
-                return launch_wsf0(layer0_operand(d, a->xyz, a->points, sv), g.M, a->conv_w[0], g.Cin[0], mom, nmom, d->training ? 1 : 0,
-                                   a->conv_b[0], a->bn_w[0], a->bn_b[0], a->bn_rm[0], a->bn_rv[0],
-                                   d->training ? (long long *)a->bn_nbt[0] : nullptr, d->momentum, d->eps, sv.mean[0], sv.istd[0],
-                                   sv.scale[0], sv.shift[0], a->conv_w[1], g.Cin[1], Eop, ns, st);
-            return launch_gemm(Aop, Wop, g.M, d->C[l], g.Kd[l], Eop, ns, st);
-        };
-        AOperand A;
-        if (l == 0) {
-            A = layer0_operand(d, a->xyz, a->points, sv);
-        } else {
-            A.mode = A_BNRELU;
-            A.a = sv.z[l - 1];
-            A.lda = d->C[l - 1];
-            A.scale = sv.scale[l - 1];
-            A.shift = sv.shift[l - 1];
-        }
-        Epilogue E;
-        E.c = sv.z[l];
-        E.ldc = d->C[l];
-        BOperand W;  // the conv weight (C_l x Cin_l) is read in place; layer 0 maps features-first k' to xyz-first columns
-        W.b = a->conv_w[l];
-        W.ldb = g.Cin[l];
-        W.trans = 1;
-        W.perm_D = l == 0 ? d->D : -1;
-        W.rows = g.Cin[l];
-        int nslab = 0;
-        if (l == 0 && sa_delayed(d)) {  // P = F W_f^T on the source points, then Z = P[idx] + W_xyz (x - c) with statistics
-            AOperand F;
-            F.a = a->points;
-            F.lda = d->D;
-            BOperand Wf;
-            Wf.b = a->conv_w[0] + 3;
-            Wf.ldb = g.Cin[0];
-            Wf.trans = 1;
-            Wf.rows = d->D;
-            Epilogue Ep;
-            Ep.mode = E_STORE;
-            Ep.c = sc.src;
-            Ep.ldc = d->C[0];
-            PNPP_TRY(launch_gemm(F, Wf, d->B * d->N, d->C[0], d->D, Ep, nullptr, st));
-            PNPP_TRY(launch_gather_rel_stats(sc.src, A, a->conv_w[0], g.Cin[0], g.M, d->C[0], sv.z[0],
-                                             d->training ? sc.slab : nullptr, &nslab, st));
-            StatsView V;
-            if (d->training) PNPP_TRY(stats_exchange(sc.slab, nslab, d->C[0], (double)g.M, st, &V));
-            PNPP_TRY(launch_bn_finalize_fwd(V.slab, V.nslab, d->C[0], (double)g.M, a->conv_b[0],
-                                            a->bn_w[0], a->bn_b[0], a->bn_rm[0], a->bn_rv[0],
-                                            d->training ? (long long *)a->bn_nbt[0] : nullptr, d->momentum, d->eps, d->training ? 1 : 0,
-                                            sv.mean[0], sv.istd[0], sv.scale[0], sv.shift[0], st, V.count_dev));
-        } else if (d->training) {
-            E.mode = E_STORE_STATS;
-            E.slab = sc.slab;
-            // last layer of a level with 32-row neighbourhoods: the max over the neighbourhood is taken from the GEMM's accumulators
-            // and finished by the statistics launch (sv.zmax holds the extreme pre-BN values; the backward pass reads them too)
-            const bool pool_here = l == d->L - 1 && l > 0 && pool_fused_on() && gemm_pools_in_epilogue(A, g.M, d->C[l], g.Kd[l], d->K);
-            if (pool_here) E.pool_ext = sv.zmax, E.pool_arg = sv.arg, E.pool_gamma = a->bn_w[l];
-            PNPP_TRY(gemm_l(A, W, E, &nslab));
-            StatsView V;
-            PNPP_TRY(stats_exchange(sc.slab, nslab, d->C[l], (double)g.M, st, &V));
-            PNPP_TRY(launch_bn_finalize_fwd(V.slab, V.nslab, d->C[l], (double)g.M, a->conv_b[l], a->bn_w[l], a->bn_b[l],
-                                            a->bn_rm[l], a->bn_rv[l], (long long *)a->bn_nbt[l], d->momentum, d->eps, 1, sv.mean[l], sv.istd[l],
-                                            sv.scale[l], sv.shift[l], st, V.count_dev, pool_here ? sv.zmax : nullptr,
-                                            pool_here ? a->out : nullptr, g.G, pool_here ? sv.arg : nullptr,
-                                            d->group_all ? a->new_xyz : nullptr, d->group_all ? sv.new_xyz : nullptr,
-                                            d->group_all ? g.G * 3 : 0));
-            pooled = pool_here;
-        } else {
-            E.mode = E_STORE;
-            PNPP_TRY(launch_bn_finalize_fwd(nullptr, 0, d->C[l], (double)g.M, a->conv_b[l], a->bn_w[l], a->bn_b[l],
-                                            a->bn_rm[l], a->bn_rv[l], nullptr, d->momentum, d->eps, 0, sv.mean[l], sv.istd[l],
-                                            sv.scale[l], sv.shift[l], st));
-            PNPP_TRY(gemm_l(A, W, E, nullptr));
-        }
-    }
-
-    // 3. max over the neighbourhood (pointnet_pp_8dir.py:42-43), unless the last layer's launches have taken it
-    const int Lm = d->L - 1;
-    if (!pooled) PNPP_TRY(launch_pool_fwd(sv.z[Lm], sv.scale[Lm], sv.shift[Lm], g.G, d->K, d->C[Lm], a->out, sv.arg, st,
-                             d->group_all ? a->new_xyz : nullptr, d->group_all ? sv.new_xyz : nullptr, d->group_all ? g.G * 3 : 0,
-                             sc.dy[0],   // dy[0] (M x C floats) is idle in the forward pass: >= the K/64 partials per (group, channel)
-                             sa_keeps_zmax(d, g) ? sv.zmax : nullptr));
+    sa_level_bind(L, a->saved, a->scratch, a->xyz, a->points, a->conv_w, a->bn_w, st);
+    L->hyper = BnHyper{d->momentum, d->eps, d->training ? 1 : 0};
     return PNPP_OK;
 }
 
-static int sa_backward_impl(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, hipStream_t st) {
-    SaGeom g;
-    PNPP_TRY(sa_geom(d, &g));
+// 1. centres and neighbours (pointnet_pp_8dir.py:23-31)
+static int sa_fwd_group(const SaLevel &L, const pnpp_sa_fwd_args *a) {
+    const pnpp_sa_desc *d = L.d;
+    const SaSaved &sv = L.sv;
+    if (d->group_all) return PNPP_OK;   // the centres are the origin: written by the pooling launch that ends this forward
+    PNPP_REQUIRE(d->S <= d->N, PNPP_ERR_RANGE, "sa_forward: npoint=%d > N=%d", d->S, d->N);
+    if (a->neighbour_idx == sv.idx) return PNPP_OK;   // grouped ahead of time by pnpp_sa_group_pair: everything is already in place
+    if (!a->neighbour_idx)   // the neighbour search gathers its own queries and writes the centre coordinates on the way
+        return launch_knn_centres(a->xyz, a->centre_idx, d->B, d->S, d->N, d->K, sv.idx, a->new_xyz, sv.new_xyz, L.st);
+    PNPP_TRY(launch_gather_centres(a->xyz, a->centre_idx, d->B, d->N, d->S, a->new_xyz, sv.new_xyz, L.st));
+    hipError_t e = hipMemcpyAsync(sv.idx, a->neighbour_idx, (size_t)L.g.M * sizeof(int32_t), hipMemcpyDeviceToDevice, L.st);
+    PNPP_REQUIRE(e == hipSuccess, PNPP_ERR_LAUNCH, "sa_forward: neighbour copy failed: %s", hipGetErrorString(e));
+    return PNPP_OK;
+}
+
+// Layer l's BatchNorm: training from the nslab partial sums in sc.slab (exchanged over the ranks first under SyncBN), eval from the
+// running statistics.  tail: what else rides in the launch (the pooled output, a group_all level's centres).
+static int sa_fwd_finalize(const SaLevel &L, int l, int nslab, const PoolTail *tail = nullptr) {
+    StatsView V;
+    if (L.d->training) PNPP_TRY(stats_exchange(L.sc.slab, nslab, L.d->C[l], L.count(), L.st, &V));
+    return launch_bn_finalize_fwd(V, L.count(), L.bn[l], L.hyper, L.st, tail);
+}
+
+// layer l's product; layer 1 of a level on raw coordinates is the product that also finishes layer 0's BatchNorm from (mom, nmom)
+static int sa_fwd_gemm(const SaLevel &L, int l, const AOperand &A, const BOperand &W, const Epilogue &E, const double *mom, int nmom, int *ns) {
+    if (L.xyz0 && l == 1)
+        return launch_wsf0(L.layer0_operand(), L.g.M, L.weight(0, 0), mom, nmom, L.bn[0], L.hyper, L.weight(1, 0), E, ns, L.st);
+    return launch_gemm(A, W, L.g.M, L.d->C[l], L.g.Kd[l], E, ns, L.st);
+}
+
+// delayed layer 0: P = F W_f^T on the source points, then Z = P[idx] + W_xyz (x - c) with statistics
+static int sa_fwd_delayed0(const SaLevel &L, const AOperand &geo) {
+    const pnpp_sa_desc *d = L.d;
+    AOperand F;
+    F.a = L.points, F.lda = d->D;
+    BOperand Wf = L.w0_features();
+    Wf.trans = 1, Wf.rows = d->D;
+    int nslab = 0;
+    PNPP_TRY(launch_gemm(F, Wf, d->B * d->N, d->C[0], d->D, store_to(L.sc.src, d->C[0]), nullptr, L.st));
+    PNPP_TRY(launch_gather_rel_stats(L.sc.src, geo, L.conv_w[0], L.g.Cin[0], L.g.M, d->C[0], L.sv.z[0], d->training ? L.sc.slab : nullptr,
+                                     &nslab, L.st));
+    return sa_fwd_finalize(L, 0, nslab);
+}
+
+static int sa_forward_impl(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, hipStream_t st) {
+    SaLevel L;
+    PNPP_TRY(sa_level_fwd(d, a, st, &L));
+    const SaGeom &g = L.g;
+    const SaSaved &sv = L.sv;
+    const SaScratch &sc = L.sc;
+    PNPP_TRY(sa_fwd_group(L, a));
+    // 2. conv -> BN -> ReLU chain; BN apply + ReLU of layer l-1 happen inside layer l's operand loader
+    const int Lm = d->L - 1;
+    bool pooled = false;
+    int nmom = 0;
+    const double *mom = sc.mom;   // a level on raw coordinates, training: the moment partials layer 0's statistics come from
+    for (int l = 0; l < d->L; ++l) {
+        if (L.xyz0 && l == 0) {   // no product: layer 1's launch builds this layer from the coordinates
+            if (!d->training) PNPP_TRY(sa_fwd_finalize(L, 0, 0));
+            else if (a->neighbour_idx == sv.idx && L.pair_moments) mom = sv.mom, nmom = knn_pair_moment_partials(d->B, d->S, d->N);
+            else PNPP_TRY(launch_rel_moments(L.layer0_operand(), g.M, sc.mom, &nmom, st));
+            continue;
+        }
+        const AOperand A = L.input_of(l);
+        if (l == 0 && L.delayed) {
+            PNPP_TRY(sa_fwd_delayed0(L, A));
+            continue;
+        }
+        Epilogue E = store_to(sv.z[l], d->C[l]);
+        BOperand W = L.weight(l, g.Cin[l]);  // the conv weight is read in place; layer 0 maps features-first k' to xyz-first columns
+        W.trans = 1, W.perm_D = l == 0 ? d->D : -1;
+        if (!d->training) {
+            PNPP_TRY(sa_fwd_finalize(L, l, 0));
+            PNPP_TRY(sa_fwd_gemm(L, l, A, W, E, mom, nmom, nullptr));
+            continue;
+        }
+        E.mode = E_STORE_STATS, E.slab = sc.slab;
+        // last layer of a level with 32-row neighbourhoods: the max over the neighbourhood is taken from the GEMM's accumulators
+        // and finished by the statistics launch (sv.zmax holds the extreme pre-BN values; the backward pass reads them too)
+        const bool pool_here = l == Lm && l > 0 && pool_fused_on() && gemm_pools_in_epilogue(A, g.M, d->C[l], g.Kd[l], d->K);
+        PoolTail T;
+        T.G = g.G;
+        if (pool_here) {
+            E.pool_ext = sv.zmax, E.pool_arg = sv.arg, E.pool_gamma = L.bn[l].gamma;
+            T.pool_ext = sv.zmax, T.pool_out = a->out, T.pool_arg = sv.arg;
+        }
+        if (d->group_all) T.origin_a = a->new_xyz, T.origin_b = sv.new_xyz, T.norigin = g.G * 3;
+        int nslab = 0;
+        PNPP_TRY(sa_fwd_gemm(L, l, A, W, E, mom, nmom, &nslab));
+        PNPP_TRY(sa_fwd_finalize(L, l, nslab, &T));
+        pooled = pool_here;
+    }
+    // 3. max over the neighbourhood (pointnet_pp_8dir.py:42-43), unless the last layer's launches have taken it
+    // (the split form's partials go to dy[0], M x C floats idle in the forward pass: >= the K/64 partials per (group, channel))
+    if (!pooled) PNPP_TRY(launch_pool_fwd(sv.z[Lm], sv.scale[Lm], sv.shift[Lm], g.G, d->K, d->C[Lm], a->out, sv.arg, st,
+                             d->group_all ? a->new_xyz : nullptr, d->group_all ? sv.new_xyz : nullptr, d->group_all ? g.G * 3 : 0,
+                             sc.dy[0], L.keeps_zmax ? sv.zmax : nullptr));
+    return PNPP_OK;
+}
+
+// ---- backward: sa_backward_impl drives the steps below, top layer first ----
+static int sa_level_bwd(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, hipStream_t st, SaLevel *L) {
+    PNPP_TRY(sa_level_plan(d, L));
     PNPP_REQUIRE(a && a->xyz && a->dout && a->saved && a->scratch, PNPP_ERR_ARG, "sa_backward: null pointer");
     for (int l = 0; l < d->L; ++l)
         PNPP_REQUIRE(a->conv_w[l] && a->bn_w[l] && a->d_conv_w[l] && a->d_conv_b[l] && a->d_bn_w[l] && a->d_bn_b[l], PNPP_ERR_ARG,
                      "sa_backward: null pointer in layer %d", l);
-    const bool want_dpoints = d->D > 0 && a->dpoints != nullptr;
-    if (want_dpoints) PNPP_REQUIRE(d->D % 4 == 0, PNPP_ERR_ARG, "sa_backward: feature width D=%d must be a multiple of 4", d->D);
-    const SaSaved sv = sa_saved_layout(d, g, const_cast<void *>(a->saved));
-    const SaScratch sc = sa_scratch_layout(d, g, a->scratch);
+    L->want_dpoints = d->D > 0 && a->dpoints != nullptr;
+    if (L->want_dpoints) PNPP_REQUIRE(d->D % 4 == 0, PNPP_ERR_ARG, "sa_backward: feature width D=%d must be a multiple of 4", d->D);
+    sa_level_bind(L, const_cast<void *>(a->saved), a->scratch, a->xyz, a->points, a->conv_w, a->bn_w, st);
+    for (int l = 0; l < d->L; ++l) L->dbn[l] = BnGrads{a->d_bn_w[l], a->d_bn_b[l], a->d_conv_b[l]};
+    return PNPP_OK;
+}
 
+struct SaBwdState {   // what one step of the backward driver leaves for the next
+    int cur = 0;                 // sc.dy[cur] holds dY of the layer being processed; sc.dy[cur ^ 1] is free
+    bool dz_ready = false;       // small-M levels: sc.dzbuf already holds dZ of the layer about to be processed
+    bool dpoints_done = false;   // layer 0's dW launch has written the feature gradient as well
+};
+
+// the view layer l's BatchNorm-backward sums (nslab partials in sc.slab) are finalised from
+static int sa_bwd_stats(const SaLevel &L, int l, int nslab, StatsView *V) {
+    V->slab = L.sc.slab, V->nslab = nslab;
+    if (L.d->training) PNPP_TRY(stats_exchange(L.sc.slab, nslab, L.d->C[l], L.count(), L.st, V));
+    return PNPP_OK;
+}
+
+// The top: the pooled gradient through max + ReLU, and the top layer's BatchNorm-backward constants (sc.cst).
+// A level with few groups (group_all: one per cloud) whose dZ is materialised anyway: the finalisation launch takes the pooled
+// gradient as it is -- no pool_bwd launch, no dm tensor (PNPP_NO_POOL_BWD_FUSION=1 keeps the launch)
+static int sa_bwd_top(const SaLevel &L, const pnpp_sa_bwd_args *a, SaBwdState *S) {
+    const pnpp_sa_desc *d = L.d;
+    const SaGeom &g = L.g;
+    const SaSaved &sv = L.sv;
+    const SaScratch &sc = L.sc;
     const int Lm = d->L - 1;
-    int cur = 0, nslab = 0, nslab_next = 0;
-    // a level with few groups (group_all: one per cloud) whose dZ is materialised anyway: the finalisation launch takes the pooled
-    // gradient as it is -- no pool_bwd launch, no dm tensor (PNPP_NO_POOL_BWD_FUSION=1 keeps the launch)
-    static const bool pool_bwd_fused = env_int("PNPP_NO_POOL_BWD_FUSION", 0) == 0;
-    const bool pooled_src = pool_bwd_fused && g.M <= kSmallM && g.G <= 64 && sa_keeps_zmax(d, g) && (d->C[Lm] & 3) == 0 &&
+    const bool pooled_src = pool_bwd_fused_on() && L.small && g.G <= 64 && L.keeps_zmax && (d->C[Lm] & 3) == 0 &&
                             !(d->training && stats_sync_on());
-    if (!pooled_src)
-        PNPP_TRY(launch_pool_bwd(a->dout, sv.arg, sv.z[Lm], sv.scale[Lm], sv.shift[Lm], sv.mean[Lm], sv.istd[Lm], g.G, d->K,
-                                 d->C[Lm], sc.dm, sc.slab, &nslab, st, sa_keeps_zmax(d, g) ? sv.zmax : nullptr));
-    // sc.cst holds the BatchNorm-backward constants of the layer being processed; layer l-1's are produced (together with
-    // layer l's weight-gradient reduction) by the post-GEMM launch that ends iteration l
-    // small-M levels materialise dZ once per layer; that pass rides in the launch that finalises the layer's BatchNorm sums
-    const bool small = g.M <= kSmallM;
-    auto dz_operand = [&](int l, int buf) {
-        AOperand dz;  // the top layer's dense gradient is never materialised (A_DZ_POOL rebuilds it from dm / arg)
-        dz.mode = l == Lm ? A_DZ_POOL : A_DZ;
-        dz.a = l == Lm ? sc.dm : sc.dy[buf];
-        dz.arg = sv.arg;
-        dz.K = d->K;
-        dz.lda = d->C[l];
-        dz.z = sv.z[l];
-        dz.cst = sc.cst;
-        dz.C = d->C[l];
-        return dz;
-    };
-    AOperand dz_top = dz_operand(Lm, 0);
+    AOperand dz_top = L.dz_operand(Lm, 0);
+    S->dz_ready = L.small;
     if (pooled_src) {
         dz_top.a = a->dout;   // the dZ job masks it itself
         PooledSource ps;
         ps.dout = a->dout, ps.zsel = sv.zmax, ps.scale = sv.scale[Lm], ps.shift = sv.shift[Lm], ps.G = g.G;
-        PNPP_TRY(launch_bn_finalize_bwd(nullptr, 0, d->C[Lm], (double)g.M, d->training, a->bn_w[Lm], sv.mean[Lm], sv.istd[Lm], sc.cst,
-                                        a->d_bn_w[Lm], a->d_bn_b[Lm], a->d_conv_b[Lm], st, &dz_top, g.M, sc.dzbuf, nullptr, nullptr, &ps));
-    } else {
-        StatsView V;
-        V.slab = sc.slab, V.nslab = nslab;
-        if (d->training) PNPP_TRY(stats_exchange(sc.slab, nslab, d->C[Lm], (double)g.M, st, &V));
-        PNPP_TRY(launch_bn_finalize_bwd(V.slab, V.nslab, d->C[Lm], (double)g.M, d->training, a->bn_w[Lm], sv.mean[Lm], sv.istd[Lm],
-                                        sc.cst, a->d_bn_w[Lm], a->d_bn_b[Lm], a->d_conv_b[Lm], st, small ? &dz_top : nullptr, g.M,
-                                        small ? sc.dzbuf : nullptr, V.count_dev, V.local));
+        return launch_bn_finalize_bwd(StatsView(), L.count(), d->training, L.bn[Lm], sc.cst, L.dbn[Lm], L.st, L.dz_side(&dz_top), &ps);
     }
-    bool dz_ready = small;  // sc.dzbuf holds dZ of the layer about to be processed
-    bool dpoints_done = false;
-    for (int l = Lm; l >= 0; --l) {
-        const int C = d->C[l];
-        AOperand dz = dz_operand(l, cur);
-        if (small) {  // every consumer would rebuild dZ per 32 x 32 tile: it was written out once instead
-            if (!dz_ready) PNPP_TRY(launch_dz_materialize(dz, g.M, C, sc.dzbuf, st));
-            dz_ready = false;
-            dz = AOperand();
-            dz.mode = A_PLAIN;
-            dz.a = sc.dzbuf;
-            dz.lda = C;
-        }
+    int nslab = 0;
+    PNPP_TRY(launch_pool_bwd(a->dout, sv.arg, sv.z[Lm], sv.scale[Lm], sv.shift[Lm], sv.mean[Lm], sv.istd[Lm], g.G, d->K, d->C[Lm], sc.dm,
+                             sc.slab, &nslab, L.st, L.keeps_zmax ? sv.zmax : nullptr));
+    StatsView V;
+    PNPP_TRY(sa_bwd_stats(L, Lm, nslab, &V));
+    return launch_bn_finalize_bwd(V, L.count(), d->training, L.bn[Lm], sc.cst, L.dbn[Lm], L.st, L.dz_side(&dz_top));
+}
 
-        if (l == 1 && xyz0_applies(g.M, d->D, d->K, d->group_all, d->L, d->C)) {
-            // layer 0 convolves relative coordinates only: layer 1's backward rebuilds Z_0 from them, keeps dY_0 on chip and hands
-            // layer 0's parameter gradients to the launch that reduces dW_1 (gemm_wsx_kernels.hip) -- two launches end the level
-            const AOperand geo = layer0_operand(d, a->xyz, a->points, sv);
-            BOperand W;
-            W.b = a->conv_w[1];
-            W.ldb = d->C[0];
-            W.rows = C;
-            int workers = 0, rc = PNPP_OK;
-            if (try_launch_wsx(dz, W, g.M, C, d->C[0], geo, a->conv_w[0], g.Cin[0], sv.scale[0], sv.shift[0], sc.dwslab, sc.slab, &workers, st,
-                               &rc)) {
-                PNPP_TRY(rc);
-                PNPP_TRY(launch_xyz0_post(sc.dwslab, workers, C, a->d_conv_w[1], g.Cin[1], sc.slab, a->conv_w[0], g.Cin[0], a->bn_w[0],
-                                          sv.mean[0], sv.istd[0], (double)g.M, d->training, a->d_conv_w[0], g.Cin[0], a->d_bn_w[0],
-                                          a->d_bn_b[0], a->d_conv_b[0], st));
-                break;
-            }
-            // the forward pass of this level kept no Z_0: there is no generic path to fall back to
-            PNPP_REQUIRE(false, PNPP_ERR_ARG, "sa_backward: the coordinate-level backward kernel does not take this call (alignment?)");
-        }
-        AOperand a2;
-        if (l == 0) {
-            a2 = layer0_operand(d, a->xyz, a->points, sv);
-        } else {
-            a2.mode = A_BNRELU;
-            a2.a = sv.z[l - 1];
-            a2.lda = d->C[l - 1];
-            a2.scale = sv.scale[l - 1];
-            a2.shift = sv.shift[l - 1];
-        }
-        int nsplit, kp_pad;
-        dw_plan(g.M, C, g.Cin[l], &nsplit, &kp_pad);
-        int fused_slabs = 0;
-        bool pair_done = false;
-        if (l > 0) {
-            // dY_{l-1} = (dZ_l * W_l) masked by ReLU'(layer l-1), with layer l-1's BN-backward sums; where the
-            // weights-stationary kernel applies, dW_l = dZ_l^T * relu(bn(Z_{l-1})) is accumulated in the same launch
-            Epilogue E;
-            E.mode = E_MASK_STATS;
-            E.c = sc.dy[cur ^ 1];
-            E.ldc = d->C[l - 1];
-            E.slab = sc.slab;
-            E.zp = sv.z[l - 1];
-            E.scale = sv.scale[l - 1];
-            E.shift = sv.shift[l - 1];
-            E.mu = sv.mean[l - 1];
-            E.istd = sv.istd[l - 1];
-            E.dwslab = sc.dwslab;
-            E.dw_ld = d->C[l - 1];
-            BOperand W;  // W_l (C_l x C_{l-1}) row-major as stored
-            W.b = a->conv_w[l];
-            W.ldb = d->C[l - 1];
-            W.rows = C;
-            int dw_slabs = 0, rc = PNPP_OK;
-            if (try_launch_da_dw(dz, W, g.M, d->C[l - 1], C, E, &nslab_next, a2, g.Cin[l], sc.dwslab, &nsplit, &kp_pad, st, &rc,
-                                 a->d_conv_w[l], g.Cin[l])) {
-                PNPP_TRY(rc);  // small-M level: dA and dW of this layer went out as one launch
-                pair_done = true;
-            } else {
-                PNPP_TRY(launch_gemm(dz, W, g.M, d->C[l - 1], C, E, &nslab_next, st, &dw_slabs));
-            }
-            fused_slabs = dw_slabs;
-        }
-        const bool xyz_only = l == 0 && d->D == 0 && (a2.mode == A_GATHER || (a2.mode == A_CONCAT && g.M >= 8192)) &&
-                              dw_xyz_splits(g.M) <= nsplit * (kp_pad / 4);
-        if (l == 0 && sa_delayed(d)) {
-            // G = dZ_0 summed per source point (dW_xyz = dZ_0^T (x - c) in the same pass); dW_f = G^T F, dF = G W_f
-            const int R = d->B * d->N;
-            PNPP_TRY(launch_scatter_dz(dz, a2, d->B, d->S * d->K, C, sc.src, sc.xslab, st));
-            AOperand G, F;
-            G.a = sc.src;
-            G.lda = C;
-            F.a = a->points;
-            F.lda = d->D;
-            dw_plan(R, C, d->D, &nsplit, &kp_pad);
-            bool paired = false;
-            if (want_dpoints) {  // dW_f = G^T F and dF = G W_f only share G: one launch
-                Epilogue E;
-                E.mode = E_STORE;
-                E.c = a->dpoints;
-                E.ldc = d->D;
-                BOperand W;
-                W.b = a->conv_w[0] + 3;
-                W.ldb = g.Cin[0];
-                W.rows = C;
-                int rc = PNPP_OK;
-                paired = try_launch_da_dw(G, W, R, d->D, C, E, nullptr, F, d->D, sc.dwslab, &nsplit, &kp_pad, st, &rc);
-                if (paired) PNPP_TRY(rc);
-            }
-            if (!paired) PNPP_TRY(launch_dw(G, C, F, d->D, R, sc.dwslab, nsplit, kp_pad, st));
-            // both partial sets of W_0 -- coordinate columns 0..2, feature columns 3.. -- in one launch
-            PNPP_TRY(launch_slab_reduce2(sc.xslab, scatter_dz_splits(R), C, 4, 3, a->d_conv_w[0], g.Cin[0], sc.dwslab, nsplit, C, kp_pad,
-                                         d->D, a->d_conv_w[0] + 3, g.Cin[0], st));
-            if (want_dpoints && !paired) {
-                Epilogue E;
-                E.mode = E_STORE;
-                E.c = a->dpoints;
-                E.ldc = d->D;
-                BOperand W;
-                W.b = a->conv_w[0] + 3;
-                W.ldb = g.Cin[0];
-                W.rows = C;
-                PNPP_TRY(launch_gemm(G, W, R, d->D, C, E, nullptr, st));
-            }
-            break;
-        }
-        if (xyz_only) {  // C x 3 gradient: streaming kernel (the MFMA tiles would be 95 % padding)
-            PNPP_TRY(launch_dw_xyz(dz, C, a2, g.M, sc.dwslab, st));
-            nsplit = dw_xyz_splits(g.M), kp_pad = 4;
-        } else if (fused_slabs == 0 && !pair_done) {  // dW_l = dZ_l^T * A_l as its own launch (layer 0, group_all layers, odd shapes)
-            // group_all layer 0 with a feature gradient to return: dW_0 and dF = dZ_0 W_f only share dZ_0 -- one launch
-            bool paired0 = false;
-            if (l == 0 && want_dpoints && d->group_all) {
-                Epilogue E;
-                E.mode = E_STORE;
-                E.ldc = d->D;
-                E.c = a->dpoints;
-                BOperand W;
-                W.b = a->conv_w[0] + 3;
-                W.ldb = g.Cin[0];
-                W.rows = C;
-                int rc = PNPP_OK;
-                paired0 = try_launch_da_dw(dz, W, g.M, d->D, C, E, nullptr, a2, g.Cin[0], sc.dwslab, &nsplit, &kp_pad, st, &rc);
-                if (paired0) PNPP_TRY(rc);
-                dpoints_done = paired0;
-            }
-            if (!paired0) PNPP_TRY(launch_dw(dz, C, a2, g.Cin[l], g.M, sc.dwslab, nsplit, kp_pad, st));
-        }
-        if (l > 0) {  // reduce dW_l's partials and finalise layer l-1's BatchNorm-backward sums in one launch
-            const int Cp = d->C[l - 1];
-            const AOperand dz_next = dz_operand(l - 1, cur ^ 1);  // dY_{l-1} was just written to sc.dy[cur ^ 1]
-            StatsView V;
-            V.slab = sc.slab, V.nslab = nslab_next;
-            if (d->training) PNPP_TRY(stats_exchange(sc.slab, nslab_next, Cp, (double)g.M, st, &V));
-            PNPP_TRY(launch_post_gemm(V.slab, V.nslab, Cp, (double)g.M, d->training, a->bn_w[l - 1], sv.mean[l - 1],
-                                      sv.istd[l - 1], sc.cst, a->d_bn_w[l - 1], a->d_bn_b[l - 1],
-                                      a->d_conv_b[l - 1], sc.dwslab, fused_slabs > 0 ? fused_slabs : nsplit, C,
-                                      fused_slabs > 0 ? Cp : kp_pad, g.Cin[l], -1, a->d_conv_w[l], g.Cin[l], st,
-                                      small ? &dz_next : nullptr, g.M, small ? sc.dzbuf : nullptr, V.count_dev, V.local));
-            dz_ready = small;
-        } else {
-            PNPP_TRY(launch_slab_reduce(sc.dwslab, nsplit, C, kp_pad, g.Cin[l], d->D, a->d_conv_w[l], g.Cin[l], st));
-        }
+// dZ_l as layer l's launches read it: rebuilt on the fly, or -- small-M levels, where every consumer would rebuild it per
+// 32 x 32 tile -- written out once (by the finalisation before, or here)
+static int sa_bwd_dz(const SaLevel &L, int l, SaBwdState *S, AOperand *dz) {
+    *dz = L.dz_operand(l, S->cur);
+    if (!L.small) return PNPP_OK;
+    if (!S->dz_ready) PNPP_TRY(launch_dz_materialize(*dz, L.g.M, L.d->C[l], L.sc.dzbuf, L.st));
+    S->dz_ready = false;
+    *dz = AOperand();
+    dz->mode = A_PLAIN, dz->a = L.sc.dzbuf, dz->lda = L.d->C[l];
+    return PNPP_OK;
+}
 
-        if (l > 0) {
-            nslab = nslab_next;
-            cur ^= 1;
-        } else if (want_dpoints) {
-            Epilogue E;
-            E.mode = E_STORE;
-            E.ldc = d->D;
-            BOperand W;  // feature columns of W_0: (C_0 x (3+D)) row-major, skip the three xyz columns
-            W.b = a->conv_w[0] + 3;
-            W.ldb = g.Cin[0];
-            W.rows = C;
-            if (d->group_all) {  // rows are the points themselves
-                E.c = a->dpoints;
-                if (!dpoints_done) PNPP_TRY(launch_gemm(dz, W, g.M, d->D, C, E, nullptr, st));
-            } else {
-                E.c = sc.dy[cur ^ 1];
-                PNPP_TRY(launch_gemm(dz, W, g.M, d->D, C, E, nullptr, st));
-                PNPP_TRY(launch_fill_zero(a->dpoints, (size_t)d->B * d->N * d->D * sizeof(float), st));
-                PNPP_TRY(launch_scatter_rows_bwd(sc.dy[cur ^ 1], sv.idx, d->B, d->N, d->D, d->S * d->K, a->dpoints, st));
-            }
+// Layers 1 and 0 of a level on raw coordinates end the pass in two launches: layer 1's backward rebuilds Z_0 from the coordinates,
+// keeps dY_0 on chip and hands layer 0's parameter gradients to the launch that reduces dW_1 (gemm_wsx_kernels.hip)
+static int sa_bwd_xyz0_tail(const SaLevel &L, const pnpp_sa_bwd_args *a, const AOperand &dz) {
+    const pnpp_sa_desc *d = L.d;
+    const SaGeom &g = L.g;
+    int workers = 0, rc = PNPP_OK, C = d->C[1];
+    const bool taken = try_launch_wsx(dz, L.weight(1, C), g.M, C, d->C[0], L.layer0_operand(), L.conv_w[0], g.Cin[0], L.sv.scale[0],
+                                      L.sv.shift[0], L.sc.dwslab, L.sc.slab, &workers, L.st, &rc);
+    // the forward pass of this level kept no Z_0: there is no generic path to fall back to
+    PNPP_REQUIRE(taken, PNPP_ERR_ARG, "sa_backward: the coordinate-level backward kernel does not take this call (alignment?)");
+    PNPP_TRY(rc);
+    const SlabReduceArgs R1{L.sc.dwslab, workers, C, 64, 64, -1, a->d_conv_w[1], g.Cin[1]};
+    return launch_xyz0_post(R1, L.sc.slab, L.weight(0, 0), L.bn[0], L.count(), d->training, a->d_conv_w[0], g.Cin[0], L.dbn[0], L.st);
+}
+
+// Delayed layer 0 ends the pass: G = dZ_0 summed per source point (dW_xyz = dZ_0^T (x - c) in the same pass); dW_f = G^T F, dF = G W_f
+static int sa_bwd_delayed0(const SaLevel &L, const pnpp_sa_bwd_args *a, const AOperand &dz) {
+    const pnpp_sa_desc *d = L.d;
+    const SaScratch &sc = L.sc;
+    const int C = d->C[0], R = d->B * d->N, ldw = L.g.Cin[0];
+    PNPP_TRY(launch_scatter_dz(dz, L.layer0_operand(), d->B, d->S * d->K, C, sc.src, sc.xslab, L.st));
+    AOperand G, F;
+    G.a = sc.src, G.lda = C;
+    F.a = L.points, F.lda = d->D;
+    int nsplit, kp_pad;
+    dw_plan(R, C, d->D, &nsplit, &kp_pad);
+    const BOperand Wf = L.w0_features();
+    const Epilogue E = store_to(a->dpoints, d->D);
+    bool paired = false;
+    if (L.want_dpoints) {  // dW_f = G^T F and dF = G W_f only share G: one launch
+        int rc = PNPP_OK;
+        paired = try_launch_da_dw(G, Wf, R, d->D, C, E, nullptr, F, d->D, sc.dwslab, &nsplit, &kp_pad, L.st, &rc);
+        if (paired) PNPP_TRY(rc);
+    }
+    if (!paired) PNPP_TRY(launch_dw(G, C, F, d->D, R, sc.dwslab, nsplit, kp_pad, L.st));
+    // both partial sets of W_0 -- coordinate columns 0..2, feature columns 3.. -- in one launch
+    PNPP_TRY(launch_slab_reduce2(sc.xslab, scatter_dz_splits(R), C, 4, 3, a->d_conv_w[0], ldw, sc.dwslab, nsplit, C, kp_pad, d->D,
+                                 a->d_conv_w[0] + 3, ldw, L.st));
+    if (L.want_dpoints && !paired) PNPP_TRY(launch_gemm(G, Wf, R, d->D, C, E, nullptr, L.st));
+    return PNPP_OK;
+}
+
+// One layer: dY_{l-1} (l > 0), dW_l, then the launch that reduces dW_l's partials and (l > 0) finalises layer l-1's sums into sc.cst.
+static int sa_bwd_layer(const SaLevel &L, const pnpp_sa_bwd_args *a, int l, const AOperand &dz, SaBwdState *S) {
+    const pnpp_sa_desc *d = L.d;
+    const SaGeom &g = L.g;
+    const SaSaved &sv = L.sv;
+    const SaScratch &sc = L.sc;
+    const int C = d->C[l];
+    const AOperand a2 = L.input_of(l);
+    int nsplit, kp_pad;
+    dw_plan(g.M, C, g.Cin[l], &nsplit, &kp_pad);
+    int fused_slabs = 0, nslab_next = 0;
+    bool pair_done = false;
+    if (l > 0) {
+        // dY_{l-1} = (dZ_l * W_l) masked by ReLU'(layer l-1), with layer l-1's BN-backward sums; where the
+        // weights-stationary kernel applies, dW_l = dZ_l^T * relu(bn(Z_{l-1})) is accumulated in the same launch
+        Epilogue E;
+        E.mode = E_MASK_STATS;
+        E.c = sc.dy[S->cur ^ 1], E.ldc = d->C[l - 1], E.slab = sc.slab, E.zp = sv.z[l - 1];
+        E.scale = sv.scale[l - 1], E.shift = sv.shift[l - 1], E.mu = sv.mean[l - 1], E.istd = sv.istd[l - 1];
+        E.dwslab = sc.dwslab, E.dw_ld = d->C[l - 1];
+        const BOperand W = L.weight(l, C);
+        int rc = PNPP_OK;
+        pair_done = try_launch_da_dw(dz, W, g.M, d->C[l - 1], C, E, &nslab_next, a2, g.Cin[l], sc.dwslab, &nsplit, &kp_pad, L.st, &rc,
+                                     a->d_conv_w[l], g.Cin[l]);   // small-M level: dA and dW of this layer go out as one launch
+        if (pair_done) PNPP_TRY(rc);
+        else PNPP_TRY(launch_gemm(dz, W, g.M, d->C[l - 1], C, E, &nslab_next, L.st, &fused_slabs));
+    }
+    const bool xyz_only = l == 0 && d->D == 0 && (a2.mode == A_GATHER || (a2.mode == A_CONCAT && g.M >= 8192)) &&
+                          dw_xyz_splits(g.M) <= nsplit * (kp_pad / 4);
+    if (xyz_only) {  // C x 3 gradient: streaming kernel (the MFMA tiles would be 95 % padding)
+        PNPP_TRY(launch_dw_xyz(dz, C, a2, g.M, sc.dwslab, L.st));
+        nsplit = dw_xyz_splits(g.M), kp_pad = 4;
+    } else if (fused_slabs == 0 && !pair_done) {  // dW_l = dZ_l^T * A_l as its own launch (layer 0, group_all layers, odd shapes)
+        // group_all layer 0 with a feature gradient to return: dW_0 and dF = dZ_0 W_f only share dZ_0 -- one launch
+        if (l == 0 && L.want_dpoints && d->group_all) {
+            int rc = PNPP_OK;
+            S->dpoints_done = try_launch_da_dw(dz, L.w0_features(), g.M, d->D, C, store_to(a->dpoints, d->D), nullptr, a2, g.Cin[0],
+                                               sc.dwslab, &nsplit, &kp_pad, L.st, &rc);
+            if (S->dpoints_done) PNPP_TRY(rc);
         }
+        if (!S->dpoints_done) PNPP_TRY(launch_dw(dz, C, a2, g.Cin[l], g.M, sc.dwslab, nsplit, kp_pad, L.st));
+    }
+    if (l == 0) return launch_slab_reduce(sc.dwslab, nsplit, C, kp_pad, g.Cin[l], d->D, a->d_conv_w[l], g.Cin[l], L.st);
+    // reduce dW_l's partials and finalise layer l-1's BatchNorm-backward sums in one launch
+    const AOperand dz_next = L.dz_operand(l - 1, S->cur ^ 1);  // dY_{l-1} was just written to sc.dy[cur ^ 1]
+    StatsView V;
+    PNPP_TRY(sa_bwd_stats(L, l - 1, nslab_next, &V));
+    const SlabReduceArgs R{sc.dwslab, fused_slabs > 0 ? fused_slabs : nsplit, C, fused_slabs > 0 ? d->C[l - 1] : kp_pad, g.Cin[l], -1,
+                           a->d_conv_w[l], g.Cin[l]};
+    PNPP_TRY(launch_post_gemm(V, L.count(), d->training, L.bn[l - 1], sc.cst, L.dbn[l - 1], R, L.st, L.dz_side(&dz_next)));
+    S->dz_ready = L.small;
+    S->cur ^= 1;
+    return PNPP_OK;
+}
+
+// The feature gradient dF = dZ_0 W_f, unless layer 0's dW launch has written it: a group_all level's rows are the points
+// themselves; a grouped level's rows are summed per source point
+static int sa_bwd_dpoints(const SaLevel &L, const pnpp_sa_bwd_args *a, const AOperand &dz, const SaBwdState &S) {
+    const pnpp_sa_desc *d = L.d;
+    const int C = d->C[0];
+    if (d->group_all) {
+        if (S.dpoints_done) return PNPP_OK;
+        return launch_gemm(dz, L.w0_features(), L.g.M, d->D, C, store_to(a->dpoints, d->D), nullptr, L.st);
+    }
+    float *rows = L.sc.dy[S.cur ^ 1];
+    PNPP_TRY(launch_gemm(dz, L.w0_features(), L.g.M, d->D, C, store_to(rows, d->D), nullptr, L.st));
+    PNPP_TRY(launch_fill_zero(a->dpoints, (size_t)d->B * d->N * d->D * sizeof(float), L.st));
+    return launch_scatter_rows_bwd(rows, L.sv.idx, d->B, d->N, d->D, d->S * d->K, a->dpoints, L.st);
+}
+
+static int sa_backward_impl(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, hipStream_t st) {
+    SaLevel L;
+    PNPP_TRY(sa_level_bwd(d, a, st, &L));
+    SaBwdState S;
+    PNPP_TRY(sa_bwd_top(L, a, &S));
+    for (int l = d->L - 1; l >= 0; --l) {
+        AOperand dz;
+        PNPP_TRY(sa_bwd_dz(L, l, &S, &dz));
+        if (l == 1 && L.xyz0) return sa_bwd_xyz0_tail(L, a, dz);
+        if (l == 0 && L.delayed) return sa_bwd_delayed0(L, a, dz);
+        PNPP_TRY(sa_bwd_layer(L, a, l, dz, &S));
+        if (l == 0 && L.want_dpoints) PNPP_TRY(sa_bwd_dpoints(L, a, dz, S));
     }
     return PNPP_OK;
 }
@@ -625,110 +527,49 @@ static int sa_backward_impl(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, hi
 
 using namespace pnpp;
 
-extern "C" const char *pnpp_last_error(void) { return g_err; }
-extern "C" int pnpp_abi_version(void) { return 5; }
-
-extern "C" int pnpp_set_stats_exchange(pnpp_stats_exchange_fn fn, void *user, double *buf, size_t buf_doubles) {
-    if (!fn) {
-        g_sx = StatsExchange();
-        return PNPP_OK;
-    }
-    PNPP_REQUIRE(buf && buf_doubles >= 2 * (2 * 32 + 1), PNPP_ERR_ARG, "set_stats_exchange: a device buffer of doubles is required");
-    g_sx.fn = fn, g_sx.user = user, g_sx.buf = buf, g_sx.half = buf_doubles / 2;
-    return PNPP_OK;
-}
-extern "C" int pnpp_stats_exchange_enabled(void) { return g_sx.fn ? 1 : 0; }
-
-extern "C" int pnpp_profile_enable(int on) {
-    for (auto &r : g_recs) {
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
-    }
-    g_recs.clear();
-    g_prof = on != 0;
-    return PNPP_OK;
-}
-
-extern "C" int pnpp_profile_report(char *buf, size_t buflen) {
-    PNPP_REQUIRE(buf && buflen > 0, PNPP_ERR_ARG, "profile_report: null buffer");
-    std::map<std::string, std::pair<long, double>> agg;
-    std::vector<std::string> order;
-    for (auto &r : g_recs) {
-        float ms = 0.f;
-        if (hipEventSynchronize(r.b) != hipSuccess || hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) {
-            set_error("profile_report: event query failed");
-            return PNPP_ERR_LAUNCH;
-        }
-        if (!agg.count(r.tag)) order.push_back(r.tag);
-        agg[r.tag].first += 1;
-        agg[r.tag].second += (double)ms;
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
-    }
-    g_recs.clear();
-    size_t off = 0;
-    buf[0] = 0;
-    for (auto &t : order) {
-        int n = snprintf(buf + off, buflen - off, "%s\t%ld\t%.6f\n", t.c_str(), agg[t].first, agg[t].second);
-        if (n < 0 || (size_t)n >= buflen - off) break;
-        off += (size_t)n;
-    }
-    return (int)order.size();
-}
-
 extern "C" size_t pnpp_sa_saved_bytes(const pnpp_sa_desc *d) {
-    SaGeom g;
-    if (sa_geom(d, &g) != PNPP_OK) return 0;
-    return sa_saved_layout(d, g, nullptr).bytes;
+    SaLevel L;
+    return sa_level_plan(d, &L) == PNPP_OK ? sa_saved_layout(L, nullptr).bytes : 0;
 }
 extern "C" size_t pnpp_sa_scratch_bytes(const pnpp_sa_desc *d) {
-    SaGeom g;
-    if (sa_geom(d, &g) != PNPP_OK) return 0;
-    return sa_scratch_layout(d, g, nullptr).bytes;
+    SaLevel L;
+    return sa_level_plan(d, &L) == PNPP_OK ? sa_scratch_layout(L, nullptr).bytes : 0;
 }
 extern "C" const int32_t *pnpp_sa_saved_neighbours(const pnpp_sa_desc *d, const void *saved) {
-    SaGeom g;
-    if (sa_geom(d, &g) != PNPP_OK || d->group_all) return nullptr;
-    return sa_saved_layout(d, g, const_cast<void *>(saved)).idx;
+    SaLevel L;
+    return sa_level_plan(d, &L) == PNPP_OK && !d->group_all ? sa_saved_layout(L, const_cast<void *>(saved)).idx : nullptr;
 }
 extern "C" const int32_t *pnpp_sa_saved_argmax(const pnpp_sa_desc *d, const void *saved) {
-    SaGeom g;
-    if (sa_geom(d, &g) != PNPP_OK) return nullptr;
-    return sa_saved_layout(d, g, const_cast<void *>(saved)).arg;
+    SaLevel L;
+    return sa_level_plan(d, &L) == PNPP_OK ? sa_saved_layout(L, const_cast<void *>(saved)).arg : nullptr;
 }
 extern "C" int pnpp_sa_saved_relu_mask(const pnpp_sa_desc *d, const void *saved, const float *xyz, const float *conv_w0, int layer,
                                        uint8_t *out, void *stream) {
-    SaGeom g;
-    PNPP_TRY(sa_geom(d, &g));
+    SaLevel L;
+    PNPP_TRY(sa_level_plan(d, &L));
     PNPP_REQUIRE(saved && out && layer >= 0 && layer < d->L, PNPP_ERR_ARG, "sa_saved_relu_mask: null pointer or layer %d out of range", layer);
-    const SaSaved sv = sa_saved_layout(d, g, const_cast<void *>(saved));
-    if (layer == 0 && xyz0_applies(g.M, d->D, d->K, d->group_all, d->L, d->C)) {   // never stored: rebuilt as the kernels rebuild it
+    L.sv = sa_saved_layout(L, const_cast<void *>(saved));
+    L.xyz = xyz;
+    const SaSaved &sv = L.sv;
+    if (layer == 0 && L.xyz0) {   // never stored: rebuilt as the kernels rebuild it
         PNPP_REQUIRE(xyz && conv_w0, PNPP_ERR_ARG, "sa_saved_relu_mask: layer 0 of a level on raw coordinates needs xyz and conv_w0");
-        return launch_xyz0_mask(layer0_operand(d, xyz, nullptr, sv), g.M, conv_w0, g.Cin[0], sv.scale[0], sv.shift[0], out, as_stream(stream));
+        return launch_xyz0_mask(L.layer0_operand(), L.g.M, conv_w0, L.g.Cin[0], sv.scale[0], sv.shift[0], out, as_stream(stream));
     }
-    return launch_relu_mask(sv.z[layer], sv.scale[layer], sv.shift[layer], (size_t)g.M * d->C[layer], d->C[layer], out, as_stream(stream));
-}
-extern "C" unsigned pnpp_build_flags(void) {
-    return gemm_build_flags() | wsp_build_flags() | wsx_build_flags() | wsq_build_flags() | fc_build_flags() | wsf_build_flags() | wsd3_build_flags() |
-           mid3_build_flags();
+    return launch_relu_mask(sv.z[layer], sv.scale[layer], sv.shift[layer], (size_t)L.g.M * d->C[layer], d->C[layer], out, as_stream(stream));
 }
 extern "C" int pnpp_sa_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *centre1,
                                   const int32_t *centre2, void *saved1, float *new_xyz1, void *saved2, float *new_xyz2, void *stream) {
-    SaGeom g1, g2;
-    PNPP_TRY(sa_geom(d1, &g1));
-    PNPP_TRY(sa_geom(d2, &g2));
+    SaLevel L1, L2;
+    PNPP_TRY(sa_level_plan(d1, &L1));
+    PNPP_TRY(sa_level_plan(d2, &L2));
     PNPP_REQUIRE(!d1->group_all && !d2->group_all, PNPP_ERR_ARG, "sa_group_pair: both levels must group neighbourhoods");
     PNPP_REQUIRE(d1->B == d2->B && d2->N == d1->S, PNPP_ERR_ARG, "sa_group_pair: level 2 must take level 1's %d centres (got N=%d)",
                  d1->S, d2->N);
     PNPP_REQUIRE(xyz && centre1 && centre2 && saved1 && saved2 && new_xyz1 && new_xyz2, PNPP_ERR_ARG, "sa_group_pair: null pointer");
-    const SaSaved s1 = sa_saved_layout(d1, g1, saved1), s2 = sa_saved_layout(d2, g2, saved2);
+    const SaSaved s1 = sa_saved_layout(L1, saved1), s2 = sa_saved_layout(L2, saved2);
     return launch_knn_pair(xyz, d1->B, d1->N, centre1, d1->S, d1->K, s1.idx, new_xyz1, s1.new_xyz, centre2, d2->S, d2->K, s2.idx,
-                           new_xyz2, s2.new_xyz, sa_pair_moments(d1, g1) ? s1.mom : nullptr, as_stream(stream));
+                           new_xyz2, s2.new_xyz, L1.pair_moments ? s1.mom : nullptr, as_stream(stream));
 }
 
-extern "C" int pnpp_sa_forward(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, void *stream) {
-    return sa_forward_impl(d, a, as_stream(stream));
-}
-extern "C" int pnpp_sa_backward(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, void *stream) {
-    return sa_backward_impl(d, a, as_stream(stream));
-}
+extern "C" int pnpp_sa_forward(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, void *stream) { return sa_forward_impl(d, a, as_stream(stream)); }
+extern "C" int pnpp_sa_backward(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, void *stream) { return sa_backward_impl(d, a, as_stream(stream)); }

@@ -40,6 +40,7 @@ SOURCES = {
     "gemm_wsq_kernels.hip": [],
     "loss_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
     "cls_loss_kernels.hip": [],
+    "runtime.hip": [],
     "sa_api.hip": [],
     "sa_infer_kernels.hip": [],
     "fc_api.hip": [],

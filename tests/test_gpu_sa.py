@@ -377,3 +377,45 @@ def test_two_levels_grouped_in_one_launch_equal_the_per_level_path(B, N, S1, K1,
         assert torch.equal(ta["neighbours"], tb["neighbours"]) and torch.equal(ta["argmax"], tb["argmax"])
     for ga, gb in zip(a[5], b[5]):
         assert torch.equal(ga, gb)
+
+
+@pytest.mark.parametrize("training", [True, False], ids=["train", "eval"])
+@pytest.mark.parametrize("case", ["group_all", "grouped"])
+def test_feature_gradient_steps_of_the_backward_driver(oracle, case, training):
+    """The two ends of the backward driver (csrc/sa_api.hip) that return a feature gradient without pairing it with a weight gradient,
+    at the smallest shapes that reach them, in both BatchNorm modes:
+      group_all, B 2, N 32, D 4, [32, 32, 64] (64 rows, 2 groups): the top takes the pooled gradient as it is (no pool_bwd launch), layer
+        0's dW is a launch of its own (32 channels are too few for the paired dW_0 + dF launch) and dF = dZ_0 W_f is a product on the rows;
+      grouped, B 2, N 256, S 4, K 16, D 8, [32, 32, 64] (S*K <= N: layer 0 is not convolved before the gather): dF's rows are zero-filled
+        and summed per source point by scatter_rows_bwd.
+    Against the float64 oracle with the kernels' max-pool routing and ReLU decisions, under the gate of the cases above."""
+    from dispatch import expect, record
+    from models.pointnet_pp_8dir import PointNetSetAbstraction
+    group_all = case == "group_all"
+    B, N, S, K, D = (2, 32, None, None, 4) if group_all else (2, 256, 4, 16, 8)
+    torch.manual_seed(17)
+    sa = PointNetSetAbstraction(S, K, D, [32, 32, 64], group_all=group_all).cuda()
+    with torch.no_grad():
+        for bn in sa.bns:
+            bn.running_mean.uniform_(-0.2, 0.2)
+            bn.running_var.uniform_(0.5, 1.5)
+            bn.weight.uniform_(0.5, 1.5)
+            bn.bias.uniform_(-0.2, 0.2)
+    sa.train(training)
+    g = torch.Generator().manual_seed(18)
+    xyz = torch.rand(B, N, 3, generator=g) * 2 - 1
+    pts = torch.randn(B, N, D, generator=g)
+    centres = None if group_all else torch.stack([torch.randperm(N, generator=g)[:S] for _ in range(B)])
+    gy = torch.randn(B, 1 if group_all else S, 64, generator=g)
+    out = {}
+    tags = record(lambda: out.update(r=routed_level(oracle, sa, xyz, pts, centres, gy, K, group_all, training=training)))
+    res, diag = out["r"]
+    print(f"\n[{case} training={training}] flips {diag['relu_flips']} " + ", ".join(f"{k} {v:.1e}" for k, v in res.items()) +
+          "\n    " + "\n    ".join(tags))
+    top = ["bn_finalize_bwd_kernel C=64 +dZ +pool"]
+    if group_all:
+        expect(tags, top + ["dw_kernel<A0,A3> M=64 N=32 K=7"], ["pool_bwd_kernel", "da_dw_kernel<E0", "scatter_rows_bwd_kernel"])
+    else:
+        expect(tags, top + ["dw_kernel<A0,A2> M=128 N=32 K=11", "scatter_rows_bwd_kernel B=2 N=256 C=8 M=64"],
+               ["pool_bwd_kernel", "scatter_dz_kernel", "gather_rel_stats_kernel"])
+    assert "d_points" in res and max(res.values()) <= 1e-5, res
