@@ -406,7 +406,7 @@ attention_bwd_dkv_kernel(const float *__restrict__ qkv, const float *__restrict_
     put(fetch(0), fetch_ld(0), 0);
     __syncthreads();
     const float vmask = l31 < ATT_DH ? 1.f : 0.f;
-    const float kvalid = key < Nv ? 1.f : 0.f;
+    const bool kvalid = key < Nv;
     for (int qb = 0; qb < nqbv; ++qb) {
         const int buf = qb & 1;
         const float4 nxt = fetch(min(qb + 1, nqbv - 1));
@@ -444,10 +444,10 @@ attention_bwd_dkv_kernel(const float *__restrict__ qkv, const float *__restrict_
     }
     float *drow = dqkv + ((size_t)b * N + key) * ld + h * ATT_DH;
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {   // padding keys took no part in the forward softmax: their rows are written as zeros
-        const int d = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        drow[E + d] = dk[r] * kvalid;
-        drow[2 * E + d] = dv[r] * kvalid;
+    for (int r = 0; r < 8; ++r) {   // padding keys took no part in the forward softmax: their rows are written as zeros.  Selected, not
+        const int d = (r & 3) + 8 * (r >> 2) + 4 * lh;   // multiplied by 0: P of a padding key is exp(its score - L) of whatever the
+        drow[E + d] = kvalid ? dk[r] : 0.f;              // padding row holds, and overflows to inf once that is large
+        drow[2 * E + d] = kvalid ? dv[r] : 0.f;
     }
 }
 

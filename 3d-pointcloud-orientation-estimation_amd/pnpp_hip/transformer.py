@@ -127,6 +127,8 @@ def attention(qkv: torch.Tensor, num_heads: int, want_lse: bool = False, p: floa
     """qkv (B,N,3E), in_proj bias included -> (B,N,E) [, log-sum-exp of the scaled scores (B,H,N)].
     N (rows per cloud) must be a multiple of 128; n_valid <= N (default N) says how many of them are points -- the rest is
     the caller's padding: it receives no attention weight, its own output rows are to be ignored and its d_out must be zero.
+    The padding rows of qkv may hold any finite values whose products with the points' rows stay finite in float32: nothing a
+    point's row receives (out, lse, d qkv) depends on them, and the padding rows of d qkv come back as zeros.
     p > 0 applies dropout to the attention weights with the keep bits `masks` = attention_dropout_mask(...)
     (drawn here when not given)."""
     if p > 0.0 and masks is None:

@@ -9,6 +9,9 @@ pinned below by the Random123 known-answer vectors), so that a draw is a pure fu
                     the npoint points with the smallest (key, n) in ascending order -- a uniform random ordered subset
   point subsampling L >= num: the same with n over the cloud's L points; L < num: index_j = floor(key(j) * L / 2^32)
                     (with replacement), j = 0..num-1;  L == 0: zeros
+  attention dropout one keep bit per (cloud, head, query, key), 32 keys to a word: the word of (bh, q, kb) takes the 8 x 4 output
+                    words of philox(counter = (q * N/32 + kb, bh, lo, hi of 8 * stream_id + c), key = (seed_lo, seed_hi)),
+                    c = 0..7; bit 4c + e is set (keep) iff word e >= thresh = min(2^32 - 1, floor(float32(p) * 2^32))
 
 Only tests/ may import this module."""
 import numpy as np
@@ -58,3 +61,26 @@ def subsample_indices(seed: int, stream_id: int, slot: int, L: int, num: int) ->
         return ((u * np.uint64(L)) >> np.uint64(32)).astype(np.int64)
     word = (_keys(L, slot, seed, stream_id) << np.uint64(32)) | np.arange(L, dtype=np.uint64)
     return (np.sort(word)[:num] & MASK).astype(np.int64)
+
+
+def attention_dropout_mask(seed: int, stream_id: int, B: int, N: int, H: int, p: float):
+    """(mask, maskT), each (B, H, N, N/32) uint32: the keep bits of attention_dropout_mask_kernel (csrc/transformer_kernels.hip).
+    mask[b, h, q, kb] bit j belongs to (query q, key 32 kb + j); maskT[b, h, k, qb] bit j to (query 32 qb + j, key k)."""
+    nw = N // 32
+    assert N % 32 == 0 and nw > 0
+    thresh = min(0xFFFFFFFF, int(float(np.float32(p)) * 4294967296.0))
+    bh = np.arange(B * H, dtype=np.uint64)[:, None, None, None]
+    q = np.arange(N, dtype=np.uint64)[None, :, None, None]
+    kb = np.arange(nw, dtype=np.uint64)[None, None, :, None]
+    sc = [(8 * int(stream_id) + c) & 0xFFFFFFFFFFFFFFFF for c in range(8)]
+    lo = np.array([v & 0xFFFFFFFF for v in sc], dtype=np.uint64)
+    hi = np.array([v >> 32 for v in sc], dtype=np.uint64)
+    words = philox4x32_10(q * np.uint64(nw) + kb, bh, lo, hi, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    keep = np.stack(words, axis=-1) >= np.uint32(thresh)            # (B H, N, nw, c, e): bit 4c + e of the word
+    keep = keep.reshape(B * H, N, N)                                # dense: [bh, query, key]
+    sh = np.arange(32, dtype=np.uint32)
+
+    def pack(dense):
+        return (dense.reshape(B * H, N, nw, 32).astype(np.uint32) << sh).sum(axis=-1, dtype=np.uint32).reshape(B, H, N, nw)
+
+    return pack(keep), pack(keep.transpose(0, 2, 1))

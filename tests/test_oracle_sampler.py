@@ -42,3 +42,26 @@ def test_subsample_indices_replacement_rule():
     assert b.shape == (1024,) and b.max() < 300 and len(set(b.tolist())) > 250     # len < num: with replacement
     assert sorted(S.subsample_indices(1, 1, 0, 1024, 1024).tolist()) == list(range(1024))   # len == num: a permutation
     assert S.subsample_indices(1, 1, 0, 0, 8).size == 0
+
+
+def _unpack(m):
+    """(B, H, N, N/32) uint32 -> dense (B, H, N, N) of {0, 1}: bit j of word w is column 32 w + j"""
+    return ((m[..., None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(*m.shape[:3], m.shape[2])
+
+
+def test_attention_dropout_mask_restatement():
+    """The restated keep bits of the attention dropout: all ones at p = 0, maskT the bitwise transpose of mask, the keep rate of
+    Bernoulli(1 - p), and a pure function of (seed, stream id) that changes with either."""
+    mask, maskT = S.attention_dropout_mask(11, 1, 2, 128, 2, 0.0)
+    assert mask.shape == maskT.shape == (2, 2, 128, 4) and mask.dtype == maskT.dtype == np.uint32
+    assert (mask == 0xFFFFFFFF).all() and (maskT == 0xFFFFFFFF).all()
+    p = 0.3
+    for B, N, H, sid in ((1, 128, 1, 3), (2, 256, 3, (3 << 40) + 17)):
+        mask, maskT = S.attention_dropout_mask(11, sid, B, N, H, p)
+        keep = _unpack(mask)
+        assert np.array_equal(keep, _unpack(maskT).transpose(0, 1, 3, 2))
+        assert abs(keep.mean() - (1 - p)) < 4 * np.sqrt(p * (1 - p) / keep.size), keep.mean()
+        again, _ = S.attention_dropout_mask(11, sid, B, N, H, p)
+        other, _ = S.attention_dropout_mask(11, sid + 1, B, N, H, p)
+        seed, _ = S.attention_dropout_mask(12, sid, B, N, H, p)
+        assert np.array_equal(mask, again) and not np.array_equal(mask, other) and not np.array_equal(mask, seed)
