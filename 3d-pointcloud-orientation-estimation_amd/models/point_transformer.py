@@ -21,6 +21,7 @@ class PointTransformer(nn.Module):
         self.transformer = nn.TransformerEncoder(encoder_layer, num_layers=depth)
         self.fc_out = nn.Linear(embed_dim, 3)
         self.num_heads = num_heads
+        self.attention_form = "float32"     # a plain attribute, not a parameter or buffer: see set_attention
 
     def forward(self, x: torch.Tensor):
         """x (B,N,3) -> (B,3)."""
@@ -33,4 +34,11 @@ class PointTransformer(nn.Module):
         for layer in self.transformer.layers:
             layer.dropout.p = layer.dropout1.p = layer.dropout2.p = float(p)
             layer.self_attn.dropout = float(p)
+        return self
+
+    def set_attention(self, form: str) -> "PointTransformer":
+        """Chooses the kernels of every layer's attention, forward and backward: "float32" (the default, v_mfma_f32_32x32x2_f32) or "split"
+        (every product on the bf16 matrix pipe from exact three-way splits of the float32 operands; pnpp_hip.transformer.attention)."""
+        from pnpp_hip import transformer as T
+        self.attention_form = T._check_form(form)
         return self

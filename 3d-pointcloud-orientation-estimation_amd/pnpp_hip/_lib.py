@@ -150,6 +150,9 @@ SIGNATURES = {
     "pnpp_pt_infer_pool": (_i, [C.POINTER(PtInferDesc), _fp, _fp, _fp, _i, _fp, _fp]),
     "pnpp_attention_infer": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _fp]),
     "pnpp_attention_infer_supported": (_i, [_i, _i, _i, _i, _i]),
+    "pnpp_attention_split_fwd": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _f, _fp, _fp, _fp]),
+    "pnpp_attention_split_bwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _f, _fp, _fp, _fp]),
+    "pnpp_attention_split_supported": (_i, [_i, _i, _i, _i, _i]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

@@ -50,6 +50,7 @@ SOURCES = {
     "pointnet_infer_kernels.hip": [],
     "transformer_infer_kernels.hip": _NOSLP,
     "attention_infer_kernels.hip": _NOSLP,
+    "attention_train_kernels.hip": _NOSLP,
 }
 
 

@@ -87,9 +87,21 @@ def attention_dropout_mask(B: int, N: int, H: int, p: float, device, seed=None, 
     return mask, maskT
 
 
+ATTENTION_FORMS = ("float32", "split")
+
+
+def _check_form(form):
+    if form not in ATTENTION_FORMS:
+        raise ValueError(f"attention: form={form!r} is not one of {ATTENTION_FORMS}")
+    return form
+
+
 class _Attention(torch.autograd.Function):
+    """The forward records the form ("float32": pnpp_attention_fwd / _bwd on v_mfma_f32_32x32x2_f32; "split": pnpp_attention_split_fwd /
+    _split_bwd, every product on the bf16 matrix pipe from exact three-way splits) and the backward runs in the same one."""
+
     @staticmethod
-    def forward(ctx, qkv, num_heads, p, masks, n_valid):
+    def forward(ctx, qkv, num_heads, p, masks, n_valid, form):
         qkv = _f32(qkv, "qkv")
         B, N, E3 = qkv.shape
         if N % 128 != 0 or not 0 < n_valid <= N:
@@ -97,14 +109,17 @@ class _Attention(torch.autograd.Function):
         if E3 % (3 * num_heads) != 0:
             raise ValueError(f"attention: last dimension {E3} is not 3 * heads * head_dim")
         E = E3 // 3
+        lib = L.lib()
+        if form == "split" and not lib.pnpp_attention_split_supported(B, N, int(n_valid), num_heads, E // num_heads):
+            raise ValueError(f"attention(form='split'): {L.last_error()}")       # no silent fall-back to the float32 kernels in training
         mask, maskT = masks if masks is not None else (None, None)
         out = torch.empty(B, N, E, device=qkv.device, dtype=torch.float32)
         lse = torch.empty(B, num_heads, N, device=qkv.device, dtype=torch.float32)
-        L.check(L.lib().pnpp_attention_fwd(qkv.data_ptr(), B, N, int(n_valid), num_heads, E // num_heads,
-                                           None if mask is None else mask.data_ptr(), float(p), out.data_ptr(), lse.data_ptr(),
-                                           _stream()))
+        fwd = lib.pnpp_attention_split_fwd if form == "split" else lib.pnpp_attention_fwd
+        L.check(fwd(qkv.data_ptr(), B, N, int(n_valid), num_heads, E // num_heads, None if mask is None else mask.data_ptr(), float(p),
+                    out.data_ptr(), lse.data_ptr(), _stream()))
         ctx.save_for_backward(qkv, out, lse)
-        ctx.heads, ctx.p, ctx.masks, ctx.n_valid = num_heads, float(p), (mask, maskT), int(n_valid)
+        ctx.heads, ctx.p, ctx.masks, ctx.n_valid, ctx.form = num_heads, float(p), (mask, maskT), int(n_valid), form
         ctx.mark_non_differentiable(lse)
         return out, lse
 
@@ -116,24 +131,28 @@ class _Attention(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         dsum = torch.empty_like(lse)
         mask, maskT = ctx.masks
-        L.check(L.lib().pnpp_attention_bwd(qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), B, N, ctx.n_valid, ctx.heads,
-                                           E3 // 3 // ctx.heads, None if mask is None else mask.data_ptr(),
-                                           None if maskT is None else maskT.data_ptr(), ctx.p, dqkv.data_ptr(), dsum.data_ptr(),
-                                           _stream()))
-        return dqkv, None, None, None, None
+        bwd = L.lib().pnpp_attention_split_bwd if ctx.form == "split" else L.lib().pnpp_attention_bwd
+        L.check(bwd(qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), B, N, ctx.n_valid, ctx.heads, E3 // 3 // ctx.heads,
+                    None if mask is None else mask.data_ptr(), None if maskT is None else maskT.data_ptr(), ctx.p, dqkv.data_ptr(),
+                    dsum.data_ptr(), _stream()))
+        return dqkv, None, None, None, None, None
 
 
-def attention(qkv: torch.Tensor, num_heads: int, want_lse: bool = False, p: float = 0.0, masks=None, n_valid=None):
+def attention(qkv: torch.Tensor, num_heads: int, want_lse: bool = False, p: float = 0.0, masks=None, n_valid=None, form: str = "float32"):
     """qkv (B,N,3E), in_proj bias included -> (B,N,E) [, log-sum-exp of the scaled scores (B,H,N)].
     N (rows per cloud) must be a multiple of 128; n_valid <= N (default N) says how many of them are points -- the rest is
     the caller's padding: it receives no attention weight, its own output rows are to be ignored and its d_out must be zero.
     The padding rows of qkv may hold any finite values whose products with the points' rows stay finite in float32: nothing a
     point's row receives (out, lse, d qkv) depends on them, and the padding rows of d qkv come back as zeros.
     p > 0 applies dropout to the attention weights with the keep bits `masks` = attention_dropout_mask(...)
-    (drawn here when not given)."""
+    (drawn here when not given).
+    form: "float32" (the default) runs the kernels of csrc/transformer_kernels.hip; "split" runs csrc/attention_train_kernels.hip, forward
+    and backward: the same buffers and contract with every product on the bf16 matrix pipe from exact three-way splits.  A shape that
+    pnpp_attention_split_supported refuses raises ValueError naming the field; there is no fall-back."""
+    _check_form(form)
     if p > 0.0 and masks is None:
         masks = attention_dropout_mask(qkv.shape[0], qkv.shape[1], num_heads, p, qkv.device)
-    out, lse = _Attention.apply(qkv, num_heads, p if masks is not None else 0.0, masks, qkv.shape[1] if n_valid is None else n_valid)
+    out, lse = _Attention.apply(qkv, num_heads, p if masks is not None else 0.0, masks, qkv.shape[1] if n_valid is None else n_valid, form)
     return (out, lse) if want_lse else out
 
 
@@ -221,12 +240,13 @@ def point_transformer_forward(model, xyz: torch.Tensor) -> torch.Tensor:
     x = linear_smallk(xyz.reshape(B * N, K), model.input_proj)                        # (B*N, E)
     E = x.shape[1]
     tr = model.training
+    form = _check_form(getattr(model, "attention_form", "float32"))
     for layer in model.transformer.layers:
         att = layer.self_attn
         if layer.norm_first or att.in_proj_weight is None or not att.batch_first:
             raise NotImplementedError("only the post-norm, packed in_proj, batch_first encoder layer of the reference")
         qkv = ops.fc_block(x, _Affine(att.in_proj_weight, att.in_proj_bias), training=tr)   # (B*N, 3E), bias added
-        o = attention(qkv.view(B, N, 3 * E), att.num_heads, p=att.dropout if tr else 0.0, n_valid=n_pts).view(B * N, E)
+        o = attention(qkv.view(B, N, 3 * E), att.num_heads, p=att.dropout if tr else 0.0, n_valid=n_pts, form=form).view(B * N, E)
         o = ops.fc_block(o, att.out_proj, dropout=layer.dropout1, training=tr)
         x = add_layernorm(x, o, layer.norm1)
         hid = ops.fc_block(x, layer.linear1, relu=True, dropout=layer.dropout, training=tr)   # dropout(relu(W1 x + b1))

@@ -687,6 +687,21 @@ int pnpp_pt_infer_pool(const pnpp_pt_infer_desc *d, const void *scratch, const f
 int pnpp_attention_infer(const float *qkv, int B, int N, int n_valid, int H, int head_dim, float *out, void *stream);
 /* 1: pnpp_attention_infer takes the shape.  0: it does not, pnpp_last_error() names the field */
 int pnpp_attention_infer_supported(int B, int N, int n_valid, int H, int head_dim);
+/* The TRAINING attention in the same form (additive to ABI 5; csrc/attention_train_kernels.hip).  pnpp_attention_split_fwd mirrors
+ * pnpp_attention_fwd and pnpp_attention_split_bwd mirrors pnpp_attention_bwd: the same argument lists, buffers (qkv, mask / maskT, out,
+ * lse, d_out, dqkv, dsum), status codes and padding contract (d_out rows >= n_valid zero; rows >= n_valid of dqkv come back as exact
+ * zeros; nothing a row < n_valid receives depends on what the padding rows hold), with every matrix product formed on
+ * v_mfma_f32_32x32x16_bf16 from the exact three-way bfloat16 splits of its float32 operands.  The softmax denominator, hence lse, is over
+ * the undropped weights and does not depend on the mask, bit for bit.  No workspace, no allocation, no host copy, no synchronisation:
+ * stream-ordered and capturable; no atomics: repeats are bit-equal.  One launch forward, two backward.  Shapes taken: those of
+ * pnpp_attention_infer; arguments are validated before anything is launched. */
+int pnpp_attention_split_fwd(const float *qkv, int B, int N, int n_valid, int H, int head_dim, const uint32_t *mask, float p,
+                             float *out, float *lse, void *stream);
+int pnpp_attention_split_bwd(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N, int n_valid, int H,
+                             int head_dim, const uint32_t *mask, const uint32_t *maskT, float p, float *dqkv, float *dsum,
+                             void *stream);
+/* 1: the two entries above take the shape.  0: they do not, pnpp_last_error() names the field */
+int pnpp_attention_split_supported(int B, int N, int n_valid, int H, int head_dim);
 
 /* ------------------------------------------------------------------------------------------
  * Step glue on one flat parameter / gradient buffer
