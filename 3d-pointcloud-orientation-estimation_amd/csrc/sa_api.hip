@@ -337,7 +337,10 @@ static int sa_level_bwd(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, hipStr
         PNPP_REQUIRE(a->conv_w[l] && a->bn_w[l] && a->d_conv_w[l] && a->d_conv_b[l] && a->d_bn_w[l] && a->d_bn_b[l], PNPP_ERR_ARG,
                      "sa_backward: null pointer in layer %d", l);
     L->want_dpoints = d->D > 0 && a->dpoints != nullptr;
-    if (L->want_dpoints) PNPP_REQUIRE(d->D % 4 == 0, PNPP_ERR_ARG, "sa_backward: feature width D=%d must be a multiple of 4", d->D);
+    // a grouped level returns dF through the generic GEMM (scalar stores) and the row scatter, which take any width
+    // (tests/test_gpu_cls_bands.py: D = 3); the whole-cloud level's paired dA + dW launch stays with the widths it was written for
+    if (L->want_dpoints && d->group_all)
+        PNPP_REQUIRE(d->D % 4 == 0, PNPP_ERR_ARG, "sa_backward: feature width D=%d must be a multiple of 4", d->D);
     sa_level_bind(L, const_cast<void *>(a->saved), a->scratch, a->xyz, a->points, a->conv_w, a->bn_w, st);
     for (int l = 0; l < d->L; ++l) L->dbn[l] = BnGrads{a->d_bn_w[l], a->d_bn_b[l], a->d_conv_b[l]};
     return PNPP_OK;

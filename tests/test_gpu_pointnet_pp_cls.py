@@ -4,7 +4,8 @@ csrc/sa_infer_kernels.hip, pnpp_hip.inference.ClsPredictor).
 Gates are those of the tests each part belongs with: the loss operators as tests/test_gpu_head_loss.py gates soft_ce (rtol 1e-5,
 atol 1e-6 against float64); a bare level as tests/test_gpu_sa.py (3e-5 of the tensor's max-abs for outputs and gradients, 1e-5 for
 running statistics); the fused level launch and the Predictor as tests/test_gpu_inference.py's _compare (1e-4 * max(1, max|ref|));
-the model against the reference's capture as tests/test_gpu_pointnet.py (its _check_grads / _check_after are imported)."""
+the model against the reference's capture as tests/test_gpu_pointnet.py (its _check_grads / _check_after are imported).
+The levels across the dispatcher's kernel bands, routed float64 at 1e-5 with the kernels asserted: tests/test_gpu_cls_bands.py."""
 import ctypes as C
 import math
 
