@@ -348,7 +348,9 @@ constexpr int MATCH_KMAX = 8;
 
 __device__ __forceinline__ void kl_multi_eval(double mp, double kp_raw, double mq, double kq_raw, double &kl, double &dmu,
                                               double &dk) {
-    const double kp = fmin(fmax(kp_raw, 1e-6), 500.0), kq = fmin(fmax(kq_raw, 1e-6), 500.0);
+    // torch.clamp keeps a NaN (fmax / fmin would return the other operand and turn it into 1e-6): it has to reach nan_to_num
+    auto clamp_k = [](double k) -> double { return k < 1e-6 ? 1e-6 : k > 500.0 ? 500.0 : k; };
+    const double kp = clamp_k(kp_raw), kq = clamp_k(kq_raw);
     double d = fmod(mp - mq + kPi, 2.0 * kPi);  // python %: result takes the sign of the divisor
     if (d < 0.0) d += 2.0 * kPi;
     d -= kPi;

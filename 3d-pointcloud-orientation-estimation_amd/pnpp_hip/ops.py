@@ -670,6 +670,19 @@ def vm_head_kl_loss_backward(o, mu_gt, kappa_gt) -> torch.Tensor:
     return loss
 
 
+def _draw_centres(job) -> None:
+    """The centre draw of sampling.CentreRing.job() as a launch of its own: the same draws from the same counter as when it rides in
+    a tail launch (a tail that does not take the one-launch form, or a cloud whose candidate table exceeds that launch's LDS)."""
+    seed, counter, offset, Bs, N1, c1, N2, c2 = job
+    L.check(L.lib().pnpp_sample_random_dev2(int(seed) & (2**64 - 1), counter.data_ptr(), int(offset), Bs, N1, c1.shape[1],
+                                            c1.data_ptr(), N2, c2.shape[1], c2.data_ptr(), _stream()))
+
+
+def _rider_fits(job, lds_limit: int) -> bool:
+    """The riding draw keeps an (N + 1)-entry table of 8-byte candidates in the tail launch's LDS."""
+    return 8 * (max(job[4], job[6]) + 1) <= lds_limit
+
+
 def vm_fc_head_kl_loss_backward(x, linear, mu_gt, kappa_gt, next_centres=None) -> torch.Tensor:
     """`o = linear(x)` (the model's fc3, two outputs), head, single-peak KL, `.mean()` and `loss.backward()` in ONE launch
     (pointnet_pp_vonMises.py:35-37 + train_single_peak_vonMises_KL.py:82-84): the gradients of `linear` land in its
@@ -683,10 +696,11 @@ def vm_fc_head_kl_loss_backward(x, linear, mu_gt, kappa_gt, next_centres=None) -
     if 4 * (2 * B + 2 * K + 8 + (B * K if B * K <= 12288 else 0)) > 56 * 1024:
         # the one-launch form stages fc3's weights and the outputs in LDS (56 KB); wider heads take the three launches it fuses
         if next_centres is not None:
-            seed, counter, offset, Bs, N1, c1, N2, c2 = next_centres
-            L.check(L.lib().pnpp_sample_random_dev2(int(seed) & (2**64 - 1), counter.data_ptr(), int(offset), Bs, N1, c1.shape[1],
-                                                    c1.data_ptr(), N2, c2.shape[1], c2.data_ptr(), _stream()))
+            _draw_centres(next_centres)
         return vm_head_kl_loss_backward(fc_block(x, linear, training=True), mu_gt, kappa_gt)
+    if next_centres is not None and not _rider_fits(next_centres, 56 * 1024):   # clouds of N >= 7168: the draw takes its own launch
+        _draw_centres(next_centres)
+        next_centres = None
     loss = torch.empty((), device=x32.device, dtype=torch.float32)
     sinks = [grad_sink(p) for p in (linear.weight, linear.bias)]
     dw = sinks[0] if sinks[0] is not None else torch.empty_like(w)
@@ -724,20 +738,23 @@ def mvm_heads_match_loss_backward(x, head_pi, head_mu, head_kappa, vm_gt, K_gt, 
     B, K = x32.shape
     maxK = head_pi.weight.shape[0]
     heads = (head_pi, head_mu, head_kappa)
-    fits = maxK in (4, 8) and K % 4 == 0 and 4 * (4 * maxK * (B + K) + B * K + 3 * B * maxK * (1 + maxK)) <= 96 * 1024
+    # the one-launch form stages x with 16-byte loads: K % 4 == 0 and an aligned x (a contiguous view may start anywhere)
+    fits = (maxK in (4, 8) and K % 4 == 0 and x32.data_ptr() % 16 == 0
+            and 4 * (4 * maxK * (B + K) + B * K + 3 * B * maxK * (1 + maxK)) <= 96 * 1024)
     if (head_mu.weight.shape[0] != 2 * maxK or head_kappa.weight.shape[0] != maxK or any(h.weight.shape[1] != K for h in heads)
             or tuple(vm_gt.shape) != (B, maxK, 3)):
         raise ValueError("mvm_heads_match_loss_backward: heads must map K -> max_K / 2 max_K / max_K and vm_gt must be (B, max_K, 3)")
     if not fits:
         if next_centres is not None:
-            seed, counter, offset, Bs, N1, c1, N2, c2 = next_centres
-            L.check(L.lib().pnpp_sample_random_dev2(int(seed) & (2**64 - 1), counter.data_ptr(), int(offset), Bs, N1, c1.shape[1],
-                                                    c1.data_ptr(), N2, c2.shape[1], c2.data_ptr(), _stream()))
+            _draw_centres(next_centres)
         mu, kappa, weight = mvm_head(*[fc_block(x, h, training=True) for h in heads], temp, kappa_max)
         loss = match_loss(mu, kappa, weight, vm_gt, K_gt).mean()
         loss.backward()
         loss = loss.detach()
         return (loss, mu.detach(), kappa.detach(), weight.detach()) if outputs else loss
+    if next_centres is not None and not _rider_fits(next_centres, 96 * 1024):   # clouds of N >= 12288: the draw takes its own launch
+        _draw_centres(next_centres)
+        next_centres = None
     ws = [_f32(h.weight, "weight") for h in heads]
     bs = [_f32(h.bias, "bias") for h in heads]
     loss = torch.empty((), device=x32.device, dtype=torch.float32)
