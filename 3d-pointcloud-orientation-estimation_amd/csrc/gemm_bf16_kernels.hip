@@ -1,7 +1,7 @@
 // gemm_bf16_kernels.hip -- bf16-OPERAND variant of the weights-stationary GEMM of the grouped layers (throughput mode).
 //
 // The reference computes in float32 (models/pointnet_pp_8dir.py:40-42 run under torch's default dtype) and so does the
-// default path of this library (gemm_kernels.hip, v_mfma_f32_32x32x2_f32).  BASELINE.json's configs[1] names a bf16 mode
+// default path of this library (gemm_ws_kernels.hip, v_mfma_f32_32x32x2_f32).  BASELINE.json's configs[1] names a bf16 mode
 // for the metric configuration; this file is that mode, selected explicitly (pnpp_set_matmul_precision(1) /
 // PNPP_MATMUL=bf16) and reported under its own metric key, never as the float32 headline:
 //   * the two MFMA operands are rounded to bfloat16 (round to nearest even) when they are staged in LDS; products are

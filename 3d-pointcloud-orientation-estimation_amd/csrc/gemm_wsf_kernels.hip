@@ -5,7 +5,7 @@
 // previous layer is applied while the operand is staged, the column statistics of this layer are collected in the epilogue, and for a
 // level's last layer the max over the 32-row neighbourhood is taken from the accumulators: kernels.h, Epilogue::pool_ext).
 //
-// Why a second weights-stationary form.  gemm_ws_kernel (gemm_kernels.hip) stages a 64-row tile cooperatively: three barriers per
+// Why a second weights-stationary form.  gemm_ws_kernel (gemm_ws_kernels.hip) stages a 64-row tile cooperatively: three barriers per
 // tile couple the four waves of a workgroup, each of which shares its SIMD with a wave of ANOTHER workgroup -- the round-3 counters
 // show what that costs: cutting a third of the VALU instructions of such a kernel moved the same number of cycles from "issuing" to
 // "waiting" and left the launch time where it was.  The forward product needs no cross-row data at all (the fused dW of the backward

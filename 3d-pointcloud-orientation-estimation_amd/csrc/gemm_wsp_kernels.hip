@@ -6,7 +6,7 @@
 //   dY_{l-1} = (dZ_l W_l) masked by ReLU'(layer l-1), + its BatchNorm-backward column sums            (epilogue E_MASK_STATS)
 //   dW_l  = dZ_l^T relu(bn(Z_{l-1}))                                                                  (fused second product)
 //
-// gemm_ws_kernel<..., dW> (gemm_kernels.hip) does this on 64-row tiles staged by the whole workgroup: three barriers per tile, two
+// gemm_ws_kernel<..., dW> (gemm_ws_kernels.hip) does this on 64-row tiles staged by the whole workgroup: three barriers per tile, two
 // waves of different workgroups per SIMD.  Round 3's counters say what that form waits for: a third fewer VALU instructions moved
 // the same number of cycles from "issuing" to "waiting" (profiles/round3_sq_counters*.txt).  The only cross-row quantity here is the
 // SUM over rows in dW, and a sum can be kept per wave: with C_{l-1} = 64 the whole dW (C_l x 64, C_l <= 128) is at most eight

@@ -7,7 +7,7 @@
 //   dY_{l-1} = (dZ_l W_l) masked by ReLU'(layer l-1), + its BatchNorm-backward column sums            (epilogue E_MASK_STATS)
 //   dW_l  = dZ_l^T relu(bn(Z_{l-1}))                                                                  (fused second product)
 //
-// gemm_ws_kernel<256,64,64,A5,E2,dW> (gemm_kernels.hip) does this with ~1,200 vector instructions per wave and 64-row tile beside its 256
+// gemm_ws_kernel<256,64,64,A5,E2,dW> (gemm_ws_kernels.hip) does this with ~1,200 vector instructions per wave and 64-row tile beside its 256
 // matrix instructions -- and on this chip a float32 MFMA and the vector instructions of the same SIMD do not overlap:
 // a launch is MFMA time + the rest.  A wave-private form (gemm_wsp_kernels.hip) does not fit here -- 256 x 128 weight-gradient
 // accumulators are 512 registers -- so the tile stays a workgroup's, but the rest of that kernel's diet carries over:

@@ -15,7 +15,7 @@ size_t knn_pair_moment_doubles(int B, int S1, int N);   // ... and the doubles t
 int launch_gather_centres(const float *xyz, const int32_t *centre, int B, int N, int S, float *out_a, float *out_b, hipStream_t st);
 int launch_scatter_rows_bwd(const float *dout, const int32_t *idx, int B, int N, int C, int M, float *dpoints, hipStream_t st);
 
-// ---- gemm_kernels.hip ----
+// ---- the fused GEMMs and what surrounds them (gemm_kernels.hip and the files named below) ----
 // How the A operand (activation rows) of a fused GEMM is produced on the fly.
 enum AMode {
     A_PLAIN = 0,   // A[row][k]
@@ -127,7 +127,7 @@ struct PoolTail {
 };
 // backward, optional: also materialise dZ = BN-backward(dz operand) of the layer being finalised, M x C (small-M levels)
 struct DzSide { const AOperand *dz = nullptr; int M = 0; float *out = nullptr; };
-// out[c][perm(k)] = sum_s slab[s][c][k] (gemm_kernels.hip: launch_slab_reduce, post_gemm_kernel); perm_D < 0: identity; else
+// out[c][perm(k)] = sum_s slab[s][c][k] (bn_pool_kernels.hip: launch_slab_reduce, post_gemm_kernel); perm_D < 0: identity; else
 // feature-first -> xyz-first column order
 struct SlabReduceArgs {
     const float *slab;
@@ -141,6 +141,12 @@ struct SlabReduceArgs {
 // *dw_slabs (optional) receives the number of dW partial slabs written when E.dwslab was honoured, else 0.
 int launch_gemm(const AOperand &A, const BOperand &B, int M, int Nout, int Kd, const Epilogue &E, int *nslab,
                 hipStream_t st, int *dw_slabs = nullptr);
+// gemm_kernels.hip: the one reader of PNPP_NO_MID (1: the group_all level stays on the 32 x 32 split-K kernels, no 64 x 64 tiles)
+bool mid_tiles_on();
+// gemm_ws_kernels.hip: the float32 weights-stationary kernel of the grouped layers (M >= 8192, K in {4, 64, 128, 132, 256}): the weight
+// panel stays in LDS, whole-workgroup 64-row tiles, dW fused into the backward launches when E.dwslab is given
+bool try_launch_ws(const AOperand &A, const BOperand &B, int M, int Nout, int Kd, const Epilogue &E, int *nslab, hipStream_t st, int *rc,
+                   int *dw_slabs);
 
 // gemm_bf16_kernels.hip: the bf16-operand / float32-accumulate variant of the weights-stationary kernel (throughput mode,
 // off by default; pnpp_set_matmul_precision / PNPP_MATMUL=bf16).  Returns false when the shape stays on the float32 kernels.
@@ -149,16 +155,16 @@ void set_matmul_precision(int bf16);
 bool try_launch_ws_bf16(const AOperand &A, const BOperand &B, int M, int Nout, int Kd, const Epilogue &E, int *nslab, hipStream_t st,
                         int *rc, int *dw_slabs);
 
-// dW[Nc x Kp] = dZ^T[Nc x M] * A2[M x Kp], split over `nsplit` row ranges into slab[nsplit][Nc][kp_pad].
+// dw_kernels.hip: dW[Nc x Kp] = dZ^T[Nc x M] * A2[M x Kp], split over `nsplit` row ranges into slab[nsplit][Nc][kp_pad].
 // dz is produced as in A_DZ (or read directly when dz.mode == A_PLAIN); A2 by its own AOperand.
 int launch_dw(const AOperand &dz, int Nc, const AOperand &a2, int Kp, int M, float *slab, int nsplit, int kp_pad,
               hipStream_t st);
-// out[M x C] = the A_DZ / A_DZ_POOL operand written out densely (used for small M, see gemm_kernels.hip)
+// out[M x C] = the A_DZ / A_DZ_POOL operand written out densely (used for small M, see gemm_kernels.hip: dz_materialize_kernel)
 int launch_dz_materialize(const AOperand &dz, int M, int C, float *out, hipStream_t st);
 // picks the split count / padded pitch launch_dw will use (so callers can size the slab)
 void dw_plan(int M, int Nc, int Kp, int *nsplit, int *kp_pad);
 // xyz-only layer 0 (second operand A_GATHER with D == 0): streaming kernel, one [Nc][4] partial per 256 rows
-// layer 0 of a grouped level with features, convolved before the gather (see gemm_kernels.hip)
+// layer 0 of a grouped level with features, convolved before the gather (see dw_kernels.hip: gather_rel_stats_kernel, scatter_dz_kernel)
 bool delayed_layer0_ok(int C);
 int launch_gather_rel_stats(const float *P, const AOperand &geo, const float *W0, int ldw, int M, int C, float *z,
                             double *slab, int *nslab, hipStream_t st);
@@ -166,6 +172,7 @@ int scatter_dz_splits(int rows);  // number of [C][4] dW_xyz partials launch_sca
 int launch_scatter_dz(const AOperand &dz, const AOperand &geo, int B, int Mc, int C, float *G, float *wslab, hipStream_t st);
 int dw_xyz_splits(int M);
 int launch_dw_xyz(const AOperand &dz, int Nc, const AOperand &a2, int M, float *slab, hipStream_t st);
+// gemm_kernels.hip: the head layers (M <= 32): dx = dz W on the small-M body and dW = dz^T x in one launch
 bool try_launch_fc_dx_dw(const float *dz, const float *w, const float *x, int M, int N, int K, float *dx, float *dw, hipStream_t st,
                          int *rc);
 // *nsplit / *kp_pad: in = what dw_plan chose (the slab is sized for it); out = the partial count and pitch actually written
@@ -227,6 +234,7 @@ unsigned fc_build_flags();
 bool try_launch_mid_da_dw(const AOperand &dz, const BOperand &W, int M, int Nout, int Kd, const Epilogue &E, int *nslab, const AOperand &a2,
                           int Kp, float *slab, int *nsplit_out, int *kp_pad_out, hipStream_t st, int *rc, float *dw_direct = nullptr,
                           int dw_ld = 0);   // dw_direct (Nc x dw_ld, dw_ld == Kp): written in place when one row range suffices; *nsplit_out = 0 then
+// bn_pool_kernels.hip: slab reductions, BatchNorm finalisation, pooling
 int launch_slab_reduce2(const float *slab1, int nsplit1, int Nc1, int kp_pad1, int Kvalid1, float *out1, int ldo1, const float *slab2,
                         int nsplit2, int Nc2, int kp_pad2, int Kvalid2, float *out2, int ldo2, hipStream_t st);
 int launch_slab_reduce(const float *slab, int nsplit, int Nc, int kp_pad, int Kvalid, int perm_D, float *out, int ldo,

@@ -28,7 +28,10 @@ COMMON = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wno-unused-v
 _NOSLP = [] if os.environ.get("PNPP_SLP") else ["-fno-slp-vectorize"]
 SOURCES = {
     "index_kernels.hip": ["-ffp-contract=off"],
-    "gemm_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
+    "gemm_kernels.hip": [],
+    "gemm_ws_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
+    "dw_kernels.hip": [],
+    "bn_pool_kernels.hip": [],
     "gemm_bf16_kernels.hip": [],
     "gemm_mid_kernels.hip": (["-DMID3_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
     "gemm_wsf_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []) + ([f"-DWSF_EXP={os.environ['PNPP_WSF_EXP']}"] if os.environ.get("PNPP_WSF_EXP") else []),

@@ -301,7 +301,7 @@ def test_sa1_backward_of_layers_0_and_1_from_the_coordinates(oracle, B, N):
 @pytest.mark.parametrize("c0,npoint,nsample,n", [(256, 96, 64, 256), (512, 40, 16, 128), (64, 160, 32, 512)])
 def test_sa_layer0_convolved_before_the_gather(oracle, c0, npoint, nsample, n):
     """Grouped levels with input features run layer 0 on the source points and gather afterwards (P[idx] + W_xyz (x - c),
-    csrc/gemm_kernels.hip gather_rel_stats / scatter_dz): wide layers (2 and 4 channel chunks per lane in the scatter),
+    csrc/dw_kernels.hip gather_rel_stats / scatter_dz): wide layers (2 and 4 channel chunks per lane in the scatter),
     both the on-the-fly dZ (B*S*K > 4096 rows) and the materialised one, against the fp64 oracle of the reference's
     gather-then-convolve order (pointnet_pp_8dir.py:28-43)."""
     from models.pointnet_pp_8dir import PointNetSetAbstraction

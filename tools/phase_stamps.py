@@ -3,7 +3,7 @@
 at each stamp -- which serialises what would otherwise overlap, so the numbers locate costs, they do not add up to the
 un-instrumented time).  Needs the instrumented build, which is not the shipped one:
 
-    PNPP_STAMPS=1 python -c "import __graft_entry__ as g; g.build()"   (after deleting csrc/_obj/gemm_kernels.o)
+    PNPP_STAMPS=1 python -c "import __graft_entry__ as g; g.build()"   (after deleting csrc/_obj/gemm_ws_kernels.o)
     python tools/phase_stamps.py
 """
 import ctypes, sys, os
