@@ -48,7 +48,8 @@ same gate.  After every case the wave-pair kernels' bounded polls must not have 
 
 gemm_wsd3<256> and <128,A4> always run with 64 workers (M >= 8192 gives at least 256 strips for 4 x 64 wave slots), so their XCD map
 is the only one they can take; the custom shapes reach them with a ragged last round instead.  sa1 / sa2 change band again only at
-B >= 2048 (the 32-bit offset guards), out of scope here.
+B >= 2048 (the 32-bit offset guards), out of scope here.  Every case here runs with training=True; the same band edges in eval mode
+(E_STORE products, BatchNorm from the running statistics) are tests/test_gpu_eval_bands.py.
 """
 import pytest
 import torch
