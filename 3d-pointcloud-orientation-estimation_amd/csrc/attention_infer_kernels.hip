@@ -3,6 +3,8 @@
 // v_mfma_f32_32x32x16_bf16 from the exact three-way bf16 splits of their float32 operands (split_infer.h) in place of
 // v_mfma_f32_32x32x2_f32.  Same buffers, same padding contract: N a multiple of 128, keys >= n_valid get no weight, key blocks without a
 // point are not visited, padded query rows are computed like any other (finite for finite input).
+// Ragged form (pnpp_attention_infer_ragged, `lengths` non-null): n_valid becomes the cloud's own min(max(lengths[b], 1), n_valid), rows
+// from there on are written as zeros, and a workgroup wholly beyond its cloud writes its zeros and leaves before any barrier.
 //
 // Workgroup = 128 queries of one (cloud, head): 4 waves x 32 queries, as the float32 kernel.  Keys / values stream through LDS in
 // stages of 64 (two 32-key tiles), double buffered, one barrier per stage; they are split into their three planes while they are
@@ -44,13 +46,20 @@ constexpr float AI_LOG2E = 1.4426950408889634f;
 __device__ __forceinline__ f32x16 ai_mfma(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 
 __global__ void __launch_bounds__(256, 4)   // at least four waves per SIMD (here: four workgroups per CU): a wave's softmax and splits issue beside the MFMAs of three others
-attention_infer_kernel(const float *__restrict__ qkv, int N, int Nv, int H, float *__restrict__ out) {
+attention_infer_kernel(const float *__restrict__ qkv, int N, int Nv, const int *__restrict__ lengths, int H, float *__restrict__ out) {
     __shared__ __attribute__((aligned(16))) unsigned short Ks[2][3][AI_KPLANE];
     __shared__ __attribute__((aligned(16))) unsigned short Vs[2][3][AI_VPLANE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int h = blockIdx.y, b = blockIdx.z, E = H * AI_DH, ld = 3 * E;
     const float *base = qkv + (size_t)b * N * ld;
     const int q = blockIdx.x * 128 + wave * 32 + l31;   // this lane's query (N % 128 == 0: the row exists)
+    const int Nz = att_ragged_rows(lengths, b, N, Nv);  // ragged form: Nv becomes the cloud's own length, rows from Nz on are written as zeros
+    if ((int)blockIdx.x * 128 >= Nz) {                  // a workgroup wholly beyond its cloud (by blockIdx: all of it leaves before any barrier)
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 *orow = reinterpret_cast<float4 *>(out + ((size_t)b * N + q) * E + h * AI_DH + 4 * lh);
+        orow[0] = z, orow[2] = z;
+        return;
+    }
 
     // rows 16 .. 31 of the V^T planes, both buffers: ones in row 16 of the leading plane, zeros elsewhere; staging never writes them
     for (int i = tid; i < 2 * 3 * 8 * AI_VP; i += 256) {   // 32-bit words
@@ -172,7 +181,7 @@ attention_infer_kernel(const float *__restrict__ qkv, int N, int Nv, int H, floa
 #pragma unroll
     for (int r = 0; r < 9; ++r) t[r] = o[r] + ol[r];
     const float l = t[8] + __shfl_xor(t[8], 32, 64);   // row 16 sits in the lower half-wave, the upper one holds zero row 20 there
-    const float inv = 1.f / l;
+    const float inv = q < Nz ? 1.f / l : 0.f;   // ragged form: a padding query's row is written as zeros (its sums are finite: the keys are points)
     float4 *orow = reinterpret_cast<float4 *>(out + ((size_t)b * N + q) * E + h * AI_DH + 4 * lh);
     orow[0] = make_float4(t[0] * inv, t[1] * inv, t[2] * inv, t[3] * inv);   // dims 4 h + 0 .. 3
     orow[2] = make_float4(t[4] * inv, t[5] * inv, t[6] * inv, t[7] * inv);   // dims 8 + 4 h + 0 .. 3
@@ -198,12 +207,24 @@ extern "C" int pnpp_attention_infer_supported(int B, int N, int n_valid, int H, 
     return ai_check("attention_infer", B, N, n_valid, H, head_dim) == PNPP_OK ? 1 : 0;
 }
 
-extern "C" int pnpp_attention_infer(const float *qkv, int B, int N, int n_valid, int H, int head_dim, float *out, void *stream) {
+// lengths == nullptr: the uniform call; otherwise the ragged one (pnpp_attention_infer_ragged refuses a null tensor before it comes here)
+static int attention_infer_launch(const float *qkv, int B, int N, int n_valid, const int32_t *lengths, int H, int head_dim, float *out,
+                                  void *stream) {
     PNPP_REQUIRE(qkv && out, PNPP_ERR_ARG, "attention_infer: null pointer");
     const int rc = ai_check("attention_infer", B, N, n_valid, H, head_dim);
     if (rc != PNPP_OK) return rc;
-    ProfScope ps(as_stream(stream), "attention_fwd_kernel<split> B=%d N=%d H=%d", B, N, H);
-    hipLaunchKernelGGL(attention_infer_kernel, dim3(N / 128, H, B), dim3(256), 0, as_stream(stream), qkv, N, n_valid, H, out);
+    ProfScope ps(as_stream(stream), lengths ? "attention_fwd_kernel<split> B=%d N=%d H=%d ragged=1" : "attention_fwd_kernel<split> B=%d N=%d H=%d", B, N, H);
+    hipLaunchKernelGGL(attention_infer_kernel, dim3(N / 128, H, B), dim3(256), 0, as_stream(stream), qkv, N, n_valid, lengths, H, out);
     PNPP_CHECK_LAUNCH("attention_infer");
     return PNPP_OK;
+}
+
+extern "C" int pnpp_attention_infer(const float *qkv, int B, int N, int n_valid, int H, int head_dim, float *out, void *stream) {
+    return attention_infer_launch(qkv, B, N, n_valid, nullptr, H, head_dim, out, stream);
+}
+
+extern "C" int pnpp_attention_infer_ragged(const float *qkv, int B, int N, int n_valid, const int32_t *lengths, int H, int head_dim, float *out,
+                                           void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "attention_infer_ragged: null lengths pointer (the uniform call is pnpp_attention_infer)");
+    return attention_infer_launch(qkv, B, N, n_valid, lengths, H, head_dim, out, stream);
 }

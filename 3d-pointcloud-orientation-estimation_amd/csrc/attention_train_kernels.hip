@@ -4,6 +4,8 @@
 // in both orientations, lse and dsum (B, H, N), padding rows of dqkv exact zeros, nothing a valid row receives depends on the padding,
 // no atomics), with every matrix product on v_mfma_f32_32x32x16_bf16 from the exact three-way bf16 splits of its float32 operands
 // (split_prims.h) in place of v_mfma_f32_32x32x2_f32.  The form is chosen by the entry point called; no environment switch.
+// Ragged form (the _ragged entry points, `lengths` non-null): as in transformer_kernels.hip -- Nv is the cloud's own length (att_ragged_rows,
+// common.h), out / lse / dQ rows beyond it are zeros, workgroups wholly beyond their cloud leave by blockIdx before any barrier.
 //
 // All three kernels: workgroup = 128 rows of one (cloud, head), 4 waves x 32 rows, a lane is a row (a query in the forward and dQ, a
 // key in dK/dV) whose own operands are split once; the other side streams through LDS in stages of 64 rows (two 32-row tiles), double
@@ -129,14 +131,22 @@ struct Stager {
 
 // ---- forward: attention_infer_kernel's tiling, plus lse and the keep bits --------------------------------------------------------------
 __global__ void __launch_bounds__(256, 3)   // the row sum, lse and the keep words do not fit the inference kernel's 128 registers without scratch (72 bytes at four waves)
-attention_train_fwd_kernel(const float *__restrict__ qkv, int N, int Nv, int H, const unsigned *__restrict__ mask, float keep_scale,
-                           float *__restrict__ out, float *__restrict__ lse) {
+attention_train_fwd_kernel(const float *__restrict__ qkv, int N, int Nv, const int *__restrict__ lengths, int H,
+                           const unsigned *__restrict__ mask, float keep_scale, float *__restrict__ out, float *__restrict__ lse) {
     __shared__ __attribute__((aligned(16))) unsigned short Ks[2][3][AT_RPLANE];
     __shared__ __attribute__((aligned(16))) unsigned short Vs[2][3][AT_TPLANE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int h = blockIdx.y, b = blockIdx.z, E = H * AT_DH, ld = 3 * E;
     const float *base = qkv + (size_t)b * N * ld;
     const int q = blockIdx.x * 128 + wave * 32 + l31;   // this lane's query (N % 128 == 0: the row exists)
+    const int Nz = att_ragged_rows(lengths, b, N, Nv);  // ragged form: Nv becomes the cloud's own length, rows from Nz on are written as zeros
+    if ((int)blockIdx.x * 128 >= Nz) {                  // a workgroup wholly beyond its cloud (by blockIdx: all of it leaves before any barrier)
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 *orow = reinterpret_cast<float4 *>(out + ((size_t)b * N + q) * E + h * AT_DH + 4 * lh);
+        orow[0] = z, orow[2] = z;
+        if (lse && lh == 0) lse[((size_t)b * H + h) * N + q] = 0.f;
+        return;
+    }
 
     Frag3 qf;   // Q^T operand: dims 8 h .. 8 h + 7 of this lane's query, scaled
     {
@@ -224,26 +234,33 @@ attention_train_fwd_kernel(const float *__restrict__ qkv, int N, int Nv, int H, 
     const float inv = 1.f / l_run;
     float tr[8];
 #pragma unroll
-    for (int r = 0; r < 8; ++r) tr[r] = (o[r] + ol[r]) * inv;
+    for (int r = 0; r < 8; ++r) tr[r] = q < Nz ? (o[r] + ol[r]) * inv : 0.f;
     float4 *orow = reinterpret_cast<float4 *>(out + ((size_t)b * N + q) * E + h * AT_DH + 4 * lh);
     orow[0] = make_float4(tr[0], tr[1], tr[2], tr[3]);   // dims 4 h + 0 .. 3
     orow[2] = make_float4(tr[4], tr[5], tr[6], tr[7]);   // dims 8 + 4 h + 0 .. 3
     // natural log, although the loop works in the log2 domain: the probabilities are exp2(s log2(e) - ml) with ml the ROUNDED m log2(e),
     // so their sum is that of exp(s - m) times exp2(m log2(e) - ml); the residual is exact in one fma
-    if (lse && lh == 0) lse[((size_t)b * H + h) * N + q] = m_run + (logf(l_run) - fmaf(m_run, AT_LOG2E, -ml_run) * AT_LN2);
+    if (lse && lh == 0) lse[((size_t)b * H + h) * N + q] = q < Nz ? m_run + (logf(l_run) - fmaf(m_run, AT_LOG2E, -ml_run) * AT_LN2) : 0.f;
 }
 
 // ---- dQ: a wave owns 32 queries and walks the keys.  S^T = K Q^T, dP^T = V dO^T, dS^T = P^T (keep dP^T - D), dQ^T += K^T dS^T ---------------
 __global__ void __launch_bounds__(256, 2)
 attention_train_dq_kernel(const float *__restrict__ qkv, const float *__restrict__ o, const float *__restrict__ d_o,
-                          const float *__restrict__ lse, int N, int Nv, int H, const unsigned *__restrict__ mask, float keep_scale,
-                          float *__restrict__ dqkv, float *__restrict__ dsum) {
+                          const float *__restrict__ lse, int N, int Nv, const int *__restrict__ lengths, int H,
+                          const unsigned *__restrict__ mask, float keep_scale, float *__restrict__ dqkv, float *__restrict__ dsum) {
     __shared__ __attribute__((aligned(16))) unsigned short Kr[2][3][AT_RPLANE], Vr[2][3][AT_RPLANE];
     __shared__ __attribute__((aligned(16))) unsigned short Kt[2][3][AT_TPLANE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int h = blockIdx.y, b = blockIdx.z, E = H * AT_DH, ld = 3 * E;
     const float *base = qkv + (size_t)b * N * ld;
     const int q = blockIdx.x * 128 + wave * 32 + l31;
+    const int Nz = att_ragged_rows(lengths, b, N, Nv);
+    if ((int)blockIdx.x * 128 >= Nz) {   // wholly beyond the cloud: zero dQ rows (dsum of these rows is never read: the dK/dV kernel skips them)
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 *drow = reinterpret_cast<float4 *>(dqkv + ((size_t)b * N + q) * ld + h * AT_DH + 4 * lh);
+        drow[0] = z, drow[2] = z;
+        return;
+    }
 
     Frag3 qf, gf;   // this lane's query and its dO row, dims 8 h .. 8 h + 7, split once
     float D;
@@ -314,7 +331,7 @@ attention_train_dq_kernel(const float *__restrict__ qkv, const float *__restrict
     }
     float tr[8];
 #pragma unroll
-    for (int r = 0; r < 8; ++r) tr[r] = (dq[r] + dql[r]) * AT_SCALE;
+    for (int r = 0; r < 8; ++r) tr[r] = q < Nz ? (dq[r] + dql[r]) * AT_SCALE : 0.f;
     float4 *drow = reinterpret_cast<float4 *>(dqkv + ((size_t)b * N + q) * ld + h * AT_DH + 4 * lh);
     drow[0] = make_float4(tr[0], tr[1], tr[2], tr[3]);
     drow[2] = make_float4(tr[4], tr[5], tr[6], tr[7]);
@@ -323,8 +340,8 @@ attention_train_dq_kernel(const float *__restrict__ qkv, const float *__restrict
 // ---- dK, dV: a wave owns 32 keys and walks the query blocks.  S = (scale Q) K^T, dP = dO V^T, dV^T += dO^T (P keep), dK^T += (scale Q)^T dS ----
 __global__ void __launch_bounds__(256, 2)
 attention_train_dkv_kernel(const float *__restrict__ qkv, const float *__restrict__ d_o, const float *__restrict__ lse,
-                           const float *__restrict__ dsum, int N, int Nv, int H, const unsigned *__restrict__ maskT, float keep_scale,
-                           float *__restrict__ dqkv) {
+                           const float *__restrict__ dsum, int N, int Nv, const int *__restrict__ lengths, int H,
+                           const unsigned *__restrict__ maskT, float keep_scale, float *__restrict__ dqkv) {
     __shared__ __attribute__((aligned(16))) unsigned short Qr[2][3][AT_RPLANE], Gr[2][3][AT_RPLANE];
     __shared__ __attribute__((aligned(16))) unsigned short Qt[2][3][AT_TPLANE], Gt[2][3][AT_TPLANE];
     __shared__ __attribute__((aligned(16))) float Ls[2][AT_ST], Ds[2][AT_ST];
@@ -332,6 +349,13 @@ attention_train_dkv_kernel(const float *__restrict__ qkv, const float *__restric
     const int h = blockIdx.y, b = blockIdx.z, E = H * AT_DH, ld = 3 * E;
     const float *base = qkv + (size_t)b * N * ld;
     const int key = blockIdx.x * 128 + wave * 32 + l31;
+    if ((int)blockIdx.x * 128 >= att_ragged_rows(lengths, b, N, Nv)) {   // every key of the workgroup is padding: zero rows, no walk over the queries
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        float *drow = dqkv + ((size_t)b * N + key) * ld + h * AT_DH + 4 * lh;
+        float4 *krow = reinterpret_cast<float4 *>(drow + E), *vrow = reinterpret_cast<float4 *>(drow + 2 * E);
+        krow[0] = z, krow[2] = z, vrow[0] = z, vrow[2] = z;
+        return;
+    }
     const bool kvalid = key < Nv;
 
     Frag3 kf3, vf3;   // this lane's key and value rows, split once.  A padding key's are taken as zeros: what its row holds is never used
@@ -445,22 +469,35 @@ extern "C" int pnpp_attention_split_supported(int B, int N, int n_valid, int H, 
     return at_check("attention_split", B, N, n_valid, H, head_dim) == PNPP_OK ? 1 : 0;
 }
 
-extern "C" int pnpp_attention_split_fwd(const float *qkv, int B, int N, int n_valid, int H, int head_dim, const uint32_t *mask, float p,
-                                        float *out, float *lse, void *stream) {
+// lengths == nullptr: the uniform call; otherwise the ragged one (the _ragged entry points refuse a null tensor before they come here)
+static int attention_split_fwd_launch(const float *qkv, int B, int N, int n_valid, const int32_t *lengths, int H, int head_dim,
+                                      const uint32_t *mask, float p, float *out, float *lse, void *stream) {
     PNPP_REQUIRE(qkv && out, PNPP_ERR_ARG, "attention_split_fwd: null pointer");
     const int rc = at_check("attention_split_fwd", B, N, n_valid, H, head_dim);
     if (rc != PNPP_OK) return rc;
     PNPP_REQUIRE(p >= 0.f && p < 1.f, PNPP_ERR_ARG, "attention_split_fwd: dropout p=%g outside [0, 1)", (double)p);
-    ProfScope ps(as_stream(stream), "attention_fwd_kernel<split,train> B=%d N=%d H=%d", B, N, H);
-    hipLaunchKernelGGL(attention_train_fwd_kernel, dim3(N / 128, H, B), dim3(256), 0, as_stream(stream), qkv, N, n_valid, H, mask,
+    ProfScope ps(as_stream(stream), lengths ? "attention_fwd_kernel<split,train> B=%d N=%d H=%d ragged=1" : "attention_fwd_kernel<split,train> B=%d N=%d H=%d",
+                 B, N, H);
+    hipLaunchKernelGGL(attention_train_fwd_kernel, dim3(N / 128, H, B), dim3(256), 0, as_stream(stream), qkv, N, n_valid, lengths, H, mask,
                        1.0f / (1.0f - p), out, lse);
     PNPP_CHECK_LAUNCH("attention_split_fwd");
     return PNPP_OK;
 }
 
-extern "C" int pnpp_attention_split_bwd(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N, int n_valid,
-                                        int H, int head_dim, const uint32_t *mask, const uint32_t *maskT, float p, float *dqkv, float *dsum,
-                                        void *stream) {
+extern "C" int pnpp_attention_split_fwd(const float *qkv, int B, int N, int n_valid, int H, int head_dim, const uint32_t *mask, float p,
+                                        float *out, float *lse, void *stream) {
+    return attention_split_fwd_launch(qkv, B, N, n_valid, nullptr, H, head_dim, mask, p, out, lse, stream);
+}
+
+extern "C" int pnpp_attention_split_fwd_ragged(const float *qkv, int B, int N, int n_valid, const int32_t *lengths, int H, int head_dim,
+                                               const uint32_t *mask, float p, float *out, float *lse, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "attention_split_fwd_ragged: null lengths pointer (the uniform call is pnpp_attention_split_fwd)");
+    return attention_split_fwd_launch(qkv, B, N, n_valid, lengths, H, head_dim, mask, p, out, lse, stream);
+}
+
+static int attention_split_bwd_launch(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N, int n_valid,
+                                      const int32_t *lengths, int H, int head_dim, const uint32_t *mask, const uint32_t *maskT, float p,
+                                      float *dqkv, float *dsum, void *stream) {
     PNPP_REQUIRE((mask == nullptr) == (maskT == nullptr), PNPP_ERR_ARG, "attention_split_bwd: pass both mask orientations or neither");
     PNPP_REQUIRE(p >= 0.f && p < 1.f, PNPP_ERR_ARG, "attention_split_bwd: dropout p=%g outside [0, 1)", (double)p);
     PNPP_REQUIRE(qkv && out && d_out && lse && dqkv && dsum, PNPP_ERR_ARG, "attention_split_bwd: null pointer");
@@ -469,16 +506,29 @@ extern "C" int pnpp_attention_split_bwd(const float *qkv, const float *out, cons
     const float keep_scale = 1.0f / (1.0f - p);
     hipStream_t st = as_stream(stream);
     {
-        ProfScope ps(st, "attention_bwd_dq_kernel<split> B=%d N=%d H=%d", B, N, H);
-        hipLaunchKernelGGL(attention_train_dq_kernel, dim3(N / 128, H, B), dim3(256), 0, st, qkv, out, d_out, lse, N, n_valid, H, mask,
+        ProfScope ps(st, lengths ? "attention_bwd_dq_kernel<split> B=%d N=%d H=%d ragged=1" : "attention_bwd_dq_kernel<split> B=%d N=%d H=%d", B, N, H);
+        hipLaunchKernelGGL(attention_train_dq_kernel, dim3(N / 128, H, B), dim3(256), 0, st, qkv, out, d_out, lse, N, n_valid, lengths, H, mask,
                            keep_scale, dqkv, dsum);
         PNPP_CHECK_LAUNCH("attention_split_bwd_dq");
     }
     {
-        ProfScope ps(st, "attention_bwd_dkv_kernel<split> B=%d N=%d H=%d", B, N, H);
-        hipLaunchKernelGGL(attention_train_dkv_kernel, dim3(N / 128, H, B), dim3(256), 0, st, qkv, d_out, lse, dsum, N, n_valid, H, maskT,
+        ProfScope ps(st, lengths ? "attention_bwd_dkv_kernel<split> B=%d N=%d H=%d ragged=1" : "attention_bwd_dkv_kernel<split> B=%d N=%d H=%d", B, N, H);
+        hipLaunchKernelGGL(attention_train_dkv_kernel, dim3(N / 128, H, B), dim3(256), 0, st, qkv, d_out, lse, dsum, N, n_valid, lengths, H, maskT,
                            keep_scale, dqkv);
         PNPP_CHECK_LAUNCH("attention_split_bwd_dkv");
     }
     return PNPP_OK;
+}
+
+extern "C" int pnpp_attention_split_bwd(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N, int n_valid,
+                                        int H, int head_dim, const uint32_t *mask, const uint32_t *maskT, float p, float *dqkv, float *dsum,
+                                        void *stream) {
+    return attention_split_bwd_launch(qkv, out, d_out, lse, B, N, n_valid, nullptr, H, head_dim, mask, maskT, p, dqkv, dsum, stream);
+}
+
+extern "C" int pnpp_attention_split_bwd_ragged(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N,
+                                               int n_valid, const int32_t *lengths, int H, int head_dim, const uint32_t *mask,
+                                               const uint32_t *maskT, float p, float *dqkv, float *dsum, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "attention_split_bwd_ragged: null lengths pointer (the uniform call is pnpp_attention_split_bwd)");
+    return attention_split_bwd_launch(qkv, out, d_out, lse, B, N, n_valid, lengths, H, head_dim, mask, maskT, p, dqkv, dsum, stream);
 }

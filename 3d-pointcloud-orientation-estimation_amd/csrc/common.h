@@ -147,5 +147,15 @@ __device__ __forceinline__ unsigned f32_sortable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// Ragged batches of the attention kernels: `lengths` (B) int32, or null.  Non-null: the cloud's Nv becomes min(max(lengths[b], 1), Nv)
+// -- one scalar load per workgroup, and the clamp keeps any value in that tensor inside the rows the uniform call walks -- and the
+// rows from the returned bound on are written as exact zeros.  Null: Nv stays, the bound is N, and the kernel does what it did
+// without the argument.
+__device__ __forceinline__ int att_ragged_rows(const int *__restrict__ lengths, int b, int N, int &Nv) {
+    if (!lengths) return N;
+    Nv = min(max(lengths[b], 1), Nv);
+    return Nv;
+}
+
 }  // namespace pnpp
 #endif

@@ -8,6 +8,9 @@
 //                          32-row block's rows n < n_valid
 //   pt_pool_infer_kernel   adds a cloud's partial sums in a fixed order, divides by n_valid, applies fc_out
 // The attention between two of them stays pnpp_attention_fwd (lse = NULL): 1 + depth * 2 + 1 launches per forward.
+// Ragged form (the _ragged entry points): n_valid becomes the cloud's own length in the head's zero-point rule, in the last layer's
+// pooling and in the divisor.  No block is skipped: every row of x_next / qkv_next is written on every call, finite, because the
+// attention stages keys 64 rows at a time and multiplies what lies beyond the cloud by zero weights -- a stale NaN there would spread.
 //
 // Products: split_infer.h (float32 products on v_mfma_f32_32x32x16_bf16 from exact three-way splits, leading and small products in
 // separate accumulators).  The weights' planes are written once by pnpp_pt_infer_fold, an activation is split once, by the lane that
@@ -217,8 +220,14 @@ struct PtHeadArgs {
     const unsigned short *w_in;  // layer 0's in_proj planes
     const float *b_in;
     float *x0, *qkv0;
+    const int *lengths;          // (B) int32 or null: the ragged form, cloud b holds min(max(lengths[b], 1), n_valid) points
     int N, n_valid, in_dim;
 };
+
+// the points of cloud b: n_valid, or in the ragged form the cloud's own length, clamped into 1 .. n_valid
+__device__ __forceinline__ int pt_cloud_rows(const int *__restrict__ lengths, int b, int n_valid) {
+    return lengths ? min(max(lengths[b], 1), n_valid) : n_valid;
+}
 
 __global__ __launch_bounds__(kPtThreads) void pt_head_infer_kernel(const PtHeadArgs P) {
     extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
@@ -226,6 +235,7 @@ __global__ __launch_bounds__(kPtThreads) void pt_head_infer_kernel(const PtHeadA
     unsigned short *tile = lds + wave * kPtTile;
     const size_t row0 = (size_t)blockIdx.x * kPtRows + wave * 32;
     const int b = (int)(row0 / P.N), n0 = (int)(row0 % P.N);
+    const int len = pt_cloud_rows(P.lengths, b, P.n_valid);   // every row is written on every call, whatever the length: the next kernels read them
     float w[2][kPtMaxIn], bias[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -241,7 +251,7 @@ __global__ __launch_bounds__(kPtThreads) void pt_head_infer_kernel(const PtHeadA
         float a0 = bias[0], a1 = bias[1];
 #pragma unroll
         for (int k = 0; k < kPtMaxIn; ++k) {
-            const float x = (n < P.n_valid && k < P.in_dim) ? xr[k] : 0.f;   // rows beyond the cloud are zero points
+            const float x = (n < len && k < P.in_dim) ? xr[k] : 0.f;   // rows beyond the cloud are zero points, whatever they hold
             a0 = fmaf(x, w[0][k], a0), a1 = fmaf(x, w[1][k], a1);
         }
         v[0][i] = a0, v[1][i] = a1;
@@ -261,6 +271,7 @@ struct PtTailArgs {
     const unsigned short *w_in;                // the next layer's in_proj planes, or null in the last layer
     const float *b_in;
     float *x_next, *qkv_next, *part;           // (M, E); (M, 3E) or null; (B, N/32, E) or null
+    const int *lengths;                        // (B) int32 or null, as PtHeadArgs: only the last layer's pooling looks at it
     int N, n_valid, F;
     float eps;
 };
@@ -357,11 +368,12 @@ __global__ __launch_bounds__(kPtThreads) void pt_tail_infer_kernel(const PtTailA
         pt_in_proj(ut, P.w_in, P.b_in, P.qkv_next, row0);
     } else {
         const int b = (int)(row0 / P.N), n0 = (int)(row0 % P.N);
+        const int len = pt_cloud_rows(P.lengths, b, P.n_valid);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             float s = 0.f;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) s += (n0 + pt_row(i, h) < P.n_valid) ? v[j][i] : 0.f;   // padding rows are never pooled
+            for (int i = 0; i < 16; ++i) s += (n0 + pt_row(i, h) < len) ? v[j][i] : 0.f;   // padding rows are never pooled
             s += __shfl_xor(s, 32, 64);
             if (h == 0) P.part[((size_t)b * (P.N / 32) + n0 / 32) * kPtE + 32 * j + r] = s;
         }
@@ -369,13 +381,14 @@ __global__ __launch_bounds__(kPtThreads) void pt_tail_infer_kernel(const PtTailA
 }
 
 // out[b] = (sum of the cloud's partial rows / n_valid) W_fc^T + b_fc; one wave per cloud, float64, fixed order
-__global__ __launch_bounds__(64) void pt_pool_infer_kernel(const float *__restrict__ part, int tiles, int n_valid, const float *__restrict__ fw,
-                                                           const float *__restrict__ fb, int n_out, float *__restrict__ out) {
+__global__ __launch_bounds__(64) void pt_pool_infer_kernel(const float *__restrict__ part, int tiles, int n_valid, const int *__restrict__ lengths,
+                                                           const float *__restrict__ fw, const float *__restrict__ fb, int n_out,
+                                                           float *__restrict__ out) {
     __shared__ double mean[kPtE];
     const int b = blockIdx.x, c = threadIdx.x;
     double s = 0.0;
-    for (int t = 0; t < tiles; ++t) s += (double)part[((size_t)b * tiles + t) * kPtE + c];
-    mean[c] = s / (double)n_valid;
+    for (int t = 0; t < tiles; ++t) s += (double)part[((size_t)b * tiles + t) * kPtE + c];   // blocks beyond the cloud hold exact zeros
+    mean[c] = s / (double)pt_cloud_rows(lengths, b, n_valid);
     __syncthreads();
     for (int o = c; o < n_out; o += 64) {
         double a = (double)fb[o];
@@ -483,7 +496,9 @@ extern "C" int pnpp_pt_infer_fold(const pnpp_pt_infer_desc *d, int layer, const 
     return PNPP_OK;
 }
 
-extern "C" int pnpp_pt_infer_head(const pnpp_pt_infer_desc *d, const float *xyz, const void *weights0, float *x0, float *qkv0, void *stream) {
+// lengths == nullptr: the uniform call; otherwise the ragged one (the _ragged entry points refuse a null tensor before they come here)
+static int pt_infer_head_launch(const pnpp_pt_infer_desc *d, const int32_t *lengths, const float *xyz, const void *weights0, float *x0, float *qkv0,
+                                void *stream) {
     PtPlan p;
     int rc = pt_plan(d, &p);
     if (rc != PNPP_OK) return rc;
@@ -495,19 +510,30 @@ extern "C" int pnpp_pt_infer_head(const pnpp_pt_infer_desc *d, const float *xyz,
     PtHeadArgs P;
     P.xyz = xyz, P.wp = reinterpret_cast<const float *>(base + wp), P.bp = reinterpret_cast<const float *>(base + bp);
     P.w_in = reinterpret_cast<const unsigned short *>(base + o.w[PT_IN_PROJ]), P.b_in = reinterpret_cast<const float *>(base + o.b[PT_IN_PROJ]);
-    P.x0 = x0, P.qkv0 = qkv0, P.N = d->N, P.n_valid = d->n_valid, P.in_dim = d->in_dim;
+    P.x0 = x0, P.qkv0 = qkv0, P.lengths = lengths, P.N = d->N, P.n_valid = d->n_valid, P.in_dim = d->in_dim;
     static bool granted = false;
     rc = pt_allow_lds((const void *)pt_head_infer_kernel, kPtHeadLds, &granted, "pt_infer_head");
     if (rc != PNPP_OK) return rc;
     hipStream_t st = as_stream(stream);
-    ProfScope ps(st, "pt_head_infer_kernel M=%d E=%d F=%d K=%d valid=%d", p.M, kPtE, d->F, d->in_dim, d->n_valid);
+    ProfScope ps(st, lengths ? "pt_head_infer_kernel M=%d E=%d F=%d K=%d valid=%d ragged=1" : "pt_head_infer_kernel M=%d E=%d F=%d K=%d valid=%d", p.M, kPtE,
+                 d->F, d->in_dim, d->n_valid);
     hipLaunchKernelGGL(pt_head_infer_kernel, dim3(p.M / kPtRows), dim3(kPtThreads), kPtHeadLds, st, P);
     PNPP_CHECK_LAUNCH("pt_infer_head");
     return PNPP_OK;
 }
 
-extern "C" int pnpp_pt_infer_tail(const pnpp_pt_infer_desc *d, int layer, const float *x, const float *o, const void *weights,
-                                  const void *weights_next, float *x_next, float *qkv_next, void *scratch, void *stream) {
+extern "C" int pnpp_pt_infer_head(const pnpp_pt_infer_desc *d, const float *xyz, const void *weights0, float *x0, float *qkv0, void *stream) {
+    return pt_infer_head_launch(d, nullptr, xyz, weights0, x0, qkv0, stream);
+}
+
+extern "C" int pnpp_pt_infer_head_ragged(const pnpp_pt_infer_desc *d, const int32_t *lengths, const float *xyz, const void *weights0, float *x0,
+                                         float *qkv0, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "pt_infer_head_ragged: null lengths pointer (the uniform call is pnpp_pt_infer_head)");
+    return pt_infer_head_launch(d, lengths, xyz, weights0, x0, qkv0, stream);
+}
+
+static int pt_infer_tail_launch(const pnpp_pt_infer_desc *d, const int32_t *lengths, int layer, const float *x, const float *o, const void *weights,
+                                const void *weights_next, float *x_next, float *qkv_next, void *scratch, void *stream) {
     PtPlan p;
     int rc = pt_plan(d, &p);
     if (rc != PNPP_OK) return rc;
@@ -534,28 +560,53 @@ extern "C" int pnpp_pt_infer_tail(const pnpp_pt_infer_desc *d, int layer, const 
         const char *nb = static_cast<const char *>(weights_next);
         P.w_in = planes(nb, w.w[PT_IN_PROJ]), P.b_in = floats(nb, w.b[PT_IN_PROJ]), P.qkv_next = qkv_next;
     }
-    P.x_next = x_next, P.N = d->N, P.n_valid = d->n_valid, P.F = d->F, P.eps = d->eps;
+    P.x_next = x_next, P.lengths = lengths, P.N = d->N, P.n_valid = d->n_valid, P.F = d->F, P.eps = d->eps;
     static bool granted = false;
     rc = pt_allow_lds((const void *)pt_tail_infer_kernel, kPtTailLds, &granted, "pt_infer_tail");
     if (rc != PNPP_OK) return rc;
     hipStream_t st = as_stream(stream);
-    ProfScope ps(st, "pt_tail_infer_kernel M=%d E=%d F=%d valid=%d last=%d", p.M, kPtE, d->F, d->n_valid, last ? 1 : 0);
+    ProfScope ps(st, lengths ? "pt_tail_infer_kernel M=%d E=%d F=%d valid=%d last=%d ragged=1" : "pt_tail_infer_kernel M=%d E=%d F=%d valid=%d last=%d", p.M, kPtE,
+                 d->F, d->n_valid, last ? 1 : 0);
     hipLaunchKernelGGL(pt_tail_infer_kernel, dim3(p.M / kPtRows), dim3(kPtThreads), kPtTailLds, st, P);
     PNPP_CHECK_LAUNCH("pt_infer_tail");
     return PNPP_OK;
 }
 
-extern "C" int pnpp_pt_infer_pool(const pnpp_pt_infer_desc *d, const void *scratch, const float *fc_w, const float *fc_b, int n_out, float *out,
-                                  void *stream) {
+extern "C" int pnpp_pt_infer_tail(const pnpp_pt_infer_desc *d, int layer, const float *x, const float *o, const void *weights,
+                                  const void *weights_next, float *x_next, float *qkv_next, void *scratch, void *stream) {
+    return pt_infer_tail_launch(d, nullptr, layer, x, o, weights, weights_next, x_next, qkv_next, scratch, stream);
+}
+
+extern "C" int pnpp_pt_infer_tail_ragged(const pnpp_pt_infer_desc *d, const int32_t *lengths, int layer, const float *x, const float *o,
+                                         const void *weights, const void *weights_next, float *x_next, float *qkv_next, void *scratch,
+                                         void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "pt_infer_tail_ragged: null lengths pointer (the uniform call is pnpp_pt_infer_tail)");
+    return pt_infer_tail_launch(d, lengths, layer, x, o, weights, weights_next, x_next, qkv_next, scratch, stream);
+}
+
+static int pt_infer_pool_launch(const pnpp_pt_infer_desc *d, const int32_t *lengths, const void *scratch, const float *fc_w, const float *fc_b,
+                                int n_out, float *out, void *stream) {
     PtPlan p;
     int rc = pt_plan(d, &p);
     if (rc != PNPP_OK) return rc;
     PNPP_REQUIRE(scratch && fc_w && fc_b && out, PNPP_ERR_ARG, "pt_infer_pool: null pointer");
     PNPP_REQUIRE(n_out > 0, PNPP_ERR_ARG, "pt_infer_pool: n_out=%d must be positive", n_out);
     hipStream_t st = as_stream(stream);
-    ProfScope ps(st, "pt_pool_infer_kernel M=%d E=%d F=%d B=%d valid=%d out=%d", p.M, kPtE, d->F, d->B, d->n_valid, n_out);
-    hipLaunchKernelGGL(pt_pool_infer_kernel, dim3(d->B), dim3(64), 0, st, static_cast<const float *>(scratch), p.tiles32, d->n_valid, fc_w, fc_b,
-                       n_out, out);
+    ProfScope ps(st, lengths ? "pt_pool_infer_kernel M=%d E=%d F=%d B=%d valid=%d out=%d ragged=1" : "pt_pool_infer_kernel M=%d E=%d F=%d B=%d valid=%d out=%d",
+                 p.M, kPtE, d->F, d->B, d->n_valid, n_out);
+    hipLaunchKernelGGL(pt_pool_infer_kernel, dim3(d->B), dim3(64), 0, st, static_cast<const float *>(scratch), p.tiles32, d->n_valid, lengths, fc_w,
+                       fc_b, n_out, out);
     PNPP_CHECK_LAUNCH("pt_infer_pool");
     return PNPP_OK;
+}
+
+extern "C" int pnpp_pt_infer_pool(const pnpp_pt_infer_desc *d, const void *scratch, const float *fc_w, const float *fc_b, int n_out, float *out,
+                                  void *stream) {
+    return pt_infer_pool_launch(d, nullptr, scratch, fc_w, fc_b, n_out, out, stream);
+}
+
+extern "C" int pnpp_pt_infer_pool_ragged(const pnpp_pt_infer_desc *d, const int32_t *lengths, const void *scratch, const float *fc_w,
+                                         const float *fc_b, int n_out, float *out, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "pt_infer_pool_ragged: null lengths pointer (the uniform call is pnpp_pt_infer_pool)");
+    return pt_infer_pool_launch(d, lengths, scratch, fc_w, fc_b, n_out, out, stream);
 }

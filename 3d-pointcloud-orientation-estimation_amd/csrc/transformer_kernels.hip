@@ -8,6 +8,11 @@
 //   mean_points_kernel     mean over the points of a cloud
 //
 // The dense projections (in_proj, out_proj, linear1 + ReLU, linear2, fc_out) go through pnpp_fc_forward.
+//
+// Ragged batches (the _ragged entry points): the attention kernels and mean_points take `lengths` (B) int32 or null.  Non-null, a cloud's
+// Nv is min(max(lengths[b], 1), n_valid) (att_ragged_rows, common.h: one scalar load per workgroup), rows from there on are written as
+// exact zeros (lse: 0), and a 128-row workgroup wholly beyond its cloud writes its zeros and leaves by blockIdx, before any barrier.
+// Null: the kernels do what they did without the argument.
 #include "common.h"
 #include "kernels.h"
 
@@ -121,13 +126,21 @@ constexpr int ATT_DH = 16;
 constexpr int ATT_KP = 17;  // LDS pitch of the key / value tiles
 
 __global__ void __launch_bounds__(256)
-attention_fwd_kernel(const float *__restrict__ qkv, int N, int Nv, int H, float scale, const unsigned *__restrict__ mask,
-                     float keep_scale, float *__restrict__ out, float *__restrict__ lse) {
+attention_fwd_kernel(const float *__restrict__ qkv, int N, int Nv, const int *__restrict__ lengths, int H, float scale,
+                     const unsigned *__restrict__ mask, float keep_scale, float *__restrict__ out, float *__restrict__ lse) {
     __shared__ float Ks[2][32][ATT_KP], Vs[2][32][ATT_KP];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int h = blockIdx.y, b = blockIdx.z, E = H * ATT_DH, ld = 3 * E;
     const float *base = qkv + (size_t)b * N * ld;
     const int q = blockIdx.x * 128 + wave * 32 + l31;  // this lane's query (N % 128 == 0: always valid)
+    const int Nz = att_ragged_rows(lengths, b, N, Nv);  // ragged form: Nv becomes the cloud's own length, rows from Nz on are written as zeros
+    if ((int)blockIdx.x * 128 >= Nz) {                  // a workgroup wholly beyond its cloud (by blockIdx: all of it leaves before any barrier)
+        float *orow = out + ((size_t)b * N + q) * E + h * ATT_DH;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) orow[(r & 3) + 8 * (r >> 2) + 4 * lh] = 0.f;
+        if (lse && lh == 0) lse[((size_t)b * H + h) * N + q] = 0.f;
+        return;
+    }
 
     float qreg[8];  // Q^T operand: dims 2s + lh of this lane's query, pre-scaled (1/sqrt(16) is exact)
 #pragma unroll
@@ -197,8 +210,8 @@ attention_fwd_kernel(const float *__restrict__ qkv, int N, int Nv, int H, float 
     const float inv = 1.f / l_run;
     float *orow = out + ((size_t)b * N + q) * E + h * ATT_DH;
 #pragma unroll
-    for (int r = 0; r < 8; ++r) orow[(r & 3) + 8 * (r >> 2) + 4 * lh] = o[r] * inv;
-    if (lse && lh == 0) lse[((size_t)b * H + h) * N + q] = m_run + logf(l_run);
+    for (int r = 0; r < 8; ++r) orow[(r & 3) + 8 * (r >> 2) + 4 * lh] = q < Nz ? o[r] * inv : 0.f;
+    if (lse && lh == 0) lse[((size_t)b * H + h) * N + q] = q < Nz ? m_run + logf(l_run) : 0.f;
 }
 
 // y = LayerNorm(x + r) over the last dimension E (64 or 128); one wave per row, two-pass statistics in float64
@@ -233,16 +246,19 @@ __global__ void __launch_bounds__(256) add_layernorm_kernel(const float *__restr
 }
 
 // y[b][c] = mean_n x[b][n][c]; one workgroup per cloud, fixed-order float64 sums
-__global__ void __launch_bounds__(256) mean_points_kernel(const float *__restrict__ x, int N, int E, float *__restrict__ y) {
+// With `lengths` (ragged form): the mean over the cloud's first min(max(lengths[b], 1), N) rows, read in place at row pitch N.
+__global__ void __launch_bounds__(256) mean_points_kernel(const float *__restrict__ x, int N, const int *__restrict__ lengths, int E,
+                                                          float *__restrict__ y) {
     __shared__ double red[4][64];
     const int b = blockIdx.x, c = threadIdx.x & 63, rl = threadIdx.x >> 6;
+    const int len = lengths ? min(max(lengths[b], 1), N) : N;
     for (int c0 = 0; c0 < E; c0 += 64) {
         double acc = 0.0;
         if (c0 + c < E)
-            for (int n = rl; n < N; n += 4) acc += (double)x[((size_t)b * N + n) * E + c0 + c];
+            for (int n = rl; n < len; n += 4) acc += (double)x[((size_t)b * N + n) * E + c0 + c];
         red[rl][c] = acc;
         __syncthreads();
-        if (rl == 0 && c0 + c < E) y[(size_t)b * E + c0 + c] = (float)(((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / (double)N);
+        if (rl == 0 && c0 + c < E) y[(size_t)b * E + c0 + c] = (float)(((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) / (double)len);
         __syncthreads();
     }
 }
@@ -291,13 +307,20 @@ __global__ void __launch_bounds__(256) linear_smallk_bwd_kernel(const float *__r
 // Also writes D (B,H,N) for the dK/dV kernel.
 __global__ void __launch_bounds__(256)
 attention_bwd_dq_kernel(const float *__restrict__ qkv, const float *__restrict__ o, const float *__restrict__ d_o,
-                        const float *__restrict__ lse, int N, int Nv, int H, float scale, const unsigned *__restrict__ mask,
-                        float keep_scale, float *__restrict__ dqkv, float *__restrict__ dsum) {
+                        const float *__restrict__ lse, int N, int Nv, const int *__restrict__ lengths, int H, float scale,
+                        const unsigned *__restrict__ mask, float keep_scale, float *__restrict__ dqkv, float *__restrict__ dsum) {
     __shared__ float Ks[2][32][ATT_KP], Vs[2][32][ATT_KP];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int h = blockIdx.y, b = blockIdx.z, E = H * ATT_DH, ld = 3 * E;
     const float *base = qkv + (size_t)b * N * ld;
     const int q = blockIdx.x * 128 + wave * 32 + l31;
+    const int Nz = att_ragged_rows(lengths, b, N, Nv);
+    if ((int)blockIdx.x * 128 >= Nz) {   // wholly beyond the cloud: zero dQ rows (dsum of these rows is never read: the dK/dV kernel skips them)
+        float *drow = dqkv + ((size_t)b * N + q) * ld + h * ATT_DH;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) drow[(r & 3) + 8 * (r >> 2) + 4 * lh] = 0.f;
+        return;
+    }
     float qreg[8], doreg[8], dpart = 0.f;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -356,20 +379,29 @@ attention_bwd_dq_kernel(const float *__restrict__ qkv, const float *__restrict__
     }
     float *drow = dqkv + ((size_t)b * N + q) * ld + h * ATT_DH;
 #pragma unroll
-    for (int r = 0; r < 8; ++r) drow[(r & 3) + 8 * (r >> 2) + 4 * lh] = dq[r] * scale;
+    for (int r = 0; r < 8; ++r) drow[(r & 3) + 8 * (r >> 2) + 4 * lh] = q < Nz ? dq[r] * scale : 0.f;
 }
 
 // dK, dV: a wave owns 32 keys and walks the query blocks.  S and dP tiles are lane = key, register = query; P and dS are
 // directly the B operands of dV^T = dO^T P and dK^T = (scale Q)^T dS.  Per-query L and D come from LDS (one per register).
 __global__ void __launch_bounds__(256)
 attention_bwd_dkv_kernel(const float *__restrict__ qkv, const float *__restrict__ d_o, const float *__restrict__ lse,
-                         const float *__restrict__ dsum, int N, int Nv, int H, float scale, const unsigned *__restrict__ maskT,
-                         float keep_scale, float *__restrict__ dqkv) {
+                         const float *__restrict__ dsum, int N, int Nv, const int *__restrict__ lengths, int H, float scale,
+                         const unsigned *__restrict__ maskT, float keep_scale, float *__restrict__ dqkv) {
     __shared__ float Qs[2][32][ATT_KP], Gs[2][32][ATT_KP], Ls[2][32], Ds[2][32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int h = blockIdx.y, b = blockIdx.z, E = H * ATT_DH, ld = 3 * E;
     const float *base = qkv + (size_t)b * N * ld;
     const int key = blockIdx.x * 128 + wave * 32 + l31;
+    if ((int)blockIdx.x * 128 >= att_ragged_rows(lengths, b, N, Nv)) {   // every key of the workgroup is padding: zero rows, no walk over the queries
+        float *drow = dqkv + ((size_t)b * N + key) * ld + h * ATT_DH;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int d = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            drow[E + d] = 0.f, drow[2 * E + d] = 0.f;
+        }
+        return;
+    }
     float kreg[8], vreg[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -521,6 +553,16 @@ __global__ void __launch_bounds__(256) mean_points_bwd_kernel(const float *__res
     }
 }
 
+// the ragged form: dx[b][n][c] = dy[b][c] / len_b for n < len_b, an exact 0 for the padding rows
+__global__ void __launch_bounds__(256) mean_points_ragged_bwd_kernel(const float *__restrict__ dy, int N, const int *__restrict__ lengths,
+                                                                     int E, size_t total, float *__restrict__ dx) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t bn = i / E, b = bn / N;
+        const int len = min(max(lengths[b], 1), N);
+        dx[i] = (int)(bn - b * N) < len ? dy[b * E + (i - bn * E)] * (1.f / (float)len) : 0.f;
+    }
+}
+
 }  // namespace pnpp
 
 using namespace pnpp;
@@ -565,20 +607,32 @@ extern "C" int pnpp_attention_dropout_mask_dev(uint64_t seed, uint64_t *stream_i
     return attention_dropout_mask_impl(seed, offset, stream_id_dev, B, N, H, p, mask, maskT, stream);
 }
 
-extern "C" int pnpp_attention_fwd(const float *qkv, int B, int N, int n_valid, int H, int head_dim, const uint32_t *mask, float p,
-                                  float *out, float *lse, void *stream) {
+// lengths == nullptr: the uniform call; otherwise the ragged one (the _ragged entry points refuse a null tensor before they come here)
+static int attention_fwd_launch(const float *qkv, int B, int N, int n_valid, const int32_t *lengths, int H, int head_dim, const uint32_t *mask,
+                                float p, float *out, float *lse, void *stream) {
     PNPP_REQUIRE(qkv && out, PNPP_ERR_ARG, "attention_fwd: null pointer");
     PNPP_REQUIRE(B > 0 && N > 0 && H > 0, PNPP_ERR_ARG, "attention_fwd: non-positive size");
     PNPP_REQUIRE(head_dim == ATT_DH, PNPP_ERR_ARG, "attention_fwd: head dimension %d is not supported (only %d)", head_dim, ATT_DH);
     PNPP_REQUIRE(N % 128 == 0, PNPP_ERR_ARG, "attention_fwd: the row count N=%d must be a multiple of 128 (pad, and pass n_valid)", N);
     PNPP_REQUIRE(n_valid > 0 && n_valid <= N, PNPP_ERR_ARG, "attention_fwd: n_valid=%d outside 1..N=%d", n_valid, N);
     PNPP_REQUIRE(B <= 65535 && H <= 65535, PNPP_ERR_ARG, "attention_fwd: B or H exceeds the grid limit");
-    ProfScope ps(as_stream(stream), "attention_fwd_kernel B=%d N=%d H=%d", B, N, H);
     PNPP_REQUIRE(p >= 0.f && p < 1.f, PNPP_ERR_ARG, "attention_fwd: dropout p=%g outside [0, 1)", (double)p);
-    hipLaunchKernelGGL(attention_fwd_kernel, dim3(N / 128, H, B), dim3(256), 0, as_stream(stream), qkv, N, n_valid, H,
+    ProfScope ps(as_stream(stream), lengths ? "attention_fwd_kernel B=%d N=%d H=%d ragged=1" : "attention_fwd_kernel B=%d N=%d H=%d", B, N, H);
+    hipLaunchKernelGGL(attention_fwd_kernel, dim3(N / 128, H, B), dim3(256), 0, as_stream(stream), qkv, N, n_valid, lengths, H,
                        1.0f / sqrtf((float)head_dim), mask, 1.0f / (1.0f - p), out, lse);
     PNPP_CHECK_LAUNCH("attention_fwd");
     return PNPP_OK;
+}
+
+extern "C" int pnpp_attention_fwd(const float *qkv, int B, int N, int n_valid, int H, int head_dim, const uint32_t *mask, float p,
+                                  float *out, float *lse, void *stream) {
+    return attention_fwd_launch(qkv, B, N, n_valid, nullptr, H, head_dim, mask, p, out, lse, stream);
+}
+
+extern "C" int pnpp_attention_fwd_ragged(const float *qkv, int B, int N, int n_valid, const int32_t *lengths, int H, int head_dim,
+                                         const uint32_t *mask, float p, float *out, float *lse, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "attention_fwd_ragged: null lengths pointer (the uniform call is pnpp_attention_fwd)");
+    return attention_fwd_launch(qkv, B, N, n_valid, lengths, H, head_dim, mask, p, out, lse, stream);
 }
 
 extern "C" int pnpp_add_layernorm(const float *x, const float *r, const float *w, const float *b, int M, int E, float eps,
@@ -591,13 +645,22 @@ extern "C" int pnpp_add_layernorm(const float *x, const float *r, const float *w
     return PNPP_OK;
 }
 
-extern "C" int pnpp_mean_points(const float *x, int B, int N, int E, float *y, void *stream) {
+static int mean_points_launch(const float *x, int B, int N, const int32_t *lengths, int E, float *y, void *stream) {
     PNPP_REQUIRE(x && y, PNPP_ERR_ARG, "mean_points: null pointer");
     PNPP_REQUIRE(B > 0 && N > 0 && E > 0, PNPP_ERR_ARG, "mean_points: non-positive size");
-    ProfScope ps(as_stream(stream), "mean_points_kernel B=%d N=%d E=%d", B, N, E);
-    hipLaunchKernelGGL(mean_points_kernel, dim3(B), dim3(256), 0, as_stream(stream), x, N, E, y);
+    ProfScope ps(as_stream(stream), lengths ? "mean_points_kernel B=%d N=%d E=%d ragged=1" : "mean_points_kernel B=%d N=%d E=%d", B, N, E);
+    hipLaunchKernelGGL(mean_points_kernel, dim3(B), dim3(256), 0, as_stream(stream), x, N, lengths, E, y);
     PNPP_CHECK_LAUNCH("mean_points");
     return PNPP_OK;
+}
+
+extern "C" int pnpp_mean_points(const float *x, int B, int N, int E, float *y, void *stream) {
+    return mean_points_launch(x, B, N, nullptr, E, y, stream);
+}
+
+extern "C" int pnpp_mean_points_ragged(const float *x, int B, int N, const int32_t *lengths, int E, float *y, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "mean_points_ragged: null lengths pointer (the uniform call is pnpp_mean_points)");
+    return mean_points_launch(x, B, N, lengths, E, y, stream);
 }
 
 extern "C" size_t pnpp_linear_smallk_bwd_scratch_bytes(int M, int N) { return (size_t)cdiv(M, 256) * N * 16 * sizeof(float); }
@@ -621,9 +684,9 @@ extern "C" int pnpp_linear_smallk_bwd(const float *x, const float *dy, int M, in
     return rc;
 }
 
-extern "C" int pnpp_attention_bwd(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N, int n_valid, int H,
-                                  int head_dim, const uint32_t *mask, const uint32_t *maskT, float p, float *dqkv, float *dsum,
-                                  void *stream) {
+static int attention_bwd_launch(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N, int n_valid,
+                                const int32_t *lengths, int H, int head_dim, const uint32_t *mask, const uint32_t *maskT, float p, float *dqkv,
+                                float *dsum, void *stream) {
     PNPP_REQUIRE((mask == nullptr) == (maskT == nullptr), PNPP_ERR_ARG, "attention_bwd: pass both mask orientations or neither");
     PNPP_REQUIRE(p >= 0.f && p < 1.f, PNPP_ERR_ARG, "attention_bwd: dropout p=%g outside [0, 1)", (double)p);
     const float keep_scale = 1.0f / (1.0f - p);
@@ -636,18 +699,31 @@ extern "C" int pnpp_attention_bwd(const float *qkv, const float *out, const floa
     hipStream_t st = as_stream(stream);
     const float scale = 1.0f / sqrtf((float)head_dim);
     {
-        ProfScope ps(st, "attention_bwd_dq_kernel B=%d N=%d H=%d", B, N, H);
-        hipLaunchKernelGGL(attention_bwd_dq_kernel, dim3(N / 128, H, B), dim3(256), 0, st, qkv, out, d_out, lse, N, n_valid, H, scale, mask,
-                           keep_scale, dqkv, dsum);
+        ProfScope ps(st, lengths ? "attention_bwd_dq_kernel B=%d N=%d H=%d ragged=1" : "attention_bwd_dq_kernel B=%d N=%d H=%d", B, N, H);
+        hipLaunchKernelGGL(attention_bwd_dq_kernel, dim3(N / 128, H, B), dim3(256), 0, st, qkv, out, d_out, lse, N, n_valid, lengths, H, scale,
+                           mask, keep_scale, dqkv, dsum);
         PNPP_CHECK_LAUNCH("attention_bwd_dq");
     }
     {
-        ProfScope ps(st, "attention_bwd_dkv_kernel B=%d N=%d H=%d", B, N, H);
-        hipLaunchKernelGGL(attention_bwd_dkv_kernel, dim3(N / 128, H, B), dim3(256), 0, st, qkv, d_out, lse, dsum, N, n_valid, H, scale, maskT,
-                           keep_scale, dqkv);
+        ProfScope ps(st, lengths ? "attention_bwd_dkv_kernel B=%d N=%d H=%d ragged=1" : "attention_bwd_dkv_kernel B=%d N=%d H=%d", B, N, H);
+        hipLaunchKernelGGL(attention_bwd_dkv_kernel, dim3(N / 128, H, B), dim3(256), 0, st, qkv, d_out, lse, dsum, N, n_valid, lengths, H, scale,
+                           maskT, keep_scale, dqkv);
         PNPP_CHECK_LAUNCH("attention_bwd_dkv");
     }
     return PNPP_OK;
+}
+
+extern "C" int pnpp_attention_bwd(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N, int n_valid, int H,
+                                  int head_dim, const uint32_t *mask, const uint32_t *maskT, float p, float *dqkv, float *dsum,
+                                  void *stream) {
+    return attention_bwd_launch(qkv, out, d_out, lse, B, N, n_valid, nullptr, H, head_dim, mask, maskT, p, dqkv, dsum, stream);
+}
+
+extern "C" int pnpp_attention_bwd_ragged(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N, int n_valid,
+                                         const int32_t *lengths, int H, int head_dim, const uint32_t *mask, const uint32_t *maskT, float p,
+                                         float *dqkv, float *dsum, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "attention_bwd_ragged: null lengths pointer (the uniform call is pnpp_attention_bwd)");
+    return attention_bwd_launch(qkv, out, d_out, lse, B, N, n_valid, lengths, H, head_dim, mask, maskT, p, dqkv, dsum, stream);
 }
 
 extern "C" size_t pnpp_add_layernorm_bwd_scratch_bytes(int M, int E) { return (size_t)cdiv(M, 64) * 2 * E * sizeof(float); }
@@ -675,5 +751,17 @@ extern "C" int pnpp_mean_points_bwd(const float *dy, int B, int N, int E, float 
     ProfScope ps(as_stream(stream), "mean_points_bwd_kernel B=%d N=%d E=%d", B, N, E);
     hipLaunchKernelGGL(mean_points_bwd_kernel, dim3(grid), dim3(256), 0, as_stream(stream), dy, N, E, total, dx);
     PNPP_CHECK_LAUNCH("mean_points_bwd");
+    return PNPP_OK;
+}
+
+extern "C" int pnpp_mean_points_bwd_ragged(const float *dy, int B, int N, const int32_t *lengths, int E, float *dx, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "mean_points_bwd_ragged: null lengths pointer (the uniform call is pnpp_mean_points_bwd)");
+    PNPP_REQUIRE(dy && dx, PNPP_ERR_ARG, "mean_points_bwd_ragged: null pointer");
+    PNPP_REQUIRE(B > 0 && N > 0 && E > 0, PNPP_ERR_ARG, "mean_points_bwd_ragged: non-positive size");
+    const size_t total = (size_t)B * N * E;
+    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    ProfScope ps(as_stream(stream), "mean_points_bwd_kernel B=%d N=%d E=%d ragged=1", B, N, E);
+    hipLaunchKernelGGL(mean_points_ragged_bwd_kernel, dim3(grid), dim3(256), 0, as_stream(stream), dy, N, lengths, E, total, dx);
+    PNPP_CHECK_LAUNCH("mean_points_bwd_ragged");
     return PNPP_OK;
 }

@@ -140,6 +140,7 @@ class DeviceCloudBank:
             host[i, :len(c)] = c
         self.bank = torch.from_numpy(host).to(device)
         self.lengths = torch.tensor([len(c) for c in clouds], dtype=torch.int32, device=device)
+        self._host_lengths = np.array([len(c) for c in clouds], np.int64)   # padded() sizes its result from these, without a device read
         self.seed, self.draws = int(seed), 0
 
     def __len__(self):
@@ -151,6 +152,20 @@ class DeviceCloudBank:
         ids = torch.as_tensor(cloud_ids, dtype=torch.int32, device=self.bank.device)
         self.draws += 1
         return ops.subsample_points(self.seed, self.draws, self.bank, self.lengths, num_points, ids)
+
+    def padded(self, cloud_ids):
+        """The clouds themselves, not a sample of them: -> (xyz (B, longest_in_batch, 3) float32, lengths (B,) int32), both on the
+        bank's device -- a ragged batch as PointTransformer.forward(x, lengths) and TransformerPredictor(xyz, lengths) take it.  Plain
+        indexing of the resident bank (rows beyond a cloud's length are the bank's zeros), no sampling, no draw counted; works on a CPU
+        bank too.  `cloud_ids` given as a list or a CPU tensor costs no device read; a device tensor is read back once, for the sizes."""
+        import torch
+        host_ids = cloud_ids.detach().cpu().numpy() if isinstance(cloud_ids, torch.Tensor) else np.asarray(cloud_ids)
+        host_ids = host_ids.astype(np.int64).reshape(-1)
+        if host_ids.size == 0 or host_ids.min() < 0 or host_ids.max() >= len(self):
+            raise IndexError(f"DeviceCloudBank.padded: cloud ids must be a non-empty selection of 0..{len(self) - 1}")
+        longest = max(int(self._host_lengths[host_ids].max()), 1)
+        ids = torch.as_tensor(host_ids, dtype=torch.int64, device=self.bank.device)
+        return self.bank[ids, :longest].contiguous(), self.lengths[ids].contiguous()
 
 
 class BankLoader:

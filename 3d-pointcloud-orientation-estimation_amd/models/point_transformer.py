@@ -23,10 +23,12 @@ class PointTransformer(nn.Module):
         self.num_heads = num_heads
         self.attention_form = "float32"     # a plain attribute, not a parameter or buffer: see set_attention
 
-    def forward(self, x: torch.Tensor):
-        """x (B,N,3) -> (B,3)."""
+    def forward(self, x: torch.Tensor, lengths=None):
+        """x (B,N,3) -> (B,3).  lengths (B,), optional: a ragged batch, cloud b = rows 0 .. lengths[b] - 1 of the padded x, the rest of
+        its rows padding that may hold anything; row b of the result is what the model returns for x[b:b+1, :lengths[b]] alone
+        (pnpp_hip.transformer.point_transformer_forward says how a list, a CPU tensor and a device tensor are handled)."""
         from pnpp_hip import transformer as T
-        return T.point_transformer_forward(self, x)
+        return T.point_transformer_forward(self, x, lengths)
 
     def set_dropout(self, p: float) -> "PointTransformer":
         """Sets the four dropout probabilities of every encoder layer (the reference's constructor leaves them at

@@ -153,6 +153,17 @@ SIGNATURES = {
     "pnpp_attention_split_fwd": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _f, _fp, _fp, _fp]),
     "pnpp_attention_split_bwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _f, _fp, _fp, _fp]),
     "pnpp_attention_split_supported": (_i, [_i, _i, _i, _i, _i]),
+    # ragged batches: the namesake's list with the lengths tensor after n_valid (after the descriptor for pnpp_pt_infer_*)
+    "pnpp_attention_fwd_ragged": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _fp, _f, _fp, _fp, _fp]),
+    "pnpp_attention_bwd_ragged": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp, _i, _i, _fp, _fp, _f, _fp, _fp, _fp]),
+    "pnpp_attention_split_fwd_ragged": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _fp, _f, _fp, _fp, _fp]),
+    "pnpp_attention_split_bwd_ragged": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp, _i, _i, _fp, _fp, _f, _fp, _fp, _fp]),
+    "pnpp_attention_infer_ragged": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _fp, _fp]),
+    "pnpp_mean_points_ragged": (_i, [_fp, _i, _i, _fp, _i, _fp, _fp]),
+    "pnpp_mean_points_bwd_ragged": (_i, [_fp, _i, _i, _fp, _i, _fp, _fp]),
+    "pnpp_pt_infer_head_ragged": (_i, [C.POINTER(PtInferDesc), _fp, _fp, _fp, _fp, _fp, _fp]),
+    "pnpp_pt_infer_tail_ragged": (_i, [C.POINTER(PtInferDesc), _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "pnpp_pt_infer_pool_ragged": (_i, [C.POINTER(PtInferDesc), _fp, _fp, _fp, _fp, _i, _fp, _fp]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

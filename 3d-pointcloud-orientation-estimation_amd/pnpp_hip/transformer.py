@@ -87,6 +87,40 @@ def attention_dropout_mask(B: int, N: int, H: int, p: float, device, seed=None, 
     return mask, maskT
 
 
+def check_lengths(lengths, B: int, n_pts: int) -> torch.Tensor:
+    """Host-side validation of a ragged batch's per-cloud lengths, given as a list (or anything torch.as_tensor takes) or a CPU
+    tensor: integer dtype, shape (B,), 1 <= lengths[b] <= n_pts.  -> the values as a CPU int32 tensor.  A violation raises ValueError
+    naming the offending cloud.  Runs without a GPU."""
+    t = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths)
+    if t.is_cuda:
+        raise ValueError("check_lengths validates host values; a device tensor is used as it is (see ragged_lengths)")
+    if t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError(f"lengths must have an integer dtype, got {t.dtype}")
+    if tuple(t.shape) != (B,):
+        raise ValueError(f"lengths must have shape ({B},), one entry per cloud, got {tuple(t.shape)}")
+    t = t.to(torch.int64)
+    bad = ((t < 1) | (t > n_pts)).nonzero()
+    if bad.numel():
+        b = int(bad[0])
+        raise ValueError(f"lengths[{b}] = {int(t[b])}: cloud {b} must hold between 1 and n_pts = {n_pts} points")
+    return t.to(torch.int32).contiguous()
+
+
+def ragged_lengths(lengths, B: int, n_pts: int, device) -> torch.Tensor:
+    """The (B,) int32 device tensor the ragged kernels read.  A list or a CPU tensor is validated on the host (check_lengths) and
+    uploaded.  An int32 tensor already on the device is used as it is, without a synchronisation: only its dtype, shape and device are
+    looked at, THE CALLER VOUCHES FOR THE RANGE 1 <= lengths[b] <= n_pts, and the kernels clamp every value into that range, so a bad
+    one cannot cause an access out of bounds -- it gives the result of the clamped length."""
+    device = torch.device(device)
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+            raise ValueError(f"a device lengths tensor must be int32 of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
+        if lengths.device != device:
+            raise ValueError(f"lengths is on {lengths.device}, the batch on {device}")
+        return lengths.contiguous()
+    return check_lengths(lengths, B, n_pts).to(device)
+
+
 ATTENTION_FORMS = ("float32", "split")
 
 
@@ -101,7 +135,7 @@ class _Attention(torch.autograd.Function):
     _split_bwd, every product on the bf16 matrix pipe from exact three-way splits) and the backward runs in the same one."""
 
     @staticmethod
-    def forward(ctx, qkv, num_heads, p, masks, n_valid, form):
+    def forward(ctx, qkv, num_heads, p, masks, n_valid, form, lengths=None):
         qkv = _f32(qkv, "qkv")
         B, N, E3 = qkv.shape
         if N % 128 != 0 or not 0 < n_valid <= N:
@@ -115,11 +149,16 @@ class _Attention(torch.autograd.Function):
         mask, maskT = masks if masks is not None else (None, None)
         out = torch.empty(B, N, E, device=qkv.device, dtype=torch.float32)
         lse = torch.empty(B, num_heads, N, device=qkv.device, dtype=torch.float32)
-        fwd = lib.pnpp_attention_split_fwd if form == "split" else lib.pnpp_attention_fwd
-        L.check(fwd(qkv.data_ptr(), B, N, int(n_valid), num_heads, E // num_heads, None if mask is None else mask.data_ptr(), float(p),
-                    out.data_ptr(), lse.data_ptr(), _stream()))
+        tail = (num_heads, E // num_heads, None if mask is None else mask.data_ptr(), float(p), out.data_ptr(), lse.data_ptr(), _stream())
+        if lengths is None:
+            fwd = lib.pnpp_attention_split_fwd if form == "split" else lib.pnpp_attention_fwd
+            L.check(fwd(qkv.data_ptr(), B, N, int(n_valid), *tail))
+        else:
+            fwd = lib.pnpp_attention_split_fwd_ragged if form == "split" else lib.pnpp_attention_fwd_ragged
+            L.check(fwd(qkv.data_ptr(), B, N, int(n_valid), lengths.data_ptr(), *tail))
         ctx.save_for_backward(qkv, out, lse)
         ctx.heads, ctx.p, ctx.masks, ctx.n_valid, ctx.form = num_heads, float(p), (mask, maskT), int(n_valid), form
+        ctx.lengths = lengths           # the backward pass reads the same tensor
         ctx.mark_non_differentiable(lse)
         return out, lse
 
@@ -131,14 +170,21 @@ class _Attention(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         dsum = torch.empty_like(lse)
         mask, maskT = ctx.masks
-        bwd = L.lib().pnpp_attention_split_bwd if ctx.form == "split" else L.lib().pnpp_attention_bwd
-        L.check(bwd(qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), B, N, ctx.n_valid, ctx.heads, E3 // 3 // ctx.heads,
-                    None if mask is None else mask.data_ptr(), None if maskT is None else maskT.data_ptr(), ctx.p, dqkv.data_ptr(),
-                    dsum.data_ptr(), _stream()))
-        return dqkv, None, None, None, None, None
+        lib = L.lib()
+        head = (qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), B, N, ctx.n_valid)
+        tail = (ctx.heads, E3 // 3 // ctx.heads, None if mask is None else mask.data_ptr(), None if maskT is None else maskT.data_ptr(), ctx.p,
+                dqkv.data_ptr(), dsum.data_ptr(), _stream())
+        if ctx.lengths is None:
+            bwd = lib.pnpp_attention_split_bwd if ctx.form == "split" else lib.pnpp_attention_bwd
+            L.check(bwd(*head, *tail))
+        else:
+            bwd = lib.pnpp_attention_split_bwd_ragged if ctx.form == "split" else lib.pnpp_attention_bwd_ragged
+            L.check(bwd(*head, ctx.lengths.data_ptr(), *tail))
+        return dqkv, None, None, None, None, None, None
 
 
-def attention(qkv: torch.Tensor, num_heads: int, want_lse: bool = False, p: float = 0.0, masks=None, n_valid=None, form: str = "float32"):
+def attention(qkv: torch.Tensor, num_heads: int, want_lse: bool = False, p: float = 0.0, masks=None, n_valid=None, lengths=None,
+              form: str = "float32"):
     """qkv (B,N,3E), in_proj bias included -> (B,N,E) [, log-sum-exp of the scaled scores (B,H,N)].
     N (rows per cloud) must be a multiple of 128; n_valid <= N (default N) says how many of them are points -- the rest is
     the caller's padding: it receives no attention weight, its own output rows are to be ignored and its d_out must be zero.
@@ -148,11 +194,18 @@ def attention(qkv: torch.Tensor, num_heads: int, want_lse: bool = False, p: floa
     (drawn here when not given).
     form: "float32" (the default) runs the kernels of csrc/transformer_kernels.hip; "split" runs csrc/attention_train_kernels.hip, forward
     and backward: the same buffers and contract with every product on the bf16 matrix pipe from exact three-way splits.  A shape that
-    pnpp_attention_split_supported refuses raises ValueError naming the field; there is no fall-back."""
+    pnpp_attention_split_supported refuses raises ValueError naming the field; there is no fall-back.
+    lengths: a ragged batch -- (B,) per-cloud point counts, lengths[b] <= n_valid (n_valid keeps its meaning: the rows that may hold
+    points); a list, a CPU tensor or an int32 device tensor (ragged_lengths says how each is handled).  Cloud b then gets, bit for bit,
+    what the call on qkv[b:b+1] with n_valid = lengths[b] gives; its rows >= lengths[b] of out and d qkv are exact zeros and lse is 0
+    there; 128-row workgroups wholly beyond a cloud do no work.  The backward pass uses the same tensor."""
     _check_form(form)
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, qkv.shape[0], qkv.shape[1] if n_valid is None else n_valid, qkv.device)
     if p > 0.0 and masks is None:
         masks = attention_dropout_mask(qkv.shape[0], qkv.shape[1], num_heads, p, qkv.device)
-    out, lse = _Attention.apply(qkv, num_heads, p if masks is not None else 0.0, masks, qkv.shape[1] if n_valid is None else n_valid, form)
+    out, lse = _Attention.apply(qkv, num_heads, p if masks is not None else 0.0, masks, qkv.shape[1] if n_valid is None else n_valid, form,
+                                lengths)
     return (out, lse) if want_lse else out
 
 
@@ -197,12 +250,15 @@ def add_layernorm(x2d: torch.Tensor, r2d, norm: torch.nn.LayerNorm) -> torch.Ten
 
 class _MeanPoints(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, lengths=None):
         x = _f32(x, "x")
         B, N, E = x.shape
         y = torch.empty(B, E, device=x.device, dtype=torch.float32)
-        L.check(L.lib().pnpp_mean_points(x.data_ptr(), B, N, E, y.data_ptr(), _stream()))
-        ctx.dims = (B, N, E)
+        if lengths is None:
+            L.check(L.lib().pnpp_mean_points(x.data_ptr(), B, N, E, y.data_ptr(), _stream()))
+        else:
+            L.check(L.lib().pnpp_mean_points_ragged(x.data_ptr(), B, N, lengths.data_ptr(), E, y.data_ptr(), _stream()))
+        ctx.dims, ctx.lengths = (B, N, E), lengths
         return y
 
     @staticmethod
@@ -210,12 +266,19 @@ class _MeanPoints(torch.autograd.Function):
         B, N, E = ctx.dims
         dy = _f32(dy, "dy")
         dx = torch.empty(B, N, E, device=dy.device, dtype=torch.float32)
-        L.check(L.lib().pnpp_mean_points_bwd(dy.data_ptr(), B, N, E, dx.data_ptr(), _stream()))
-        return dx
+        if ctx.lengths is None:
+            L.check(L.lib().pnpp_mean_points_bwd(dy.data_ptr(), B, N, E, dx.data_ptr(), _stream()))
+        else:
+            L.check(L.lib().pnpp_mean_points_bwd_ragged(dy.data_ptr(), B, N, ctx.lengths.data_ptr(), E, dx.data_ptr(), _stream()))
+        return dx, None
 
 
-def mean_points(x: torch.Tensor) -> torch.Tensor:
-    return _MeanPoints.apply(x)
+def mean_points(x: torch.Tensor, lengths=None) -> torch.Tensor:
+    """x (B,N,E) -> the mean over each cloud's points (B,E), fixed-order float64 sums.  With `lengths` (as attention's): the mean over
+    the cloud's first lengths[b] rows, read from the padded tensor in place; the padding rows' gradient is an exact zero."""
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, x.shape[0], x.shape[1], x.device)
+    return _MeanPoints.apply(x, lengths)
 
 
 class _Affine:
@@ -225,13 +288,22 @@ class _Affine:
         self.weight, self.bias = weight, bias
 
 
-def point_transformer_forward(model, xyz: torch.Tensor) -> torch.Tensor:
+def point_transformer_forward(model, xyz: torch.Tensor, lengths=None) -> torch.Tensor:
     """models/point_transformer.py:15-20, differentiable.  In train mode the four dropouts of every
     nn.TransformerEncoderLayer are applied: on the attention weights inside the attention kernels (counter-based keep
     bits), after out_proj (dropout1), after the ReLU (dropout) and after linear2 (dropout2) as keep-masks of the
-    projection kernels."""
+    projection kernels.
+    lengths: a ragged batch -- xyz (B, n_pts, in_dim) padded, cloud b = rows 0 .. lengths[b] - 1 (a list, a CPU tensor, or an int32
+    device tensor that is used as it is, without a synchronisation: ragged_lengths).  Row b of the result is what the model returns for
+    xyz[b:b+1, :lengths[b]] alone.  The padding rows of xyz are overwritten by zeros on entry (in a copy), so they may hold anything, NaN
+    included; attention and pooling run in their ragged forms, everything row-wise is unchanged, and a padding row's gradient is zero
+    on the way down (mean_points' backward gives it zero, every row-wise backward maps zero rows to zero rows)."""
     xyz = _f32(xyz, "xyz")
     B, n_pts, K = xyz.shape
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, B, n_pts, xyz.device)
+        rows = torch.arange(n_pts, device=xyz.device, dtype=torch.int32)
+        xyz = torch.where((rows[None, :] < lengths[:, None])[:, :, None], xyz, xyz.new_zeros(()))   # a select: NaN padding does not pass
     N = (n_pts + 127) // 128 * 128          # rows per cloud: the attention kernels walk 128-query / 32-key blocks
     if N != n_pts:                          # any cloud size (the reference's data has 10,000 points): zero rows are appended,
         pad = xyz.new_zeros(B, N, K)        # the attention kernels give them no weight, and the pooling below leaves them out
@@ -246,11 +318,14 @@ def point_transformer_forward(model, xyz: torch.Tensor) -> torch.Tensor:
         if layer.norm_first or att.in_proj_weight is None or not att.batch_first:
             raise NotImplementedError("only the post-norm, packed in_proj, batch_first encoder layer of the reference")
         qkv = ops.fc_block(x, _Affine(att.in_proj_weight, att.in_proj_bias), training=tr)   # (B*N, 3E), bias added
-        o = attention(qkv.view(B, N, 3 * E), att.num_heads, p=att.dropout if tr else 0.0, n_valid=n_pts, form=form).view(B * N, E)
+        o = attention(qkv.view(B, N, 3 * E), att.num_heads, p=att.dropout if tr else 0.0, n_valid=n_pts, lengths=lengths, form=form).view(B * N, E)
         o = ops.fc_block(o, att.out_proj, dropout=layer.dropout1, training=tr)
         x = add_layernorm(x, o, layer.norm1)
         hid = ops.fc_block(x, layer.linear1, relu=True, dropout=layer.dropout, training=tr)   # dropout(relu(W1 x + b1))
         f = ops.fc_block(hid, layer.linear2, dropout=layer.dropout2, training=tr)
         x = add_layernorm(x, f, layer.norm2)
-    pooled = mean_points(x.view(B, N, E) if N == n_pts else x.view(B, N, E)[:, :n_pts])
+    if lengths is not None:
+        pooled = mean_points(x.view(B, N, E), lengths)      # the padded buffer in place: no slice copy
+    else:
+        pooled = mean_points(x.view(B, N, E) if N == n_pts else x.view(B, N, E)[:, :n_pts])
     return ops.fc_block(pooled, model.fc_out, training=tr)

@@ -18,6 +18,11 @@ kernel.  Without the keyword the form is DEFAULT_ATTENTION below.  A model the k
 width, head count or feed-forward size that is no multiple of 64, pre-norm, GELU, ...) runs transformer.point_transformer_forward
 on a private eval-mode copy.
 
+A ragged batch is predictor(xyz, lengths): xyz (B, n_pts, in_dim) padded, cloud b = rows 0 .. lengths[b] - 1 (a list, a CPU tensor, or
+an int32 device tensor used as it is, without a synchronisation -- pnpp_hip.transformer.ragged_lengths); row b of the result is what
+the call on xyz[b:b+1, :lengths[b]] alone returns, whatever the padding rows hold.  The same kernels run in their ragged forms, in both
+attention forms; every row of the reused buffers is written on every call, so nothing stale reaches a later kernel.
+
 Same contract as the other Predictors: a snapshot (refresh() folds again), not differentiable, nothing written to the model,
 evaluated in eval mode whatever model.training says, any n_pts >= 1 (padded to a multiple of 128 inside), no CPU fallback.
 """
@@ -197,38 +202,57 @@ class TransformerPredictor(Predictor):
         """the form this call runs: the Predictor's own, or "float32" where the split kernel does not take the call's sizes"""
         return "split" if self.attention == "split" and self._split_supported(d) else "float32"
 
-    def _attention(self, d, qkv, att, form):
-        if form == "split":
-            L.check(L.lib().pnpp_attention_infer(qkv.data_ptr(), d.B, d.N, d.n_valid, d.H, d.E // d.H, att.data_ptr(), ops._stream()))
+    def _attention(self, d, qkv, att, form, lengths=None):
+        lib, hd = L.lib(), d.E // d.H
+        if lengths is None:
+            if form == "split":
+                L.check(lib.pnpp_attention_infer(qkv.data_ptr(), d.B, d.N, d.n_valid, d.H, hd, att.data_ptr(), ops._stream()))
+            else:
+                L.check(lib.pnpp_attention_fwd(qkv.data_ptr(), d.B, d.N, d.n_valid, d.H, hd, None, 0.0, att.data_ptr(), None, ops._stream()))
+        elif form == "split":
+            L.check(lib.pnpp_attention_infer_ragged(qkv.data_ptr(), d.B, d.N, d.n_valid, lengths.data_ptr(), d.H, hd, att.data_ptr(), ops._stream()))
         else:
-            L.check(L.lib().pnpp_attention_fwd(qkv.data_ptr(), d.B, d.N, d.n_valid, d.H, d.E // d.H, None, 0.0, att.data_ptr(), None, ops._stream()))
+            L.check(lib.pnpp_attention_fwd_ragged(qkv.data_ptr(), d.B, d.N, d.n_valid, lengths.data_ptr(), d.H, hd, None, 0.0, att.data_ptr(), None,
+                                                  ops._stream()))
         self.last_attention = form
 
-    def _pool(self, d, part, w, b):
+    def _pool(self, d, part, w, b, lengths=None):
         out = torch.empty(d.B, w.shape[0], device=self.device, dtype=torch.float32)
-        L.check(L.lib().pnpp_pt_infer_pool(C.byref(d), part.data_ptr(), w.data_ptr(), b.data_ptr(), w.shape[0], out.data_ptr(), ops._stream()))
+        if lengths is None:
+            L.check(L.lib().pnpp_pt_infer_pool(C.byref(d), part.data_ptr(), w.data_ptr(), b.data_ptr(), w.shape[0], out.data_ptr(), ops._stream()))
+        else:
+            L.check(L.lib().pnpp_pt_infer_pool_ragged(C.byref(d), lengths.data_ptr(), part.data_ptr(), w.data_ptr(), b.data_ptr(), w.shape[0],
+                                                      out.data_ptr(), ops._stream()))
         return out
 
     @torch.no_grad()
-    def __call__(self, xyz: torch.Tensor) -> torch.Tensor:
+    def __call__(self, xyz: torch.Tensor, lengths=None) -> torch.Tensor:
         ops._need_gpu(xyz, "xyz")
         with torch.cuda.device(self.device):
             xyz, d, B, n_pts, N = self._sizes(xyz.detach())
+            from . import transformer
+            if lengths is not None:
+                lengths = transformer.ragged_lengths(lengths, B, n_pts, xyz.device)
             self.last_plan = {s: "fused" if d is not None else "eval-path" for s in self.stages}
             if d is None:
-                from . import transformer
-                return transformer.point_transformer_forward(self._snap, xyz)
+                return transformer.point_transformer_forward(self._snap, xyz, lengths)
             lib, st = L.lib(), ops._stream()
             blobs = [b.data_ptr() for b in self._blobs] + [None]
             x, qkv, att, part = self._buffers(d)
             form = self._attention_form(d)
-            L.check(lib.pnpp_pt_infer_head(C.byref(d), xyz.data_ptr(), blobs[0], x[0].data_ptr(), qkv.data_ptr(), st))
+            if lengths is None:
+                L.check(lib.pnpp_pt_infer_head(C.byref(d), xyz.data_ptr(), blobs[0], x[0].data_ptr(), qkv.data_ptr(), st))
+            else:
+                L.check(lib.pnpp_pt_infer_head_ragged(C.byref(d), lengths.data_ptr(), xyz.data_ptr(), blobs[0], x[0].data_ptr(), qkv.data_ptr(), st))
             for l in range(self.depth):
-                self._attention(d, qkv, att, form)
-                L.check(lib.pnpp_pt_infer_tail(C.byref(d), l, x[l & 1].data_ptr(), att.data_ptr(), blobs[l], blobs[l + 1], x[(l + 1) & 1].data_ptr(),
-                                               qkv.data_ptr(), part.data_ptr(), st))
+                self._attention(d, qkv, att, form, lengths)
+                args = (l, x[l & 1].data_ptr(), att.data_ptr(), blobs[l], blobs[l + 1], x[(l + 1) & 1].data_ptr(), qkv.data_ptr(), part.data_ptr(), st)
+                if lengths is None:
+                    L.check(lib.pnpp_pt_infer_tail(C.byref(d), *args))
+                else:
+                    L.check(lib.pnpp_pt_infer_tail_ragged(C.byref(d), lengths.data_ptr(), *args))
             fc = self._snap.fc_out
-            return self._pool(d, part, fc.weight, fc.bias)
+            return self._pool(d, part, fc.weight, fc.bias, lengths)
 
     # ---- single stages (parity tests, tools) -------------------------------------------------------------------------------
     @torch.no_grad()

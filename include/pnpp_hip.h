@@ -703,6 +703,41 @@ int pnpp_attention_split_bwd(const float *qkv, const float *out, const float *d_
 /* 1: the two entries above take the shape.  0: they do not, pnpp_last_error() names the field */
 int pnpp_attention_split_supported(int B, int N, int n_valid, int H, int head_dim);
 
+/* Ragged batches of the point transformer (additive to ABI 5): the padded layout stays -- x (B, N rows, ...) -- and `lengths` (B) int32
+ * in device memory says how many of cloud b's rows are points: rows 0 .. lengths[b] - 1; the rest of its rows are padding.  Each entry
+ * is its namesake with that tensor added, runs the same kernels through the same launch code (the namesake is the call with
+ * lengths == NULL) and obeys the same size rules; a null `lengths` is PNPP_ERR_ARG, and every argument is checked before anything is
+ * launched.  Inside the kernels a cloud's length is min(max(lengths[b], 1), n_valid): no value in the tensor can cause an access
+ * outside the rows the uniform call touches, and the host never reads it (no synchronisation; a captured graph stays valid while the
+ * lengths change).  Per cloud b the results are those of the namesake on that cloud alone with n_valid = lengths[b], bit for bit; in
+ * addition the rows >= lengths[b] of out and dqkv come back as exact zeros and lse is 0 there, and a 128-row workgroup that lies wholly
+ * beyond its cloud does no attention work.  What the padding rows of qkv hold must be finite, as for the namesakes.
+ *   pnpp_mean_points_ragged      y[b] = sum_{n < len_b} x[b][n] / len_b, x (B, N, E) read in place at row pitch N
+ *   pnpp_mean_points_bwd_ragged  dx[b][n] = dy[b] / len_b for n < len_b, an exact 0 otherwise
+ *   pnpp_pt_infer_*_ragged       head: xyz (B, n_valid, in_dim), rows >= len_b are taken as zero points whatever they hold (NaN included);
+ *                                tail: the last layer pools rows < len_b only; pool: divides by len_b.  Every row of x_next and qkv_next is
+ *                                written on every call, so no stale value of a reused buffer reaches a later kernel. */
+int pnpp_attention_fwd_ragged(const float *qkv, int B, int N, int n_valid, const int32_t *lengths, int H, int head_dim, const uint32_t *mask,
+                              float p, float *out, float *lse, void *stream);
+int pnpp_attention_bwd_ragged(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N, int n_valid,
+                              const int32_t *lengths, int H, int head_dim, const uint32_t *mask, const uint32_t *maskT, float p, float *dqkv,
+                              float *dsum, void *stream);
+int pnpp_attention_split_fwd_ragged(const float *qkv, int B, int N, int n_valid, const int32_t *lengths, int H, int head_dim,
+                                    const uint32_t *mask, float p, float *out, float *lse, void *stream);
+int pnpp_attention_split_bwd_ragged(const float *qkv, const float *out, const float *d_out, const float *lse, int B, int N, int n_valid,
+                                    const int32_t *lengths, int H, int head_dim, const uint32_t *mask, const uint32_t *maskT, float p,
+                                    float *dqkv, float *dsum, void *stream);
+int pnpp_attention_infer_ragged(const float *qkv, int B, int N, int n_valid, const int32_t *lengths, int H, int head_dim, float *out,
+                                void *stream);
+int pnpp_mean_points_ragged(const float *x, int B, int N, const int32_t *lengths, int E, float *y, void *stream);
+int pnpp_mean_points_bwd_ragged(const float *dy, int B, int N, const int32_t *lengths, int E, float *dx, void *stream);
+int pnpp_pt_infer_head_ragged(const pnpp_pt_infer_desc *d, const int32_t *lengths, const float *xyz, const void *weights0, float *x0,
+                              float *qkv0, void *stream);
+int pnpp_pt_infer_tail_ragged(const pnpp_pt_infer_desc *d, const int32_t *lengths, int layer, const float *x, const float *o,
+                              const void *weights, const void *weights_next, float *x_next, float *qkv_next, void *scratch, void *stream);
+int pnpp_pt_infer_pool_ragged(const pnpp_pt_infer_desc *d, const int32_t *lengths, const void *scratch, const float *fc_w, const float *fc_b,
+                              int n_out, float *out, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Step glue on one flat parameter / gradient buffer
  * (train_single_peak_vonMises_KL.py:80,85; train_multi_peaks_vonMises_KL.py:221,235-236)

@@ -6,7 +6,12 @@ in bench.py's format (tools/benchline.py: `roofline` for its costliest kernel) p
 --attention float32|split chooses the form of the training attention (PointTransformer.set_attention).  --attention both runs the two
 forms alternately in one process, in windows (as tools/bench_pt_inference.py), and prints one JSON line with, per form: ms per step (median
 of the windows), the spread of the windows, the three attention kernels' per-launch times and TFLOP/s from one profiled step, and final_loss;
---out appends that line to a file (profiles/pt_attention_training.json holds the four lines of 8 x 4096 and 32 x 1024 at dropout 0 and 0.1)."""
+--out appends that line to a file (profiles/pt_attention_training.json holds the four lines of 8 x 4096 and 32 x 1024 at dropout 0 and 0.1).
+
+--lengths times the step on a RAGGED batch (seeded per-cloud lengths, uniform on [N/4, N], model(xyz, lengths)) against the status quo for
+the same clouds (every cloud resampled to N rows with replacement, no lengths), at 8 x 4096 and 32 x 1024 in the form --attention names,
+the two paths alternately in the same windows; one JSON line per shape (tools/bench_pt_inference.py says what the fields are), appended
+to --out (profiles/pt_ragged.json)."""
 import argparse
 import json
 import os
@@ -46,8 +51,14 @@ def main():
                     help="the form of the training attention (PointTransformer.set_attention); both: the two forms alternately, in windows")
     ap.add_argument("--windows", type=int, default=5, help="--attention both: windows per form")
     ap.add_argument("--window", type=float, default=0.5, help="--attention both: seconds of device time per window")
-    ap.add_argument("--out", default=None, help="--attention both: also append the JSON line to this file")
+    ap.add_argument("--out", default=None, help="--attention both / --lengths: also append the JSON line to this file")
+    ap.add_argument("--lengths", action="store_true",
+                    help="a ragged batch (seeded lengths, uniform on [N/4, N]) against every cloud resampled to N rows, at 8 x 4096 and 32 x 1024")
     a = ap.parse_args()
+    if a.lengths:
+        for B, N in ((8, 4096), (32, 1024)):
+            ragged(a, B, N)
+        return
     from models.point_transformer import PointTransformer
     from pnpp_hip import _lib, ops, optim
     import benchline
@@ -96,6 +107,46 @@ def main():
     print(json.dumps(benchline.line(f"configs[4]: models/point_transformer.py N={a.points} batch={a.batch}/GPU, fwd+MSE+bwd+Adam, "
                                     f"dropout p={a.dropout}, attention={a.attention}", a.batch, dt, a.steps, a.warmup, rows, 1, layers=L,
                                     final_loss=float(loss.detach()), top_kernels=table)))
+
+
+def ragged(a, B, N):
+    """One training step on a ragged batch against the same clouds resampled to N rows: one model and optimiser each from the same seed,
+    timed alternately in windows."""
+    from models.point_transformer import PointTransformer
+    from pnpp_hip import ops, optim
+    from bench_pt_inference import alternate, ragged_batch, ragged_record
+    form = "float32" if a.attention == "both" else a.attention
+    x, lengths, full = ragged_batch(B, N)
+    dev_lengths = lengths.to(torch.int32).cuda()
+    tgt = torch.randn(B, 3, generator=torch.Generator().manual_seed(7)).cuda()
+    loss = {}
+
+    def make(name, xyz, lens):
+        torch.manual_seed(42)
+        model = PointTransformer().cuda().train().set_dropout(a.dropout).set_attention(form)
+        opt = optim.FlatAdam(model.parameters(), lr=1e-3)
+
+        def step():
+            opt.zero_grad()
+            loss[name] = ops.mse_loss(model(xyz, lens), tgt)
+            loss[name].backward()
+            opt.step()
+        return step
+
+    runs = {"ragged": make("ragged", x, dev_lengths), "resampled": make("resampled", full, None)}
+    for _ in range(a.warmup):
+        for step in runs.values():
+            step()
+    torch.cuda.synchronize()
+    res = alternate(runs, a.windows, a.window, 2)
+    rec = {"workload": "models/point_transformer.py fwd+MSE+bwd+Adam, ragged batch against every cloud resampled to N rows", "B": B, "N": N,
+           "dropout": a.dropout, "attention": form, "device": torch.cuda.get_device_name(0), "windows": a.windows, "window_s": a.window,
+           "final_loss": {k: float(v.detach()) for k, v in loss.items()}}
+    line = json.dumps(ragged_record(rec, res, lengths, N))
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
 
 
 def both(a, make):

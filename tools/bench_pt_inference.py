@@ -17,7 +17,14 @@ each path's min / max, library launches per forward, the Predictor's algorithmic
 shapes), the max-abs difference of the paths' outputs, `faster`: the acceptance condition median(eval) - median(predictor) >
 spread(eval) + spread(predictor), `attention_speedup` / `attention_faster`: float32 over split and the same condition between the two attention forms, and
 `attention_err_split` / `attention_err_float32`: max |attend(qkv_0) - float64| over cloud 0, float64 softmax attention on the float32
-qkv of layer 0."""
+qkv of layer 0.
+
+    python tools/bench_pt_inference.py --lengths --out profiles/pt_ragged.json   # appends one line per shape
+
+--lengths times a RAGGED batch -- seeded per-cloud lengths, uniform on [N/4, N], Predictor(model)(xyz, lengths) -- against the status quo
+for the same clouds: every cloud resampled to N rows with replacement (what dataloader_common.sample_pts does for a short cloud) and run
+without lengths.  The two paths alternate in one process, in the same windows.  `ragged_not_slower` is the condition that follows from
+the code (the ragged batch does a subset of the full batch's work): median(ragged) - median(resampled) <= spread(ragged) + spread(resampled)."""
 import argparse
 import datetime
 import json
@@ -55,6 +62,55 @@ def make():
 
 def cloud(B, N):
     return torch.randn(B, N, 3, generator=torch.Generator().manual_seed(1234)).cuda()
+
+
+def ragged_batch(B, N, seed=2048):
+    """(xyz (B, N, 3) whose cloud b is its first lengths[b] rows, lengths (B,) int64 on the host, seeded and uniform on [N/4, N], and the
+    status quo for the same clouds: every cloud resampled to N rows with replacement), all but the lengths on the GPU"""
+    g = torch.Generator().manual_seed(seed)
+    lengths = torch.randint(N // 4, N + 1, (B,), generator=g)
+    x = torch.randn(B, N, 3, generator=torch.Generator().manual_seed(1234))
+    full = torch.stack([x[b, torch.randint(0, int(n), (N,), generator=g)] for b, n in enumerate(lengths)])
+    return x.cuda(), lengths, full.cuda()
+
+
+def alternate(runs, windows, seconds, reps0):
+    """the paths timed alternately in windows: {path: {"ms", "ms_min", "ms_max", "spread_ms"}} (median, extremes and spread of the windows)"""
+    t, reps = {k: [] for k in runs}, {k: reps0 for k in runs}
+    for _ in range(windows):   # alternately: drift of the clocks hits every path alike
+        for k, fn in runs.items():
+            ms, reps[k] = window(fn, seconds, reps[k])
+            t[k].append(ms)
+    return {k: {"ms": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4), "spread_ms": round(max(v) - min(v), 4)}
+            for k, v in t.items()}
+
+
+def ragged_record(rec, res, lengths, N):
+    """the fields both --lengths tools report"""
+    rec.update({"lengths": [int(n) for n in lengths], "mean_length_over_N": round(float(lengths.double().mean()) / N, 4), **res})
+    rec["ragged_over_resampled"] = round(res["ragged"]["ms"] / res["resampled"]["ms"], 4)
+    rec["ragged_not_slower"] = bool(res["ragged"]["ms"] - res["resampled"]["ms"] <= res["ragged"]["spread_ms"] + res["resampled"]["spread_ms"])
+    return rec
+
+
+def ragged_case(B, N, windows, seconds):
+    from pnpp_hip import Predictor
+    model = make()
+    pred = Predictor(model)
+    x, lengths, full = ragged_batch(B, N)
+    dev_lengths = lengths.to(torch.int32).cuda()   # on the device already: used as it is, no synchronisation per call
+    runs = {"ragged": lambda: pred(x, dev_lengths), "resampled": lambda: pred(full)}
+    alone = torch.cat([pred(x[b:b + 1, :int(n)].contiguous()) for b, n in enumerate(lengths)])
+    diff = float((runs["ragged"]() - alone).abs().max())
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    res = alternate(runs, windows, seconds, 4)
+    rec = {"workload": "Predictor(PointTransformer()) forward, ragged batch against every cloud resampled to N rows", "B": B, "N": N,
+           "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0), "windows": windows, "window_s": seconds,
+           "attention": pred.last_attention, "plan": pred.last_plan, "max_abs_diff_to_each_cloud_alone": diff}
+    return ragged_record(rec, res, lengths, N)
 
 
 def attention_errors(preds, x):
@@ -120,8 +176,18 @@ def main():
     ap.add_argument("--window", type=float, default=0.5, help="seconds of device time per window")
     ap.add_argument("--out", default=None, help="also write the JSON lines to this file (overwritten)")
     ap.add_argument("--trace-only", type=int, default=0, help="run this many forwards of each path at 8 x 4096 and exit")
+    ap.add_argument("--lengths", action="store_true",
+                    help="a ragged batch (seeded lengths, uniform on [N/4, N]) against every cloud resampled to N rows; --out is appended to")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_pt_inference needs an AMD GPU"
+    if args.lengths:
+        for B, N in ((8, 4096), (32, 1024)):
+            line = json.dumps(ragged_case(B, N, args.windows, args.window))
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+        return
     if args.trace_only:
         from pnpp_hip import Predictor
         model = make()
