@@ -121,6 +121,7 @@ struct KnnJob {
     double *mom;               // [B * nblocks][KNN_MOM_PITCH] or nullptr
     int qpw;                   // queries per wave: 1, or 2 on a cloud of one tile (the tile is then staged once for eight queries)
     int nblocks;               // workgroups per cloud of this job
+    const int32_t *lengths;    // ragged batch (RAGGED bodies only): cloud b's candidates are its first min(max(lengths[b], 1), N) rows
 };
 
 struct alignas(16) KnnLds {   // one copy per workgroup, shared by the two instantiations of the body a pair kernel contains
@@ -129,7 +130,10 @@ struct alignas(16) KnnLds {   // one copy per workgroup, shared by the two insta
     unsigned long long pool[4][KNN_POOL];
 };
 
-template <bool GATHER, int TILE, bool MOM>
+// RAGGED: N below is the cloud's own extent Nv (one scalar load per workgroup); the host still sized TILE, qpw and the grid from the
+// padded J.N, so Nv <= J.N tiles are walked, `cur` flips once per tile actually walked, and a list asked for more neighbours than
+// the cloud has points (k > Nv, which the host refuses where it sees the lengths) repeats slot 0 in the slots >= Nv.
+template <bool GATHER, int TILE, bool MOM, bool RAGGED = false>
 __device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const int b, KnnLds &L) {
     constexpr int CPL = TILE / 64;              // candidates per lane per tile
     constexpr int SPT = (TILE + 255) / 256;     // staged points per thread per tile
@@ -139,7 +143,9 @@ __device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const in
     const int32_t *__restrict__ gather = GATHER ? J.gather + (size_t)b * J.N : nullptr;
     int32_t *__restrict__ idx = J.idx;
     float *__restrict__ out_a = J.out_a, *__restrict__ out_b = J.out_b;
-    const int S = J.S, N = J.N, k = J.k;
+    const int S = J.S, k = J.k;
+    int N = J.N;
+    if constexpr (RAGGED) N = min(max(J.lengths[b], 1), N);   // wave-uniform: b is the workgroup's cloud
     float(&sx)[KNN_TILE] = L.sx, (&sy)[KNN_TILE] = L.sy, (&sz)[KNN_TILE] = L.sz, (&sn)[KNN_TILE] = L.sn;
     unsigned long long(&best)[4][2][KNN_KMAX] = L.best;
     unsigned long long(&pool)[4][KNN_POOL] = L.pool;
@@ -266,7 +272,7 @@ __device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const in
         }
         if (active) {
             int32_t *o = idx + ((size_t)b * S + q) * k;
-            for (int j = lane; j < k; j += 64) o[j] = (int32_t)(unsigned)(best[wave][cur][j] & 0xffffffffu);
+            for (int j = lane; j < k; j += 64) o[j] = (int32_t)(unsigned)(best[wave][cur][RAGGED && j >= N ? 0 : j] & 0xffffffffu);
         }
     }
     if constexpr (MOM) {
@@ -282,7 +288,7 @@ __device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const in
                 const float ax = a[0], ay = a[1], az = a[2];
                 const unsigned long long *list = best[wave][(pass ^ ntiles) & 1];
                 for (int j = lane; j < k; j += 64) {
-                    const unsigned n = (unsigned)(list[j] & 0xffffffffu);
+                    const unsigned n = (unsigned)(list[RAGGED && j >= N ? 0 : j] & 0xffffffffu);
                     float nx, ny, nz;
                     if (N <= TILE) nx = sx[n], ny = sy[n], nz = sz[n];   // the one tile is still staged
                     else nx = cloud[(size_t)n * 3], ny = cloud[(size_t)n * 3 + 1], nz = cloud[(size_t)n * 3 + 2];
@@ -312,9 +318,10 @@ __device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const in
     }
 }
 
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) knn_kernel(const KnnJob J) {
     __shared__ KnnLds L;
-    knn_body<false, KNN_TILE, false>(J, blockIdx.x, blockIdx.y, L);
+    knn_body<false, KNN_TILE, false, RAGGED>(J, blockIdx.x, blockIdx.y, L);
 }
 
 // The neighbour searches of two stacked levels in ONE launch (they are independent once both levels' centre indices are drawn:
@@ -322,11 +329,12 @@ __global__ void __launch_bounds__(256) knn_kernel(const KnnJob J) {
 // 5 workgroups per CU (<= 96 registers): 32 clouds x (32 + 8) workgroups = 1,280 are then all resident at once on 256 CUs -- at 4 per
 // CU the last 256 start only when a slot frees up and the launch takes a round and a half (measured: 21.1 us against 12.6 + 7.0 for
 // the two separate launches).  The short level-2 workgroups come first.  TILE2: level 2's tile (KNN_TILE_SMALL when its cloud fits).
-template <int TILE2>
+// RAGGED: level 1 reads its cloud's length; level 2 searches level 1's centres, which are uniform.
+template <int TILE2, bool RAGGED>
 __global__ void __launch_bounds__(256, 5) knn_pair_kernel(const KnnJob J1, const KnnJob J2, int nb2) {
     __shared__ KnnLds L;
     if ((int)blockIdx.x < nb2) knn_body<true, TILE2, false>(J2, blockIdx.x, blockIdx.y, L);
-    else knn_body<false, KNN_TILE, true>(J1, blockIdx.x - nb2, blockIdx.y, L);
+    else knn_body<false, KNN_TILE, true, RAGGED>(J1, blockIdx.x - nb2, blockIdx.y, L);
 }
 
 // Wave-wide maximum of a 64-bit key, result in every lane.  Six dependent ds_bpermute round trips (what __shfl_xor compiles
@@ -368,9 +376,12 @@ __device__ __forceinline__ unsigned long long wave_max_u64_dpp(unsigned long lon
 //   * ties: key = (distance bits << 32) | ~index, i.e. the FIRST maximum, as torch.max(distance, -1)[1] (line 28).
 // Distances are the reference's exact float32 sequence ((dx^2 + dy^2) + dz^2, no FMA) -> indices are bit-exact.
 // ---------------------------------------------------------------------------------------------
-template <int T, int PPT>
-__global__ void __launch_bounds__(T) fps_kernel(const float *__restrict__ xyz, int N, int npoint,
-                                                const int32_t *__restrict__ start, int32_t *__restrict__ out, int ntail) {
+// RAGGED: register and tail slots at or beyond the cloud's own extent Nv = min(max(lengths[b], 1), N) are slots past the cloud
+// (distance -1, coordinates of row Nv - 1); start[b] < Nv is the caller's to keep.  T / PPT / ntail come from the padded N.
+template <int T, int PPT, bool RAGGED>
+__global__ void __launch_bounds__(T) fps_kernel(const float *__restrict__ xyz, const int Npad, int npoint,
+                                                const int32_t *__restrict__ start, int32_t *__restrict__ out, int ntail,
+                                                const int32_t *__restrict__ lengths) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NW = T / 64;
     // one LDS object (a second __shared__ array beside a dynamic one can cost a vmcnt(0) per read, guide 5.4 item 4a):
@@ -380,7 +391,9 @@ __global__ void __launch_bounds__(T) fps_kernel(const float *__restrict__ xyz, i
     float *sx = wxyz + 2 * NW * 4, *sy = sx + ntail, *sz = sy + ntail, *sd = sz + ntail;
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *cloud = xyz + (size_t)b * N * 3;
+    const float *cloud = xyz + (size_t)b * Npad * 3;
+    int N = Npad;
+    if constexpr (RAGGED) N = min(max(lengths[b], 1), Npad);
     float px[PPT], py[PPT], pz[PPT], pd[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
@@ -389,8 +402,8 @@ __global__ void __launch_bounds__(T) fps_kernel(const float *__restrict__ xyz, i
         pd[j] = p < N ? 1e10f : -1.f;   // a slot past the cloud: min(d, -1) = -1 never beats a real (non-negative) distance
     }
     for (int q = tid; q < ntail; q += T) {
-        const int p = T * PPT + q;
-        sx[q] = cloud[p * 3 + 0], sy[q] = cloud[p * 3 + 1], sz[q] = cloud[p * 3 + 2], sd[q] = 1e10f;
+        const int p = T * PPT + q, pc = RAGGED && p >= N ? N - 1 : p;
+        sx[q] = cloud[pc * 3 + 0], sy[q] = cloud[pc * 3 + 1], sz[q] = cloud[pc * 3 + 2], sd[q] = RAGGED && p >= N ? -1.f : 1e10f;
     }
     int far = start[b];
     float cx = cloud[far * 3 + 0], cy = cloud[far * 3 + 1], cz = cloud[far * 3 + 2];
@@ -447,8 +460,11 @@ __global__ void __launch_bounds__(T) fps_kernel(const float *__restrict__ xyz, i
 // radius ball query (PointNet++Demo.py:49-70): one wavefront per centre, ascending index scan,
 // ballot + prefix popcount compaction, early exit once nsample hits were written.
 // ---------------------------------------------------------------------------------------------
+// RAGGED: the scan covers the cloud's own rows < Nv = min(max(lengths[b], 1), N), and a centre without a member is filled with Nv.
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) ball_query_kernel(const float *__restrict__ new_xyz, const float *__restrict__ xyz,
-                                                         int S, int N, float r2, int nsample, int32_t *__restrict__ idx) {
+                                                         int S, const int Npad, float r2, int nsample, int32_t *__restrict__ idx,
+                                                         const int32_t *__restrict__ lengths) {
     __shared__ float sx[KNN_TILE], sy[KNN_TILE], sz[KNN_TILE];
     const int b = blockIdx.y;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -461,8 +477,10 @@ __global__ void __launch_bounds__(256) ball_query_kernel(const float *__restrict
         ax = a[0], ay = a[1], az = a[2];
         o = idx + ((size_t)b * S + q) * nsample;
     }
+    int N = Npad;
+    if constexpr (RAGGED) N = min(max(lengths[b], 1), Npad);
     int cnt = 0, first = N;  // wave-uniform
-    const float *cloud = xyz + (size_t)b * N * 3;
+    const float *cloud = xyz + (size_t)b * Npad * 3;
     for (int t0 = 0; t0 < N; t0 += KNN_TILE) {
         __syncthreads();
         const int tc = min(KNN_TILE, N - t0);
@@ -500,13 +518,15 @@ __global__ void __launch_bounds__(256) ball_query_kernel(const float *__restrict
 // out[rank] = n for rank < npoint.  Fully deterministic (a pure function of seed, stream id and cloud).
 // ---------------------------------------------------------------------------------------------
 // (philox_key and the sampling body: sampler_device.h)
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) sample_random_kernel(unsigned seed_lo, unsigned seed_hi, unsigned str_lo,
                                                             unsigned str_hi, unsigned long long *__restrict__ str_dev,
                                                             int N, int npoint, int32_t *__restrict__ out, int B1, int N2,
-                                                            int npoint2, int32_t *__restrict__ out2) {
+                                                            int npoint2, int32_t *__restrict__ out2, const int32_t *__restrict__ lengths) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long cand[];
     __shared__ int nc_s;
-    sample_random_body(seed_lo, seed_hi, str_lo, str_hi, str_dev, N, npoint, out, B1, N2, npoint2, out2, blockIdx.x, gridDim.x, cand, nc_s);
+    sample_random_body<RAGGED>(seed_lo, seed_hi, str_lo, str_hi, str_dev, N, npoint, out, B1, N2, npoint2, out2, blockIdx.x, gridDim.x, cand,
+                               nc_s, lengths);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -690,30 +710,34 @@ __global__ void __launch_bounds__(256) gather_centres_kernel(const float *__rest
 // ---------------------------------------------------------------------------------------------
 // host launchers (internal C++ API, used by the C ABI and by the set-abstraction orchestrator)
 // ---------------------------------------------------------------------------------------------
-int launch_knn(const float *new_xyz, const float *xyz, int B, int S, int N, int k, int32_t *idx, hipStream_t st) {
+// lengths != nullptr (here and in the launchers below): a ragged batch, cloud b's candidates are its first lengths[b] rows; the size
+// checks stay those of the padded N (the device cannot refuse k > lengths[b]: see knn_body)
+int launch_knn(const float *new_xyz, const float *xyz, int B, int S, int N, int k, int32_t *idx, hipStream_t st, const int32_t *lengths) {
     PNPP_REQUIRE(new_xyz && xyz && idx, PNPP_ERR_ARG, "knn: null pointer");
     PNPP_REQUIRE(B > 0 && S > 0 && N > 0 && k > 0, PNPP_ERR_ARG, "knn: non-positive size (B=%d S=%d N=%d k=%d)", B, S, N, k);
     PNPP_REQUIRE(k <= N, PNPP_ERR_RANGE, "selected index k out of range (k=%d > N=%d)", k, N);
     PNPP_REQUIRE(k <= KNN_KMAX, PNPP_ERR_ARG, "knn: nsample=%d exceeds the supported maximum %d", k, KNN_KMAX);
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "knn: batch %d exceeds grid limit", B);
-    ProfScope ps(st, "knn_kernel B=%d S=%d N=%d k=%d", B, S, N, k);
-    const KnnJob J{new_xyz, xyz, nullptr, N, S, N, k, idx, nullptr, nullptr, nullptr, nullptr, 1, cdiv(S, 4)};
-    hipLaunchKernelGGL(knn_kernel, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
+    ProfScope ps(st, "knn_kernel B=%d S=%d N=%d k=%d%s", B, S, N, k, lengths ? " ragged" : "");
+    const KnnJob J{new_xyz, xyz, nullptr, N, S, N, k, idx, nullptr, nullptr, nullptr, nullptr, 1, cdiv(S, 4), lengths};
+    if (lengths) hipLaunchKernelGGL(knn_kernel<true>, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
+    else hipLaunchKernelGGL(knn_kernel<false>, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
     PNPP_CHECK_LAUNCH("knn");
     return PNPP_OK;
 }
 
 // kNN whose queries are gathered centres: also writes the centre coordinates (out_a, optional out_b)
 int launch_knn_centres(const float *xyz, const int32_t *centre, int B, int S, int N, int k, int32_t *idx, float *out_a,
-                       float *out_b, hipStream_t st) {
+                       float *out_b, hipStream_t st, const int32_t *lengths) {
     PNPP_REQUIRE(xyz && centre && idx && out_a, PNPP_ERR_ARG, "knn: null pointer");
     PNPP_REQUIRE(B > 0 && S > 0 && N > 0 && k > 0, PNPP_ERR_ARG, "knn: non-positive size (B=%d S=%d N=%d k=%d)", B, S, N, k);
     PNPP_REQUIRE(k <= N, PNPP_ERR_RANGE, "selected index k out of range (k=%d > N=%d)", k, N);
     PNPP_REQUIRE(k <= KNN_KMAX, PNPP_ERR_ARG, "knn: nsample=%d exceeds the supported maximum %d", k, KNN_KMAX);
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "knn: batch %d exceeds grid limit", B);
-    ProfScope ps(st, "knn_kernel B=%d S=%d N=%d k=%d", B, S, N, k);
-    const KnnJob J{nullptr, xyz, nullptr, N, S, N, k, idx, centre, out_a, out_b, nullptr, 1, cdiv(S, 4)};
-    hipLaunchKernelGGL(knn_kernel, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
+    ProfScope ps(st, "knn_kernel B=%d S=%d N=%d k=%d%s", B, S, N, k, lengths ? " ragged" : "");
+    const KnnJob J{nullptr, xyz, nullptr, N, S, N, k, idx, centre, out_a, out_b, nullptr, 1, cdiv(S, 4), lengths};
+    if (lengths) hipLaunchKernelGGL(knn_kernel<true>, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
+    else hipLaunchKernelGGL(knn_kernel<false>, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
     PNPP_CHECK_LAUNCH("knn");
     return PNPP_OK;
 }
@@ -729,7 +753,8 @@ size_t knn_pair_moment_doubles(int B, int S1, int N) { return (size_t)knn_pair_m
 // points; level 2 = S2 of those centres (positions centre2 in 0..S1-1), k2 neighbours among the S1 centres.
 // mom != nullptr: level 1 also writes knn_pair_moment_partials(B, S1, N) moment partials of its relative coordinates.
 int launch_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int S1, int k1, int32_t *idx1, float *a1, float *b1,
-                    const int32_t *centre2, int S2, int k2, int32_t *idx2, float *a2, float *b2, double *mom, hipStream_t st) {
+                    const int32_t *centre2, int S2, int k2, int32_t *idx2, float *a2, float *b2, double *mom, hipStream_t st,
+                    const int32_t *lengths) {
     PNPP_REQUIRE(xyz && centre1 && centre2 && idx1 && idx2 && a1 && a2, PNPP_ERR_ARG, "knn_pair: null pointer");
     PNPP_REQUIRE(B > 0 && N > 0 && S1 > 0 && S2 > 0 && k1 > 0 && k2 > 0, PNPP_ERR_ARG, "knn_pair: non-positive size");
     PNPP_REQUIRE(k1 <= N && k2 <= S1, PNPP_ERR_RANGE, "selected index k out of range (k=%d > N=%d)", k1 <= N ? k2 : k1, k1 <= N ? S1 : N);
@@ -738,13 +763,18 @@ int launch_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int 
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "knn: batch %d exceeds grid limit", B);
     static_assert(KNN_MOM_PITCH == kMomPitch, "moment partial pitch");
     const int qpw = knn_pair_qpw(N), nb1 = cdiv(S1, 4 * qpw), nb2 = cdiv(S2, 4);
-    ProfScope ps(st, "knn_pair_kernel B=%d | S=%d N=%d k=%d | S=%d N=%d k=%d%s", B, S1, N, k1, S2, S1, k2, mom ? " +moments" : "");
-    const KnnJob J1{nullptr, xyz, nullptr, N, S1, N, k1, idx1, centre1, a1, b1, mom, qpw, nb1};
-    const KnnJob J2{nullptr, xyz, centre1, N, S2, S1, k2, idx2, centre2, a2, b2, nullptr, 1, nb2};
-    if (S1 <= KNN_TILE_SMALL)
-        hipLaunchKernelGGL(knn_pair_kernel<KNN_TILE_SMALL>, dim3(nb1 + nb2, B), dim3(256), 0, st, J1, J2, nb2);
-    else
-        hipLaunchKernelGGL(knn_pair_kernel<KNN_TILE>, dim3(nb1 + nb2, B), dim3(256), 0, st, J1, J2, nb2);
+    ProfScope ps(st, "knn_pair_kernel B=%d | S=%d N=%d k=%d | S=%d N=%d k=%d%s%s", B, S1, N, k1, S2, S1, k2, mom ? " +moments" : "",
+                 lengths ? " ragged" : "");
+    const KnnJob J1{nullptr, xyz, nullptr, N, S1, N, k1, idx1, centre1, a1, b1, mom, qpw, nb1, lengths};
+    const KnnJob J2{nullptr, xyz, centre1, N, S2, S1, k2, idx2, centre2, a2, b2, nullptr, 1, nb2, nullptr};
+    const dim3 grid(nb1 + nb2, B);
+    if (S1 <= KNN_TILE_SMALL) {
+        if (lengths) hipLaunchKernelGGL((knn_pair_kernel<KNN_TILE_SMALL, true>), grid, dim3(256), 0, st, J1, J2, nb2);
+        else hipLaunchKernelGGL((knn_pair_kernel<KNN_TILE_SMALL, false>), grid, dim3(256), 0, st, J1, J2, nb2);
+    } else {
+        if (lengths) hipLaunchKernelGGL((knn_pair_kernel<KNN_TILE, true>), grid, dim3(256), 0, st, J1, J2, nb2);
+        else hipLaunchKernelGGL((knn_pair_kernel<KNN_TILE, false>), grid, dim3(256), 0, st, J1, J2, nb2);
+    }
     PNPP_CHECK_LAUNCH("knn_pair");
     return PNPP_OK;
 }
@@ -786,15 +816,29 @@ extern "C" int pnpp_knn(const float *new_xyz, const float *xyz, int B, int S, in
     return launch_knn(new_xyz, xyz, B, S, N, k, idx, as_stream(stream));
 }
 
+extern "C" int pnpp_knn_ragged(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, int k, int32_t *idx,
+                               void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "knn_ragged: null lengths");
+    return launch_knn(new_xyz, xyz, B, S, N, k, idx, as_stream(stream), lengths);
+}
+
 extern "C" int pnpp_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int S1, int k1, int32_t *idx1, float *new_xyz1,
                              const int32_t *centre2, int S2, int k2, int32_t *idx2, float *new_xyz2, double *mom, void *stream) {
     return launch_knn_pair(xyz, B, N, centre1, S1, k1, idx1, new_xyz1, nullptr, centre2, S2, k2, idx2, new_xyz2, nullptr, mom, as_stream(stream));
+}
+extern "C" int pnpp_knn_pair_ragged(const float *xyz, int B, int N, const int32_t *lengths, const int32_t *centre1, int S1, int k1,
+                                    int32_t *idx1, float *new_xyz1, const int32_t *centre2, int S2, int k2, int32_t *idx2,
+                                    float *new_xyz2, double *mom, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "knn_pair_ragged: null lengths");
+    return launch_knn_pair(xyz, B, N, centre1, S1, k1, idx1, new_xyz1, nullptr, centre2, S2, k2, idx2, new_xyz2, nullptr, mom, as_stream(stream),
+                           lengths);
 }
 extern "C" int pnpp_knn_pair_partials(int B, int S1, int N) {
     return (B > 0 && S1 > 0 && N > 0) ? knn_pair_moment_partials(B, S1, N) : 0;
 }
 
-extern "C" int pnpp_fps(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out, void *stream) {
+template <bool RAGGED>
+static int fps_impl(const float *xyz, int B, int N, const int32_t *lengths, int npoint, const int32_t *start, int32_t *out, void *stream) {
     PNPP_REQUIRE(xyz && start && out, PNPP_ERR_ARG, "fps: null pointer");
     PNPP_REQUIRE(B > 0 && N > 0 && npoint > 0, PNPP_ERR_ARG, "fps: non-positive size");
     // npoint > N is legal, as in the reference (PointNet++Demo.py:8-29): once every distance is 0 the first maximum is point 0
@@ -807,36 +851,64 @@ extern "C" int pnpp_fps(const float *xyz, int B, int N, int npoint, const int32_
     auto go = [&](auto kfn, int T) {
         const size_t lds = ((size_t)2 * 2 * (T / 64) + (size_t)2 * (T / 64) * 4 + (size_t)4 * ntail) * sizeof(float);
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        ProfScope ps(st, "fps_kernel<%d> B=%d N=%d npoint=%d", T, B, N, npoint);
-        hipLaunchKernelGGL(kfn, dim3(B), dim3(T), lds, st, xyz, N, npoint, start, out, ntail);
+        ProfScope ps(st, "fps_kernel<%d> B=%d N=%d npoint=%d%s", T, B, N, npoint, RAGGED ? " ragged" : "");
+        hipLaunchKernelGGL(kfn, dim3(B), dim3(T), lds, st, xyz, N, npoint, start, out, ntail, lengths);
     };
-    if (N <= 1024) go(fps_kernel<256, 4>, 256);
-    else if (N <= 2048) go(fps_kernel<256, 8>, 256);
-    else if (N <= 4096) go(fps_kernel<512, 8>, 512);
-    else if (N <= 8192) go(fps_kernel<1024, 8>, 1024);
-    else go(fps_kernel<1024, 16>, 1024);
+    if (N <= 1024) go(fps_kernel<256, 4, RAGGED>, 256);
+    else if (N <= 2048) go(fps_kernel<256, 8, RAGGED>, 256);
+    else if (N <= 4096) go(fps_kernel<512, 8, RAGGED>, 512);
+    else if (N <= 8192) go(fps_kernel<1024, 8, RAGGED>, 1024);
+    else go(fps_kernel<1024, 16, RAGGED>, 1024);
     PNPP_CHECK_LAUNCH("fps");
+    return PNPP_OK;
+}
+
+extern "C" int pnpp_fps(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out, void *stream) {
+    return fps_impl<false>(xyz, B, N, nullptr, npoint, start, out, stream);
+}
+extern "C" int pnpp_fps_ragged(const float *xyz, int B, int N, const int32_t *lengths, int npoint, const int32_t *start, int32_t *out,
+                               void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "fps_ragged: null lengths");
+    return fps_impl<true>(xyz, B, N, lengths, npoint, start, out, stream);
+}
+
+static int ball_query_impl(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, float radius, int nsample,
+                           int32_t *idx, void *stream) {
+    PNPP_REQUIRE(new_xyz && xyz && idx, PNPP_ERR_ARG, "ball_query: null pointer");
+    PNPP_REQUIRE(B > 0 && S > 0 && N > 0 && nsample > 0, PNPP_ERR_ARG, "ball_query: non-positive size");
+    PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "ball_query: batch exceeds grid limit");
+    const float r2 = (float)((double)radius * (double)radius);  // Demo.py:65: python float squared, compared in float32
+    ProfScope ps(as_stream(stream), "ball_query_kernel B=%d S=%d N=%d nsample=%d%s", B, S, N, nsample, lengths ? " ragged" : "");
+    if (lengths)
+        hipLaunchKernelGGL(ball_query_kernel<true>, dim3(cdiv(S, 4), B), dim3(256), 0, as_stream(stream), new_xyz, xyz, S, N, r2, nsample, idx,
+                           lengths);
+    else
+        hipLaunchKernelGGL(ball_query_kernel<false>, dim3(cdiv(S, 4), B), dim3(256), 0, as_stream(stream), new_xyz, xyz, S, N, r2, nsample, idx,
+                           lengths);
+    PNPP_CHECK_LAUNCH("ball_query");
     return PNPP_OK;
 }
 
 extern "C" int pnpp_ball_query(const float *new_xyz, const float *xyz, int B, int S, int N, float radius, int nsample,
                                int32_t *idx, void *stream) {
-    PNPP_REQUIRE(new_xyz && xyz && idx, PNPP_ERR_ARG, "ball_query: null pointer");
-    PNPP_REQUIRE(B > 0 && S > 0 && N > 0 && nsample > 0, PNPP_ERR_ARG, "ball_query: non-positive size");
-    PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "ball_query: batch exceeds grid limit");
-    const float r2 = (float)((double)radius * (double)radius);  // Demo.py:65: python float squared, compared in float32
-    ProfScope ps(as_stream(stream), "ball_query_kernel B=%d S=%d N=%d nsample=%d", B, S, N, nsample);
-    hipLaunchKernelGGL(ball_query_kernel, dim3(cdiv(S, 4), B), dim3(256), 0, as_stream(stream), new_xyz, xyz, S, N, r2,
-                       nsample, idx);
-    PNPP_CHECK_LAUNCH("ball_query");
-    return PNPP_OK;
+    return ball_query_impl(new_xyz, xyz, B, S, N, nullptr, radius, nsample, idx, stream);
+}
+extern "C" int pnpp_ball_query_ragged(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, float radius,
+                                      int nsample, int32_t *idx, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "ball_query_ragged: null lengths");
+    return ball_query_impl(new_xyz, xyz, B, S, N, lengths, radius, nsample, idx, stream);
 }
 
 static int sample_random_impl(uint64_t seed, uint64_t stream_id, uint64_t *stream_id_dev, int B, int N, int npoint,
-                              int32_t *out, void *stream);
+                              int32_t *out, void *stream, const int32_t *lengths = nullptr);
 
 extern "C" int pnpp_sample_random(uint64_t seed, uint64_t stream_id, int B, int N, int npoint, int32_t *out, void *stream) {
     return sample_random_impl(seed, stream_id, nullptr, B, N, npoint, out, stream);
+}
+extern "C" int pnpp_sample_random_ragged(uint64_t seed, uint64_t stream_id, int B, int N, const int32_t *lengths, int npoint, int32_t *out,
+                                         void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "sample_random_ragged: null lengths");
+    return sample_random_impl(seed, stream_id, nullptr, B, N, npoint, out, stream, lengths);
 }
 
 extern "C" int pnpp_subsample_points(uint64_t seed, uint64_t stream_id, const float *bank, const int32_t *lengths,
@@ -872,27 +944,45 @@ extern "C" int pnpp_sample_random_dev(uint64_t seed, uint64_t *stream_id_dev, ui
     PNPP_REQUIRE(stream_id_dev, PNPP_ERR_ARG, "sample_random_dev: null counter pointer");
     return sample_random_impl(seed, offset, stream_id_dev, B, N, npoint, out, stream);
 }
+extern "C" int pnpp_sample_random_dev_ragged(uint64_t seed, uint64_t *stream_id_dev, uint64_t offset, int B, int N, const int32_t *lengths,
+                                             int npoint, int32_t *out, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "sample_random_dev_ragged: null lengths");
+    PNPP_REQUIRE(stream_id_dev, PNPP_ERR_ARG, "sample_random_dev: null counter pointer");
+    return sample_random_impl(seed, offset, stream_id_dev, B, N, npoint, out, stream, lengths);
+}
+
+// one launch of sample_random_kernel, ragged (lengths != nullptr: of the first draw) or not
+static void sample_random_launch(int grid, size_t lds, void *stream, uint64_t seed, uint64_t sid, uint64_t *stream_id_dev, int N1, int npoint1,
+                                 int32_t *out1, int B1, int N2, int npoint2, int32_t *out2, const int32_t *lengths) {
+    unsigned long long *dev = reinterpret_cast<unsigned long long *>(stream_id_dev);
+    const unsigned s0 = (unsigned)seed, s1 = (unsigned)(seed >> 32), i0 = (unsigned)sid, i1 = (unsigned)(sid >> 32);
+    if (lengths) {
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)sample_random_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(sample_random_kernel<true>, dim3(grid), dim3(256), lds, as_stream(stream), s0, s1, i0, i1, dev, N1, npoint1, out1, B1,
+                           N2, npoint2, out2, lengths);
+    } else {
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)sample_random_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(sample_random_kernel<false>, dim3(grid), dim3(256), lds, as_stream(stream), s0, s1, i0, i1, dev, N1, npoint1, out1, B1,
+                           N2, npoint2, out2, lengths);
+    }
+}
 
 static int sample_random_impl(uint64_t seed, uint64_t stream_id, uint64_t *stream_id_dev, int B, int N, int npoint,
-                              int32_t *out, void *stream) {
+                              int32_t *out, void *stream, const int32_t *lengths) {
     PNPP_REQUIRE(out, PNPP_ERR_ARG, "sample_random: null pointer");
     PNPP_REQUIRE(B > 0 && N > 0 && npoint > 0, PNPP_ERR_ARG, "sample_random: non-positive size");
     PNPP_REQUIRE(npoint <= N, PNPP_ERR_RANGE, "sample_random: npoint=%d > N=%d", npoint, N);
     PNPP_REQUIRE((size_t)(N + 1) * 8 <= 128 * 1024, PNPP_ERR_ARG, "sample_random: N=%d too large", N);
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "sample_random: batch exceeds grid limit");
     const size_t lds = (size_t)(N + 1) * sizeof(unsigned long long);
-    if (lds > 48 * 1024)
-        hipFuncSetAttribute((const void *)sample_random_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    ProfScope ps(as_stream(stream), "sample_random_kernel B=%d N=%d npoint=%d", B, N, npoint);
-    hipLaunchKernelGGL(sample_random_kernel, dim3(B), dim3(256), lds, as_stream(stream), (unsigned)seed,
-                       (unsigned)(seed >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32),
-                       reinterpret_cast<unsigned long long *>(stream_id_dev), N, npoint, out, 0, 0, 0, (int32_t *)nullptr);
+    ProfScope ps(as_stream(stream), "sample_random_kernel B=%d N=%d npoint=%d%s", B, N, npoint, lengths ? " ragged" : "");
+    sample_random_launch(B, lds, stream, seed, stream_id, stream_id_dev, N, npoint, out, 0, 0, 0, nullptr, lengths);
     PNPP_CHECK_LAUNCH("sample_random");
     return PNPP_OK;
 }
 
-extern "C" int pnpp_sample_random_dev2(uint64_t seed, uint64_t *stream_id_dev, uint64_t offset, int B, int N1, int npoint1,
-                                       int32_t *out1, int N2, int npoint2, int32_t *out2, void *stream) {
+static int sample_random_dev2_impl(uint64_t seed, uint64_t *stream_id_dev, uint64_t offset, int B, int N1, const int32_t *lengths, int npoint1,
+                                   int32_t *out1, int N2, int npoint2, int32_t *out2, void *stream) {
     PNPP_REQUIRE(stream_id_dev && out1 && out2, PNPP_ERR_ARG, "sample_random_dev2: null pointer");
     PNPP_REQUIRE(B > 0 && N1 > 0 && npoint1 > 0 && N2 > 0 && npoint2 > 0, PNPP_ERR_ARG, "sample_random_dev2: non-positive size");
     PNPP_REQUIRE(npoint1 <= N1 && npoint2 <= N2, PNPP_ERR_RANGE, "sample_random_dev2: npoint exceeds N");
@@ -900,14 +990,21 @@ extern "C" int pnpp_sample_random_dev2(uint64_t seed, uint64_t *stream_id_dev, u
     PNPP_REQUIRE((size_t)(Nmax + 1) * 8 <= 128 * 1024, PNPP_ERR_ARG, "sample_random_dev2: N=%d too large", Nmax);
     PNPP_REQUIRE(2 * B <= 65535, PNPP_ERR_ARG, "sample_random_dev2: batch exceeds grid limit");
     const size_t lds = (size_t)(Nmax + 1) * sizeof(unsigned long long);
-    if (lds > 48 * 1024)
-        hipFuncSetAttribute((const void *)sample_random_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    ProfScope ps(as_stream(stream), "sample_random_kernel B=%d N=%d npoint=%d + N=%d npoint=%d", B, N1, npoint1, N2, npoint2);
-    hipLaunchKernelGGL(sample_random_kernel, dim3(2 * B), dim3(256), lds, as_stream(stream), (unsigned)seed, (unsigned)(seed >> 32),
-                       (unsigned)offset, (unsigned)(offset >> 32), reinterpret_cast<unsigned long long *>(stream_id_dev), N1, npoint1,
-                       out1, B, N2, npoint2, out2);
+    ProfScope ps(as_stream(stream), "sample_random_kernel B=%d N=%d npoint=%d + N=%d npoint=%d%s", B, N1, npoint1, N2, npoint2,
+                 lengths ? " ragged" : "");
+    sample_random_launch(2 * B, lds, stream, seed, offset, stream_id_dev, N1, npoint1, out1, B, N2, npoint2, out2, lengths);
     PNPP_CHECK_LAUNCH("sample_random_dev2");
     return PNPP_OK;
+}
+
+extern "C" int pnpp_sample_random_dev2(uint64_t seed, uint64_t *stream_id_dev, uint64_t offset, int B, int N1, int npoint1,
+                                       int32_t *out1, int N2, int npoint2, int32_t *out2, void *stream) {
+    return sample_random_dev2_impl(seed, stream_id_dev, offset, B, N1, nullptr, npoint1, out1, N2, npoint2, out2, stream);
+}
+extern "C" int pnpp_sample_random_dev2_ragged(uint64_t seed, uint64_t *stream_id_dev, uint64_t offset, int B, int N1, const int32_t *lengths,
+                                              int npoint1, int32_t *out1, int N2, int npoint2, int32_t *out2, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "sample_random_dev2_ragged: null lengths");
+    return sample_random_dev2_impl(seed, stream_id_dev, offset, B, N1, lengths, npoint1, out1, N2, npoint2, out2, stream);
 }
 
 extern "C" int pnpp_index_points(const float *points, const int32_t *idx, int B, int N, int C, int M, float *out, void *stream) {

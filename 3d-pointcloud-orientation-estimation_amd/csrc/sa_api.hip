@@ -560,8 +560,8 @@ extern "C" int pnpp_sa_saved_relu_mask(const pnpp_sa_desc *d, const void *saved,
     }
     return launch_relu_mask(sv.z[layer], sv.scale[layer], sv.shift[layer], (size_t)L.g.M * d->C[layer], d->C[layer], out, as_stream(stream));
 }
-extern "C" int pnpp_sa_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *centre1,
-                                  const int32_t *centre2, void *saved1, float *new_xyz1, void *saved2, float *new_xyz2, void *stream) {
+static int sa_group_pair_impl(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *lengths, const int32_t *centre1,
+                              const int32_t *centre2, void *saved1, float *new_xyz1, void *saved2, float *new_xyz2, void *stream) {
     SaLevel L1, L2;
     PNPP_TRY(sa_level_plan(d1, &L1));
     PNPP_TRY(sa_level_plan(d2, &L2));
@@ -571,7 +571,18 @@ extern "C" int pnpp_sa_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2
     PNPP_REQUIRE(xyz && centre1 && centre2 && saved1 && saved2 && new_xyz1 && new_xyz2, PNPP_ERR_ARG, "sa_group_pair: null pointer");
     const SaSaved s1 = sa_saved_layout(L1, saved1), s2 = sa_saved_layout(L2, saved2);
     return launch_knn_pair(xyz, d1->B, d1->N, centre1, d1->S, d1->K, s1.idx, new_xyz1, s1.new_xyz, centre2, d2->S, d2->K, s2.idx,
-                           new_xyz2, s2.new_xyz, L1.pair_moments ? s1.mom : nullptr, as_stream(stream));
+                           new_xyz2, s2.new_xyz, L1.pair_moments ? s1.mom : nullptr, as_stream(stream), lengths);
+}
+extern "C" int pnpp_sa_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *centre1,
+                                  const int32_t *centre2, void *saved1, float *new_xyz1, void *saved2, float *new_xyz2, void *stream) {
+    return sa_group_pair_impl(d1, d2, xyz, nullptr, centre1, centre2, saved1, new_xyz1, saved2, new_xyz2, stream);
+}
+// ... of a ragged batch: level 1 searches each cloud's first lengths[b] rows (level 2 searches level 1's centres: uniform)
+extern "C" int pnpp_sa_group_pair_ragged(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *lengths,
+                                         const int32_t *centre1, const int32_t *centre2, void *saved1, float *new_xyz1, void *saved2,
+                                         float *new_xyz2, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "sa_group_pair_ragged: null lengths");
+    return sa_group_pair_impl(d1, d2, xyz, lengths, centre1, centre2, saved1, new_xyz1, saved2, new_xyz2, stream);
 }
 
 extern "C" int pnpp_sa_forward(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, void *stream) { return sa_forward_impl(d, a, as_stream(stream)); }

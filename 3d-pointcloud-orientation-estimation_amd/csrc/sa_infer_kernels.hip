@@ -529,15 +529,26 @@ extern "C" int pnpp_sa_infer_fold(const pnpp_sa_desc *d, const pnpp_sa_fwd_args 
     return sa_infer_fold(d, params, weights, as_stream(stream));
 }
 extern "C" int pnpp_sa_infer(const pnpp_sa_desc *d, const pnpp_sa_infer_args *a, void *stream) { return sa_infer(d, a, as_stream(stream)); }
-extern "C" int pnpp_sa_infer_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *centre1,
-                                        const int32_t *centre2, int32_t *idx1, float *new_xyz1, int32_t *idx2, float *new_xyz2, void *stream) {
+static int sa_infer_group_pair_impl(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *lengths,
+                                    const int32_t *centre1, const int32_t *centre2, int32_t *idx1, float *new_xyz1, int32_t *idx2,
+                                    float *new_xyz2, void *stream) {
     PNPP_REQUIRE(d1 && d2, PNPP_ERR_ARG, "sa_infer_group_pair: null descriptor");
     PNPP_REQUIRE(!d1->group_all && !d2->group_all, PNPP_ERR_ARG, "sa_infer_group_pair: both levels must group neighbourhoods");
     PNPP_REQUIRE(d1->B == d2->B && d2->N == d1->S, PNPP_ERR_ARG, "sa_infer_group_pair: level 2 must take level 1's %d centres (got N=%d)", d1->S,
                  d2->N);
     PNPP_REQUIRE(xyz && centre1 && centre2 && idx1 && idx2 && new_xyz1 && new_xyz2, PNPP_ERR_ARG, "sa_infer_group_pair: null pointer");
     return launch_knn_pair(xyz, d1->B, d1->N, centre1, d1->S, d1->K, idx1, new_xyz1, nullptr, centre2, d2->S, d2->K, idx2, new_xyz2, nullptr, nullptr,
-                           as_stream(stream));
+                           as_stream(stream), lengths);
+}
+extern "C" int pnpp_sa_infer_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *centre1,
+                                        const int32_t *centre2, int32_t *idx1, float *new_xyz1, int32_t *idx2, float *new_xyz2, void *stream) {
+    return sa_infer_group_pair_impl(d1, d2, xyz, nullptr, centre1, centre2, idx1, new_xyz1, idx2, new_xyz2, stream);
+}
+extern "C" int pnpp_sa_infer_group_pair_ragged(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *lengths,
+                                               const int32_t *centre1, const int32_t *centre2, int32_t *idx1, float *new_xyz1, int32_t *idx2,
+                                               float *new_xyz2, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "sa_infer_group_pair_ragged: null lengths");
+    return sa_infer_group_pair_impl(d1, d2, xyz, lengths, centre1, centre2, idx1, new_xyz1, idx2, new_xyz2, stream);
 }
 extern "C" int pnpp_fc_infer_fold(int N, int K, const float *w, const float *b, const float *gamma, const float *beta, const float *rm,
                                   const float *rv, float eps, float *w_out, float *b_out, void *stream) {

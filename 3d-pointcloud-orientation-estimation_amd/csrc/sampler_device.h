@@ -29,12 +29,20 @@ __device__ __forceinline__ unsigned philox_key(unsigned c0, unsigned c1, unsigne
 // two consecutive calls' results from one launch, the device counter advances by two.
 // `b` = this workgroup's index among the `nblocks` sampling workgroups of the launch (they may share a launch with other work:
 // vm_fc_head_kl_step_kernel draws the NEXT step's centres beside the single workgroup of the step's tail); cand / nc_s: LDS.
+// RAGGED: the first draw of cloud b ranks its own points n < Nv = min(max(lengths[b], 1), N) -- keys, cut and retry rule are those
+// of the uniform draw at N = Nv, so the result is bit-equal to it; asked for more centres than the cloud has points (which the
+// host refuses where it sees the lengths), rank r >= Nv repeats rank r mod Nv.  The second draw ranks level 1's centres: uniform.
+template <bool RAGGED = false>
 __device__ __forceinline__ void sample_random_body(unsigned seed_lo, unsigned seed_hi, unsigned str_lo, unsigned str_hi,
                                                    unsigned long long *__restrict__ str_dev, int N, int npoint,
                                                    int32_t *__restrict__ out, int B1, int N2, int npoint2, int32_t *__restrict__ out2,
-                                                   int b, const int nblocks, unsigned long long *__restrict__ cand, int &nc_s) {
+                                                   int b, const int nblocks, unsigned long long *__restrict__ cand, int &nc_s,
+                                                   const int32_t *__restrict__ lengths = nullptr) {
     const bool second = B1 > 0 && b >= B1;
     if (second) b -= B1, N = N2, npoint = npoint2, out = out2;
+    if constexpr (RAGGED) {
+        if (!second) N = min(max(lengths[b], 1), N);
+    }
     {   // stream id: (str_hi:str_lo) [+ the device counter: graph replays draw fresh centres] [+ 1 for the second draw]
         unsigned long long sid = (((unsigned long long)str_hi << 32) | str_lo) + (second ? 1ull : 0ull);
         if (str_dev) sid += str_dev[0];
@@ -78,6 +86,9 @@ __device__ __forceinline__ void sample_random_body(unsigned seed_lo, unsigned se
             rank += (o.x < mine) + (o.y < mine);
         }
         if (rank < npoint) out[(size_t)b * npoint + rank] = (int32_t)(unsigned)mine;
+        if constexpr (RAGGED) {   // npoint > Nv: every point is a candidate (the cut is off), ranks wrap around the cloud
+            for (int r = rank + N; r < npoint; r += N) out[(size_t)b * npoint + r] = (int32_t)(unsigned)mine;
+        }
     }
     if (str_dev) {
         // post-increment of the device counter: every workgroup has read str_dev[0] before it takes a ticket, so

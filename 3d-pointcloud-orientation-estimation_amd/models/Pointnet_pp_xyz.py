@@ -14,8 +14,8 @@ class PointNetPPXYZ(BackboneBNHead):
         self.head_x = nn.Linear(256, 3)
         self.head_y = nn.Linear(256, 3)
 
-    def forward(self, x, centres=None, drop_mask=None):
-        feat = self.trunk(x, centres, drop_mask)
+    def forward(self, x, centres=None, drop_mask=None, lengths=None):
+        feat = self.trunk(x, centres, drop_mask, lengths=lengths)
         v1 = ops.l2_normalize(ops.fc_block(feat, self.head_x, training=self.training))
         v2 = ops.l2_normalize(ops.fc_block(feat, self.head_y, training=self.training))
         return v1, v2

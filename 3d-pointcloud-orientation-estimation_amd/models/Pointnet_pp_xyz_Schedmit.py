@@ -14,8 +14,8 @@ class PointNetPPXYZ_Schedmit(BackboneBNHead):
         self.head_y = nn.Linear(256, 3)
         self.head_z = nn.Linear(256, 3)
 
-    def forward(self, x, centres=None, drop_mask=None):
-        feat = self.trunk(x, centres, drop_mask)
+    def forward(self, x, centres=None, drop_mask=None, lengths=None):
+        feat = self.trunk(x, centres, drop_mask, lengths=lengths)
         v2 = ops.l2_normalize(ops.fc_block(feat, self.head_y, training=self.training))
         v3 = ops.l2_normalize(ops.fc_block(feat, self.head_z, training=self.training))
         return v2, v3

@@ -13,5 +13,5 @@ class PointNetPP(BackboneBNHead):
         super().__init__(sampler, grouper)
         self.fc3 = nn.Linear(256, 3)
 
-    def forward(self, x, centres=None, drop_mask=None):
-        return ops.fc_block(self.trunk(x, centres, drop_mask), self.fc3, training=self.training)
+    def forward(self, x, centres=None, drop_mask=None, lengths=None):
+        return ops.fc_block(self.trunk(x, centres, drop_mask, lengths=lengths), self.fc3, training=self.training)

@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from pnpp_hip import ops
+from pnpp_hip.lengths import fps_starts, ragged_lengths
 
 
 class _Level(nn.Module):
@@ -65,13 +66,21 @@ class SimpleSetAbstraction(_Level):
     def grouper(self):
         return ("ball", self.radius)
 
-    def _centres(self, xyz, start=None):
-        return ops.farthest_point_sample(xyz, self.npoint, start)
+    def _centres(self, xyz, start=None, lengths=None):
+        return ops.farthest_point_sample(xyz, self.npoint, start, lengths=lengths)
 
-    def rows(self, xyz, points, start=None):
-        """xyz (B,N,3), points (B,N,D) or None -> new_xyz (B,S,3), new_points (B,S,C); start (B,) injects the first centre index."""
-        centre = self._centres(xyz, start)
-        nbr = ops.ball_query(self.radius, self.nsample, xyz, ops.index_points(xyz, centre))
+    def rows(self, xyz, points, start=None, lengths=None):
+        """xyz (B,N,3), points (B,N,D) or None -> new_xyz (B,S,3), new_points (B,S,C); start (B,) injects the first centre index.
+        lengths (B,): a ragged batch -- cloud b is its first lengths[b] rows (any length from 1: farthest-point sampling may revisit
+        points and the radius query pads its lists); sampling and query read them, the level's output is uniform.  Without `start`
+        the first index of cloud b is torch.randint(0, lengths[b]) on the host generator, which reads a device `lengths` back once."""
+        if lengths is not None:   # checked / uploaded once for the sampling and the query
+            dev = ragged_lengths(lengths, xyz.shape[0], xyz.shape[1], xyz.device)
+            if start is None:
+                start = fps_starts(lengths)
+            lengths = dev
+        centre = self._centres(xyz, start, lengths)
+        nbr = ops.ball_query(self.radius, self.nsample, xyz, ops.index_points(xyz, centre), lengths=lengths)
         return ops.set_abstraction(xyz, points, centre, self.nsample, False, self.training, self.mlp_convs, self.mlp_bns,
                                    neighbour_idx=nbr)
 
@@ -120,15 +129,16 @@ class PointNetPlusPlusCls(nn.Module):
         rows = x.detach().transpose(1, 2)
         return rows[:, :, :3].contiguous(), rows[:, :, 3:].contiguous()
 
-    def forward(self, x, start=None, drop_masks=None):
+    def forward(self, x, start=None, drop_masks=None, lengths=None):
         """x (B, 6, N) -> (B, num_classes) log-probabilities.  start = (sa1 start indices (B,), sa2 start indices (B,)) and
-        drop_masks = ((B,512), (B,256)) keep-masks inject the random draws (parity runs)."""
+        drop_masks = ((B,512), (B,256)) keep-masks inject the random draws (parity runs).  lengths (B,): a ragged batch -- cloud b
+        is x[b, :, :lengths[b]] (SimpleSetAbstraction.rows); only the first level reads them."""
         xyz, points = self.split_input(x)
         B = xyz.size(0)
         s1, s2 = start if start is not None else (None, None)
         m1, m2 = drop_masks if drop_masks is not None else (None, None)
         t = self.training
-        l1_xyz, l1_points = self.sa1.rows(xyz, points, s1)
+        l1_xyz, l1_points = self.sa1.rows(xyz, points, s1, lengths=lengths)
         l2_xyz, l2_points = self.sa2.rows(l1_xyz, l1_points, s2)
         _, l3_points = self.sa3.rows(l2_xyz, l2_points)
         h = l3_points.view(B, -1)

@@ -13,9 +13,9 @@ class PointNetPPVonMises(BackboneBNHead):
         super().__init__(sampler, grouper)
         self.fc3 = nn.Linear(256, 2)
 
-    def features(self, xyz, centres=None, drop_mask=None):
+    def features(self, xyz, centres=None, drop_mask=None, lengths=None):
         """The raw fc3 output (B,2), in front of the tanh / softplus activations (and of the fused loss kernels)."""
-        return ops.fc_block(self.trunk(xyz, centres, drop_mask), self.fc3, training=self.training)
+        return ops.fc_block(self.trunk(xyz, centres, drop_mask, lengths=lengths), self.fc3, training=self.training)
 
-    def forward(self, xyz, centres=None, drop_mask=None):
-        return ops.vm_head(self.features(xyz, centres, drop_mask))       # mu = tanh(out[:,0]) * pi, kappa = softplus(out[:,1])
+    def forward(self, xyz, centres=None, drop_mask=None, lengths=None):
+        return ops.vm_head(self.features(xyz, centres, drop_mask, lengths))       # mu = tanh(out[:,0]) * pi, kappa = softplus(out[:,1])

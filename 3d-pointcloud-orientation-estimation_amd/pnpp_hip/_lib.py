@@ -164,6 +164,16 @@ SIGNATURES = {
     "pnpp_pt_infer_head_ragged": (_i, [C.POINTER(PtInferDesc), _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnpp_pt_infer_tail_ragged": (_i, [C.POINTER(PtInferDesc), _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnpp_pt_infer_pool_ragged": (_i, [C.POINTER(PtInferDesc), _fp, _fp, _fp, _fp, _i, _fp, _fp]),
+    # ... of the index primitives and the paired launches: the lengths tensor after N (after xyz for the two descriptor calls)
+    "pnpp_knn_ragged": (_i, [_fp, _fp, _i, _i, _i, _fp, _i, _fp, _fp]),
+    "pnpp_fps_ragged": (_i, [_fp, _i, _i, _fp, _i, _fp, _fp, _fp]),
+    "pnpp_ball_query_ragged": (_i, [_fp, _fp, _i, _i, _i, _fp, _f, _i, _fp, _fp]),
+    "pnpp_sample_random_ragged": (_i, [_u64, _u64, _i, _i, _fp, _i, _fp, _fp]),
+    "pnpp_sample_random_dev_ragged": (_i, [_u64, _fp, _u64, _i, _i, _fp, _i, _fp, _fp]),
+    "pnpp_sample_random_dev2_ragged": (_i, [_u64, _fp, _u64, _i, _i, _fp, _i, _fp, _i, _i, _fp, _fp]),
+    "pnpp_knn_pair_ragged": (_i, [_fp, _i, _i, _fp, _fp, _i, _i, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp]),
+    "pnpp_sa_group_pair_ragged": (_i, [C.POINTER(SaDesc), C.POINTER(SaDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "pnpp_sa_infer_group_pair_ragged": (_i, [C.POINTER(SaDesc), C.POINTER(SaDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

@@ -38,6 +38,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops, sampling
+from .lengths import device_and_draw_lengths, fps_starts, ragged_lengths
 
 
 class _Folded:
@@ -70,11 +71,11 @@ class _Proxy:
     def __setattr__(self, name, value):
         raise AttributeError("a Predictor does not write to its model")
 
-    def trunk(self, xyz, centres=None, drop_mask=None):
-        return self._pred._trunk(xyz, centres)
+    def trunk(self, xyz, centres=None, drop_mask=None, lengths=None):
+        return self._pred._trunk(xyz, centres, lengths)
 
-    def _global_feat(self, pts, centres=None, drop_masks=(None, None)):
-        return self._pred._trunk(pts, centres)
+    def _global_feat(self, pts, centres=None, drop_masks=(None, None), lengths=None):
+        return self._pred._trunk(pts, centres, lengths)
 
 
 def _ball(grouper):
@@ -317,7 +318,17 @@ class SetAbstractionPredictor(Predictor):
         L.check(L.lib().pnpp_sa_infer(C.byref(d), C.byref(a), ops._stream()))
         return new_xyz, out
 
-    def _eval_level(self, i, xyz, points, centre):
+    @staticmethod
+    def _neighbours(sa, xyz, centre, lengths):
+        """the neighbour lists a level needs handed to it: the radius query's, or -- a ragged level 1 -- the ragged kNN's (the
+        level's own search knows no lengths); None: the level searches for itself"""
+        if sa.grouper != "knn":
+            return ops.ball_query(_ball(sa.grouper), sa.nsample, xyz, ops.index_points(xyz, centre), lengths=lengths)
+        if lengths is not None:
+            return ops.knn(ops.index_points(xyz, centre), xyz, sa.nsample, lengths=lengths)
+        return None
+
+    def _eval_level(self, i, xyz, points, centre, lengths=None):
         """the level through the library's existing eval-mode forward (PointNetSetAbstraction.forward with training = False):
         sizes, sampler and grouper are the model's, the parameters the snapshot's"""
         sa = self._levels[i]
@@ -326,44 +337,48 @@ class SetAbstractionPredictor(Predictor):
             return ops.set_abstraction(xyz, points, None, None, True, False, w.convs, w.bns)
         if centre is None:
             centre = sa._centres(xyz)
-        nbr = None
-        if sa.grouper != "knn":
-            nbr = ops.ball_query(_ball(sa.grouper), sa.nsample, xyz, ops.index_points(xyz, centre))
+        nbr = self._neighbours(sa, xyz, centre, lengths)
         return ops.set_abstraction(xyz, points, centre, sa.nsample, False, False, w.convs, w.bns, neighbour_idx=nbr)
 
-    def _level(self, i: int, xyz, points, centre=None):
+    def _level(self, i: int, xyz, points, centre=None, lengths=None):
+        """lengths: the device tensor of a ragged level 1 (the centres are then given: drawn by the caller from the lengths)"""
         sa = self._levels[i]
         B, N, _ = xyz.shape
         d = self._takes(i, B, N)
         self.last_plan[self._names[i]] = "fused" if d is not None else "eval-path"
         if d is None:
-            return self._eval_level(i, xyz, points, centre)
+            return self._eval_level(i, xyz, points, centre, lengths)
         if sa.group_all:
             return self._fused(i, d, xyz, points, None, None)
         if centre is None:
             centre = sa._centres(xyz)
         centre = ops._i32(centre, "centre_idx")
-        nbr = None
-        if sa.grouper != "knn":
-            nbr = ops._i32(ops.ball_query(_ball(sa.grouper), sa.nsample, xyz, ops.index_points(xyz, centre)), "neighbour_idx")
+        nbr = self._neighbours(sa, xyz, centre, lengths)
+        if nbr is not None:
+            nbr = ops._i32(nbr, "neighbour_idx")
         return self._fused(i, d, xyz, points, centre, nbr)
 
-    def _levels12(self, xyz, centres):
-        """sa1 + sa2 with the draws of BackboneBNHead.levels12 / stacked_levels, in their order"""
+    def _levels12(self, xyz, centres, lengths=None):
+        """sa1 + sa2 with the draws of BackboneBNHead.levels12 / stacked_levels, in their order; lengths (B,): a ragged batch"""
         sa1, sa2 = self._levels[0], self._levels[1]
         B, N, _ = xyz.shape
         c1, c2 = centres if centres is not None else (None, None)
+        draw_lengths = lengths
+        if lengths is not None and not sa1.group_all:
+            lengths, draw_lengths = device_and_draw_lengths(lengths, B, N, xyz.device, sa1.min_length(), sa1.sampler)
         if centres is None and sa1.sampler == "device" and sa2.sampler == "device" and not sa1.group_all and not sa2.group_all:
-            c1, c2 = sampling.device_random_centres_pair(B, N, sa1.npoint, sa1.npoint, sa2.npoint, xyz.device)
+            c1, c2 = sampling.device_random_centres_pair(B, N, sa1.npoint, sa1.npoint, sa2.npoint, xyz.device, lengths=lengths)
         pair_ok = (not sa1.group_all and not sa2.group_all and sa1.grouper == "knn" and sa2.grouper == "knn"
                    and (c1 is not None or sa1.sampler != "fps") and (c2 is not None or sa2.sampler != "fps")
                    and sa1.npoint <= N and sa2.npoint <= sa1.npoint and sa1.nsample <= N and sa2.nsample <= sa1.npoint)
         if pair_ok:
             # the same draws whichever path each level takes (stacked_levels draws both before either level runs)
             if c1 is None:
-                c1 = sa1._centres(xyz)
+                c1 = sa1._centres(xyz, draw_lengths)
             if c2 is None:
                 c2 = sa2._centres(xyz[:, :sa1.npoint])
+        elif c1 is None and lengths is not None:
+            c1 = sa1._centres(xyz, draw_lengths)
         d1 = self._takes(0, B, N) if pair_ok else None
         d2 = self._takes(1, B, sa1.npoint) if pair_ok else None
         if d1 is not None and d2 is not None:   # both neighbour searches in one launch, then the two level launches
@@ -373,11 +388,14 @@ class SetAbstractionPredictor(Predictor):
             idx2 = self._buf("sa2.idx", (B, d2.S, d2.K), torch.int32)
             nx1 = self._buf("sa1.new_xyz", (B, d1.S, 3), torch.float32)
             nx2 = self._buf("sa2.new_xyz", (B, d2.S, 3), torch.float32)
-            L.check(L.lib().pnpp_sa_infer_group_pair(C.byref(d1), C.byref(d2), xyz.data_ptr(), c1.data_ptr(), c2.data_ptr(),
-                                                     idx1.data_ptr(), nx1.data_ptr(), idx2.data_ptr(), nx2.data_ptr(), ops._stream()))
+            tail = (c1.data_ptr(), c2.data_ptr(), idx1.data_ptr(), nx1.data_ptr(), idx2.data_ptr(), nx2.data_ptr(), ops._stream())
+            if lengths is not None:
+                L.check(L.lib().pnpp_sa_infer_group_pair_ragged(C.byref(d1), C.byref(d2), xyz.data_ptr(), lengths.data_ptr(), *tail))
+            else:
+                L.check(L.lib().pnpp_sa_infer_group_pair(C.byref(d1), C.byref(d2), xyz.data_ptr(), *tail))
             l1_xyz, l1_pts = self._fused(0, d1, xyz, None, c1, idx1)
             return self._fused(1, d2, l1_xyz, l1_pts, c2, idx2)
-        l1_xyz, l1_pts = self._level(0, xyz, None, c1)
+        l1_xyz, l1_pts = self._level(0, xyz, None, c1, lengths)
         return self._level(1, l1_xyz, l1_pts, c2)
 
     def _eval_head(self, name, x):
@@ -385,20 +403,25 @@ class SetAbstractionPredictor(Predictor):
         norm = getattr(m, "bn" + name[2:], None) or getattr(m, "ln" + name[2:], None)
         return ops.fc_block(x, getattr(m, name), norm, relu=True, dropout=m.drop, training=False)
 
-    def _trunk(self, xyz, centres):
+    def _trunk(self, xyz, centres, lengths=None):
         xyz = ops._f32(xyz, "xyz")
         B = xyz.size(0)
-        l2_xyz, l2_pts = self._levels12(xyz, centres)
+        l2_xyz, l2_pts = self._levels12(xyz, centres, lengths)
         x = self._level(2, l2_xyz, l2_pts)[1].reshape(B, -1)
         for name in ("fc1", "fc2"):
             x = self._run_head(name, x, self._eval_head)
         return x
 
     @torch.no_grad()
-    def __call__(self, xyz: torch.Tensor, centres=None):
+    def __call__(self, xyz: torch.Tensor, centres=None, lengths=None):
+        """lengths (B,): a ragged batch, as model.eval()(xyz, centres=centres, lengths=lengths) -- row b is the result for
+        xyz[b:b+1, :lengths[b]] given the same draws; the pair route, a level-1 launch on the ragged kernel's neighbour lists and
+        the eval-path fall-back all take it."""
         ops._need_gpu(xyz, "xyz")
         with torch.cuda.device(self.device):
-            return type(self.model).forward(_Proxy(self), xyz, centres=centres)
+            if lengths is None:
+                return type(self.model).forward(_Proxy(self), xyz, centres=centres)
+            return type(self.model).forward(_Proxy(self), xyz, centres=centres, lengths=lengths)
 
 
 class ClsPredictor(SetAbstractionPredictor):
@@ -418,13 +441,19 @@ class ClsPredictor(SetAbstractionPredictor):
         return ops.fc_block(x, self._snap[name], self._snap["bn" + name[2:]], relu=True, training=False)
 
     @torch.no_grad()
-    def __call__(self, x: torch.Tensor, start=None):
+    def __call__(self, x: torch.Tensor, start=None, lengths=None):
+        """lengths (B,): a ragged batch, as model.eval()(x, start=start, lengths=lengths)"""
         ops._need_gpu(x, "x")
         with torch.cuda.device(self.device):
             xyz, points = self.model.split_input(x)
             s1, s2 = start if start is not None else (None, None)
             sa1, sa2 = self._levels[0], self._levels[1]
-            l1_xyz, l1_pts = self._level(0, xyz, points, sa1._centres(xyz, s1))
+            if lengths is not None:   # checked / uploaded once; the start draws of SimpleSetAbstraction.rows
+                dev = ragged_lengths(lengths, xyz.size(0), xyz.size(1), xyz.device)
+                if s1 is None:
+                    s1 = fps_starts(lengths)
+                lengths = dev
+            l1_xyz, l1_pts = self._level(0, xyz, points, sa1._centres(xyz, s1, lengths), lengths)
             l2_xyz, l2_pts = self._level(1, l1_xyz, l1_pts, sa2._centres(l1_xyz, s2))
             h = self._level(2, l2_xyz, l2_pts)[1].reshape(xyz.size(0), -1)
             for name in ("fc1", "fc2"):

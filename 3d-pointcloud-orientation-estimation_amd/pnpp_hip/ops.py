@@ -11,6 +11,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from .lengths import fps_starts, ragged_lengths
 
 
 # ------------------------------------------------------------------------------------------------
@@ -139,19 +140,38 @@ def square_distance(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def knn(new_xyz: torch.Tensor, xyz: torch.Tensor, k: int) -> torch.Tensor:
-    """(B,S,k) int32 neighbour indices, ascending (distance, index)."""
+def knn(new_xyz: torch.Tensor, xyz: torch.Tensor, k: int, lengths=None) -> torch.Tensor:
+    """(B,S,k) int32 neighbour indices, ascending (distance, index).
+    lengths (B,): a ragged batch -- cloud b is xyz[b, :lengths[b]], row b of the result is what the call on that slice alone returns
+    (every index < lengths[b]); a list or CPU tensor is checked here (k <= lengths[b] <= N), a device int32 tensor is used as it is."""
     new_xyz, xyz = _f32(new_xyz, "new_xyz"), _f32(xyz, "xyz")
     B, S, _ = new_xyz.shape
     N = xyz.shape[1]
     idx = torch.empty(B, S, k, device=xyz.device, dtype=torch.int32)
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, B, N, xyz.device, minimum=k)
+        L.check(L.lib().pnpp_knn_ragged(new_xyz.data_ptr(), xyz.data_ptr(), B, S, N, lengths.data_ptr(), int(k), idx.data_ptr(), _stream()))
+        return idx
     L.check(L.lib().pnpp_knn(new_xyz.data_ptr(), xyz.data_ptr(), B, S, N, int(k), idx.data_ptr(), _stream()))
     return idx
 
 
-def farthest_point_sample(xyz: torch.Tensor, npoint: int, start: Optional[torch.Tensor] = None) -> torch.Tensor:
+def farthest_point_sample(xyz: torch.Tensor, npoint: int, start: Optional[torch.Tensor] = None, lengths=None) -> torch.Tensor:
+    """lengths (B,): a ragged batch -- row b is the sampling of xyz[b, :lengths[b]] alone (npoint may exceed a length, as it may
+    exceed N); start[b] < lengths[b].  Without `start` the first index of cloud b is torch.randint(0, lengths[b]) on the host
+    generator, cloud after cloud -- the draws of the per-cloud calls in batch order; that needs the lengths on the host, so a device
+    `lengths` is read back once (inject `start` to avoid it)."""
     xyz = _f32(xyz, "xyz")
     B, N, _ = xyz.shape
+    if lengths is not None:
+        dev_lengths = ragged_lengths(lengths, B, N, xyz.device)
+        if start is None:
+            start = fps_starts(lengths)
+        start = start.to(device=xyz.device, dtype=torch.int32).contiguous()
+        out = torch.empty(B, npoint, device=xyz.device, dtype=torch.int32)
+        L.check(L.lib().pnpp_fps_ragged(xyz.data_ptr(), B, N, dev_lengths.data_ptr(), int(npoint), start.data_ptr(), out.data_ptr(),
+                                        _stream()))
+        return out
     if start is None:  # PointNet++Demo.py:20 draws the first index with torch.randint
         start = torch.randint(0, N, (B,), dtype=torch.long)
     start = start.to(device=xyz.device, dtype=torch.int32).contiguous()
@@ -160,43 +180,69 @@ def farthest_point_sample(xyz: torch.Tensor, npoint: int, start: Optional[torch.
     return out
 
 
-def ball_query(radius: float, nsample: int, xyz: torch.Tensor, new_xyz: torch.Tensor) -> torch.Tensor:
+def ball_query(radius: float, nsample: int, xyz: torch.Tensor, new_xyz: torch.Tensor, lengths=None) -> torch.Tensor:
+    """lengths (B,): a ragged batch -- row b lists members of xyz[b, :lengths[b]] only, as the call on that slice alone does."""
     xyz, new_xyz = _f32(xyz, "xyz"), _f32(new_xyz, "new_xyz")
     B, N, _ = xyz.shape
     S = new_xyz.shape[1]
     idx = torch.empty(B, S, nsample, device=xyz.device, dtype=torch.int32)
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, B, N, xyz.device)
+        L.check(L.lib().pnpp_ball_query_ragged(new_xyz.data_ptr(), xyz.data_ptr(), B, S, N, lengths.data_ptr(), float(radius),
+                                               int(nsample), idx.data_ptr(), _stream()))
+        return idx
     L.check(L.lib().pnpp_ball_query(new_xyz.data_ptr(), xyz.data_ptr(), B, S, N, float(radius), int(nsample),
                                     idx.data_ptr(), _stream()))
     return idx
 
 
-def sample_random(seed: int, stream_id: int, B: int, N: int, npoint: int, device) -> torch.Tensor:
+def sample_random(seed: int, stream_id: int, B: int, N: int, npoint: int, device, lengths=None) -> torch.Tensor:
+    """lengths (B,): a ragged batch -- row b is drawn from cloud b's first lengths[b] rows, bit-equal to row b of the uniform draw
+    at N = lengths[b] (a list or CPU tensor is checked here: npoint <= lengths[b] <= N)."""
     out = torch.empty(B, npoint, device=device, dtype=torch.int32)
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, B, N, device, minimum=npoint)
+        L.check(L.lib().pnpp_sample_random_ragged(int(seed) & (2**64 - 1), int(stream_id) & (2**64 - 1), B, N, lengths.data_ptr(),
+                                                  int(npoint), out.data_ptr(), _stream()))
+        return out
     L.check(L.lib().pnpp_sample_random(int(seed) & (2**64 - 1), int(stream_id) & (2**64 - 1), B, N, int(npoint),
                                        out.data_ptr(), _stream()))
     return out
 
 
-def sample_random_dev(seed: int, counter: torch.Tensor, offset: int, B: int, N: int, npoint: int) -> torch.Tensor:
+def sample_random_dev(seed: int, counter: torch.Tensor, offset: int, B: int, N: int, npoint: int, lengths=None) -> torch.Tensor:
     """Like sample_random, with stream id = counter[0] + offset read at kernel time; the kernel then adds 1 to
     counter[0].  `counter` is an int64 device tensor of two words (call counter, ticket word kept at zero)."""
     _need_gpu(counter, "counter")
     if counter.dtype != torch.int64 or counter.numel() != 2 or not counter.is_contiguous():
         raise ValueError("counter must be a contiguous int64 tensor of 2 elements")
     out = torch.empty(B, npoint, device=counter.device, dtype=torch.int32)
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, B, N, counter.device, minimum=npoint)
+        L.check(L.lib().pnpp_sample_random_dev_ragged(int(seed) & (2**64 - 1), counter.data_ptr(), int(offset) & (2**64 - 1), B, N,
+                                                      lengths.data_ptr(), int(npoint), out.data_ptr(), _stream()))
+        return out
     L.check(L.lib().pnpp_sample_random_dev(int(seed) & (2**64 - 1), counter.data_ptr(), int(offset) & (2**64 - 1), B, N,
                                            int(npoint), out.data_ptr(), _stream()))
     return out
 
 
-def sample_random_dev2(seed: int, counter: torch.Tensor, offset: int, B: int, N1: int, npoint1: int, N2: int, npoint2: int):
+def sample_random_dev2(seed: int, counter: torch.Tensor, offset: int, B: int, N1: int, npoint1: int, N2: int, npoint2: int,
+                       lengths=None):
     """Two consecutive sample_random_dev draws in one launch: (B,npoint1) from N1 with the counter's value, (B,npoint2)
-    from N2 with the next one; counter[0] += 2.  Bit-identical to the two separate calls."""
+    from N2 with the next one; counter[0] += 2.  Bit-identical to the two separate calls.  lengths (B,) belong to the first draw
+    (the second ranks the first level's centres, which are uniform)."""
     _need_gpu(counter, "counter")
     if counter.dtype != torch.int64 or counter.numel() != 2 or not counter.is_contiguous():
         raise ValueError("counter must be a contiguous int64 tensor of 2 elements")
     out1 = torch.empty(B, npoint1, device=counter.device, dtype=torch.int32)
     out2 = torch.empty(B, npoint2, device=counter.device, dtype=torch.int32)
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, B, N1, counter.device, minimum=npoint1)
+        L.check(L.lib().pnpp_sample_random_dev2_ragged(int(seed) & (2**64 - 1), counter.data_ptr(), int(offset) & (2**64 - 1), B, N1,
+                                                       lengths.data_ptr(), int(npoint1), out1.data_ptr(), N2, int(npoint2),
+                                                       out2.data_ptr(), _stream()))
+        return out1, out2
     L.check(L.lib().pnpp_sample_random_dev2(int(seed) & (2**64 - 1), counter.data_ptr(), int(offset) & (2**64 - 1), B, N1,
                                             int(npoint1), out1.data_ptr(), N2, int(npoint2), out2.data_ptr(), _stream()))
     return out1, out2
@@ -394,12 +440,13 @@ class _SetAbstraction(torch.autograd.Function):
         return (None, dpoints, None, None, None, None, *grads)
 
 
-def group_pair(xyz, centre1, centre2, nsample1, convs1, nsample2, convs2, training=True):
+def group_pair(xyz, centre1, centre2, nsample1, convs1, nsample2, convs2, training=True, lengths=None):
     """Centre gather + neighbour search of two stacked set-abstraction levels (sa1 on the cloud, sa2 on sa1's centres) in ONE
     launch, ahead of both forward passes (models/pointnet_pp_8dir.py:28-31 of each level): level 2 searches among level 1's
     centres, which are rows of the same cloud, so it does not wait for level 1's MLP.  centre1 (B,S1) rows of xyz, centre2
     (B,S2) positions among level 1's centres.  Returns the two `pre=` workspaces for set_abstraction; the neighbour sets are
-    those the per-level search finds (same coordinates, same arithmetic)."""
+    those the per-level search finds (same coordinates, same arithmetic).  lengths (B,): a ragged batch -- level 1 searches
+    xyz[b, :lengths[b]] (same launch, same grid; level 2 searches level 1's centres and is uniform either way)."""
     xyz = _f32(xyz, "xyz")
     B, N, _ = xyz.shape
     c1, c2 = _i32(centre1, "centre_idx"), _i32(centre2, "centre_idx")
@@ -415,8 +462,13 @@ def group_pair(xyz, centre1, centre2, nsample1, convs1, nsample2, convs2, traini
             L.check(L.PNPP_ERR_ARG)
         pres.append({"saved": torch.empty(sb, dtype=torch.uint8, device=xyz.device),
                      "new_xyz": torch.empty(B, S, 3, device=xyz.device, dtype=torch.float32)})
-    L.check(lib.pnpp_sa_group_pair(C.byref(d1), C.byref(d2), xyz.data_ptr(), c1.data_ptr(), c2.data_ptr(), pres[0]["saved"].data_ptr(),
-                                   pres[0]["new_xyz"].data_ptr(), pres[1]["saved"].data_ptr(), pres[1]["new_xyz"].data_ptr(), _stream()))
+    tail = (c1.data_ptr(), c2.data_ptr(), pres[0]["saved"].data_ptr(), pres[0]["new_xyz"].data_ptr(), pres[1]["saved"].data_ptr(),
+            pres[1]["new_xyz"].data_ptr(), _stream())
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, B, N, xyz.device, minimum=max(S1, int(nsample1)))
+        L.check(lib.pnpp_sa_group_pair_ragged(C.byref(d1), C.byref(d2), xyz.data_ptr(), lengths.data_ptr(), *tail))
+    else:
+        L.check(lib.pnpp_sa_group_pair(C.byref(d1), C.byref(d2), xyz.data_ptr(), *tail))
     return pres[0], pres[1]
 
 

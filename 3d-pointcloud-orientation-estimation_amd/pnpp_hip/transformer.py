@@ -14,6 +14,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .lengths import check_lengths, ragged_lengths   # noqa: F401  (their home is pnpp_hip.lengths; importable from here as before)
 from .ops import _f32, _scratch, _stream
 
 
@@ -85,40 +86,6 @@ def attention_dropout_mask(B: int, N: int, H: int, p: float, device, seed=None, 
         L.check(L.lib().pnpp_attention_dropout_mask(int(seed) & (2**64 - 1), int(stream_id) & (2**64 - 1), B, N, H, float(p),
                                                     mask.data_ptr(), maskT.data_ptr(), _stream()))
     return mask, maskT
-
-
-def check_lengths(lengths, B: int, n_pts: int) -> torch.Tensor:
-    """Host-side validation of a ragged batch's per-cloud lengths, given as a list (or anything torch.as_tensor takes) or a CPU
-    tensor: integer dtype, shape (B,), 1 <= lengths[b] <= n_pts.  -> the values as a CPU int32 tensor.  A violation raises ValueError
-    naming the offending cloud.  Runs without a GPU."""
-    t = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths)
-    if t.is_cuda:
-        raise ValueError("check_lengths validates host values; a device tensor is used as it is (see ragged_lengths)")
-    if t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
-        raise ValueError(f"lengths must have an integer dtype, got {t.dtype}")
-    if tuple(t.shape) != (B,):
-        raise ValueError(f"lengths must have shape ({B},), one entry per cloud, got {tuple(t.shape)}")
-    t = t.to(torch.int64)
-    bad = ((t < 1) | (t > n_pts)).nonzero()
-    if bad.numel():
-        b = int(bad[0])
-        raise ValueError(f"lengths[{b}] = {int(t[b])}: cloud {b} must hold between 1 and n_pts = {n_pts} points")
-    return t.to(torch.int32).contiguous()
-
-
-def ragged_lengths(lengths, B: int, n_pts: int, device) -> torch.Tensor:
-    """The (B,) int32 device tensor the ragged kernels read.  A list or a CPU tensor is validated on the host (check_lengths) and
-    uploaded.  An int32 tensor already on the device is used as it is, without a synchronisation: only its dtype, shape and device are
-    looked at, THE CALLER VOUCHES FOR THE RANGE 1 <= lengths[b] <= n_pts, and the kernels clamp every value into that range, so a bad
-    one cannot cause an access out of bounds -- it gives the result of the clamped length."""
-    device = torch.device(device)
-    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
-        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
-            raise ValueError(f"a device lengths tensor must be int32 of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
-        if lengths.device != device:
-            raise ValueError(f"lengths is on {lengths.device}, the batch on {device}")
-        return lengths.contiguous()
-    return check_lengths(lengths, B, n_pts).to(device)
 
 
 ATTENTION_FORMS = ("float32", "split")

@@ -95,6 +95,27 @@ int pnpp_sample_random_dev(uint64_t seed, uint64_t *stream_id_dev, uint64_t offs
 int pnpp_sample_random_dev2(uint64_t seed, uint64_t *stream_id_dev, uint64_t offset, int B, int N1, int npoint1, int32_t *out1,
                             int N2, int npoint2, int32_t *out2, void *stream);
 
+/* Ragged batches of the index primitives: xyz stays the padded (B,N,3) tensor, lengths (B) int32 in DEVICE memory says how many of
+ * cloud b's rows are points.  Each call is its namesake with `lengths` after N; a kernel reads Nv = min(max(lengths[b], 1), N) once per
+ * workgroup and uses it wherever the cloud's extent matters, so row b of a result is what the namesake returns for xyz[b, :Nv] alone
+ * and no index >= Nv is ever written; the padding rows may hold anything.  Argument checks are the namesake's (against the padded
+ * N: the host does not see the lengths) and a NULL lengths is PNPP_ERR_ARG.  What the device cannot refuse:
+ *   knn            k > Nv: the list's slots >= Nv repeat slot 0;
+ *   fps            npoint > Nv is legal as in the namesake (once every distance is 0 the first maximum is point 0); start[b] < Nv;
+ *   ball_query     a centre without a member in its cloud is filled with Nv (cannot occur when the centres are points of the cloud);
+ *   sample_random  npoint > Nv: rank r >= Nv repeats rank r mod Nv.  The draw of cloud b is the namesake's at N = Nv for the same
+ *                  batch position, bit for bit.  _dev2: lengths belong to the first draw (the second ranks level 1's centres). */
+int pnpp_knn_ragged(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, int k, int32_t *idx, void *stream);
+int pnpp_fps_ragged(const float *xyz, int B, int N, const int32_t *lengths, int npoint, const int32_t *start, int32_t *out, void *stream);
+int pnpp_ball_query_ragged(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, float radius, int nsample,
+                           int32_t *idx, void *stream);
+int pnpp_sample_random_ragged(uint64_t seed, uint64_t stream_id, int B, int N, const int32_t *lengths, int npoint, int32_t *out,
+                              void *stream);
+int pnpp_sample_random_dev_ragged(uint64_t seed, uint64_t *stream_id_dev, uint64_t offset, int B, int N, const int32_t *lengths,
+                                  int npoint, int32_t *out, void *stream);
+int pnpp_sample_random_dev2_ragged(uint64_t seed, uint64_t *stream_id_dev, uint64_t offset, int B, int N1, const int32_t *lengths,
+                                   int npoint1, int32_t *out1, int N2, int npoint2, int32_t *out2, void *stream);
+
 /* models/base.py:4-18  index_points(points (B,N,C), idx (B,M)) -> out (B,M,C); idx is int32, flattened
  * over its trailing dims.  _bwd accumulates dpoints (B,N,C) += scatter(dout) deterministically
  * (dpoints must be zero-initialised by the caller when it wants a pure gradient). */
@@ -175,6 +196,15 @@ int pnpp_sa_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const flo
 int pnpp_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int S1, int k1, int32_t *idx1, float *new_xyz1,
                   const int32_t *centre2, int S2, int k2, int32_t *idx2, float *new_xyz2, double *mom, void *stream);
 int pnpp_knn_pair_partials(int B, int S1, int N);
+/* The two calls above on a ragged batch (see pnpp_knn_ragged): lengths (B) int32 on the device are level 1's clouds; level 2 searches
+ * level 1's centres, which are uniform.  Grid, tile and the number of moment partials are those of the padded N, so a level grouped
+ * this way goes through pnpp_sa_forward / pnpp_sa_backward unchanged. */
+int pnpp_sa_group_pair_ragged(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *lengths,
+                              const int32_t *centre1, const int32_t *centre2, void *saved1, float *new_xyz1, void *saved2,
+                              float *new_xyz2, void *stream);
+int pnpp_knn_pair_ragged(const float *xyz, int B, int N, const int32_t *lengths, const int32_t *centre1, int S1, int k1, int32_t *idx1,
+                         float *new_xyz1, const int32_t *centre2, int S2, int k2, int32_t *idx2, float *new_xyz2, double *mom,
+                         void *stream);
 /* read-only view of the neighbour indices kept in `saved` ((B,S,K) int32; NULL when group_all) */
 const int32_t *pnpp_sa_saved_neighbours(const pnpp_sa_desc *d, const void *saved);
 /* read-only view of the max-pool routing kept in `saved`: (B*S, C_last) int32, the position 0..K-1 inside its group of the
@@ -557,6 +587,10 @@ int pnpp_sa_infer(const pnpp_sa_desc *d, const pnpp_sa_infer_args *a, void *stre
  * plain (B,S,K) int32 buffers, the centre coordinates to new_xyz1 / new_xyz2; pass idx1 / idx2 as neighbour_idx to pnpp_sa_infer */
 int pnpp_sa_infer_group_pair(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *centre1,
                              const int32_t *centre2, int32_t *idx1, float *new_xyz1, int32_t *idx2, float *new_xyz2, void *stream);
+/* ... of a ragged batch: lengths (B) int32 on the device, level 1's clouds (see pnpp_sa_group_pair_ragged) */
+int pnpp_sa_infer_group_pair_ragged(const pnpp_sa_desc *d1, const pnpp_sa_desc *d2, const float *xyz, const int32_t *lengths,
+                                    const int32_t *centre1, const int32_t *centre2, int32_t *idx1, float *new_xyz1, int32_t *idx2,
+                                    float *new_xyz2, void *stream);
 /* The same fold for a head block, nn.Linear (N,K) + eval-mode nn.BatchNorm1d (models/pointnet_pp_vonMises.py:32-33,
  * pointnet_pp_8dir.py:81-84): w_out (N,K), b_out (N).  The folded block then runs as pnpp_fc_forward with norm = PNPP_NORM_NONE,
  * training = 0 on (w_out, b_out): y = relu(x W'^T + b'). */

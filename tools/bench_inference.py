@@ -9,6 +9,15 @@ One JSON line per case: clouds/s and ms per forward of both paths (median over t
 launches per forward (kernels the library itself launches; torch's own copies and fills are not counted), the Predictor's algorithmic FLOPs and compulsory HBM bytes per forward (from the shapes), the max-abs
 difference of the two paths' outputs, and `faster`: the acceptance condition median(eval) - median(predictor) > spread(eval) +
 spread(predictor).  Windows are timed with device events closed by a synchronise; each is at least --window seconds long.
+
+    python tools/bench_inference.py --lengths --out profiles/sa_ragged.json   # appends one line per path (Predictor, training step)
+
+--lengths times a RAGGED batch of PointNetPPVonMises at 32 x 1024 -- DeviceCloudBank.padded(ids) of a bank whose clouds have seeded
+lengths, uniform on [N/4, N] (the first cloud keeps N points, so the padded batch has N rows) -- against the status quo for the same
+clouds: bank.sample(ids, N), every cloud resampled to N rows, run without lengths.  The two paths alternate in one process, in the same
+windows (alternate() / ragged_record() of tools/bench_pt_inference.py, which says what the fields are).  Only the index kernels' work
+shrinks with the lengths, so there is no speed target: `ragged_not_slower` is median(ragged) - median(resampled) <= spread(ragged) +
+spread(resampled).
 """
 import argparse
 import datetime
@@ -133,14 +142,88 @@ def case(cls, B, N, windows, seconds):
     }
 
 
+def ragged_bank_batch(B, N, seed=2048):
+    """a bank of B clouds with seeded lengths, uniform on [N/4, N] (cloud 0 keeps N points) -> the ragged batch bank.padded(ids) =
+    (xyz (B, N, 3), lengths (B,) int32, both on the device), the host lengths, and bank.sample(ids, N): every cloud resampled to N rows"""
+    from dataloader_common import DeviceCloudBank
+    g = torch.Generator().manual_seed(seed)
+    lengths = torch.randint(N // 4, N + 1, (B,), generator=g)
+    lengths[0] = N
+    box = torch.tensor([1.0, 0.6, 0.3])
+    bank = DeviceCloudBank([((torch.rand(int(n), 3, generator=g) * 2 - 1) * box).numpy() for n in lengths], "cuda", seed=seed)
+    ids = list(range(B))
+    xyz, dev_lengths = bank.padded(ids)
+    return xyz, dev_lengths, lengths, bank.sample(ids, N)
+
+
+def ragged_cases(B, N, windows, seconds):
+    """Predictor forward and one training step (forward, fused head + KL loss + backward) of PointNetPPVonMises(sampler='device'):
+    the ragged batch against the resampled one"""
+    from bench_pt_inference import alternate, ragged_record
+    from models.pointnet_pp_vonMises import PointNetPPVonMises
+    from pnpp_hip import ops
+    from pnpp_hip.inference import Predictor
+    torch.manual_seed(0)
+    model = PointNetPPVonMises(sampler="device").cuda()
+    xyz, dev_lengths, lengths, full = ragged_bank_batch(B, N)
+    g = torch.Generator().manual_seed(7)
+    mu_gt, kappa_gt = ((torch.rand(B, generator=g) * 2 - 1) * 3.14).cuda(), torch.full((B,), 8.0).cuda()
+    base = {"model": "PointNetPPVonMises", "sampler": "device", "B": B, "N": N, "date": datetime.date.today().isoformat(),
+            "device": torch.cuda.get_device_name(0), "windows": windows, "window_s": seconds}
+    out = []
+
+    def step(x, L):
+        model.zero_grad(set_to_none=True)
+        return ops.vm_head_kl_loss(model.features(x, lengths=L), mu_gt, kappa_gt).backward()
+
+    model.train()
+    runs = {"ragged": lambda: step(xyz, dev_lengths), "resampled": lambda: step(full, None)}
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    rec = dict(base, workload="PointNetPPVonMises forward + fused head / KL loss + backward, ragged batch (DeviceCloudBank.padded) against "
+               "every cloud resampled to N rows (DeviceCloudBank.sample)", launches={k: launches(fn) for k, fn in runs.items()})
+    out.append(ragged_record(rec, alternate(runs, windows, seconds, 8), lengths, N))
+
+    model.eval()
+    pred = Predictor(model)
+    runs = {"ragged": lambda: pred(xyz, lengths=dev_lengths), "resampled": lambda: pred(full)}
+    c1 = ops.sample_random(1, 0, B, N, model.sa1.npoint, xyz.device, lengths=dev_lengths)
+    c2 = ops.sample_random(1, 1, B, model.sa1.npoint, model.sa2.npoint, xyz.device)
+    both = pred(xyz, centres=(c1, c2), lengths=dev_lengths)
+    alone = [pred(xyz[b:b + 1, :int(n)].contiguous(), centres=(c1[b:b + 1], c2[b:b + 1])) for b, n in enumerate(lengths)]
+    diff = max(float((both[i] - torch.cat([a[i] for a in alone])).abs().max()) for i in range(len(both)))
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    rec = dict(base, workload="Predictor(PointNetPPVonMises) forward, ragged batch (DeviceCloudBank.padded) against every cloud resampled "
+               "to N rows (DeviceCloudBank.sample)", plan=pred.last_plan, launches={k: launches(fn) for k, fn in runs.items()},
+               max_abs_diff_to_each_cloud_alone=diff)
+    out.append(ragged_record(rec, alternate(runs, windows, seconds, 8), lengths, N))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.5, help="seconds of device time per window")
     ap.add_argument("--out", default=None, help="also write the JSON lines to this file (overwritten)")
     ap.add_argument("--trace-only", type=int, default=0, help="run this many Predictor forwards (B=32, N=1024) and exit")
+    ap.add_argument("--lengths", action="store_true",
+                    help="a ragged batch (seeded lengths, uniform on [N/4, N], from a DeviceCloudBank) against every cloud resampled to N "
+                         "rows, at 32 x 1024; --out is appended to")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_inference needs an AMD GPU"
+    if args.lengths:
+        for rec in ragged_cases(32, 1024, args.windows, args.window):
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+        return
     from models.pointnet_pp_vonMises import PointNetPPVonMises
     from models.pointnet_pp_8dir import PointNetPP8Dir
     if args.trace_only:

@@ -8,7 +8,13 @@
   - per level, the fused launch (pnpp_sa_infer on given centres and neighbour lists) against the eval path's level on the same
     indices, and the farthest-point sampling and radius query in front of it on their own: FPS is serial per cloud, its share of the
     Predictor's forward is recorded.
-One JSON document; `predictor_not_slower` is median(predictor) - median(eval) <= spread(eval) + spread(predictor)."""
+One JSON document; `predictor_not_slower` is median(predictor) - median(eval) <= spread(eval) + spread(predictor).
+
+    python tools/bench_pointnet_pp_cls.py --lengths --out profiles/sa_ragged.json   # appends one line per path
+
+--lengths times a RAGGED batch (tools/bench_inference.py's ragged_bank_batch: DeviceCloudBank.padded of clouds with seeded lengths,
+uniform on [N/4, N], random normals beside them) against the same clouds resampled to N rows and run without lengths -- a training
+step and the Predictor's forward, the two paths alternating in the same windows (fields: tools/bench_pt_inference.py)."""
 import argparse
 import ctypes as C
 import datetime
@@ -37,6 +43,59 @@ def timed(fns, windows, seconds):
     return {k: (statistics.median(v), min(v), max(v)) for k, v in ts.items()}
 
 
+def ragged_cases(B, N, windows, seconds):
+    from bench_inference import ragged_bank_batch
+    from bench_pt_inference import alternate, ragged_record
+    from models import PointNetPlusPlusCls
+    from pnpp_hip import ops
+    from pnpp_hip.inference import Predictor
+    torch.manual_seed(0)
+    model = PointNetPlusPlusCls().cuda()
+    xyz, dev_lengths, lengths, full = ragged_bank_batch(B, N)
+    g = torch.Generator().manual_seed(1234)
+    normals = torch.rand(B, N, 3, generator=g).cuda()
+    x, x_full = (torch.cat([t, normals], -1).transpose(1, 2).contiguous() for t in (xyz, full))     # (B, 6, N)
+    target = torch.randint(0, 40, (B,), generator=g).cuda()
+    # the first indices injected (below every length): neither path draws on the host or reads the lengths back
+    start = (torch.randint(0, N // 4, (B,), generator=g).cuda(), torch.randint(0, model.sa1.npoint, (B,), generator=g).cuda())
+    base = {"model": "PointNetPlusPlusCls", "B": B, "N": N, "C": 6, "date": datetime.date.today().isoformat(),
+            "device": torch.cuda.get_device_name(0), "windows": windows, "window_s": seconds}
+    out = []
+    opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+
+    def step(inp, L):
+        opt.zero_grad(set_to_none=True)
+        ops.nll_loss(model(inp, start=start, lengths=L), target, check=False).backward()
+        opt.step()
+
+    model.train()
+    runs = {"ragged": lambda: step(x, dev_lengths), "resampled": lambda: step(x_full, None)}
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    rec = dict(base, workload="PointNetPlusPlusCls forward + nll loss + backward + Adam, ragged batch (DeviceCloudBank.padded) against every "
+               "cloud resampled to N rows (DeviceCloudBank.sample)", launches={k: launches(fn) for k, fn in runs.items()})
+    out.append(ragged_record(rec, alternate(runs, windows, seconds, 8), lengths, N))
+
+    model.eval()
+    pred = Predictor(model)
+    runs = {"ragged": lambda: pred(x, start=start, lengths=dev_lengths), "resampled": lambda: pred(x_full, start=start)}
+    both = pred(x, start=start, lengths=dev_lengths)
+    # each cloud alone, where the level takes it alone (a level refuses npoint > N; inside a padded batch a shorter cloud is legal)
+    whole = [b for b, n in enumerate(lengths) if int(n) >= model.sa1.npoint]
+    alone = torch.cat([pred(x[b:b + 1, :, :int(lengths[b])].contiguous(), start=(start[0][b:b + 1], start[1][b:b + 1])) for b in whole])
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    rec = dict(base, workload="Predictor(PointNetPlusPlusCls) forward, ragged batch (DeviceCloudBank.padded) against every cloud resampled to N "
+               "rows (DeviceCloudBank.sample)", plan=pred.last_plan, launches={k: launches(fn) for k, fn in runs.items()},
+               max_abs_diff_to_each_cloud_alone=float((both[whole] - alone).abs().max()), clouds_compared_alone=len(whole))
+    out.append(ragged_record(rec, alternate(runs, windows, seconds, 8), lengths, N))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=32)
@@ -44,8 +103,19 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.3, help="seconds of device time per window")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lengths", action="store_true",
+                    help="a ragged batch (seeded lengths, uniform on [N/4, N], from a DeviceCloudBank) against every cloud resampled to N "
+                         "rows; --out is appended to")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_pointnet_pp_cls needs an AMD GPU"
+    if args.lengths:
+        for rec in ragged_cases(args.B, args.N, args.windows, args.window):
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+        return
     from models import PointNetPlusPlusCls
     from pnpp_hip import ops
     from pnpp_hip.inference import Predictor
