@@ -2,6 +2,7 @@
 // finalisation forward and backward (with the dZ materialisation and the slab reduction that ride in its launch: post_gemm), and the
 // max-pooling over the neighbourhood forward and backward.
 #include "launch.h"
+#include "split_prims.h"
 
 namespace pnpp {
 
@@ -678,7 +679,7 @@ __global__ void __launch_bounds__(256)
 pool_bwd_kernel(const float *__restrict__ dout, const int32_t *__restrict__ arg, const float *__restrict__ z,
                 const float *__restrict__ scale, const float *__restrict__ shift, const float *__restrict__ mean,
                 const float *__restrict__ istd, int G, int K, int C, float *__restrict__ dm, double *__restrict__ slab,
-                const float *__restrict__ zsel) {
+                const float *__restrict__ zsel, int policy) {
     __shared__ double red[4][2][64];
     const int cl = threadIdx.x & 63, gl = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + cl;
@@ -703,8 +704,8 @@ pool_bwd_kernel(const float *__restrict__ dout, const int32_t *__restrict__ arg,
         double a = 0.0, b = 0.0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) a += red[i][0][cl], b += red[i][1][cl];
-        slab[((size_t)blockIdx.y * 2 + 0) * C + c] = a;
-        slab[((size_t)blockIdx.y * 2 + 1) * C + c] = b;
+        sp_store(slab + ((size_t)blockIdx.y * 2 + 0) * C + c, a, (policy & ST_STAT_SLABS) != 0);
+        sp_store(slab + ((size_t)blockIdx.y * 2 + 1) * C + c, b, (policy & ST_STAT_SLABS) != 0);
     }
 }
 
@@ -717,7 +718,7 @@ int launch_pool_bwd(const float *dout, const int32_t *arg, const float *z, const
     *nslab = gy;
     ProfScope ps(st, "pool_bwd_kernel G=%d K=%d C=%d", G, K, C);
     hipLaunchKernelGGL(pool_bwd_kernel, dim3(cdiv(C, 64), gy), dim3(256), 0, st, dout, arg, z, scale, shift, mean, istd, G, K, C,
-                       dm, slab, zsel);
+                       dm, slab, zsel, store_policy());
     PNPP_CHECK_LAUNCH("pool_bwd");
     return PNPP_OK;
 }

@@ -8,6 +8,14 @@
 #include "../../include/pnpp_hip.h"
 
 namespace pnpp {
+// classes of store sites a launch's policy mask can make write-through (pnpp_set_store_policy; split_prims.h: sp_store)
+enum StorePolicy {
+    ST_DW_SLABS = 1,     // (a) dW partial slabs, read next by post_gemm / slab_reduce* / xyz0_post
+    ST_STAT_SLABS = 2,   // (b) float64 statistics slabs and moment partials
+    ST_STREAMS = 4,      // (c) streamed activation and gradient outputs
+    ST_ALL = 7
+};
+
 
 // ---- error plumbing (no exceptions across the C ABI) -----------------------------------
 void set_error(const char *fmt, ...);

@@ -4,6 +4,7 @@
 // loaders of operand_load.h; partial products go to slabs that bn_pool_kernels.hip reduces.
 #include "gemm_smallm.h"
 #include "launch.h"
+#include "split_prims.h"
 
 namespace pnpp {
 
@@ -16,7 +17,7 @@ namespace pnpp {
 template <int DZMODE, int A2MODE, int CT, int KT>
 __global__ void __launch_bounds__(256)
 dw_kernel(const AOperand dz, const AOperand a2, int M, int Nc, int Kp, int tilesC, int tilesK, int rows_per_split,
-          int kp_pad, float *__restrict__ slab) {
+          int kp_pad, float *__restrict__ slab, int policy) {
     constexpr int U = 4;  // row pairs fetched per batch: U*(CT+KT) independent loads in flight per lane
     const int lane = threadIdx.x & 63, l31 = lane & 31, lh = lane >> 5;
     const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -89,16 +90,18 @@ dw_kernel(const AOperand dz, const AOperand a2, int M, int Nc, int Kp, int tiles
         }
     }
     float *o = slab + (size_t)split * Nc * kp_pad;
+    sp_with_policy((policy & ST_DW_SLABS) != 0, [&](auto wt) {
 #pragma unroll
-    for (int i = 0; i < CT; ++i)
+        for (int i = 0; i < CT; ++i)
 #pragma unroll
-        for (int j = 0; j < KT; ++j)
+            for (int j = 0; j < KT; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int c = c0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const int k = k0 + j * 32 + l31;
-                if (c < Nc && k < kp_pad) o[(size_t)c * kp_pad + k] = acc[i][j][r];
-            }
+                for (int r = 0; r < 16; ++r) {
+                    const int c = c0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int k = k0 + j * 32 + l31;
+                    if (c < Nc && k < kp_pad) sp_store(o + (size_t)c * kp_pad + k, acc[i][j][r], wt());
+                }
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -111,7 +114,7 @@ dw_kernel(const AOperand dz, const AOperand a2, int M, int Nc, int Kp, int tiles
 // ---------------------------------------------------------------------------------------------
 template <int DZMODE, int A2MODE>  // A2MODE: A_GATHER (neighbourhoods) or A_CONCAT (group_all on raw coordinates: centre = origin)
 __global__ void __launch_bounds__(256)
-dw_xyz_kernel(const AOperand dz, const AOperand a2, int M, int C, float *__restrict__ slab) {
+dw_xyz_kernel(const AOperand dz, const AOperand a2, int M, int C, float *__restrict__ slab, int policy) {
     __shared__ float rel[256][4];
     __shared__ float red[4][64][3];
     const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6;
@@ -143,7 +146,8 @@ dw_xyz_kernel(const AOperand dz, const AOperand a2, int M, int C, float *__restr
         if (tid < 192) {
             const int ch = tid / 3, k = tid - 3 * ch;
             if (c0 + ch < C)
-                slab[((size_t)blockIdx.x * C + c0 + ch) * 4 + k] = (red[0][ch][k] + red[1][ch][k]) + (red[2][ch][k] + red[3][ch][k]);
+                sp_store(slab + ((size_t)blockIdx.x * C + c0 + ch) * 4 + k, (red[0][ch][k] + red[1][ch][k]) + (red[2][ch][k] + red[3][ch][k]),
+                         (policy & ST_DW_SLABS) != 0);
         }
         __syncthreads();
     }
@@ -155,9 +159,9 @@ int dw_xyz_splits(int M) { return cdiv(M, 256); }
 template <int A2MODE>
 static int launch_dw_xyz_a2(const AOperand &dz, int C, const AOperand &a2, int M, float *slab, dim3 grid, hipStream_t st) {
     switch (dz.mode) {
-        case A_PLAIN: hipLaunchKernelGGL((dw_xyz_kernel<A_PLAIN, A2MODE>), grid, dim3(256), 0, st, dz, a2, M, C, slab); break;
-        case A_DZ: hipLaunchKernelGGL((dw_xyz_kernel<A_DZ, A2MODE>), grid, dim3(256), 0, st, dz, a2, M, C, slab); break;
-        case A_DZ_POOL: hipLaunchKernelGGL((dw_xyz_kernel<A_DZ_POOL, A2MODE>), grid, dim3(256), 0, st, dz, a2, M, C, slab); break;
+        case A_PLAIN: hipLaunchKernelGGL((dw_xyz_kernel<A_PLAIN, A2MODE>), grid, dim3(256), 0, st, dz, a2, M, C, slab, store_policy()); break;
+        case A_DZ: hipLaunchKernelGGL((dw_xyz_kernel<A_DZ, A2MODE>), grid, dim3(256), 0, st, dz, a2, M, C, slab, store_policy()); break;
+        case A_DZ_POOL: hipLaunchKernelGGL((dw_xyz_kernel<A_DZ_POOL, A2MODE>), grid, dim3(256), 0, st, dz, a2, M, C, slab, store_policy()); break;
         default: set_error("dw_xyz: bad dZ mode %d", dz.mode); return PNPP_ERR_ARG;
     }
     return PNPP_OK;
@@ -188,7 +192,7 @@ int launch_dw_xyz(const AOperand &dz, int C, const AOperand &a2, int M, float *s
 __global__ void __launch_bounds__(256)
 gather_rel_stats_kernel(const float *__restrict__ P, const float *__restrict__ xyz, const float *__restrict__ new_xyz,
                         const int32_t *__restrict__ idx, const float *__restrict__ W0, int ldw, int N, int S, int K, int M,
-                        int C, int rpb, float *__restrict__ z, double *__restrict__ slab) {
+                        int C, int rpb, float *__restrict__ z, double *__restrict__ slab, int policy) {
     extern __shared__ __attribute__((aligned(16))) double gred[];  // [RPP][2][C]
     const int LPR = C >> 2, RPP = 256 / LPR;
     const int cl = threadIdx.x % LPR, rl = threadIdx.x / LPR, c4 = cl * 4;
@@ -225,6 +229,7 @@ gather_rel_stats_kernel(const float *__restrict__ P, const float *__restrict__ x
                 s1[e] += m, s2[e] = fmaf(m, m, s2[e]);
             }
             const int r = rb + u * RPP;
+            // (plain under every policy: 16-byte write-through buffer stores did not make this launch shorter)
             if (r < r1) *reinterpret_cast<float4 *>(z + (size_t)r * C + c4) = make_float4(v[0], v[1], v[2], v[3]);
         }
 #pragma unroll
@@ -241,7 +246,7 @@ gather_rel_stats_kernel(const float *__restrict__ P, const float *__restrict__ x
         const int which = f / C, c = f - which * C;
         double t = 0.0;
         for (int w = 0; w < RPP; ++w) t += gred[(w * 2 + which) * C + c];
-        slab[((size_t)blockIdx.x * 2 + which) * C + c] = t;
+        sp_store(slab + ((size_t)blockIdx.x * 2 + which) * C + c, t, (policy & ST_STAT_SLABS) != 0);
     }
 }
 
@@ -259,7 +264,7 @@ int launch_gather_rel_stats(const float *P, const AOperand &geo, const float *W0
     if (nslab) *nslab = grid;
     ProfScope ps(st, "gather_rel_stats_kernel M=%d C=%d grid=%d", M, C, grid);
     hipLaunchKernelGGL(gather_rel_stats_kernel, dim3(grid), dim3(256), (size_t)rpp * 2 * C * sizeof(double), st, P, geo.xyz,
-                       geo.new_xyz, geo.idx, W0, ldw, geo.N, geo.S, geo.K, M, C, rpb, z, slab);
+                       geo.new_xyz, geo.idx, W0, ldw, geo.N, geo.S, geo.K, M, C, rpb, z, slab, store_policy());
     PNPP_CHECK_LAUNCH("gather_rel_stats");
     return PNPP_OK;
 }
@@ -396,9 +401,25 @@ int launch_scatter_dz(const AOperand &dz, const AOperand &geo, int B, int Mc, in
 // and its four waves (64 x 64 each, 2 x 2 MFMA tiles) read them back lane-per-column -- every staged element feeds two
 // MFMA tiles.  Same partial-slab output as dw_kernel (slab[split][c][kp_pad]).
 // ---------------------------------------------------------------------------------------------
-template <int DZMODE, int A2MODE>
+// the 64 x 64 accumulators of a wave (2 x 2 MFMA tiles) into its partial: rows cb + 32 i + (r & 3) + 8 (r >> 2), columns kb + 32 j
+template <bool WT>
+__device__ __forceinline__ void dw_lds_tail(float *__restrict__ o, const f32x16 (&acc)[2][2], int cb, int kb, int Nc, int kp_pad) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int k = kb + j * 32;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int c = cb + i * 32 + (r & 3) + 8 * (r >> 2);
+                if (c < Nc && k < kp_pad) sp_store(o + (size_t)c * kp_pad + k, acc[i][j][r], WT);
+            }
+        }
+}
+
+template <int DZMODE, int A2MODE, bool POLICY>   // POLICY: the tail's stores take wt_dw (da_dw_kernel); else they are plain (dw_lds_kernel)
 __device__ __forceinline__ void dw_lds_body(const AOperand &dz, const AOperand &a2, int M, int Nc, int Kp, int tilesC, int tilesK, int rps,
-                                            int kp_pad, float *__restrict__ slab, int bx) {
+                                            int kp_pad, float *__restrict__ slab, int bx, const bool wt_dw) {
     __shared__ __attribute__((aligned(16))) float Dz[32][128];
     __shared__ __attribute__((aligned(16))) float A2[32][128];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -450,24 +471,21 @@ __device__ __forceinline__ void dw_lds_body(const AOperand &dz, const AOperand &
         }
     }
     float *o = slab + (size_t)split * Nc * kp_pad;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int k = k0 + wk * 64 + j * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int c = c0 + wc * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (c < Nc && k < kp_pad) o[(size_t)c * kp_pad + k] = acc[i][j][r];
-            }
-        }
+    // (a function, not a lambda: through a lambda's captures dw_lds_kernel<A0,A3> takes 66 registers instead of 60 and loses a wave per SIMD)
+    if constexpr (POLICY) {
+        if (wt_dw) dw_lds_tail<true>(o, acc, c0 + wc * 64 + 4 * lh, k0 + wk * 64 + l31, Nc, kp_pad);
+        else dw_lds_tail<false>(o, acc, c0 + wc * 64 + 4 * lh, k0 + wk * 64 + l31, Nc, kp_pad);
+    } else {
+        dw_lds_tail<false>(o, acc, c0 + wc * 64 + 4 * lh, k0 + wk * 64 + l31, Nc, kp_pad);
+    }
 }
 
 template <int DZMODE, int A2MODE>
 __global__ void __launch_bounds__(256)
 dw_lds_kernel(const AOperand dz, const AOperand a2, int M, int Nc, int Kp, int tilesC, int tilesK, int rps, int kp_pad,
               float *__restrict__ slab) {
-    dw_lds_body<DZMODE, A2MODE>(dz, a2, M, Nc, Kp, tilesC, tilesK, rps, kp_pad, slab, blockIdx.x);
+    // (plain under every policy: the launches of this kernel are not in the measured step; da_dw_kernel, which shares the body, takes it)
+    dw_lds_body<DZMODE, A2MODE, false>(dz, a2, M, Nc, Kp, tilesC, tilesK, rps, kp_pad, slab, blockIdx.x, false);
 }
 
 // The two products of a small-M backward layer that only share their input -- dA = dZ W (32 x 32 split-K tiles) and
@@ -480,7 +498,7 @@ da_dw_kernel(const AOperand dzA, const BOperand W, int M, int Nout, int Kd, cons
     if ((int)blockIdx.x < g1)
         gemm_smallm_body<A_PLAIN, EMODE, false, 4>(dzA, W, M, Nout, Kd, E, blockIdx.x % g1x, blockIdx.x / g1x, g1);
     else
-        dw_lds_body<A_PLAIN, A2MODE>(dzA, a2, M, Nc, Kp, tilesC, tilesK, rps, kp_pad, slab, blockIdx.x - g1);
+        dw_lds_body<A_PLAIN, A2MODE, true>(dzA, a2, M, Nc, Kp, tilesC, tilesK, rps, kp_pad, slab, blockIdx.x - g1, (E.store_policy & ST_DW_SLABS) != 0);
 }
 
 void dw_plan(int M, int Nc, int Kp, int *nsplit, int *kp_pad) {
@@ -529,7 +547,7 @@ int launch_dw(const AOperand &dz, int Nc, const AOperand &a2, int Kp, int M, flo
     const dim3 grid(cdiv(waves, 4)), block(256);
     ProfScope ps(st, "dw_kernel<A%d,A%d> M=%d N=%d K=%d split=%d grid=%dx1", dz.mode, a2.mode, M, Nc, Kp, nsplit, grid.x);
 #define PNPP_DW(DM, AM)                                                                                              \
-    hipLaunchKernelGGL((dw_kernel<DM, AM, 2, 2>), grid, block, 0, st, dz, a2, M, Nc, Kp, tilesC, tilesK, rps, kp_pad, slab); \
+    hipLaunchKernelGGL((dw_kernel<DM, AM, 2, 2>), grid, block, 0, st, dz, a2, M, Nc, Kp, tilesC, tilesK, rps, kp_pad, slab, store_policy()); \
     break;
 #define PNPP_DW_BY_A(DM)                         \
     switch (a2.mode) {                           \
@@ -554,9 +572,11 @@ int launch_dw(const AOperand &dz, int Nc, const AOperand &a2, int Kp, int M, flo
 
 // dA (+ its epilogue) and dW of one small-M backward layer in one launch; returns false (nothing launched) when the
 // pair does not fit that form, and the caller launches the two separately.
-bool try_launch_da_dw(const AOperand &dz, const BOperand &Win, int M, int Nout, int Kd, const Epilogue &E, int *nslab, const AOperand &a2,
+bool try_launch_da_dw(const AOperand &dz, const BOperand &Win, int M, int Nout, int Kd, const Epilogue &Ein, int *nslab, const AOperand &a2,
                       int Kp, float *slab, int *nsplit_io, int *kp_pad_io, hipStream_t st, int *rc, float *dw_direct, int dw_ld) {
     *rc = PNPP_OK;
+    Epilogue E = Ein;
+    E.store_policy = store_policy();
     if (mid_tiles_on() && try_launch_mid_da_dw(dz, Win, M, Nout, Kd, E, nslab, a2, Kp, slab, nsplit_io, kp_pad_io, st, rc, dw_direct, dw_ld))
         return true;   // wide layers of a group_all level: 64 x 64 tiles over the whole reduction, no 64-row partials
     const int nsplit = *nsplit_io, kp_pad = *kp_pad_io;

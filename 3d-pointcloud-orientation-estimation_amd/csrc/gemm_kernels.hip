@@ -317,8 +317,10 @@ bool gemm_pools_in_epilogue(const AOperand &A, int M, int Nout, int Kd, int nsam
     return Kd == 64 || Kd == 128 || Kd == 256;
 }
 
-int launch_gemm(const AOperand &A, const BOperand &Bin, int M, int Nout, int Kd, const Epilogue &E, int *nslab,
+int launch_gemm(const AOperand &A, const BOperand &Bin, int M, int Nout, int Kd, const Epilogue &Ein, int *nslab,
                 hipStream_t st, int *dw_slabs) {
+    Epilogue E = Ein;
+    E.store_policy = store_policy();
     if (dw_slabs) *dw_slabs = 0;
     PNPP_REQUIRE(M > 0 && Nout > 0 && Kd > 0, PNPP_ERR_ARG, "gemm: non-positive size M=%d N=%d K=%d", M, Nout, Kd);
     PNPP_REQUIRE(Bin.b && Bin.ldb > 0, PNPP_ERR_ARG, "gemm: null B operand");

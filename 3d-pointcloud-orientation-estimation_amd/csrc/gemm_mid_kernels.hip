@@ -201,20 +201,22 @@ __device__ __forceinline__ void mid_gemm_tile(const MidGemm &G, const int tm, co
     }
     float *tb = E.c + (size_t)(m0 + wm * 32 + 4 * lh) * E.ldc + col;
     float t1 = 0.f, t2 = 0.f;
+    sp_with_policy((E.store_policy & ST_STREAMS) != 0, [&](auto wt) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float v = acc[r];
-        if constexpr (EM == E_STORE_STATS) {
-            t1 += v;
-            t2 = fmaf(v, v, t2);
-        } else if constexpr (EM == E_MASK_STATS) {
-            const float z0 = zp[r];
-            v = fmaf(z0, e_sc, e_sh) > 0.f ? v : 0.f;
-            t1 += v;
-            t2 = fmaf(v, (z0 - e_mu) * e_is, t2);
+        for (int r = 0; r < 16; ++r) {
+            float v = acc[r];
+            if constexpr (EM == E_STORE_STATS) {
+                t1 += v;
+                t2 = fmaf(v, v, t2);
+            } else if constexpr (EM == E_MASK_STATS) {
+                const float z0 = zp[r];
+                v = fmaf(z0, e_sc, e_sh) > 0.f ? v : 0.f;
+                t1 += v;
+                t2 = fmaf(v, (z0 - e_mu) * e_is, t2);
+            }
+            sp_store(tb + (size_t)((r & 3) + 8 * (r >> 2)) * E.ldc, v, wt());
         }
-        tb[(size_t)((r & 3) + 8 * (r >> 2)) * E.ldc] = v;
-    }
+    });
     if constexpr (EM != E_STORE) {
         // column sums of the tile: the two row halves of a wave, then the two waves of a column, in fixed order
         __syncthreads();                                 // every operand read of the last chunk is done
@@ -224,14 +226,15 @@ __device__ __forceinline__ void mid_gemm_tile(const MidGemm &G, const int tm, co
         __syncthreads();
         if (tid < 2 * MID_T) {
             const int which = tid >> 6, cl = tid & 63;
-            E.slab[((size_t)tm * 2 + which) * G.N + n0 + cl] = red[(0 * 2 + which) * MID_T + cl] + red[(1 * 2 + which) * MID_T + cl];
+            sp_store(E.slab + ((size_t)tm * 2 + which) * G.N + n0 + cl, red[(0 * 2 + which) * MID_T + cl] + red[(1 * 2 + which) * MID_T + cl],
+                     (E.store_policy & ST_STAT_SLABS) != 0);
         }
     }
 }
 
 // ---- dW tile (64 x 64) = dZ^T a2 over one row range, one workgroup -------------------------------------------------------
 template <int A2X>
-__device__ __forceinline__ void mid_dw_tile(const MidDw &D, const int tc, const int tk, const int split, float *__restrict__ lds) {
+__device__ __forceinline__ void mid_dw_tile(const MidDw &D, const int tc, const int tk, const int split, float *__restrict__ lds, const bool wt_dw) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5, wc = wave >> 1, wk = wave & 1;
     const int q4 = 4 * (tid & 15), rb = tid >> 4;
@@ -309,8 +312,10 @@ __device__ __forceinline__ void mid_dw_tile(const MidDw &D, const int tc, const 
         }
     }
     float *o = D.out + ((size_t)split * D.Nc + c0 + wc * 32 + 4 * lh) * D.ldo + k0 + wk * 32 + l31;
+    sp_with_policy(wt_dw, [&](auto wt) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o[(size_t)((r & 3) + 8 * (r >> 2)) * D.ldo] = acc[r];
+        for (int r = 0; r < 16; ++r) sp_store(o + (size_t)((r & 3) + 8 * (r >> 2)) * D.ldo, acc[r], wt());
+    });
 }
 
 // XCD-aware tile map (speed only).  Workgroup b runs on XCD b % 8, each with its own L2: a column of tiles per XCD makes every XCD
@@ -350,7 +355,7 @@ __global__ void __launch_bounds__(256) da_dw_mid_kernel(const MidGemm G, int til
         int tc, tk;
         if ((g1 & 7) == 0 && (per & 7) == 0) mid_tile_map(b % per, tiles_c, tiles_k, tc, tk);   // (b % per) % 8 is still this block's XCD
         else tc = (b % per) / tiles_k, tk = (b % per) % tiles_k;
-        mid_dw_tile<A2X>(D, tc, tk, b / per, lds);
+        mid_dw_tile<A2X>(D, tc, tk, b / per, lds, (G.E.store_policy & ST_DW_SLABS) != 0);
     }
 }
 
@@ -542,13 +547,15 @@ __global__ void __launch_bounds__(512, 1) gemm_mid3_kernel(const MidGemm G, int 
             }
         }
         float *tb = E.c + (size_t)(m0 + wm * 32 + 4 * lh) * E.ldc + col;
+        sp_with_policy((E.store_policy & ST_STREAMS) != 0, [&](auto wt) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float v = acc[r];
-            t1 += v;
-            t2 = fmaf(v, v, t2);
-            tb[(size_t)((r & 3) + 8 * (r >> 2)) * E.ldc] = v;
-        }
+            for (int r = 0; r < 16; ++r) {
+                const float v = acc[r];
+                t1 += v;
+                t2 = fmaf(v, v, t2);
+                sp_store(tb + (size_t)((r & 3) + 8 * (r >> 2)) * E.ldc, v, wt());
+            }
+        });
     }
     if constexpr (EM == E_STORE_STATS) {
         __syncthreads();                                  // every operand read of the last chunk is done
@@ -560,7 +567,8 @@ __global__ void __launch_bounds__(512, 1) gemm_mid3_kernel(const MidGemm G, int 
         __syncthreads();
         if (tid < 2 * MID_T) {
             const int which = tid >> 6, cl = tid & 63;
-            E.slab[((size_t)tm * 2 + which) * G.N + n0 + cl] = red[(0 * 2 + which) * MID_T + cl] + red[(1 * 2 + which) * MID_T + cl];
+            sp_store(E.slab + ((size_t)tm * 2 + which) * G.N + n0 + cl, red[(0 * 2 + which) * MID_T + cl] + red[(1 * 2 + which) * MID_T + cl],
+                     (E.store_policy & ST_STAT_SLABS) != 0);
         }
     }
 #ifdef MID3_STAMPS
@@ -642,6 +650,7 @@ bool try_launch_mid_da_dw(const AOperand &dz, const BOperand &W, int M, int Nout
     if (E.mode == E_MASK_STATS && !mid_ptr_ok(E.zp, E.ldc)) return false;
     if (M / MID_T > kMaxStatBlocks) return false;
     MidGemm G{dz.a, dz.lda, nullptr, nullptr, W.b, W.ldb, M, Nout, Kd, E};
+    G.E.store_policy = store_policy();
     MidDw D{dz.a, dz.lda, a2.a, a2.lda, a2.scale, a2.shift, M, Nc, Kp, nsplit, M / nsplit, slab, Kp};
     const bool in_place = nsplit == 1 && dw_direct && dw_ld == Kp;   // a single row range: no partial sums, no reduction launch
     if (in_place) D.out = dw_direct, D.ldo = dw_ld;

@@ -124,6 +124,7 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
         col_blk = i % ncol, worker = (i / ncol) * 8 + xcd;
     }
     const int n0 = col_blk * BN;
+    const bool wt_stream = (E.store_policy & ST_STREAMS) != 0;
     const int nstrips = M / 32, stride = nworkers * 4;
     int strip = worker * 4 + pair;
     const __amdgpu_buffer_rsrc_t resNull = sp_buf_rsrc_null(A.z);
@@ -474,14 +475,16 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
             {
                 const unsigned sc_off = (unsigned)strip * (32u * (unsigned)Nout * 4u);
                 float t1 = 0.f, t2 = 0.f;
+                sp_with_policy(wt_stream, [&](auto wt) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float v = fmaf(zq[r], e_sc, e_sh) > 0.f ? (ACC2 ? acc[r] + accs[r] : acc[r]) : 0.f;   // (the mask is recomputed: a bit per row built
-                                                                                                           //  at the strip's start was a chain of 48 dependent instructions)
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), resC, (int)oq, (int)(sc_off + quni(r)), 0);
-                    t1 += v;
-                    t2 = fmaf(v, zq[r], t2);
-                }
+                    for (int r = 0; r < 16; ++r) {
+                        const float v = fmaf(zq[r], e_sc, e_sh) > 0.f ? (ACC2 ? acc[r] + accs[r] : acc[r]) : 0.f;   // (the mask is recomputed: a bit per row built
+                                                                                                               //  at the strip's start was a chain of 48 dependent instructions)
+                        sp_buf_store1(v, resC, oq, sc_off + quni(r), wt());
+                        t1 += v;
+                        t2 = fmaf(v, zq[r], t2);
+                    }
+                });
                 const double d1 = (double)t1;   // sum v xhat = istd (sum v z - mu sum v), finished in float64
                 s1 += d1, s2 += (double)e_is * ((double)t2 - (double)e_mu * d1);
             }
@@ -518,22 +521,25 @@ gemm_wsd3_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, 
     __syncthreads();
     {
         float *wb = E.dwslab + (size_t)worker * KD * E.dw_ld + n0;
-        for (int t = wave; t < CT; t += 8) {   // c-tile t
+        const bool wt_dw = (E.store_policy & ST_DW_SLABS) != 0, wt_stats = (E.store_policy & ST_STAT_SLABS) != 0;
+        sp_with_policy(wt_dw, [&](auto wt) {
+            for (int t = wave; t < CT; t += 8) {   // c-tile t
 #pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const f32x4 a0 = red[((t * 4 + 0) * 4 + r4) * 64 + lane], a1 = red[((t * 4 + 1) * 4 + r4) * 64 + lane];
-                const f32x4 a2 = red[((t * 4 + 2) * 4 + r4) * 64 + lane], a3 = red[((t * 4 + 3) * 4 + r4) * 64 + lane];
-                const int c0 = t * 32 + 8 * r4 + 4 * lh;
-                float *o = wb + (size_t)c0 * E.dw_ld + l31;
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const f32x4 a0 = red[((t * 4 + 0) * 4 + r4) * 64 + lane], a1 = red[((t * 4 + 1) * 4 + r4) * 64 + lane];
+                    const f32x4 a2 = red[((t * 4 + 2) * 4 + r4) * 64 + lane], a3 = red[((t * 4 + 3) * 4 + r4) * 64 + lane];
+                    const int c0 = t * 32 + 8 * r4 + 4 * lh;
+                    float *o = wb + (size_t)c0 * E.dw_ld + l31;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[(size_t)e * E.dw_ld] = (a0[e] + a1[e]) + (a2[e] + a3[e]);
+                    for (int e = 0; e < 4; ++e) sp_store(o + (size_t)e * E.dw_ld, (a0[e] + a1[e]) + (a2[e] + a3[e]), wt());
+                }
             }
-        }
+        });
         if (tid < 2 * BN) {
             const int which = tid / BN, cl = tid % BN;
             const double t = (dred[(0 * 2 + which) * BN + cl] + dred[(1 * 2 + which) * BN + cl]) +
                              (dred[(2 * 2 + which) * BN + cl] + dred[(3 * 2 + which) * BN + cl]);
-            E.slab[((size_t)worker * 2 + which) * Nout + n0 + cl] = t;
+            sp_store(E.slab + ((size_t)worker * 2 + which) * Nout + n0 + cl, t, wt_stats);
         }
     }
 }

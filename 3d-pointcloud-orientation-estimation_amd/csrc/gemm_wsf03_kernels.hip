@@ -35,6 +35,7 @@ gemm_wsf03_kernel(const Wsf0Args P) {
     const int worker = blockIdx.x, nworkers = gridDim.x;
     const int nstrips = P.M / 32, stride = nworkers * 4;
     int strip = worker * 4 + wave;
+    const bool wt_stream = (P.store_policy & ST_STREAMS) != 0;
     const __amdgpu_buffer_rsrc_t resI = sp_buf_rsrc(P.idx), resX = sp_buf_rsrc(P.xyz), resC = sp_buf_rsrc(P.centres);
     const __amdgpu_buffer_rsrc_t resNull = sp_buf_rsrc_null(P.xyz);
     int nidx;
@@ -211,18 +212,20 @@ gemm_wsf03_kernel(const Wsf0Args P) {
             }
         fetch_geo(nX, nC, snext);   // the next strip's coordinates: its indices were requested a whole product ago
         float *tb = P.z1 + (size_t)(strip * 32 + 4 * lh) * 64 + l31;
+        sp_with_policy(wt_stream, [&](auto wt) {
 #pragma unroll
-        for (int jn = 0; jn < 2; ++jn) {
-            float t1 = 0.f, t2 = 0.f;
+            for (int jn = 0; jn < 2; ++jn) {
+                float t1 = 0.f, t2 = 0.f;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v = acc[jn][r] + accs[jn][r];
-                tb[(size_t)((r & 3) + 8 * (r >> 2)) * 64 + jn * 32] = v;
-                t1 += v;
-                t2 = fmaf(v, v, t2);
+                for (int r = 0; r < 16; ++r) {
+                    const float v = acc[jn][r] + accs[jn][r];
+                    sp_store(tb + (size_t)((r & 3) + 8 * (r >> 2)) * 64 + jn * 32, v, wt());
+                    t1 += v;
+                    t2 = fmaf(v, v, t2);
+                }
+                if constexpr (EM == E_STORE_STATS) s1[jn] += (double)t1, s2[jn] += (double)t2;
             }
-            if constexpr (EM == E_STORE_STATS) s1[jn] += (double)t1, s2[jn] += (double)t2;
-        }
+        });
     }
     if constexpr (EM == E_STORE_STATS) {
         __syncthreads();   // every wave is done with the weight image
@@ -237,7 +240,7 @@ gemm_wsf03_kernel(const Wsf0Args P) {
             const int which = tid / BN, cl = tid % BN;
             const double t = (red[(0 * 2 + which) * BN + cl] + red[(1 * 2 + which) * BN + cl]) +
                              (red[(2 * 2 + which) * BN + cl] + red[(3 * 2 + which) * BN + cl]);
-            P.slab[((size_t)worker * 2 + which) * 64 + cl] = t;
+            sp_store(P.slab + ((size_t)worker * 2 + which) * 64 + cl, t, (P.store_policy & ST_STAT_SLABS) != 0);
         }
     }
 }

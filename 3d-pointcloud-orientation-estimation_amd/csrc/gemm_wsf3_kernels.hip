@@ -39,6 +39,7 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
         col_blk = i % ncol, worker = (i / ncol) * 8 + xcd;
     }
     const int n0 = col_blk * BN;
+    const bool wt_stream = (E.store_policy & ST_STREAMS) != 0, wt_stats = (E.store_policy & ST_STAT_SLABS) != 0;
 
     // per-channel constants of this lane's column group (k = 64 c + 4 q .. + 3)
     const int q = lane & 15, q4 = 4 * q, rb = lane >> 4;   // staging map: column group lane % 16, rows lane / 16 + 4 i
@@ -173,19 +174,24 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
     // epilogue of tiles 2 hh, 2 hh + 1 of the strip: 16 rows of one column per lane and column tile
     auto epilogue = [&](int hh, f32x16 (&acc)[2], f32x16 (&accl)[2]) {
         float *tb = E.c + (size_t)(strip * 32 + 4 * lh) * E.ldc + n0 + l31;
+        float t1[2] = {0.f, 0.f}, t2[2] = {0.f, 0.f};
+        sp_with_policy(wt_stream, [&](auto wt) {   // ONE branch for both tiles' stores (a branch per tile cost the K = 64 launch 1.5 us of 27)
+#pragma unroll
+            for (int j2 = 0; j2 < 2; ++j2) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float v = acc[j2][r] + accl[j2][r];
+                    acc[j2][r] = v;
+                    sp_store(tb + (size_t)((r & 3) + 8 * (r >> 2)) * E.ldc + (2 * hh + j2) * 32, v, wt());
+                    t1[j2] += v, t2[j2] = fmaf(v, v, t2[j2]);
+                }
+            }
+        });
 #pragma unroll
         for (int j2 = 0; j2 < 2; ++j2) {
             const int j = 2 * hh + j2;
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v = acc[j2][r] + accl[j2][r];
-                acc[j2][r] = v;
-                tb[(size_t)((r & 3) + 8 * (r >> 2)) * E.ldc + j * 32] = v;
-                t1 += v, t2 = fmaf(v, v, t2);
-            }
             if constexpr (EM == E_STORE_STATS) {
-                s1[j] += (double)t1, s2[j] += (double)t2;
+                s1[j] += (double)t1[j2], s2[j] += (double)t2[j2];
                 if (E.pool_ext) {   // the strip is one neighbourhood: extreme pre-BN value per column and its first row
                     float mx = sg[j] * acc[j2][0];
 #pragma unroll
@@ -250,7 +256,7 @@ gemm_wsf3_kernel(const float *__restrict__ A, int lda, const float *__restrict__
             double t = 0.0;
 #pragma unroll
             for (int w = 0; w < NW; ++w) t += red[(w * 2 + which) * BN + cl];
-            E.slab[((size_t)worker * 2 + which) * Nout + n0 + cl] = t;
+            sp_store(E.slab + ((size_t)worker * 2 + which) * Nout + n0 + cl, t, wt_stats);
         }
     }
 }
@@ -263,6 +269,13 @@ int split_products() {
     return g_split_products;
 }
 void set_split_products(int on) { g_split_products = on ? 1 : 0; }
+
+// Which classes of store sites write through (common.h: StorePolicy).  No environment switch: pnpp_set_store_policy is the one way in.
+// Ships: the dW partial slabs and the streamed outputs; the float64 statistics slabs stay plain (no launch moved with them).  What each
+// class measured: profiles/store_policy_kernel_stats.csv, DESIGN.md section 9.
+static int g_store_policy = ST_DW_SLABS | ST_STREAMS;
+int store_policy() { return g_store_policy; }
+void set_store_policy(int mask) { g_store_policy = mask & ST_ALL; }
 
 template <int KD, int NW, int NT, int AX, int EM>
 static void wsf3_launch(const AOperand &A, const BOperand &B, int M, int Nout, const Epilogue &E, int workers, int ncol, hipStream_t st) {
@@ -301,3 +314,12 @@ extern "C" int pnpp_set_split_products(int on) {
     return PNPP_OK;
 }
 extern "C" int pnpp_get_split_products(void) { return pnpp::split_products(); }
+extern "C" int pnpp_set_store_policy(int mask) {
+    if (mask < 0 || mask > pnpp::ST_ALL) {
+        pnpp::set_error("pnpp_set_store_policy: mask %d has bits outside %d", mask, (int)pnpp::ST_ALL);
+        return PNPP_ERR_ARG;
+    }
+    pnpp::set_store_policy(mask);
+    return PNPP_OK;
+}
+extern "C" int pnpp_get_store_policy(void) { return pnpp::store_policy(); }

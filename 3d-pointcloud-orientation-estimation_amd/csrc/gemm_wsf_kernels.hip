@@ -188,12 +188,14 @@ gemm_wsf_kernel(const float *__restrict__ A, int lda, const float *__restrict__ 
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             float t1 = 0.f, t2 = 0.f;
+            sp_with_policy((E.store_policy & ST_STREAMS) != 0, [&](auto wt) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v = acc[j][r];
-                if (!(WSF_EXP & 1)) tb[(size_t)((r & 3) + 8 * (r >> 2)) * E.ldc + j * 32] = v;
-                if (!(WSF_EXP & 8)) t1 += v, t2 = fmaf(v, v, t2);
-            }
+                for (int r = 0; r < 16; ++r) {
+                    const float v = acc[j][r];
+                    if (!(WSF_EXP & 1)) sp_store(tb + (size_t)((r & 3) + 8 * (r >> 2)) * E.ldc + j * 32, v, wt());
+                    if (!(WSF_EXP & 8)) t1 += v, t2 = fmaf(v, v, t2);
+                }
+            });
             if constexpr (EM == E_STORE_STATS && !(WSF_EXP & 8)) {
                 s1[j] += (double)t1, s2[j] += (double)t2;
                 if (E.pool_ext) {   // the strip is one neighbourhood: extreme pre-BN value per column and its first row
@@ -230,7 +232,7 @@ gemm_wsf_kernel(const float *__restrict__ A, int lda, const float *__restrict__ 
             const int which = f / BN, cl = f % BN;
             const double t = (red[(0 * 2 + which) * BN + cl] + red[(1 * 2 + which) * BN + cl]) +
                              (red[(2 * 2 + which) * BN + cl] + red[(3 * 2 + which) * BN + cl]);
-            E.slab[((size_t)worker * 2 + which) * Nout + n0 + cl] = t;
+            sp_store(E.slab + ((size_t)worker * 2 + which) * Nout + n0 + cl, t, (E.store_policy & ST_STAT_SLABS) != 0);
         }
     }
     WSF_STAMP(4)   // tail

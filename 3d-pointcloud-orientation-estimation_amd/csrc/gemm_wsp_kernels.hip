@@ -374,20 +374,23 @@ gemm_wsp_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, c
             asum[j] = (float)((ared[k] + ared[BN + k]) + (ared[2 * BN + k] + ared[3 * BN + k]));
         }
         float *wb = E.dwslab + (size_t)worker * KD * 64;
+        sp_with_policy((E.store_policy & ST_DW_SLABS) != 0, [&](auto wt) {
 #pragma unroll
-        for (int tt = 0; tt < NTILE / 4; ++tt) {
-            const int t = wave + 4 * tt, i = t >> 1, j = t & 1;
+            for (int tt = 0; tt < NTILE / 4; ++tt) {
+                const int t = wave + 4 * tt, i = t >> 1, j = t & 1;
 #pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const f32x4 a0 = red[((t * 4 + 0) * 4 + r4) * 64 + lane], a1 = red[((t * 4 + 1) * 4 + r4) * 64 + lane];
-                const f32x4 a2 = red[((t * 4 + 2) * 4 + r4) * 64 + lane], a3 = red[((t * 4 + 3) * 4 + r4) * 64 + lane];
-                const int c0 = i * 32 + 8 * r4 + 4 * lh;
-                const f32x4 sc = *reinterpret_cast<const f32x4 *>(Tsc + c0), bb = *reinterpret_cast<const f32x4 *>(Tb + c0);
-                float *o = wb + (size_t)c0 * 64 + j * 32 + l31;
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const f32x4 a0 = red[((t * 4 + 0) * 4 + r4) * 64 + lane], a1 = red[((t * 4 + 1) * 4 + r4) * 64 + lane];
+                    const f32x4 a2 = red[((t * 4 + 2) * 4 + r4) * 64 + lane], a3 = red[((t * 4 + 3) * 4 + r4) * 64 + lane];
+                    const int c0 = i * 32 + 8 * r4 + 4 * lh;
+                    const f32x4 sc = *reinterpret_cast<const f32x4 *>(Tsc + c0), bb = *reinterpret_cast<const f32x4 *>(Tb + c0);
+                    float *o = wb + (size_t)c0 * 64 + j * 32 + l31;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e * 64] = fmaf(sc[e], (a0[e] + a1[e]) + (a2[e] + a3[e]), bb[e] * (j == 0 ? asum[0] : asum[1]));
+                    for (int e = 0; e < 4; ++e)
+                        sp_store(o + e * 64, fmaf(sc[e], (a0[e] + a1[e]) + (a2[e] + a3[e]), bb[e] * (j == 0 ? asum[0] : asum[1])), wt());
+                }
             }
-        }
+        });
     }
     // ---- column statistics of the worker ----
     __syncthreads();
@@ -402,7 +405,7 @@ gemm_wsp_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, c
         const int which = tid / BN, cl = tid % BN;
         const double t = (dred[(0 * 2 + which) * BN + cl] + dred[(1 * 2 + which) * BN + cl]) +
                          (dred[(2 * 2 + which) * BN + cl] + dred[(3 * 2 + which) * BN + cl]);
-        E.slab[((size_t)worker * 2 + which) * BN + cl] = t;
+        sp_store(E.slab + ((size_t)worker * 2 + which) * BN + cl, t, (E.store_policy & ST_STAT_SLABS) != 0);
     }
     WSP_STAMP(9)   // tail: dW partial through LDS, statistics
 #ifdef PNPP_STAMPS

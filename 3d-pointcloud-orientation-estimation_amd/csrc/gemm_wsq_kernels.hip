@@ -360,27 +360,30 @@ gemm_wsq_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, i
         __syncthreads();
         const float asum = (float)(ared[(0 * 2 + wn) * 32 + l31] + ared[(1 * 2 + wn) * 32 + l31]);
         float *wb = E.dwslab + (size_t)worker * KD * E.dw_ld + n0 + 32 * wn + l31;
+        const bool wt_dw = (E.store_policy & ST_DW_SLABS) != 0;
+        sp_with_policy(wt_dw, [&](auto wtc) {
 #pragma unroll
-        for (int i = 0; i < CT; ++i) {
-            if ((i >> 2) == wm) {
+            for (int i = 0; i < CT; ++i) {
+                if ((i >> 2) == wm) {
 #pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    const f32x4 o = red[((((wn * 2 + wm) * 4 + (i & 3)) * 4 + r4) * 64) + lane];
-                    const int c0 = i * 32 + 8 * r4 + 4 * lh;
-                    const f32x4 sc = *reinterpret_cast<const f32x4 *>(Tsc + c0), bb = *reinterpret_cast<const f32x4 *>(Tb + c0);
-                    float *op = wb + (size_t)c0 * E.dw_ld;
-                    // rows in (wm = 0) + (wm = 1) order whichever wave adds them
-                    const float x0 = wm == 0 ? dw[i][4 * r4] + o[0] : o[0] + dw[i][4 * r4];
-                    const float x1 = wm == 0 ? dw[i][4 * r4 + 1] + o[1] : o[1] + dw[i][4 * r4 + 1];
-                    const float x2 = wm == 0 ? dw[i][4 * r4 + 2] + o[2] : o[2] + dw[i][4 * r4 + 2];
-                    const float x3 = wm == 0 ? dw[i][4 * r4 + 3] + o[3] : o[3] + dw[i][4 * r4 + 3];
-                    op[0] = fmaf(sc[0], x0, bb[0] * asum);
-                    op[(size_t)E.dw_ld] = fmaf(sc[1], x1, bb[1] * asum);
-                    op[(size_t)2 * E.dw_ld] = fmaf(sc[2], x2, bb[2] * asum);
-                    op[(size_t)3 * E.dw_ld] = fmaf(sc[3], x3, bb[3] * asum);
+                    for (int r4 = 0; r4 < 4; ++r4) {
+                        const f32x4 o = red[((((wn * 2 + wm) * 4 + (i & 3)) * 4 + r4) * 64) + lane];
+                        const int c0 = i * 32 + 8 * r4 + 4 * lh;
+                        const f32x4 sc = *reinterpret_cast<const f32x4 *>(Tsc + c0), bb = *reinterpret_cast<const f32x4 *>(Tb + c0);
+                        float *op = wb + (size_t)c0 * E.dw_ld;
+                        // rows in (wm = 0) + (wm = 1) order whichever wave adds them
+                        const float x0 = wm == 0 ? dw[i][4 * r4] + o[0] : o[0] + dw[i][4 * r4];
+                        const float x1 = wm == 0 ? dw[i][4 * r4 + 1] + o[1] : o[1] + dw[i][4 * r4 + 1];
+                        const float x2 = wm == 0 ? dw[i][4 * r4 + 2] + o[2] : o[2] + dw[i][4 * r4 + 2];
+                        const float x3 = wm == 0 ? dw[i][4 * r4 + 3] + o[3] : o[3] + dw[i][4 * r4 + 3];
+                        sp_store(op, fmaf(sc[0], x0, bb[0] * asum), wtc());
+                        sp_store(op + (size_t)E.dw_ld, fmaf(sc[1], x1, bb[1] * asum), wtc());
+                        sp_store(op + (size_t)2 * E.dw_ld, fmaf(sc[2], x2, bb[2] * asum), wtc());
+                        sp_store(op + (size_t)3 * E.dw_ld, fmaf(sc[3], x3, bb[3] * asum), wtc());
+                    }
                 }
             }
-        }
+        });
     }
     // ---- column statistics of the worker ----
     __syncthreads();
@@ -393,7 +396,7 @@ gemm_wsq_kernel(const AOperand A, const float *__restrict__ W, int ldw, int M, i
     if (tid < 2 * BN) {
         const int which = tid / BN, cl = tid % BN, w2 = cl >> 5, c5 = cl & 31;
         const double t = dred[((0 * 2 + w2) * 2 + which) * 32 + c5] + dred[((1 * 2 + w2) * 2 + which) * 32 + c5];
-        E.slab[((size_t)worker * 2 + which) * Nout + n0 + cl] = t;
+        sp_store(E.slab + ((size_t)worker * 2 + which) * Nout + n0 + cl, t, (E.store_policy & ST_STAT_SLABS) != 0);
     }
     WSQ_STAMP(9)   // tail
 #ifdef PNPP_STAMPS

@@ -39,6 +39,7 @@ struct WsxArgs {
     const float *scale0, *shift0;
     float *dwslab;               // [workers][KD][64]
     double *xslab;               // [workers][kWsxSlab]
+    int store_policy;            // StorePolicy bits (common.h)
 };
 
 #ifndef WSX_EXP   // timing experiments (wrong results): 2 no dW loop, 4 no dA loop, 8 no epilogue arithmetic
@@ -485,22 +486,26 @@ gemm_wsx_kernel(const WsxArgs P) {
             asum[j] = (float)((ared[k] + ared[BN + k]) + (ared[2 * BN + k] + ared[3 * BN + k]));
         }
         float *wb = P.dwslab + (size_t)worker * KD * 64;
+        const bool wt_dw = (P.store_policy & ST_DW_SLABS) != 0;
+        sp_with_policy(wt_dw, [&](auto wt) {
 #pragma unroll
-        for (int tt = 0; tt < (NTILE + 3) / 4; ++tt) {
-            const int t = wave + 4 * tt, i = t >> 1, j = t & 1;
-            if (t < NTILE) {
+            for (int tt = 0; tt < (NTILE + 3) / 4; ++tt) {
+                const int t = wave + 4 * tt, i = t >> 1, j = t & 1;
+                if (t < NTILE) {
 #pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    const f32x4 a0 = red[((t * 4 + 0) * 4 + r4) * 64 + lane], a1 = red[((t * 4 + 1) * 4 + r4) * 64 + lane];
-                    const f32x4 a2 = red[((t * 4 + 2) * 4 + r4) * 64 + lane], a3 = red[((t * 4 + 3) * 4 + r4) * 64 + lane];
-                    const int c0 = i * 32 + 8 * r4 + 4 * lh;
-                    const f32x4 sc = *reinterpret_cast<const f32x4 *>(Tsc + c0), bb = *reinterpret_cast<const f32x4 *>(Tb + c0);
-                    float *o = wb + (size_t)c0 * 64 + j * 32 + l31;
+                    for (int r4 = 0; r4 < 4; ++r4) {
+                        const f32x4 a0 = red[((t * 4 + 0) * 4 + r4) * 64 + lane], a1 = red[((t * 4 + 1) * 4 + r4) * 64 + lane];
+                        const f32x4 a2 = red[((t * 4 + 2) * 4 + r4) * 64 + lane], a3 = red[((t * 4 + 3) * 4 + r4) * 64 + lane];
+                        const int c0 = i * 32 + 8 * r4 + 4 * lh;
+                        const f32x4 sc = *reinterpret_cast<const f32x4 *>(Tsc + c0), bb = *reinterpret_cast<const f32x4 *>(Tb + c0);
+                        float *o = wb + (size_t)c0 * 64 + j * 32 + l31;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e * 64] = fmaf(sc[e], (a0[e] + a1[e]) + (a2[e] + a3[e]), bb[e] * (j == 0 ? asum[0] : asum[1]));
+                        for (int e = 0; e < 4; ++e)
+                            sp_store(o + e * 64, fmaf(sc[e], (a0[e] + a1[e]) + (a2[e] + a3[e]), bb[e] * (j == 0 ? asum[0] : asum[1])), wt());
+                    }
                 }
             }
-        }
+        });
     }
     // ---- the worker's sums for layer 0: lane halves, then the four waves in wave order; the coordinate moments over the 32 row lanes ----
     __syncthreads();
@@ -525,11 +530,13 @@ gemm_wsx_kernel(const WsxArgs P) {
     }
     __syncthreads();
     double *xs = P.xslab + (size_t)worker * kWsxSlab;
+    const bool wt_stats = (P.store_policy & ST_STAT_SLABS) != 0;
     {
         const int q = tid >> 6, cl = tid & 63;
-        xs[q * BN + cl] = (dred[(0 * 4 + q) * BN + cl] + dred[(1 * 4 + q) * BN + cl]) + (dred[(2 * 4 + q) * BN + cl] + dred[(3 * 4 + q) * BN + cl]);
+        sp_store(xs + q * BN + cl, (dred[(0 * 4 + q) * BN + cl] + dred[(1 * 4 + q) * BN + cl]) + (dred[(2 * 4 + q) * BN + cl] + dred[(3 * 4 + q) * BN + cl]),
+                 wt_stats);
     }
-    if (tid < 9) xs[4 * BN + tid] = (mred[tid] + mred[9 + tid]) + (mred[18 + tid] + mred[27 + tid]);
+    if (tid < 9) sp_store(xs + 4 * BN + tid, (mred[tid] + mred[9 + tid]) + (mred[18 + tid] + mred[27 + tid]), wt_stats);
 }
 
 // ---- the launch behind it: dW_1 = sum of the workers' partials; layer 0's parameter gradients from the workers' sums ----
@@ -998,6 +1005,7 @@ int launch_wsf0(const AOperand &geo, int M, const BOperand &W0, const double *mo
     P.mom = mom, P.nmom = nmom, P.training = h.training, P.bias0 = bn0.bias, P.gamma0 = bn0.gamma, P.beta0 = bn0.beta, P.rm0 = bn0.rm;
     P.rv0 = bn0.rv, P.nbt0 = bn0.nbt, P.momentum = h.momentum, P.eps = h.eps, P.mean0 = bn0.mean, P.istd0 = bn0.istd, P.scale0 = bn0.scale, P.shift0 = bn0.shift;
     P.W1 = W1.b, P.ldw1 = W1.ldb, P.z1 = E.c, P.slab = E.slab;
+    P.store_policy = store_policy();
     const int nstrips = M / 32;
     // PNPP_WSF0_WORKERS (256 measured: see DESIGN section 9); 0 or less: the default.  worker_count keeps it inside the statistics slab
     static const int wmax = env_int("PNPP_WSF0_WORKERS", kMaxStatBlocks);
@@ -1048,6 +1056,7 @@ bool try_launch_wsx(const AOperand &dz, const BOperand &W, int M, int C1, int C0
     P.dy = dz.a, P.z = dz.z, P.cst = dz.cst, P.W = W.b, P.ldw = W.ldb, P.M = M;
     P.xyz = geo.xyz, P.centres = geo.new_xyz, P.idx = geo.idx, P.N = geo.N, P.S = geo.S;
     P.W0 = W0, P.ldw0 = ldw0, P.scale0 = scale0, P.shift0 = shift0, P.dwslab = dwslab, P.xslab = stat;
+    P.store_policy = store_policy();
     // PNPP_WSX3=0: the dA product on the float32 instruction (A/B runs); 2: the dW_1 product on the bf16 pipe too
     static const int wsx3 = env_int("PNPP_WSX3", 1);
     const bool s3 = wsx3 != 0 && split_products() && wpc == 1;   // (two workgroups per CU leave the split form 74 registers short)

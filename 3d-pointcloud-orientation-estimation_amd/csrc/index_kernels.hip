@@ -9,6 +9,7 @@
 // compiled with -ffp-contract=off and uses explicit fmaf where -- and only where -- ATen fuses.
 #include "common.h"
 #include "sampler_device.h"
+#include "split_prims.h"
 #include "wsf0_args.h"
 
 #pragma clang fp contract(off)
@@ -122,6 +123,7 @@ struct KnnJob {
     int qpw;                   // queries per wave: 1, or 2 on a cloud of one tile (the tile is then staged once for eight queries)
     int nblocks;               // workgroups per cloud of this job
     const int32_t *lengths;    // ragged batch (RAGGED bodies only): cloud b's candidates are its first min(max(lengths[b], 1), N) rows
+    int store_policy;          // StorePolicy bits (common.h): the moment partials are a statistics slab
 };
 
 struct alignas(16) KnnLds {   // one copy per workgroup, shared by the two instantiations of the body a pair kernel contains
@@ -311,8 +313,8 @@ __device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const in
             if (threadIdx.x < 9) {
                 const double *r0 = reinterpret_cast<const double *>(pool[0]), *r1 = reinterpret_cast<const double *>(pool[1]);
                 const double *r2 = reinterpret_cast<const double *>(pool[2]), *r3 = reinterpret_cast<const double *>(pool[3]);
-                J.mom[((size_t)b * J.nblocks + bx) * KNN_MOM_PITCH + threadIdx.x] =
-                    (r0[threadIdx.x] + r1[threadIdx.x]) + (r2[threadIdx.x] + r3[threadIdx.x]);
+                sp_store(J.mom + ((size_t)b * J.nblocks + bx) * KNN_MOM_PITCH + threadIdx.x,
+                         (r0[threadIdx.x] + r1[threadIdx.x]) + (r2[threadIdx.x] + r3[threadIdx.x]), (J.store_policy & ST_STAT_SLABS) != 0);
             }
         }
     }
@@ -719,7 +721,7 @@ int launch_knn(const float *new_xyz, const float *xyz, int B, int S, int N, int 
     PNPP_REQUIRE(k <= KNN_KMAX, PNPP_ERR_ARG, "knn: nsample=%d exceeds the supported maximum %d", k, KNN_KMAX);
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "knn: batch %d exceeds grid limit", B);
     ProfScope ps(st, "knn_kernel B=%d S=%d N=%d k=%d%s", B, S, N, k, lengths ? " ragged" : "");
-    const KnnJob J{new_xyz, xyz, nullptr, N, S, N, k, idx, nullptr, nullptr, nullptr, nullptr, 1, cdiv(S, 4), lengths};
+    const KnnJob J{new_xyz, xyz, nullptr, N, S, N, k, idx, nullptr, nullptr, nullptr, nullptr, 1, cdiv(S, 4), lengths, 0};
     if (lengths) hipLaunchKernelGGL(knn_kernel<true>, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
     else hipLaunchKernelGGL(knn_kernel<false>, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
     PNPP_CHECK_LAUNCH("knn");
@@ -735,7 +737,7 @@ int launch_knn_centres(const float *xyz, const int32_t *centre, int B, int S, in
     PNPP_REQUIRE(k <= KNN_KMAX, PNPP_ERR_ARG, "knn: nsample=%d exceeds the supported maximum %d", k, KNN_KMAX);
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "knn: batch %d exceeds grid limit", B);
     ProfScope ps(st, "knn_kernel B=%d S=%d N=%d k=%d%s", B, S, N, k, lengths ? " ragged" : "");
-    const KnnJob J{nullptr, xyz, nullptr, N, S, N, k, idx, centre, out_a, out_b, nullptr, 1, cdiv(S, 4), lengths};
+    const KnnJob J{nullptr, xyz, nullptr, N, S, N, k, idx, centre, out_a, out_b, nullptr, 1, cdiv(S, 4), lengths, 0};
     if (lengths) hipLaunchKernelGGL(knn_kernel<true>, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
     else hipLaunchKernelGGL(knn_kernel<false>, dim3(cdiv(S, 4), B), dim3(256), 0, st, J);
     PNPP_CHECK_LAUNCH("knn");
@@ -765,8 +767,8 @@ int launch_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int 
     const int qpw = knn_pair_qpw(N), nb1 = cdiv(S1, 4 * qpw), nb2 = cdiv(S2, 4);
     ProfScope ps(st, "knn_pair_kernel B=%d | S=%d N=%d k=%d | S=%d N=%d k=%d%s%s", B, S1, N, k1, S2, S1, k2, mom ? " +moments" : "",
                  lengths ? " ragged" : "");
-    const KnnJob J1{nullptr, xyz, nullptr, N, S1, N, k1, idx1, centre1, a1, b1, mom, qpw, nb1, lengths};
-    const KnnJob J2{nullptr, xyz, centre1, N, S2, S1, k2, idx2, centre2, a2, b2, nullptr, 1, nb2, nullptr};
+    const KnnJob J1{nullptr, xyz, nullptr, N, S1, N, k1, idx1, centre1, a1, b1, mom, qpw, nb1, lengths, store_policy()};
+    const KnnJob J2{nullptr, xyz, centre1, N, S2, S1, k2, idx2, centre2, a2, b2, nullptr, 1, nb2, nullptr, 0};
     const dim3 grid(nb1 + nb2, B);
     if (S1 <= KNN_TILE_SMALL) {
         if (lengths) hipLaunchKernelGGL((knn_pair_kernel<KNN_TILE_SMALL, true>), grid, dim3(256), 0, st, J1, J2, nb2);

@@ -90,6 +90,7 @@ struct Epilogue {
     float *pool_ext = nullptr;
     int32_t *pool_arg = nullptr;
     const float *pool_gamma = nullptr;
+    int store_policy = 0;   // StorePolicy bits for this launch's stores; the dispatchers fill it in, callers leave it alone
     BnTail bn;
 };
 
@@ -191,6 +192,11 @@ bool wsf_applies(const AOperand &A, const BOperand &B, int M, int Nout, int Kd, 
 // splits (six bf16 x bf16 products per float32 product, float32 accumulation); pnpp_set_split_products / PNPP_SPLIT_PRODUCTS
 int split_products();
 void set_split_products(int on);
+// How the big kernels' stores leave the chip (pnpp_set_store_policy): a mask of site classes whose stores are write-through (sc1) instead
+// of plain write-back; the classes are StorePolicy (common.h), split_prims.h has the device half.  Results do not depend on it.  It travels to a kernel in Epilogue::store_policy
+// (filled by launch_gemm and the da_dw launchers) or in the kernel's own argument block.
+int store_policy();
+void set_store_policy(int mask);
 bool try_launch_wsf3(const AOperand &A, const BOperand &B, int M, int Nout, int Kd, const Epilogue &E, int *nslab, hipStream_t st, int *rc);
 // gemm_wsd3_kernels.hip: the fused backward products (dA + mask + sums + dW) of the grouped levels with split products, a producer and a
 // consumer wave per strip: a level's last layer (pooled gradient, 128 -> 64 and 256 -> 128) and a middle layer (dense gradient, 128 -> 128)

@@ -1,6 +1,6 @@
 // split_prims.h -- the device primitives every split-product kernel shares, ONE definition: the exact three-way split of float32 into
-// bfloat16 pieces, the MFMA operand casts, the transposed LDS read, the row swizzle of the plane images and the raw buffer loads.  A new
-// kernel includes this header; it does not paste from another kernel.
+// bfloat16 pieces, the MFMA operand casts, the transposed LDS read, the row swizzle of the plane images, the raw buffer loads
+// and the stores with a cache policy.  A new kernel includes this header; it does not paste from another kernel.
 //
 // Why.  gfx950 has no reduced-width float32 MFMA: v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate (64 FLOP/clk/SIMD), and on the
 // float32 forward kernels the MFMA time and the HBM time ADD.  A float32 number is the exact sum of three
@@ -20,6 +20,8 @@
 // Everything here is internal to the translation unit that includes it (anonymous namespace) and carries no pragma: each kernel file
 // keeps its own compile flags.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace pnpp {
@@ -89,6 +91,32 @@ __device__ __forceinline__ f32x4 sp_buf_load4(__amdgpu_buffer_rsrc_t r, unsigned
 }
 __device__ __forceinline__ float sp_buf_load1(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)lane_off, (int)s_off, 0));
+}
+
+// ---- stores with a cache policy --------------------------------------------------------------------------------------------------
+// A store is plain (write-back: the line stays dirty in the writing XCD's L2 until the launch ends) or write-through (sc1: the bytes
+// leave for memory as they are stored, the line is not kept).  `wt` is uniform -- one bit of the launch's policy mask
+// (pnpp_set_store_policy; common.h: StorePolicy), tested against the class of the site -- so the choice is a scalar branch, never per lane.
+// A block of stores takes the branch ONCE, around the whole block (sp_with_policy: the flag becomes a compile-time constant inside, each
+// side schedules as if the other did not exist); a branch per store inside an epilogue cost gemm_wsd3_kernel<128,32,A5> 7 us of its 39.  Values and order of the stores are the same in both forms: a policy changes no result.  Visibility stays
+// the kernel boundary's; nothing inside a launch may read what these stores wrote.
+// Forms: <= 8 bytes per lane a relaxed agent-scope atomic store on a global-address-space pointer (global_store ... sc1), buffer stores
+// by the aux immediate (16 = sc1).  Never nt: it is slower on every stored edge and is not write-through.
+template <typename F>
+__device__ __forceinline__ void sp_with_policy(bool wt, F &&f) {   // f(std::true_type) or f(std::false_type): `wt` as a constant
+    if (wt) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <typename T>
+__device__ __forceinline__ void sp_store(T *p, T v, bool wt) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one dword or two per lane");
+    typedef __attribute__((address_space(1))) T gT;
+    if (wt) __hip_atomic_store((gT *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *p = v;
+}
+__device__ __forceinline__ void sp_buf_store1(float v, __amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned s_off, bool wt) {
+    if (wt) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)lane_off, (int)s_off, 16);
+    else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)lane_off, (int)s_off, 0);
 }
 
 }  // namespace

@@ -25,6 +25,7 @@ struct Wsf0Args {
     int ldw1;
     float *z1;         // M x 64
     double *slab;      // [workers][2][64] (EM == E_STORE_STATS)
+    int store_policy;  // StorePolicy bits (common.h); gemm_wsf03_kernel honours them
 };
 
 // the split-product form (float32 products from exact three-way bf16 splits; on with split_products() unless PNPP_WSF03=0)

@@ -222,6 +222,8 @@ SIGNATURES = {
     "pnpp_get_matmul_precision": (_i, []),
     "pnpp_set_split_products": (_i, [_i]),
     "pnpp_get_split_products": (_i, []),
+    "pnpp_set_store_policy": (_i, [_i]),
+    "pnpp_get_store_policy": (_i, []),
     "pnpp_adam_step": (_i, [_fp, _fp, _fp, _fp, _sz, _i, _f, _f, _f, _f, _f, _fp]),
     "pnpp_adam_step_zero": (_i, [_fp, _fp, _fp, _fp, _sz, _i, _f, _f, _f, _f, _f, _fp]),
     "pnpp_adam_step_dev": (_i, [_fp, _fp, _fp, _fp, _sz, _fp, _f, _f, _f, _f, _f, _i, _fp]),

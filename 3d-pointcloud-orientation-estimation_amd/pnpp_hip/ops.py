@@ -128,6 +128,20 @@ def get_float32_products() -> str:
     return "split" if L.lib().pnpp_get_split_products() else "mfma"
 
 
+STORE_DW_SLABS, STORE_STAT_SLABS, STORE_STREAMS = 1, 2, 4
+
+
+def set_store_policy(mask: int) -> None:
+    """Which classes of the large kernels' stores are write-through instead of plain write-back: a sum of STORE_DW_SLABS (dW partial
+    slabs), STORE_STAT_SLABS (float64 statistics slabs) and STORE_STREAMS (streamed activation / gradient outputs).  Results do not
+    depend on it (bit-identical); default STORE_DW_SLABS + STORE_STREAMS.  Process-wide; a hipGraph captured under one mask keeps it."""
+    L.check(L.lib().pnpp_set_store_policy(int(mask)))
+
+
+def get_store_policy() -> int:
+    return L.lib().pnpp_get_store_policy()
+
+
 # ------------------------------------------------------------------------------------------------
 # index primitives
 # ------------------------------------------------------------------------------------------------

@@ -441,6 +441,19 @@ int pnpp_get_matmul_precision(void);
  * ---------------------------------------------------------------------------------------- */
 int pnpp_set_split_products(int on);
 int pnpp_get_split_products(void);
+
+/* ------------------------------------------------------------------------------------------
+ * How the large kernels' stores leave the chip: a mask of site classes whose stores are write-through (sc1: the bytes go to memory as
+ * they are stored) instead of plain write-back (the lines stay dirty in the writing XCD's L2 until the launch ends).
+ *   1  dW partial slabs (read next by post_gemm / slab_reduce / xyz0_post)
+ *   2  float64 statistics slabs and moment partials
+ *   4  streamed activation and gradient outputs of the fused GEMMs
+ * Values and order of every store are the same under every mask: results are bit-identical (tests/test_gpu_store_policy.py).
+ * Process-wide, default 5 (classes 1 and 4: the ones that measured faster on the training step); no environment variable.  A hipGraph captured under one mask keeps it.  A mask with other bits is
+ * PNPP_ERR_ARG.
+ * ---------------------------------------------------------------------------------------- */
+int pnpp_set_store_policy(int mask);
+int pnpp_get_store_policy(void);
 /* diagnostics: non-zero once a bounded LDS poll of the wave-pair kernel (csrc/gemm_wsd3_kernels.hip) has given up in this process */
 int pnpp_debug_wsd3_timeouts(void);
 
