@@ -65,7 +65,8 @@ PoolBwdScratch pool_bwd_scratch(const pnpp_pn_pool_desc *d, void *base, size_t *
     return s;
 }
 
-int pool_check(const pnpp_pn_pool_desc *d) {
+// M_total < 0: a uniform batch of B * N rows; otherwise the packed rows of a ragged one
+int pool_check(const pnpp_pn_pool_desc *d, long long M_total = -1) {
     PNPP_REQUIRE(d, PNPP_ERR_ARG, "pn_pool: null descriptor");
     PNPP_REQUIRE(d->B > 0 && d->N > 0, PNPP_ERR_ARG, "pn_pool: non-positive size B=%d N=%d", d->B, d->N);
     PNPP_REQUIRE(d->B <= 65535, PNPP_ERR_ARG, "pn_pool: B=%d clouds (at most 65535)", d->B);
@@ -76,7 +77,13 @@ int pool_check(const pnpp_pn_pool_desc *d) {
     PNPP_REQUIRE(d->relu == 0 || d->relu == 1, PNPP_ERR_ARG, "pn_pool: relu must be 0 or 1");
     PNPP_REQUIRE(d->training == 0 || d->training == 1, PNPP_ERR_ARG, "pn_pool: training must be 0 or 1");
     PNPP_REQUIRE((long long)d->B * d->N <= (1LL << 31) - 1, PNPP_ERR_ARG, "pn_pool: B*N too large");
-    if (d->training) PNPP_REQUIRE((long long)d->B * d->N > 1, PNPP_ERR_ARG, "Expected more than 1 value per channel when training");
+    if (M_total >= 0) {
+        PNPP_REQUIRE(M_total >= d->B && M_total <= (long long)d->B * d->N, PNPP_ERR_ARG,
+                     "pn_pool: M_total=%lld packed rows for B=%d clouds of 1 .. N=%d points", M_total, d->B, d->N);
+        if (d->training) PNPP_REQUIRE(M_total > 1, PNPP_ERR_ARG, "Expected more than 1 value per channel when training");
+    } else if (d->training) {
+        PNPP_REQUIRE((long long)d->B * d->N > 1, PNPP_ERR_ARG, "Expected more than 1 value per channel when training");
+    }
     PNPP_REQUIRE(!(d->training && stats_sync_on()), PNPP_ERR_ARG,
                  "pn_pool: the statistics exchange (SyncBN) is registered; the PointNet kernels compute per-process statistics only");
     PNPP_REQUIRE(d->eps > 0.f, PNPP_ERR_ARG, "pn_pool: eps must be positive");
@@ -121,34 +128,79 @@ extern "C" void *pnpp_pn_pool_saved_ypre(const pnpp_pn_pool_desc *d, void *saved
     return pool_saved_layout(d, saved).ypre;
 }
 
-extern "C" int pnpp_pn_pool_forward(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_fwd_args *a, void *stream) {
-    PN_TRY(pool_check(d));
+static int pool_forward(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_fwd_args *a, const int32_t *offs, long long M, void *stream) {
     PNPP_REQUIRE(a && a->a && a->w && a->b && a->gamma && a->beta && a->rm && a->rv && a->out && a->saved && a->scratch, PNPP_ERR_ARG,
                  "pn_pool_forward: null pointer");
     PNPP_REQUIRE(((uintptr_t)a->a) % 16 == 0, PNPP_ERR_ARG, "pn_pool_forward: the input rows must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     const PoolSaved sv = pool_saved_layout(d, a->saved);
     const PoolFwdScratch sc = pool_fwd_scratch(d, a->scratch);
-    if (d->training) PN_TRY(launch_pn_gram(a->a, d->B, d->N, d->K, sc.gp, sc.sp, sv.S, sv.Cc, st));
-    PN_TRY(launch_pn_pool_scan(a->a, a->w, a->b, d->B, d->N, d->K, d->C, sc.zmax, sc.imax, sc.zmin, sc.imin, st));
-    return launch_pn_pool_finalize(a->w, a->b, a->gamma, a->beta, sv.S, sv.Cc, sc.zmax, sc.imax, sc.zmin, sc.imin, d->B, d->N, d->K,
+    if (d->training) PN_TRY(launch_pn_gram(a->a, offs, M, d->B, d->N, d->K, sc.gp, sc.sp, sv.S, sv.Cc, st));
+    PN_TRY(launch_pn_pool_scan(a->a, offs, a->w, a->b, d->B, d->N, d->K, d->C, sc.zmax, sc.imax, sc.zmin, sc.imin, st));
+    return launch_pn_pool_finalize(a->w, a->b, a->gamma, a->beta, sv.S, sv.Cc, sc.zmax, sc.imax, sc.zmin, sc.imin, d->B, M, d->K,
                                    d->C, d->relu, d->training, d->eps, d->momentum, a->rm, a->rv, (long long *)a->nbt, sv.mean,
                                    sv.istd, sv.zsel, sv.ypre, sv.route, a->out, st);
 }
 
-extern "C" int pnpp_pn_pool_backward(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_bwd_args *a, void *stream) {
+extern "C" int pnpp_pn_pool_forward(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_fwd_args *a, void *stream) {
     PN_TRY(pool_check(d));
+    return pool_forward(d, a, nullptr, (long long)d->B * d->N, stream);
+}
+
+extern "C" int pnpp_pn_pool_forward_ragged(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_fwd_args *a, const int32_t *offs, int M_total,
+                                           void *stream) {
+    PN_TRY(pool_check(d, M_total));
+    PNPP_REQUIRE(offs, PNPP_ERR_ARG, "pn_pool_forward_ragged: null offsets");
+    return pool_forward(d, a, offs, M_total, stream);
+}
+
+static int pool_backward(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_bwd_args *a, const int32_t *offs, long long M, void *stream) {
     PNPP_REQUIRE(a && a->a && a->w && a->gamma && a->dout && a->saved && a->scratch && a->dw && a->db && a->dgamma && a->dbeta,
                  PNPP_ERR_ARG, "pn_pool_backward: null pointer");
     hipStream_t st = as_stream(stream);
     const PoolSaved sv = pool_saved_layout(d, const_cast<void *>(a->saved));
     const PoolBwdScratch sc = pool_bwd_scratch(d, a->scratch);
-    PN_TRY(launch_pn_pool_bwd_channels(a->a, a->w, a->gamma, a->dout, sv.mean, sv.istd, sv.zsel, sv.ypre, sv.route, sv.S, sv.Cc, d->B,
+    PN_TRY(launch_pn_pool_bwd_channels(a->a, offs, M, a->w, a->gamma, a->dout, sv.mean, sv.istd, sv.zsel, sv.ypre, sv.route, sv.S, sv.Cc, d->B,
                                        d->N, d->K, d->C, d->relu, d->training, a->dw, a->db, a->dgamma, a->dbeta, sc.coef, sc.u, sc.v,
                                        st));
     if (!a->da) return PNPP_OK;
     if (d->training) PN_TRY(launch_pn_pool_bwd_q(a->w, sc.u, sc.v, d->K, d->C, sc.Q, sc.cvec, st));
-    return launch_pn_pool_bwd_da(a->a, a->w, sc.Q, sc.cvec, sc.coef, sv.route, sv.S, d->B, d->N, d->K, d->C, d->training, a->da, st);
+    return launch_pn_pool_bwd_da(a->a, offs, M, a->w, sc.Q, sc.cvec, sc.coef, sv.route, sv.S, d->B, d->N, d->K, d->C, d->training, a->da, st);
+}
+
+extern "C" int pnpp_pn_pool_backward(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_bwd_args *a, void *stream) {
+    PN_TRY(pool_check(d));
+    return pool_backward(d, a, nullptr, (long long)d->B * d->N, stream);
+}
+
+extern "C" int pnpp_pn_pool_backward_ragged(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_bwd_args *a, const int32_t *offs, int M_total,
+                                            void *stream) {
+    PN_TRY(pool_check(d, M_total));
+    PNPP_REQUIRE(offs, PNPP_ERR_ARG, "pn_pool_backward_ragged: null offsets");
+    return pool_backward(d, a, offs, M_total, stream);
+}
+
+extern "C" int pnpp_pn_offsets(const int32_t *lengths, int B, int N, int32_t *lens_out, int32_t *offs, void *stream) {
+    PNPP_REQUIRE(lengths && lens_out && offs, PNPP_ERR_ARG, "pn_offsets: null pointer");
+    PNPP_REQUIRE(B > 0 && N > 0 && B <= 65535, PNPP_ERR_ARG, "pn_offsets: B=%d clouds (1 .. 65535) of N=%d points", B, N);
+    PNPP_REQUIRE((long long)B * N <= (1LL << 31) - 1, PNPP_ERR_ARG, "pn_offsets: B*N too large");
+    return launch_pn_offsets(lengths, B, N, lens_out, offs, as_stream(stream));
+}
+
+// the workspaces of a ragged call have the uniform layout (their sizes follow B, C, K and the padded N's slices, not the row count)
+extern "C" size_t pnpp_pn_pool_saved_bytes_ragged(const pnpp_pn_pool_desc *d, int M_total) {
+    if (pool_check(d, M_total)) return 0;
+    size_t b = 0;
+    pool_saved_layout(d, nullptr, &b);
+    return b;
+}
+
+extern "C" size_t pnpp_pn_pool_scratch_bytes_ragged(const pnpp_pn_pool_desc *d, int M_total) {
+    if (pool_check(d, M_total)) return 0;
+    size_t f = 0, g = 0;
+    pool_fwd_scratch(d, nullptr, &f);
+    pool_bwd_scratch(d, nullptr, &g);
+    return f > g ? f : g;
 }
 
 static int transform_check(const float *x, const float *t, int B, int N, int D, int k, int ldy) {
@@ -165,7 +217,15 @@ extern "C" int pnpp_pn_transform(const float *x, int64_t sb, int64_t sn, int64_t
                                  float *y, void *stream) {
     PN_TRY(transform_check(x, t, B, N, D, k, ldy));
     PNPP_REQUIRE(y, PNPP_ERR_ARG, "pn_transform: null output");
-    return launch_pn_transform(x, sb, sn, sd, t, B, N, D, k, ldy, y, as_stream(stream));
+    return launch_pn_transform(x, nullptr, 0, sb, sn, sd, t, B, N, D, k, ldy, y, as_stream(stream));
+}
+
+extern "C" int pnpp_pn_transform_ragged(const float *x, int x_packed, int64_t sb, int64_t sn, int64_t sd, const float *t, const int32_t *offs,
+                                        int B, int N, int D, int k, int ldy, float *y, void *stream) {
+    PN_TRY(transform_check(x, t, B, N, D, k, ldy));
+    PNPP_REQUIRE(y, PNPP_ERR_ARG, "pn_transform_ragged: null output");
+    PNPP_REQUIRE(offs, PNPP_ERR_ARG, "pn_transform_ragged: null offsets");
+    return launch_pn_transform(x, offs, x_packed ? 1 : 0, sb, sn, sd, t, B, N, D, k, ldy, y, as_stream(stream));
 }
 
 extern "C" int pnpp_pn_transform_bwd(const float *x, int64_t sb, int64_t sn, int64_t sd, const float *t, const float *dy, int B, int N,
@@ -173,7 +233,17 @@ extern "C" int pnpp_pn_transform_bwd(const float *x, int64_t sb, int64_t sn, int
     PN_TRY(transform_check(x, t, B, N, D, k, ldy));
     PNPP_REQUIRE(dy, PNPP_ERR_ARG, "pn_transform_bwd: null output gradient");
     PNPP_REQUIRE(!dt || t, PNPP_ERR_ARG, "pn_transform_bwd: a transform gradient needs the transform");
-    return launch_pn_transform_bwd(x, sb, sn, sd, t, dy, B, N, D, k, ldy, dx, dt, as_stream(stream));
+    return launch_pn_transform_bwd(x, nullptr, 0, sb, sn, sd, t, dy, B, N, D, k, ldy, dx, dt, as_stream(stream));
+}
+
+extern "C" int pnpp_pn_transform_bwd_ragged(const float *x, int x_packed, int64_t sb, int64_t sn, int64_t sd, const float *t,
+                                            const float *dy, const int32_t *offs, int B, int N, int D, int k, int ldy, float *dx, float *dt,
+                                            void *stream) {
+    PN_TRY(transform_check(x, t, B, N, D, k, ldy));
+    PNPP_REQUIRE(dy, PNPP_ERR_ARG, "pn_transform_bwd_ragged: null output gradient");
+    PNPP_REQUIRE(!dt || t, PNPP_ERR_ARG, "pn_transform_bwd_ragged: a transform gradient needs the transform");
+    PNPP_REQUIRE(offs, PNPP_ERR_ARG, "pn_transform_bwd_ragged: null offsets");
+    return launch_pn_transform_bwd(x, offs, x_packed ? 1 : 0, sb, sn, sd, t, dy, B, N, D, k, ldy, dx, dt, as_stream(stream));
 }
 
 extern "C" int pnpp_pn_regularizer(const float *t, int B, int k, double *norms, float *out, void *stream) {
@@ -197,14 +267,31 @@ extern "C" int pnpp_pn_add_identity(const float *x, int B, int k, float *y, void
 extern "C" int pnpp_pn_concat(const float *g, const float *pf, int B, int N, int C1, int C2, float *out, void *stream) {
     PNPP_REQUIRE(g && pf && out, PNPP_ERR_ARG, "pn_concat: null pointer");
     PNPP_REQUIRE(B > 0 && N > 0 && C1 > 0 && C2 > 0, PNPP_ERR_ARG, "pn_concat: non-positive size");
-    return launch_pn_concat(g, pf, B, N, C1, C2, out, as_stream(stream));
+    return launch_pn_concat(g, pf, nullptr, 0, B, N, C1, C2, out, as_stream(stream));
+}
+
+extern "C" int pnpp_pn_concat_ragged(const float *g, const float *pf, int pf_padded, const int32_t *offs, int B, int N, int C1, int C2,
+                                     float *out, void *stream) {
+    PNPP_REQUIRE(g && pf && out, PNPP_ERR_ARG, "pn_concat_ragged: null pointer");
+    PNPP_REQUIRE(offs, PNPP_ERR_ARG, "pn_concat_ragged: null offsets");
+    PNPP_REQUIRE(B > 0 && N > 0 && C1 > 0 && C2 > 0, PNPP_ERR_ARG, "pn_concat_ragged: non-positive size");
+    return launch_pn_concat(g, pf, offs, pf_padded ? 1 : 0, B, N, C1, C2, out, as_stream(stream));
 }
 
 extern "C" int pnpp_pn_concat_bwd(const float *dout, int B, int N, int C1, int C2, float *dg, float *dpf, void *stream) {
     PNPP_REQUIRE(dout, PNPP_ERR_ARG, "pn_concat_bwd: null output gradient");
     PNPP_REQUIRE(B > 0 && N > 0 && C1 > 0 && C2 > 0, PNPP_ERR_ARG, "pn_concat_bwd: non-positive size");
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "pn_concat_bwd: B=%d clouds (at most 65535)", B);
-    return launch_pn_concat_bwd(dout, B, N, C1, C2, dg, dpf, as_stream(stream));
+    return launch_pn_concat_bwd(dout, nullptr, B, N, C1, C2, dg, dpf, as_stream(stream));
+}
+
+extern "C" int pnpp_pn_concat_bwd_ragged(const float *dout, const int32_t *offs, int B, int N, int C1, int C2, float *dg, float *dpf,
+                                         void *stream) {
+    PNPP_REQUIRE(dout, PNPP_ERR_ARG, "pn_concat_bwd_ragged: null output gradient");
+    PNPP_REQUIRE(offs, PNPP_ERR_ARG, "pn_concat_bwd_ragged: null offsets");
+    PNPP_REQUIRE(B > 0 && N > 0 && C1 > 0 && C2 > 0, PNPP_ERR_ARG, "pn_concat_bwd_ragged: non-positive size");
+    PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "pn_concat_bwd_ragged: B=%d clouds (at most 65535)", B);
+    return launch_pn_concat_bwd(dout, offs, B, N, C1, C2, dg, dpf, as_stream(stream));
 }
 
 extern "C" int pnpp_pn_bn_relu(const float *x, int M, int C, const float *gamma, const float *beta, float *rm, float *rv, int64_t *nbt,

@@ -155,6 +155,7 @@ struct PnArgs {
     int ldA, ldB;
     int tiles, nslot;
     int c_per_wg;              // columns of the last layer this workgroup's blockIdx.y owns
+    const int32_t *offs;       // ragged batches: (B + 1) exclusive prefix sums of the lengths (cloud b holds offs[b+1] - offs[b] rows)
 };
 
 // One stage of the tile, as infer_unit of sa_infer_kernels.hip.  C/D layout: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
@@ -234,7 +235,9 @@ __device__ __forceinline__ void pn_layer(const unsigned short *__restrict__ actI
     }
 }
 
-template <int TM>
+// RAGGED: the cloud's own row count Nv takes N's place in the operand build, the tapped stores and the max; the input and feat_out keep
+// their padded addressing (feat_out rows n >= Nv are written as zeros), and a tile beyond Nv leaves before the first barrier.
+template <int TM, bool RAGGED>
 __global__ __launch_bounds__(kPnThreads) void pn_infer_kernel(const PnArgs P) {
     extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
     const size_t planeA = (size_t)TM * P.ldA, planeB = (size_t)TM * P.ldB;
@@ -243,6 +246,16 @@ __global__ __launch_bounds__(kPnThreads) void pn_infer_kernel(const PnArgs P) {
     const int t = threadIdx.x;
     const int b = blockIdx.x / P.tiles;
     const int n0 = (blockIdx.x % P.tiles) * TM;
+    int Nv = P.N;
+    if (RAGGED) {
+        Nv = min(max(P.offs[b + 1] - P.offs[b], 0), P.N);   // wave-uniform loads
+        if (P.feat_out && blockIdx.y == 0) {   // the padding rows of this tile in the tapped output
+            const int cf = P.st[P.feat_stage].Cout, nz0 = max(n0, Nv), nz1 = min(n0 + TM, P.N);
+            float *fz = P.feat_out + ((size_t)b * P.N + nz0) * cf;
+            for (int e = t; e < (nz1 - nz0) * cf; e += kPnThreads) fz[e] = 0.f;
+        }
+        if (n0 >= Nv) return;   // block-uniform
+    }
 
     // 1. layer-0 operand, split as it is written: consecutive threads take consecutive rows of one column
     const float *xb = P.x + (long long)b * P.sb;
@@ -251,7 +264,7 @@ __global__ __launch_bounds__(kPnThreads) void pn_infer_kernel(const PnArgs P) {
         const int row = e % TM, c = e / TM;
         const int n = n0 + row;
         float v = 0.f;
-        if (n < P.N && c < P.D) {
+        if (n < Nv && c < P.D) {
             const float *xr = xb + (long long)n * P.sn;
             if (tb && c < 3)
                 v = fmaf(xr[2 * P.sc], tb[6 + c], fmaf(xr[P.sc], tb[3 + c], xr[0] * tb[c]));
@@ -271,7 +284,7 @@ __global__ __launch_bounds__(kPnThreads) void pn_infer_kernel(const PnArgs P) {
         const bool odd = s & 1;
         float *feat = (s == P.feat_stage && P.feat_out && blockIdx.y == 0) ? P.feat_out + (size_t)b * P.N * S.Cout : nullptr;
         pn_layer<TM, false>(odd ? bufB : bufA, odd ? P.ldB : P.ldA, odd ? planeB : planeA, S, S.w + (long long)b * S.cloud_stride, 0, S.Cout / 32,
-                            odd ? bufA : bufB, odd ? P.ldA : P.ldB, odd ? planeA : planeB, feat, n0, P.N, 0);
+                            odd ? bufA : bufB, odd ? P.ldA : P.ldB, odd ? planeA : planeB, feat, n0, Nv, 0);
         __syncthreads();
     }
     // 3. the pooled layer: one partial row per 32-row block
@@ -279,17 +292,19 @@ __global__ __launch_bounds__(kPnThreads) void pn_infer_kernel(const PnArgs P) {
     const bool odd = last & 1;
     float *part = P.part + ((size_t)b * P.nslot + n0 / 32) * S.Cout;
     pn_layer<TM, true>(odd ? bufB : bufA, odd ? P.ldB : P.ldA, odd ? planeB : planeA, S, S.w + (long long)b * S.cloud_stride,
-                       blockIdx.y * P.c_per_wg, P.c_per_wg / 32, nullptr, 0, 0, part, n0, P.N, S.Cout);
+                       blockIdx.y * P.c_per_wg, P.c_per_wg / 32, nullptr, 0, 0, part, n0, Nv, S.Cout);
 }
 
-// out[b][c] = act(max_s part[b][s][c] + b'[c])
-__global__ __launch_bounds__(256) void pn_infer_finish_kernel(const float *__restrict__ part, const float *__restrict__ bias, int nslot, int C,
-                                                              int relu, float *__restrict__ out) {
+// out[b][c] = act(max_s part[b][s][c] + b'[c]); offs (ragged batches): only the cloud's ceil(Nv / 32) partial rows were written
+__global__ __launch_bounds__(256) void pn_infer_finish_kernel(const float *__restrict__ part, const float *__restrict__ bias,
+                                                              const int32_t *__restrict__ offs, int nslot, int C, int relu,
+                                                              float *__restrict__ out) {
     const int c = blockIdx.y * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const float *p = part + (size_t)blockIdx.x * nslot * C + c;
+    const int ns = offs ? min(max((offs[blockIdx.x + 1] - offs[blockIdx.x] + 31) / 32, 1), nslot) : nslot;
     float m = p[0];
-    for (int s = 1; s < nslot; ++s) m = fmaxf(m, p[(size_t)s * C]);
+    for (int s = 1; s < ns; ++s) m = fmaxf(m, p[(size_t)s * C]);
     m += bias[c];
     out[(size_t)blockIdx.x * C + c] = relu ? fmaxf(m, 0.f) : m;
 }
@@ -313,7 +328,7 @@ static int pn_infer_fold(const pnpp_pn_infer_desc *d, const pnpp_sa_fwd_args *a,
     return PNPP_OK;
 }
 
-static int pn_infer(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, hipStream_t st) {
+static int pn_infer(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, const int32_t *offs, hipStream_t st) {
     PNPP_REQUIRE(d && a, PNPP_ERR_ARG, "pn_infer: null pointer");
     PNPP_REQUIRE(a->x && a->weights && a->scratch && a->out, PNPP_ERR_ARG, "pn_infer: null pointer");
     PnPlan p;
@@ -358,28 +373,35 @@ static int pn_infer(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, hi
     P.ldA = p.ldA, P.ldB = p.ldB;
     P.tiles = p.tiles, P.nslot = p.nslot;
     P.c_per_wg = clast / p.nsplit;
+    P.offs = offs;
     {
         ProfScope ps(st, "pn_infer_kernel TM=%d B=%d N=%d D=%d L=%d C=%d,%d,%d,%d t3=%d tk=%d split=%d", p.TM, d->B, d->N, d->D, d->L, d->C[0],
                      d->C[1], d->L > 2 ? d->C[2] : 0, d->L > 3 ? d->C[3] : 0, d->input_transform, d->transform_after, p.nsplit);
         const dim3 grid(d->B * p.tiles, p.nsplit);
         // dynamic LDS above 48 KiB has to be allowed once per kernel (process-wide flag, not per device: one process drives one GPU)
-        static bool granted[2] = {false, false};
-        const int ki = p.TM == 64 ? 0 : 1;
+        static bool granted[4] = {false, false, false, false};
+        const int ki = (p.TM == 64 ? 0 : 1) + (offs ? 2 : 0);
         if (p.lds > 48 * 1024 && !granted[ki]) {
-            const void *fn = ki == 0 ? (const void *)pn_infer_kernel<64> : (const void *)pn_infer_kernel<32>;
+            const void *fns[4] = {(const void *)pn_infer_kernel<64, false>, (const void *)pn_infer_kernel<32, false>,
+                                  (const void *)pn_infer_kernel<64, true>, (const void *)pn_infer_kernel<32, true>};
+            const void *fn = fns[ki];
             const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kPnMaxLds);
             PNPP_REQUIRE(e == hipSuccess, PNPP_ERR_LAUNCH, "pn_infer: cannot allow %d bytes of dynamic LDS: %s", kPnMaxLds, hipGetErrorString(e));
             granted[ki] = true;
         }
-        if (p.TM == 64)
-            hipLaunchKernelGGL(pn_infer_kernel<64>, grid, dim3(kPnThreads), p.lds, st, P);
+        if (p.TM == 64 && !offs)
+            hipLaunchKernelGGL((pn_infer_kernel<64, false>), grid, dim3(kPnThreads), p.lds, st, P);
+        else if (!offs)
+            hipLaunchKernelGGL((pn_infer_kernel<32, false>), grid, dim3(kPnThreads), p.lds, st, P);
+        else if (p.TM == 64)
+            hipLaunchKernelGGL((pn_infer_kernel<64, true>), grid, dim3(kPnThreads), p.lds, st, P);
         else
-            hipLaunchKernelGGL(pn_infer_kernel<32>, grid, dim3(kPnThreads), p.lds, st, P);
+            hipLaunchKernelGGL((pn_infer_kernel<32, true>), grid, dim3(kPnThreads), p.lds, st, P);
         PNPP_CHECK_LAUNCH("pn_infer");
     }
     {
         ProfScope ps(st, "pn_infer_finish_kernel B=%d slots=%d C=%d relu=%d", d->B, p.nslot, clast, d->relu_last);
-        hipLaunchKernelGGL(pn_infer_finish_kernel, dim3(d->B, (clast + 255) / 256), dim3(256), 0, st, part, bl.b[d->L - 1], p.nslot, clast,
+        hipLaunchKernelGGL(pn_infer_finish_kernel, dim3(d->B, (clast + 255) / 256), dim3(256), 0, st, part, bl.b[d->L - 1], offs, p.nslot, clast,
                            d->relu_last, a->out);
         PNPP_CHECK_LAUNCH("pn_infer_finish");
     }
@@ -422,4 +444,10 @@ extern "C" int pnpp_pn_infer_weights_layout(const pnpp_pn_infer_desc *d, int lay
 extern "C" int pnpp_pn_infer_fold(const pnpp_pn_infer_desc *d, const pnpp_sa_fwd_args *params, void *weights, void *stream) {
     return pn_infer_fold(d, params, weights, as_stream(stream));
 }
-extern "C" int pnpp_pn_infer(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, void *stream) { return pn_infer(d, a, as_stream(stream)); }
+extern "C" int pnpp_pn_infer(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, void *stream) {
+    return pn_infer(d, a, nullptr, as_stream(stream));
+}
+extern "C" int pnpp_pn_infer_ragged(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, const int32_t *offs, void *stream) {
+    PNPP_REQUIRE(offs, PNPP_ERR_ARG, "pn_infer_ragged: null offsets");
+    return pn_infer(d, a, offs, as_stream(stream));
+}

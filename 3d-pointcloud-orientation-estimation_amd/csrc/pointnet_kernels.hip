@@ -8,6 +8,10 @@
 // + beta_c) with zsel the cloud's max of z where a_c >= 0 and its min otherwise.  The forward pass keeps per (cloud, channel) the max /
 // min of z and their rows only; the training statistics come from the column sums S and the Gram matrix G of A; the backward pass
 // is one M x K x K product with Q = W^T diag(a m istd) W plus a routed scatter.
+//
+// Ragged batches ("Vanilla PointNet", "Ragged batches"): the kernels that address rows per cloud carry a RAGGED template
+// flag.  The valid rows are packed once, by pn_transform_kernel<true>, and addressed through the lengths' prefix sum `offs`; the
+// <false> instantiations are the uniform kernels as they were.
 #include "pointnet.h"
 
 #include <math.h>
@@ -26,16 +30,73 @@ __device__ inline double wave_sum_to0(double v) {
 }
 __device__ inline double wave_sum(double v) { return __shfl(wave_sum_to0(v), 0, 64); }
 
+// Ragged batches (RAGGED kernels): the clouds' valid rows are packed one cloud after the other, offs (B + 1) int32 their exclusive
+// prefix sum -- row n of cloud b at offs[b] + n, Nv = offs[b + 1] - offs[b] of the padded N.  b is a block index, so the two loads
+// are wave-uniform.  Uniform batches: row b * N + n, Nv = N.
+template <bool RAGGED>
+__device__ __forceinline__ void pn_cloud_rows(const int32_t *__restrict__ offs, int b, int N, size_t &row0, int &Nv) {
+    if (RAGGED) {
+        const int o0 = offs[b], o1 = offs[b + 1];
+        row0 = (size_t)o0;
+        Nv = min(max(o1 - o0, 0), N);
+    } else {
+        row0 = (size_t)b * N;
+        Nv = N;
+    }
+}
+
+// lens_out[b] = min(max(lengths[b], 1), N) and offs = their exclusive prefix sum (B + 1 entries): one workgroup, every thread a
+// run of consecutive clouds, the 256 run totals scanned by thread 0
+__global__ void __launch_bounds__(256) pn_offsets_kernel(const int32_t *__restrict__ lengths, int B, int N, int32_t *__restrict__ lens_out,
+                                                         int32_t *__restrict__ offs) {
+    __shared__ int run[256];
+    const int t = threadIdx.x, per = (B + 255) / 256, b0 = min(t * per, B), b1 = min(b0 + per, B);
+    int s = 0;
+    for (int b = b0; b < b1; ++b) s += min(max(lengths[b], 1), N);
+    run[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int acc = 0;
+        for (int i = 0; i < 256; ++i) {
+            const int x = run[i];
+            run[i] = acc;
+            acc += x;
+        }
+        offs[B] = acc;
+    }
+    __syncthreads();
+    int acc = run[t];
+    for (int b = b0; b < b1; ++b) {
+        const int n = min(max(lengths[b], 1), N);
+        lens_out[b] = n;
+        offs[b] = acc;
+        acc += n;
+    }
+}
+
+int launch_pn_offsets(const int32_t *lengths, int B, int N, int32_t *lens_out, int32_t *offs, hipStream_t st) {
+    ProfScope ps(st, "pn_offsets_kernel B=%d", B);
+    hipLaunchKernelGGL(pn_offsets_kernel, dim3(1), dim3(256), 0, st, lengths, B, N, lens_out, offs);
+    PNPP_CHECK_LAUNCH("pn_offsets");
+    return PNPP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // train-mode statistics: per-cloud Gram matrix / column sums (float64), then their sums and the centred Gram matrix
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) pn_gram_kernel(const float *__restrict__ a, int N, int K, int rows_per_slice,
-                                                       double *__restrict__ gp, double *__restrict__ sp) {
+// RAGGED: the slices are those of the padded N, so lengths == N gives the uniform reduction order; a (cloud, slice) without a valid
+// row writes zero partials
+template <bool RAGGED>
+__global__ void __launch_bounds__(256) pn_gram_kernel(const float *__restrict__ a, const int32_t *__restrict__ offs, int N, int K,
+                                                       int rows_per_slice, double *__restrict__ gp, double *__restrict__ sp) {
     __shared__ float As[32][PN_KMAX];
     const int nt = (K + 63) / 64;
     const int ti = blockIdx.x / nt, tj = blockIdx.x % nt, b = blockIdx.y, t = threadIdx.x;
     const int slice = blockIdx.z, part = b * gridDim.z + slice;   // partials in (cloud, slice) order
-    const int nbeg = slice * rows_per_slice, nend = min(N, nbeg + rows_per_slice);
+    size_t row0;
+    int Nv;
+    pn_cloud_rows<RAGGED>(offs, b, N, row0, Nv);
+    const int nbeg = slice * rows_per_slice, nend = min(Nv, nbeg + rows_per_slice);
     const int li = ti * 64 + (t / 16) * 4, lj = tj * 64 + (t % 16) * 4;
     double acc[4][4] = {};
     double s = 0.0;
@@ -45,7 +106,7 @@ __global__ void __launch_bounds__(256) pn_gram_kernel(const float *__restrict__ 
         __syncthreads();
         for (int idx = t; idx < 32 * PN_KMAX; idx += 256) {
             const int r = idx / PN_KMAX, k = idx % PN_KMAX, n = n0 + r;
-            As[r][k] = (n < nend && k < K) ? a[((size_t)b * N + n) * K + k] : 0.f;
+            As[r][k] = (n < nend && k < K) ? a[(row0 + n) * K + k] : 0.f;
         }
         __syncthreads();
         for (int r = 0; r < 32; ++r) {
@@ -82,15 +143,19 @@ __global__ void pn_gram_reduce_kernel(const double *__restrict__ gp, const doubl
 
 int pn_gram_slices(int N) { return N >= 8 * 128 ? 8 : N >= 4 * 64 ? 4 : 1; }
 
-int launch_pn_gram(const float *a, int B, int N, int K, double *gp, double *sp, double *S, double *Cc, hipStream_t st) {
+int launch_pn_gram(const float *a, const int32_t *offs, long long M, int B, int N, int K, double *gp, double *sp, double *S, double *Cc,
+                   hipStream_t st) {
     const int nt = cdiv(K, 64), ns = pn_gram_slices(N), rps = cdiv(cdiv(N, ns), 32) * 32;
     {
         ProfScope ps(st, "pn_gram_kernel B=%d N=%d K=%d slices=%d", B, N, K, ns);
-        hipLaunchKernelGGL(pn_gram_kernel, dim3(nt * nt, B, ns), dim3(256), 0, st, a, N, K, rps, gp, sp);
+        if (offs)
+            hipLaunchKernelGGL(pn_gram_kernel<true>, dim3(nt * nt, B, ns), dim3(256), 0, st, a, offs, N, K, rps, gp, sp);
+        else
+            hipLaunchKernelGGL(pn_gram_kernel<false>, dim3(nt * nt, B, ns), dim3(256), 0, st, a, offs, N, K, rps, gp, sp);
         PNPP_CHECK_LAUNCH("pn_gram");
     }
     ProfScope ps(st, "pn_gram_reduce_kernel K=%d", K);
-    hipLaunchKernelGGL(pn_gram_reduce_kernel, dim3(cdiv(K * K, 256)), dim3(256), 0, st, gp, sp, B * ns, K, (double)B * N, S, Cc);
+    hipLaunchKernelGGL(pn_gram_reduce_kernel, dim3(cdiv(K * K, 256)), dim3(256), 0, st, gp, sp, B * ns, K, (double)M, S, Cc);
     PNPP_CHECK_LAUNCH("pn_gram_reduce");
     return PNPP_OK;
 }
@@ -98,8 +163,9 @@ int launch_pn_gram(const float *a, int B, int N, int K, double *gp, double *sp, 
 // ------------------------------------------------------------------------------------------------
 // the max / min scan: one workgroup per (64-channel block, cloud) loops over the cloud's rows; z never leaves registers
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) pn_pool_scan_kernel(const float *__restrict__ a, const float *__restrict__ w,
-                                                            const float *__restrict__ bias, int N, int K, int C,
+template <bool RAGGED>
+__global__ void __launch_bounds__(256) pn_pool_scan_kernel(const float *__restrict__ a, const int32_t *__restrict__ offs,
+                                                            const float *__restrict__ w, const float *__restrict__ bias, int N, int K, int C,
                                                             float *__restrict__ zmax, int32_t *__restrict__ imax,
                                                             float *__restrict__ zmin, int32_t *__restrict__ imin) {
     __shared__ __attribute__((aligned(16))) float Ws[PN_KMAX][PN_CB];
@@ -116,13 +182,16 @@ __global__ void __launch_bounds__(256) pn_pool_scan_kernel(const float *__restri
     float vmax[4], vmin[4];
     int jmax[4], jmin[4];
     for (int q = 0; q < 4; ++q) vmax[q] = -INFINITY, vmin[q] = INFINITY, jmax[q] = 0, jmin[q] = 0;
-    const float *ab = a + (size_t)b * N * K;
-    for (int n0 = 0; n0 < N; n0 += PN_RT) {
+    size_t row0;
+    int Nv;
+    pn_cloud_rows<RAGGED>(offs, b, N, row0, Nv);
+    const float *ab = a + row0 * K;
+    for (int n0 = 0; n0 < Nv; n0 += PN_RT) {
         __syncthreads();
         for (int idx = t; idx < PN_RT * K4; idx += 256) {
             const int r = idx / K4, k4 = idx % K4, n = n0 + r;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (n < N) v = *reinterpret_cast<const float4 *>(ab + (size_t)n * K + k4 * 4);
+            if (n < Nv) v = *reinterpret_cast<const float4 *>(ab + (size_t)n * K + k4 * 4);
             As[k4 * 4 + 0][r] = v.x;
             As[k4 * 4 + 1][r] = v.y;
             As[k4 * 4 + 2][r] = v.z;
@@ -139,7 +208,7 @@ __global__ void __launch_bounds__(256) pn_pool_scan_kernel(const float *__restri
         }
         for (int p = 0; p < 4; ++p) {
             const int n = n0 + tr * 4 + p;
-            if (n >= N) break;
+            if (n >= Nv) break;
             for (int q = 0; q < 4; ++q) {
                 const float z = acc[p][q] + bc[q];
                 if (z > vmax[q]) vmax[q] = z, jmax[q] = n;
@@ -171,10 +240,13 @@ __global__ void __launch_bounds__(256) pn_pool_scan_kernel(const float *__restri
     }
 }
 
-int launch_pn_pool_scan(const float *a, const float *w, const float *bias, int B, int N, int K, int C, float *zmax, int32_t *imax,
-                        float *zmin, int32_t *imin, hipStream_t st) {
+int launch_pn_pool_scan(const float *a, const int32_t *offs, const float *w, const float *bias, int B, int N, int K, int C, float *zmax,
+                        int32_t *imax, float *zmin, int32_t *imin, hipStream_t st) {
     ProfScope ps(st, "pn_pool_scan_kernel B=%d N=%d K=%d C=%d", B, N, K, C);
-    hipLaunchKernelGGL(pn_pool_scan_kernel, dim3(C / PN_CB, B), dim3(256), 0, st, a, w, bias, N, K, C, zmax, imax, zmin, imin);
+    if (offs)
+        hipLaunchKernelGGL(pn_pool_scan_kernel<true>, dim3(C / PN_CB, B), dim3(256), 0, st, a, offs, w, bias, N, K, C, zmax, imax, zmin, imin);
+    else
+        hipLaunchKernelGGL(pn_pool_scan_kernel<false>, dim3(C / PN_CB, B), dim3(256), 0, st, a, offs, w, bias, N, K, C, zmax, imax, zmin, imin);
     PNPP_CHECK_LAUNCH("pn_pool_scan");
     return PNPP_OK;
 }
@@ -185,13 +257,12 @@ int launch_pn_pool_scan(const float *a, const float *w, const float *bias, int B
 __global__ void __launch_bounds__(256) pn_pool_finalize_kernel(
     const float *__restrict__ w, const float *__restrict__ bias, const float *__restrict__ gamma, const float *__restrict__ beta,
     const double *__restrict__ S, const double *__restrict__ Cc, const float *__restrict__ zmax, const int32_t *__restrict__ imax,
-    const float *__restrict__ zmin, const int32_t *__restrict__ imin, int B, int N, int K, int C, int relu, int training, float eps,
+    const float *__restrict__ zmin, const int32_t *__restrict__ imin, int B, double M, int K, int C, int relu, int training, float eps,
     float momentum, float *rm, float *rv, long long *nbt, float *__restrict__ mean, float *__restrict__ istd_out,
     float *__restrict__ zsel, float *__restrict__ ypre, int32_t *__restrict__ route, float *__restrict__ out) {
     const int lane = threadIdx.x % 64, c = blockIdx.x * 4 + threadIdx.x / 64;
     if (training && nbt && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;
     if (c >= C) return;
-    const double M = (double)B * N;
     const float *wc = w + (size_t)c * K;
     double mu, var;
     if (training) {
@@ -234,12 +305,12 @@ __global__ void __launch_bounds__(256) pn_pool_finalize_kernel(
 }
 
 int launch_pn_pool_finalize(const float *w, const float *bias, const float *gamma, const float *beta, const double *S, const double *Cc,
-                            const float *zmax, const int32_t *imax, const float *zmin, const int32_t *imin, int B, int N, int K, int C,
+                            const float *zmax, const int32_t *imax, const float *zmin, const int32_t *imin, int B, long long M, int K, int C,
                             int relu, int training, float eps, float momentum, float *rm, float *rv, long long *nbt, float *mean,
                             float *istd, float *zsel, float *ypre, int32_t *route, float *out, hipStream_t st) {
     ProfScope ps(st, "pn_pool_finalize_kernel B=%d C=%d", B, C);
     hipLaunchKernelGGL(pn_pool_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), 0, st, w, bias, gamma, beta, S, Cc, zmax, imax, zmin, imin,
-                       B, N, K, C, relu, training, eps, momentum, rm, rv, nbt, mean, istd, zsel, ypre, route, out);
+                       B, (double)M, K, C, relu, training, eps, momentum, rm, rv, nbt, mean, istd, zsel, ypre, route, out);
     PNPP_CHECK_LAUNCH("pn_pool_finalize");
     return PNPP_OK;
 }
@@ -247,15 +318,15 @@ int launch_pn_pool_finalize(const float *w, const float *bias, const float *gamm
 // ------------------------------------------------------------------------------------------------
 // backward, per channel (one wave each)
 // ------------------------------------------------------------------------------------------------
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) pn_pool_bwd_channels_kernel(
-    const float *__restrict__ a, const float *__restrict__ w, const float *__restrict__ gamma, const float *__restrict__ dout,
+    const float *__restrict__ a, const int32_t *__restrict__ offs, double M, const float *__restrict__ w, const float *__restrict__ gamma, const float *__restrict__ dout,
     const float *__restrict__ mean, const float *__restrict__ istd, const float *__restrict__ zsel, const float *__restrict__ ypre,
     const int32_t *__restrict__ route, const double *__restrict__ S, const double *__restrict__ Cc, int B, int N, int K, int C, int relu,
     int training, float *__restrict__ dw, float *__restrict__ db, float *__restrict__ dgamma, float *__restrict__ dbeta,
     float *__restrict__ coef, float *__restrict__ u, float *__restrict__ v) {
     const int lane = threadIdx.x % 64, c = blockIdx.x * 4 + threadIdx.x / 64;
     if (c >= C) return;
-    const double M = (double)B * N;
     const float is = istd[c], mu = mean[c], ac = gamma[c] * is;
     double sh = 0.0, shx = 0.0;
     for (int b = lane; b < B; b += 64) {
@@ -282,7 +353,8 @@ __global__ void __launch_bounds__(256) pn_pool_bwd_channels_kernel(
         for (int b = 0; b < B; ++b) {
             const size_t o = (size_t)b * C + c;
             const float h = (relu && !(ypre[o] > 0.f)) ? 0.f : dout[o];
-            acc += (double)h * a[((size_t)b * N + route[o]) * K + k];
+            const size_t row0 = RAGGED ? (size_t)offs[b] : (size_t)b * N;
+            acc += (double)h * a[(row0 + route[o]) * K + k];
         }
         if (training) {
             double cw = 0.0;
@@ -293,13 +365,17 @@ __global__ void __launch_bounds__(256) pn_pool_bwd_channels_kernel(
     }
 }
 
-int launch_pn_pool_bwd_channels(const float *a, const float *w, const float *gamma, const float *dout, const float *mean,
+int launch_pn_pool_bwd_channels(const float *a, const int32_t *offs, long long M, const float *w, const float *gamma, const float *dout, const float *mean,
                                 const float *istd, const float *zsel, const float *ypre, const int32_t *route, const double *S,
                                 const double *Cc, int B, int N, int K, int C, int relu, int training, float *dw, float *db,
                                 float *dgamma, float *dbeta, float *coef, float *u, float *v, hipStream_t st) {
     ProfScope ps(st, "pn_pool_bwd_channels_kernel B=%d K=%d C=%d", B, K, C);
-    hipLaunchKernelGGL(pn_pool_bwd_channels_kernel, dim3(cdiv(C, 4)), dim3(256), 0, st, a, w, gamma, dout, mean, istd, zsel, ypre,
-                       route, S, Cc, B, N, K, C, relu, training, dw, db, dgamma, dbeta, coef, u, v);
+    if (offs)
+        hipLaunchKernelGGL(pn_pool_bwd_channels_kernel<true>, dim3(cdiv(C, 4)), dim3(256), 0, st, a, offs, (double)M, w, gamma, dout, mean,
+                           istd, zsel, ypre, route, S, Cc, B, N, K, C, relu, training, dw, db, dgamma, dbeta, coef, u, v);
+    else
+        hipLaunchKernelGGL(pn_pool_bwd_channels_kernel<false>, dim3(cdiv(C, 4)), dim3(256), 0, st, a, offs, (double)M, w, gamma, dout, mean,
+                           istd, zsel, ypre, route, S, Cc, B, N, K, C, relu, training, dw, db, dgamma, dbeta, coef, u, v);
     PNPP_CHECK_LAUNCH("pn_pool_bwd_channels");
     return PNPP_OK;
 }
@@ -342,7 +418,9 @@ int launch_pn_pool_bwd_q(const float *w, const float *u, const float *v, int K, 
 
 // dA for one (64-row tile, cloud): cvec - Q (A_n - S/M) (train; the tile is centred as it is loaded, so a column whose mean is large
 // against its spread loses no digits), then the routed rows gathered in ascending channel order
-__global__ void __launch_bounds__(256) pn_pool_bwd_da_kernel(const float *__restrict__ a, const float *__restrict__ w,
+template <bool RAGGED>
+__global__ void __launch_bounds__(256) pn_pool_bwd_da_kernel(const float *__restrict__ a, const int32_t *__restrict__ offs,
+                                                              const float *__restrict__ w,
                                                               const float *__restrict__ Q, const float *__restrict__ cvec,
                                                               const float *__restrict__ coef, const int32_t *__restrict__ route,
                                                               const double *__restrict__ S, double M, int N, int K, int C,
@@ -354,6 +432,10 @@ __global__ void __launch_bounds__(256) pn_pool_bwd_da_kernel(const float *__rest
     __shared__ int cnt[257];
     __shared__ double mcol[PN_KMAX];
     const int n0 = blockIdx.x * PN_RT, b = blockIdx.y, t = threadIdx.x;
+    size_t row0;
+    int Nv;
+    pn_cloud_rows<RAGGED>(offs, b, N, row0, Nv);
+    if (RAGGED && n0 >= Nv) return;   // block-uniform, before the first barrier: no packed row belongs to this tile
     if (training && t < K) mcol[t] = S[t] / M;
     // 1. the (row, channel) pairs routed into this tile, in ascending channel order
     const int cpt = (C + 255) / 256;
@@ -388,7 +470,7 @@ __global__ void __launch_bounds__(256) pn_pool_bwd_da_kernel(const float *__rest
         for (int idx = t; idx < K * K; idx += 256) Qs[idx / K][idx % K] = Q[idx];
         for (int idx = t; idx < PN_RT * K; idx += 256) {
             const int r = idx / K, k = idx % K, n = n0 + r;
-            As[k * PN_RT + r] = n < N ? (float)((double)a[((size_t)b * N + n) * K + k] - mcol[k]) : 0.f;
+            As[k * PN_RT + r] = n < Nv ? (float)((double)a[(row0 + n) * K + k] - mcol[k]) : 0.f;
         }
         __syncthreads();
         if (tc * 8 < K)
@@ -419,15 +501,19 @@ __global__ void __launch_bounds__(256) pn_pool_bwd_da_kernel(const float *__rest
     __syncthreads();
     for (int idx = t; idx < PN_RT * K; idx += 256) {
         const int r = idx / K, k = idx % K, n = n0 + r;
-        if (n < N) da[((size_t)b * N + n) * K + k] = Os[idx];
+        if (n < Nv) da[(row0 + n) * K + k] = Os[idx];
     }
 }
 
-int launch_pn_pool_bwd_da(const float *a, const float *w, const float *Q, const float *cvec, const float *coef, const int32_t *route,
+int launch_pn_pool_bwd_da(const float *a, const int32_t *offs, long long M, const float *w, const float *Q, const float *cvec, const float *coef, const int32_t *route,
                           const double *S, int B, int N, int K, int C, int training, float *da, hipStream_t st) {
     ProfScope ps(st, "pn_pool_bwd_da_kernel B=%d N=%d K=%d C=%d", B, N, K, C);
-    hipLaunchKernelGGL(pn_pool_bwd_da_kernel, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, a, w, Q, cvec, coef, route, S, (double)B * N, N,
-                       K, C, training, da);
+    if (offs)
+        hipLaunchKernelGGL(pn_pool_bwd_da_kernel<true>, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, a, offs, w, Q, cvec, coef, route, S,
+                           (double)M, N, K, C, training, da);
+    else
+        hipLaunchKernelGGL(pn_pool_bwd_da_kernel<false>, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, a, offs, w, Q, cvec, coef, route, S,
+                           (double)M, N, K, C, training, da);
     PNPP_CHECK_LAUNCH("pn_pool_bwd_da");
     return PNPP_OK;
 }
@@ -435,12 +521,20 @@ int launch_pn_pool_bwd_da(const float *a, const float *w, const float *Q, const 
 // ------------------------------------------------------------------------------------------------
 // per-cloud transform
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) pn_transform_kernel(const float *__restrict__ x, long long sb, long long sn, long long sd,
-                                                            const float *__restrict__ tm, int N, int D, int k, int ldy,
-                                                            float *__restrict__ y) {
+// RAGGED: y holds packed rows; x is the padded input (row n of cloud b at b * sb + n * sn, rows n >= Nv never read) or, with xpacked,
+// packed rows itself (row offs[b] + n at pitch sn: the feature transform of an already packed layer)
+template <bool RAGGED>
+__global__ void __launch_bounds__(256) pn_transform_kernel(const float *__restrict__ x, const int32_t *__restrict__ offs, int xpacked,
+                                                            long long sb, long long sn, long long sd, const float *__restrict__ tm, int N,
+                                                            int D, int k, int ldy, float *__restrict__ y) {
     __shared__ float Ts[PN_TMAX * PN_TMAX];
     __shared__ float Xs[PN_RT][PN_TMAX + 1];
     const int n0 = blockIdx.x * PN_RT, b = blockIdx.y, t = threadIdx.x;
+    size_t row0;
+    int Nv;
+    pn_cloud_rows<RAGGED>(offs, b, N, row0, Nv);
+    if (RAGGED && n0 >= Nv) return;   // block-uniform, before the first barrier
+    const long long xb = (RAGGED && xpacked) ? (long long)row0 * sn : b * sb;
     if (tm)
         for (int idx = t; idx < k * k; idx += 256) Ts[idx] = tm[(size_t)b * k * k + idx];
     for (int idx = t; idx < PN_RT * D; idx += 256) {
@@ -448,42 +542,62 @@ __global__ void __launch_bounds__(256) pn_transform_kernel(const float *__restri
         if (sd == 1) r = idx / D, d = idx % D;
         else d = idx / PN_RT, r = idx % PN_RT;
         const int n = n0 + r;
-        Xs[r][d] = n < N ? x[b * sb + n * sn + d * sd] : 0.f;
+        Xs[r][d] = n < Nv ? x[xb + n * sn + d * sd] : 0.f;
     }
     __syncthreads();
     for (int idx = t; idx < PN_RT * ldy; idx += 256) {
         const int r = idx / ldy, j = idx % ldy, n = n0 + r;
-        if (n >= N) break;
+        if (n >= Nv) break;
         float val = 0.f;
         if (tm && j < k) {
             for (int i = 0; i < k; ++i) val = fmaf(Xs[r][i], Ts[i * k + j], val);
         } else if (j < D) {
             val = Xs[r][j];
         }
-        y[((size_t)b * N + n) * ldy + j] = val;
+        y[(row0 + n) * ldy + j] = val;
     }
 }
 
-int launch_pn_transform(const float *x, long long sb, long long sn, long long sd, const float *t, int B, int N, int D, int k, int ldy,
-                        float *y, hipStream_t st) {
+int launch_pn_transform(const float *x, const int32_t *offs, int xpacked, long long sb, long long sn, long long sd, const float *t, int B,
+                        int N, int D, int k, int ldy, float *y, hipStream_t st) {
     ProfScope ps(st, "pn_transform_kernel N=%d D=%d k=%d", N, D, t ? k : 0);
-    hipLaunchKernelGGL(pn_transform_kernel, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, x, sb, sn, sd, t, N, D, k, ldy, y);
+    if (offs)
+        hipLaunchKernelGGL(pn_transform_kernel<true>, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, x, offs, xpacked, sb, sn, sd, t, N, D, k, ldy,
+                           y);
+    else
+        hipLaunchKernelGGL(pn_transform_kernel<false>, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, x, offs, 0, sb, sn, sd, t, N, D, k, ldy, y);
     PNPP_CHECK_LAUNCH("pn_transform");
     return PNPP_OK;
 }
 
 // dX_b = dY_b T_b^T on the transformed columns, the passed-through columns copied; written with X's strides
+// RAGGED: dy holds packed rows; dx has the padded layout with exact zeros at rows n >= Nv, or (xpacked) the packed one
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) pn_transform_dx_kernel(const float *__restrict__ tm, const float *__restrict__ dy,
-                                                               long long sb, long long sn, long long sd, int N, int D, int k,
-                                                               int ldy, float *__restrict__ dx) {
+                                                               const int32_t *__restrict__ offs, int xpacked, long long sb, long long sn,
+                                                               long long sd, int N, int D, int k, int ldy, float *__restrict__ dx) {
     __shared__ float Ts[PN_TMAX * PN_TMAX];
     __shared__ float Ys[PN_RT][PN_TMAX + 1];
     const int n0 = blockIdx.x * PN_RT, b = blockIdx.y, t = threadIdx.x;
+    size_t row0;
+    int Nv;
+    pn_cloud_rows<RAGGED>(offs, b, N, row0, Nv);
+    const long long xb = (RAGGED && xpacked) ? (long long)row0 * sn : b * sb;
+    if (RAGGED && n0 >= Nv) {   // block-uniform, before the first barrier: a tile of padding rows alone
+        if (!xpacked)
+            for (int idx = t; idx < PN_RT * D; idx += 256) {
+                int r, i;
+                if (sd == 1) r = idx / D, i = idx % D;
+                else i = idx / PN_RT, r = idx % PN_RT;
+                if (n0 + r < N) dx[xb + (n0 + r) * sn + i * sd] = 0.f;
+            }
+        return;
+    }
     if (tm)
         for (int idx = t; idx < k * k; idx += 256) Ts[idx] = tm[(size_t)b * k * k + idx];
     for (int idx = t; idx < PN_RT * D; idx += 256) {
         const int r = idx / D, j = idx % D, n = n0 + r;
-        Ys[r][j] = n < N ? dy[((size_t)b * N + n) * ldy + j] : 0.f;
+        Ys[r][j] = n < Nv ? dy[(row0 + n) * ldy + j] : 0.f;
     }
     __syncthreads();
     for (int idx = t; idx < PN_RT * D; idx += 256) {
@@ -491,30 +605,37 @@ __global__ void __launch_bounds__(256) pn_transform_dx_kernel(const float *__res
         if (sd == 1) r = idx / D, i = idx % D;
         else i = idx / PN_RT, r = idx % PN_RT;
         const int n = n0 + r;
-        if (n >= N) continue;
+        if (n >= ((RAGGED && !xpacked) ? N : Nv)) continue;
         float val;
-        if (tm && i < k) {
+        if (RAGGED && n >= Nv) {
+            val = 0.f;
+        } else if (tm && i < k) {
             val = 0.f;
             for (int j = 0; j < k; ++j) val = fmaf(Ys[r][j], Ts[i * k + j], val);
         } else {
             val = Ys[r][i];
         }
-        dx[b * sb + n * sn + i * sd] = val;
+        dx[xb + n * sn + i * sd] = val;
     }
 }
 
 // dT_b = X_b^T dY_b over the cloud's rows, float64, slices of rows summed in a fixed order
-__global__ void __launch_bounds__(256) pn_transform_dt_kernel(const float *__restrict__ x, long long sb, long long sn, long long sd,
-                                                               const float *__restrict__ dy, int N, int k, int ldy, int epw,
-                                                               float *__restrict__ dt) {
+template <bool RAGGED>
+__global__ void __launch_bounds__(256) pn_transform_dt_kernel(const float *__restrict__ x, const int32_t *__restrict__ offs, int xpacked,
+                                                               long long sb, long long sn, long long sd, const float *__restrict__ dy, int N,
+                                                               int k, int ldy, int epw, float *__restrict__ dt) {
     __shared__ double red[256];
     const int b = blockIdx.y, t = threadIdx.x;
+    size_t row0;
+    int Nv;
+    pn_cloud_rows<RAGGED>(offs, b, N, row0, Nv);
+    const long long xb = (RAGGED && xpacked) ? (long long)row0 * sn : b * sb;
     const int e = blockIdx.x * epw + t % epw, s = t / epw, nslice = 256 / epw;
     double acc = 0.0;
     if (e < k * k) {
         const int i = e / k, j = e % k;
-        for (int n = s; n < N; n += nslice)
-            acc += (double)x[b * sb + n * sn + i * sd] * (double)dy[((size_t)b * N + n) * ldy + j];
+        for (int n = s; n < Nv; n += nslice)
+            acc += (double)x[xb + n * sn + i * sd] * (double)dy[(row0 + n) * ldy + j];
     }
     red[t] = acc;
     __syncthreads();
@@ -525,18 +646,28 @@ __global__ void __launch_bounds__(256) pn_transform_dt_kernel(const float *__res
     }
 }
 
-int launch_pn_transform_bwd(const float *x, long long sb, long long sn, long long sd, const float *t, const float *dy, int B, int N,
-                            int D, int k, int ldy, float *dx, float *dt, hipStream_t st) {
+int launch_pn_transform_bwd(const float *x, const int32_t *offs, int xpacked, long long sb, long long sn, long long sd, const float *t,
+                            const float *dy, int B, int N, int D, int k, int ldy, float *dx, float *dt, hipStream_t st) {
     if (dx) {
         ProfScope ps(st, "pn_transform_dx_kernel N=%d D=%d k=%d", N, D, t ? k : 0);
-        hipLaunchKernelGGL(pn_transform_dx_kernel, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, t, dy, sb, sn, sd, N, D, k, ldy, dx);
+        if (offs)
+            hipLaunchKernelGGL(pn_transform_dx_kernel<true>, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, t, dy, offs, xpacked, sb, sn, sd, N, D, k,
+                               ldy, dx);
+        else
+            hipLaunchKernelGGL(pn_transform_dx_kernel<false>, dim3(cdiv(N, PN_RT), B), dim3(256), 0, st, t, dy, offs, 0, sb, sn, sd, N, D, k, ldy,
+                               dx);
         PNPP_CHECK_LAUNCH("pn_transform_dx");
     }
     if (dt) {
         int epw = 1;
         while (epw < k * k && epw < 256) epw *= 2;
         ProfScope ps(st, "pn_transform_dt_kernel N=%d k=%d", N, k);
-        hipLaunchKernelGGL(pn_transform_dt_kernel, dim3(cdiv(k * k, epw), B), dim3(256), 0, st, x, sb, sn, sd, dy, N, k, ldy, epw, dt);
+        if (offs)
+            hipLaunchKernelGGL(pn_transform_dt_kernel<true>, dim3(cdiv(k * k, epw), B), dim3(256), 0, st, x, offs, xpacked, sb, sn, sd, dy, N, k,
+                               ldy, epw, dt);
+        else
+            hipLaunchKernelGGL(pn_transform_dt_kernel<false>, dim3(cdiv(k * k, epw), B), dim3(256), 0, st, x, offs, 0, sb, sn, sd, dy, N, k, ldy,
+                               epw, dt);
         PNPP_CHECK_LAUNCH("pn_transform_dt");
     }
     return PNPP_OK;
@@ -644,51 +775,85 @@ int launch_pn_add_identity(const float *x, int B, int k, float *y, hipStream_t s
 }
 
 // out (B, C1 + C2, N): rows 0..C1-1 the global feature repeated over the points, then the per-point features (rows of pf)
-__global__ void pn_concat_kernel(const float *__restrict__ g, const float *__restrict__ pf, int B, int N, int C1, int C2,
-                                 float *__restrict__ out) {
+// RAGGED: pf holds packed rows (or, pf_padded, padded ones: the Predictor's tapped features); columns n >= Nv of out are exact zeros
+template <bool RAGGED>
+__global__ void pn_concat_kernel(const float *__restrict__ g, const float *__restrict__ pf, const int32_t *__restrict__ offs, int pf_padded,
+                                 int B, int N, int C1, int C2, float *__restrict__ out) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int Ct = C1 + C2;
     if (idx >= (long long)B * Ct * N) return;
     const int n = (int)(idx % N), c = (int)((idx / N) % Ct), b = (int)(idx / ((long long)N * Ct));
-    out[idx] = c < C1 ? g[(size_t)b * C1 + c] : pf[((size_t)b * N + n) * C2 + (c - C1)];
+    size_t row0 = (size_t)b * N;
+    if (RAGGED) {
+        const int o0 = offs[b], Nv = min(max(offs[b + 1] - o0, 0), N);
+        if (n >= Nv) {
+            out[idx] = 0.f;
+            return;
+        }
+        if (!pf_padded) row0 = (size_t)o0;
+    }
+    out[idx] = c < C1 ? g[(size_t)b * C1 + c] : pf[(row0 + n) * C2 + (c - C1)];
 }
 
-__global__ void __launch_bounds__(256) pn_concat_dg_kernel(const float *__restrict__ dout, int N, int C1, int C2,
-                                                            float *__restrict__ dg) {
+// RAGGED: dout at columns n >= Nv is not read
+template <bool RAGGED>
+__global__ void __launch_bounds__(256) pn_concat_dg_kernel(const float *__restrict__ dout, const int32_t *__restrict__ offs, int N, int C1,
+                                                            int C2, float *__restrict__ dg) {
     const int lane = threadIdx.x % 64, c = blockIdx.x * 4 + threadIdx.x / 64, b = blockIdx.y;
     if (c >= C1) return;
     const float *row = dout + ((size_t)b * (C1 + C2) + c) * N;
     double s = 0.0;
-    for (int n = lane; n < N; n += 64) s += row[n];
+    size_t row0;
+    int Nv;
+    pn_cloud_rows<RAGGED>(offs, b, N, row0, Nv);
+    for (int n = lane; n < Nv; n += 64) s += row[n];
     s = wave_sum_to0(s);
     if (lane == 0) dg[(size_t)b * C1 + c] = (float)s;
 }
 
-__global__ void pn_concat_dpf_kernel(const float *__restrict__ dout, int B, int N, int C1, int C2, float *__restrict__ dpf) {
+template <bool RAGGED>
+__global__ void pn_concat_dpf_kernel(const float *__restrict__ dout, const int32_t *__restrict__ offs, int B, int N, int C1, int C2,
+                                     float *__restrict__ dpf) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long long)B * N * C2) return;
     const int j = (int)(idx % C2), n = (int)((idx / C2) % N), b = (int)(idx / ((long long)C2 * N));
+    if (RAGGED) {   // the grid covers the padded rows; the valid ones go to their packed places
+        const int o0 = offs[b], Nv = min(max(offs[b + 1] - o0, 0), N);
+        if (n < Nv) dpf[((size_t)o0 + n) * C2 + j] = dout[((size_t)b * (C1 + C2) + C1 + j) * N + n];
+        return;
+    }
     dpf[idx] = dout[((size_t)b * (C1 + C2) + C1 + j) * N + n];
 }
 
-int launch_pn_concat(const float *g, const float *pf, int B, int N, int C1, int C2, float *out, hipStream_t st) {
+int launch_pn_concat(const float *g, const float *pf, const int32_t *offs, int pf_padded, int B, int N, int C1, int C2, float *out,
+                     hipStream_t st) {
     const long long tot = (long long)B * (C1 + C2) * N;
     ProfScope ps(st, "pn_concat_kernel B=%d N=%d", B, N);
-    hipLaunchKernelGGL(pn_concat_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, g, pf, B, N, C1, C2, out);
+    if (offs)
+        hipLaunchKernelGGL(pn_concat_kernel<true>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, g, pf, offs, pf_padded, B, N, C1, C2,
+                           out);
+    else
+        hipLaunchKernelGGL(pn_concat_kernel<false>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, g, pf, offs, 0, B, N, C1, C2, out);
     PNPP_CHECK_LAUNCH("pn_concat");
     return PNPP_OK;
 }
 
-int launch_pn_concat_bwd(const float *dout, int B, int N, int C1, int C2, float *dg, float *dpf, hipStream_t st) {
+int launch_pn_concat_bwd(const float *dout, const int32_t *offs, int B, int N, int C1, int C2, float *dg, float *dpf, hipStream_t st) {
     if (dg) {
         ProfScope ps(st, "pn_concat_dg_kernel B=%d N=%d", B, N);
-        hipLaunchKernelGGL(pn_concat_dg_kernel, dim3(cdiv(C1, 4), B), dim3(256), 0, st, dout, N, C1, C2, dg);
+        if (offs)
+            hipLaunchKernelGGL(pn_concat_dg_kernel<true>, dim3(cdiv(C1, 4), B), dim3(256), 0, st, dout, offs, N, C1, C2, dg);
+        else
+            hipLaunchKernelGGL(pn_concat_dg_kernel<false>, dim3(cdiv(C1, 4), B), dim3(256), 0, st, dout, offs, N, C1, C2, dg);
         PNPP_CHECK_LAUNCH("pn_concat_dg");
     }
     if (dpf) {
         const long long tot = (long long)B * N * C2;
         ProfScope ps(st, "pn_concat_dpf_kernel B=%d N=%d", B, N);
-        hipLaunchKernelGGL(pn_concat_dpf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, dout, B, N, C1, C2, dpf);
+        if (offs)
+            hipLaunchKernelGGL(pn_concat_dpf_kernel<true>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, dout, offs, B, N, C1, C2, dpf);
+        else
+            hipLaunchKernelGGL(pn_concat_dpf_kernel<false>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, dout, offs, B, N, C1, C2, dpf);
         PNPP_CHECK_LAUNCH("pn_concat_dpf");
     }
     return PNPP_OK;

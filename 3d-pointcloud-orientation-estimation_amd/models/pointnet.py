@@ -15,6 +15,15 @@ Inputs are GPU float32 tensors; there is no CPU fallback.  PointNet.forward(x, r
 `trans_feat` (the reference drops them), for ops.feature_transform_regularizer in the loss.  Nothing of a forward pass is kept
 on the module: a tensor held there would keep the step's autograd graph -- and its gradient-accumulation nodes, bound to the
 stream they were created on -- alive into the next step, which breaks a hipGraph capture that follows eager steps.
+
+Ragged batches: every forward() takes lengths=(B,) integers, 1 <= lengths[b] <= N; cloud b is the first lengths[b] points of its
+row and the padding may hold anything (NaN included).  The first ops.pn_transform packs the valid rows, cloud after cloud, and all
+per-point work runs on the M = sum(lengths) packed rows: every per-point BatchNorm takes its statistics over exactly those rows,
+each cloud's max runs over its own rows, the gradient at padding is an exact zero, and global_feat=False returns zeros in the
+padding columns.  Eval mode: row b is what the call on x[b:b+1, :, :lengths[b]] returns.  M is data dependent, so a ragged
+TRAINING step is eager only (a device lengths tensor costs one read-back per forward; a list or CPU tensor none) unless the
+lengths are fixed across replays; the forward-only Predictor keeps padded shapes and stays capturable.  The trunks need M > 32.
+Without lengths nothing changes.
 """
 import types
 
@@ -22,6 +31,7 @@ import torch
 import torch.nn as nn
 
 from pnpp_hip import ops
+from pnpp_hip.lengths import packed_lengths
 
 
 def _pad4(d: int) -> int:
@@ -43,10 +53,16 @@ def _first_layer(conv: nn.Conv1d, width: int):
     return types.SimpleNamespace(weight=wp, bias=conv.bias)
 
 
-def _tnet_rows(m: nn.Module, rows: torch.Tensor, B: int, N: int, k: int) -> torch.Tensor:
-    """The T-Net on (B*N, width) point rows -> (B, k, k)."""
+def _packed(lengths, B: int, N: int, device):
+    """None, or the batch's PackedLengths, built once per forward and handed to every operator"""
+    return None if lengths is None else packed_lengths(lengths, B, N, device)
+
+
+def _tnet_rows(m: nn.Module, rows: torch.Tensor, B: int, N: int, k: int, lengths=None) -> torch.Tensor:
+    """The T-Net on (B*N, width) point rows -- with lengths, the sum(lengths) packed rows -> (B, k, k)."""
     t = m.training
-    g = ops.pn_trunk(rows, B, N, [(_first_layer(m.conv1, rows.shape[1]), m.bn1), (m.conv2, m.bn2)], (m.conv3, m.bn3), True, t)
+    g = ops.pn_trunk(rows, B, N, [(_first_layer(m.conv1, rows.shape[1]), m.bn1), (m.conv2, m.bn2)], (m.conv3, m.bn3), True, t,
+                     lengths=lengths)
     g = ops.fc_block(g, m.fc1, m.bn4, relu=True, training=t)
     g = ops.fc_block(g, m.fc2, m.bn5, relu=True, training=t)
     return ops.pn_add_identity(ops.fc_block(g, m.fc3, training=t), k)
@@ -68,11 +84,12 @@ class STN3d(nn.Module):
         self.bn5 = nn.BatchNorm1d(256)
         self.relu = nn.ReLU()
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """x (B, D, N) -> (B, 3, 3)."""
+    def forward(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
+        """x (B, D, N) -> (B, 3, 3).  lengths (B,): cloud b is x[b, :, :lengths[b]]."""
         B, D, N = x.shape
         _check_channels(D, self.conv1.in_channels)
-        return _tnet_rows(self, ops.pn_transform(x.transpose(1, 2), None, _pad4(D)), B, N, 3)
+        lengths = _packed(lengths, B, N, x.device)
+        return _tnet_rows(self, ops.pn_transform(x.transpose(1, 2), None, _pad4(D), lengths=lengths), B, N, 3, lengths)
 
 
 class STNkd(nn.Module):
@@ -92,11 +109,12 @@ class STNkd(nn.Module):
         self.bn5 = nn.BatchNorm1d(256)
         self.relu = nn.ReLU()
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """x (B, k, N) -> (B, k, k)."""
+    def forward(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
+        """x (B, k, N) -> (B, k, k).  lengths (B,): cloud b is x[b, :, :lengths[b]]."""
         B, D, N = x.shape
         _check_channels(D, self.k)
-        return _tnet_rows(self, ops.pn_transform(x.transpose(1, 2), None, _pad4(D)), B, N, self.k)
+        lengths = _packed(lengths, B, N, x.device)
+        return _tnet_rows(self, ops.pn_transform(x.transpose(1, 2), None, _pad4(D), lengths=lengths), B, N, self.k, lengths)
 
 
 class PointNetEncoder(nn.Module):
@@ -114,14 +132,17 @@ class PointNetEncoder(nn.Module):
         if self.feature_transform:
             self.fstn = STNkd(k=64)
 
-    def forward(self, x: torch.Tensor):
+    def forward(self, x: torch.Tensor, lengths=None):
         """x (B, D, N), D >= 3 (the first three columns are coordinates) -> (global (B, 1024) or (B, 1088, N), trans (B, 3, 3),
-        trans_feat (B, 64, 64) or None)."""
+        trans_feat (B, 64, 64) or None).  lengths (B,): cloud b is x[b, :, :lengths[b]]; the (B, 1088, N) output is zero in the
+        padding columns."""
         B, D, N = x.shape
         _check_channels(D, self.conv1.in_channels)
         t = self.training
         xr = x.transpose(1, 2)                               # (B, N, D) view, read in place
         width = _pad4(D)
+        if lengths is not None:
+            return self._forward_ragged(xr, B, N, width, _packed(lengths, B, N, x.device))
         trans = _tnet_rows(self.stn, ops.pn_transform(xr, None, width), B, N, 3)
         rows = ops.pn_transform(xr, trans, width)             # [xyz @ trans, extra columns, zero padding]
         h = ops.fc_block(rows, _first_layer(self.conv1, width), self.bn1, relu=True, training=t)
@@ -134,6 +155,21 @@ class PointNetEncoder(nn.Module):
         if self.global_feat:
             return g, trans, trans_feat
         return ops.pn_concat(g, pointfeat, N), trans, trans_feat
+
+    def _forward_ragged(self, xr, B, N, width, pk):
+        """forward() on the packed valid rows: the same operators, every (B*N, .) array replaced by its (sum(lengths), .) packing"""
+        t = self.training
+        trans = _tnet_rows(self.stn, ops.pn_transform(xr, None, width, lengths=pk), B, N, 3, pk)
+        rows = ops.pn_transform(xr, trans, width, lengths=pk)
+        h = ops.fc_block(rows, _first_layer(self.conv1, width), self.bn1, relu=True, training=t)
+        trans_feat = None
+        if self.feature_transform:
+            trans_feat = _tnet_rows(self.fstn, h, B, N, 64, pk)
+            h = ops.pn_transform(h, trans_feat, 64, lengths=pk, B=B, N=N)
+        g = ops.pn_trunk(h, B, N, [(self.conv2, self.bn2)], (self.conv3, self.bn3), False, t, lengths=pk)
+        if self.global_feat:
+            return g, trans, trans_feat
+        return ops.pn_concat(g, h, N, lengths=pk), trans, trans_feat
 
 
 class PointNet(nn.Module):
@@ -148,13 +184,14 @@ class PointNet(nn.Module):
         self.fc3 = nn.Linear(256, 3)
         self.relu = nn.ReLU()
 
-    def forward(self, x: torch.Tensor, drop_mask=None, return_transforms: bool = False):
+    def forward(self, x: torch.Tensor, drop_mask=None, return_transforms: bool = False, lengths=None):
         """x (B, D, N) or (B, N, 3|6) -> (B, 3), or (out, trans (B, 3, 3), trans_feat (B, 64, 64) | None) with
         return_transforms.  drop_mask (B, 256) of {0,1} replaces the dropout draw (parity runs); the dropout comes before bn2,
-        as in the reference's relu(bn2(dropout(fc2(x))))."""
+        as in the reference's relu(bn2(dropout(fc2(x)))).  lengths (B,): a ragged batch, cloud b its first lengths[b] points (the
+        module docstring); the head, on B rows, is unchanged."""
         if x.dim() == 3 and x.shape[2] in (3, 6):
             x = x.transpose(1, 2)
-        g, trans, trans_feat = self.encoder(x)
+        g, trans, trans_feat = self.encoder(x) if lengths is None else self.encoder(x, lengths=lengths)
         t = self.training
         h = ops.fc_block(g, self.fc1, self.bn1, relu=True, training=t)
         h = ops.fc_block(h, self.fc2, None, relu=False, dropout=self.dropout, training=t, mask=drop_mask)

@@ -247,6 +247,17 @@ SIGNATURES = {
     "pnpp_pn_concat_bwd": (_i, [_fp, _i, _i, _i, _i, _fp, _fp, _fp]),
     "pnpp_pn_bn_relu": (_i, [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _f, _f, _fp, _fp, _fp, _fp]),
     "pnpp_pn_bn_relu_bwd": (_i, [_fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp]),
+    # ragged batches of the vanilla PointNet: packed point rows addressed through offs (B + 1), see include/pnpp_hip.h
+    "pnpp_pn_offsets": (_i, [_fp, _i, _i, _fp, _fp, _fp]),
+    "pnpp_pn_pool_saved_bytes_ragged": (_sz, [C.POINTER(PnPoolDesc), _i]),
+    "pnpp_pn_pool_scratch_bytes_ragged": (_sz, [C.POINTER(PnPoolDesc), _i]),
+    "pnpp_pn_pool_forward_ragged": (_i, [C.POINTER(PnPoolDesc), C.POINTER(PnPoolFwdArgs), _fp, _i, _fp]),
+    "pnpp_pn_pool_backward_ragged": (_i, [C.POINTER(PnPoolDesc), C.POINTER(PnPoolBwdArgs), _fp, _i, _fp]),
+    "pnpp_pn_transform_ragged": (_i, [_fp, _i, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp]),
+    "pnpp_pn_transform_bwd_ragged": (_i, [_fp, _i, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _fp]),
+    "pnpp_pn_concat_ragged": (_i, [_fp, _fp, _i, _fp, _i, _i, _i, _i, _fp, _fp]),
+    "pnpp_pn_concat_bwd_ragged": (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp]),
+    "pnpp_pn_infer_ragged": (_i, [C.POINTER(PnInferDesc), C.POINTER(PnInferArgs), _fp, _fp]),
 }
 
 _lib = None

@@ -1,5 +1,8 @@
 """Per-cloud lengths of a ragged batch: a padded (B, n_pts, ...) tensor plus `lengths` (B,), cloud b holding its first lengths[b] rows.
-Shared by the point transformer (pnpp_hip.transformer) and the set-abstraction models (pnpp_hip.ops, models.pointnet_pp_*)."""
+Shared by the point transformer (pnpp_hip.transformer), the set-abstraction models (pnpp_hip.ops, models.pointnet_pp_*) and the
+vanilla PointNet (models.pointnet), whose kernels work on the PACKED valid rows and read the lengths' prefix sum (packed_lengths)."""
+from typing import NamedTuple, Optional
+
 import torch
 
 
@@ -38,6 +41,50 @@ def ragged_lengths(lengths, B: int, n_pts: int, device, minimum: int = 1) -> tor
             raise ValueError(f"lengths is on {lengths.device}, the batch on {device}")
         return lengths.contiguous()
     return check_lengths(lengths, B, n_pts, minimum).to(device)
+
+
+class PackedLengths(NamedTuple):
+    """What the packed-row kernels of the vanilla PointNet read (packed_lengths)."""
+    lens_dev: torch.Tensor      # (B,) int32 on the device
+    offs_dev: torch.Tensor      # (B + 1,) int32 on the device: exclusive prefix sum of the lengths, offs[B] = M_total
+    M_total: Optional[int]      # sum of the lengths (the packed row count), None when it was not asked for
+
+
+def packed_offsets(lengths) -> list:
+    """Host lengths -> the B + 1 exclusive prefix sums: row n of cloud b is packed row offsets[b] + n, offsets[B] the row count."""
+    offs = [0]
+    for v in host_lengths(lengths):
+        offs.append(offs[-1] + v)
+    return offs
+
+
+def packed_lengths(lengths, B: int, n_pts: int, device, need_total: bool = True) -> PackedLengths:
+    """lengths -> PackedLengths for a padded (B, n_pts) batch whose valid rows are stored packed, cloud after cloud.  A PackedLengths
+    is passed through (so a model builds it once per forward).  A list or a CPU tensor is validated on the host (check_lengths) and
+    the offsets and M_total come from the host values: no synchronisation.  An int32 tensor on the device is clamped into 1..n_pts
+    and prefix-summed there by one small launch (pnpp_pn_offsets; the caller vouches for the range, as for ragged_lengths), and
+    M_total COSTS ONE READ-BACK (a synchronisation): packed row counts size allocations, so a training step needs the number on the
+    host.  A caller that allocates nothing by it -- the forward-only Predictor, whose buffers keep the padded shape -- passes
+    need_total=False and stays free of synchronisations (and capturable)."""
+    if isinstance(lengths, PackedLengths):
+        if lengths.lens_dev.shape[0] != B:
+            raise ValueError(f"lengths were packed for {lengths.lens_dev.shape[0]} clouds, the batch has {B}")
+        if need_total and lengths.M_total is None:
+            return lengths._replace(M_total=int(lengths.offs_dev[-1].item()))
+        return lengths
+    device = torch.device(device)
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        from . import _lib as L
+        raw = ragged_lengths(lengths, B, n_pts, device)
+        both = torch.empty(2 * B + 1, dtype=torch.int32, device=raw.device)
+        lens, offs = both[:B], both[B:]
+        with torch.cuda.device(raw.device):
+            L.check(L.lib().pnpp_pn_offsets(raw.data_ptr(), B, int(n_pts), lens.data_ptr(), offs.data_ptr(),
+                                            torch.cuda.current_stream().cuda_stream))
+        return PackedLengths(lens, offs, int(offs[-1].item()) if need_total else None)
+    host = check_lengths(lengths, B, n_pts)
+    offs = packed_offsets(host)
+    return PackedLengths(host.to(device), torch.tensor(offs, dtype=torch.int32).to(device), offs[-1])
 
 
 def host_lengths(lengths) -> list:

@@ -11,7 +11,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
-from .lengths import fps_starts, ragged_lengths
+from .lengths import fps_starts, packed_lengths, ragged_lengths
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1138,36 +1138,67 @@ def _pn_pool_desc(B, N, K, C_, relu, training, eps, momentum):
     return d
 
 
+def _pn_pool_sizes(d, rag):
+    """(saved bytes, scratch bytes) of a pooled-layer call; rag: None or the batch's PackedLengths"""
+    lib = L.lib()
+    if rag is None:
+        return lib.pnpp_pn_pool_saved_bytes(C.byref(d)), lib.pnpp_pn_pool_scratch_bytes(C.byref(d))
+    return (lib.pnpp_pn_pool_saved_bytes_ragged(C.byref(d), rag.M_total), lib.pnpp_pn_pool_scratch_bytes_ragged(C.byref(d), rag.M_total))
+
+
+def _pn_pool_forward(d, x, rag) -> None:
+    if rag is None:
+        L.check(L.lib().pnpp_pn_pool_forward(C.byref(d), C.byref(x), _stream()))
+    else:
+        L.check(L.lib().pnpp_pn_pool_forward_ragged(C.byref(d), C.byref(x), rag.offs_dev.data_ptr(), rag.M_total, _stream()))
+
+
+def _pn_pool_backward(d, x, rag) -> None:
+    if rag is None:
+        L.check(L.lib().pnpp_pn_pool_backward(C.byref(d), C.byref(x), _stream()))
+    else:
+        L.check(L.lib().pnpp_pn_pool_backward_ragged(C.byref(d), C.byref(x), rag.offs_dev.data_ptr(), rag.M_total, _stream()))
+
+
+def _pn_rows(rag, B: int, N: int) -> int:
+    return B * N if rag is None else rag.M_total
+
+
+def _pn_packed(lengths, B: int, N: int, device):
+    """lengths=None -> None (the uniform code path, untouched); anything else -> the batch's PackedLengths"""
+    return None if lengths is None else packed_lengths(lengths, B, N, device)
+
+
 class _PnPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, w, b, gamma, beta, cfg):
-        B, N, relu, training, eps, momentum, rm, rv, nbt = cfg
+        B, N, relu, training, eps, momentum, rm, rv, nbt, rag = cfg
         a, w, b = _f32(a, "a"), _f32(w, "conv weight"), _f32(b, "conv bias")
         gamma, beta = _f32(gamma, "bn weight"), _f32(beta, "bn bias")
-        if a.dim() != 2 or a.shape[0] != B * N:
-            raise ValueError(f"pn_pool: expected ({B * N}, K) rows, got {tuple(a.shape)}")
+        if a.dim() != 2 or a.shape[0] != _pn_rows(rag, B, N):
+            raise ValueError(f"pn_pool: expected ({_pn_rows(rag, B, N)}, K) rows, got {tuple(a.shape)}")
         K, Cc = a.shape[1], w.shape[0]
         if w.numel() != Cc * K:
             raise ValueError(f"pn_pool: weight {tuple(w.shape)} does not map {K} inputs")
         d = _pn_pool_desc(B, N, K, Cc, relu, training, eps, momentum)
         lib = L.lib()
-        sb = lib.pnpp_pn_pool_saved_bytes(C.byref(d))
+        sb, scb = _pn_pool_sizes(d, rag)
         if sb == 0:
             L.check(L.PNPP_ERR_ARG)
         saved = torch.empty(sb, dtype=torch.uint8, device=a.device)
-        scratch = _scratch(lib.pnpp_pn_pool_scratch_bytes(C.byref(d)), a.device)
+        scratch = _scratch(scb, a.device)
         out = torch.empty(B, Cc, device=a.device, dtype=torch.float32)
         x = L.PnPoolFwdArgs()
         x.a, x.w, x.b, x.gamma, x.beta = a.data_ptr(), w.data_ptr(), b.data_ptr(), gamma.data_ptr(), beta.data_ptr()
         x.rm, x.rv, x.nbt = rm.data_ptr(), rv.data_ptr(), _p(nbt)
         x.out, x.saved, x.scratch = out.data_ptr(), saved.data_ptr(), scratch.data_ptr()
-        L.check(lib.pnpp_pn_pool_forward(C.byref(d), C.byref(x), _stream()))
+        _pn_pool_forward(d, x, rag)
         if pn_pool_tap is not None:
             r = lib.pnpp_pn_pool_saved_route(C.byref(d), saved.data_ptr()) - saved.data_ptr()
             z = lib.pnpp_pn_pool_saved_zsel(C.byref(d), saved.data_ptr()) - saved.data_ptr()
             pn_pool_tap.append({"route": saved[r:r + 4 * B * Cc].view(torch.int32).view(B, Cc),
                                 "zsel": saved[z:z + 4 * B * Cc].view(torch.float32).view(B, Cc)})
-        ctx.desc = d
+        ctx.desc, ctx.rag = d, rag
         ctx.save_for_backward(a, w, gamma, saved)
         return out
 
@@ -1176,8 +1207,7 @@ class _PnPool(torch.autograd.Function):
         a, w, gamma, saved = ctx.saved_tensors
         d = ctx.desc
         dout = _f32(dout, "dout")
-        lib = L.lib()
-        scratch = _scratch(lib.pnpp_pn_pool_scratch_bytes(C.byref(d)), a.device)
+        scratch = _scratch(_pn_pool_sizes(d, ctx.rag)[1], a.device)
         da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         dw, db = torch.empty_like(w), torch.empty(d.C, device=a.device, dtype=torch.float32)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
@@ -1185,25 +1215,30 @@ class _PnPool(torch.autograd.Function):
         x.a, x.w, x.gamma, x.dout, x.saved, x.scratch = a.data_ptr(), w.data_ptr(), gamma.data_ptr(), dout.data_ptr(), \
             saved.data_ptr(), scratch.data_ptr()
         x.da, x.dw, x.db, x.dgamma, x.dbeta = _p(da), dw.data_ptr(), db.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
-        L.check(lib.pnpp_pn_pool_backward(C.byref(d), C.byref(x), _stream()))
+        _pn_pool_backward(d, x, ctx.rag)
         return da, dw, db, dgamma, dbeta, None
 
 
-def pn_pool(a: torch.Tensor, B: int, N: int, conv, bn, relu: bool, training: bool) -> torch.Tensor:
+def pn_pool(a: torch.Tensor, B: int, N: int, conv, bn, relu: bool, training: bool, lengths=None) -> torch.Tensor:
     """max over each cloud's N rows of act(bn(conv(a))): a (B*N, K) rows, conv a 1x1 nn.Conv1d, bn its nn.BatchNorm1d (running
-    statistics updated in place when training).  Returns (B, C).  Keeps O(B*C + K*K) for the backward pass, not (B*N) x C."""
+    statistics updated in place when training).  Returns (B, C).  Keeps O(B*C + K*K) for the backward pass, not (B*N) x C.
+    lengths (B,) (pnpp_hip.lengths.packed_lengths): a holds the sum(lengths) PACKED valid rows of a ragged batch padded to N; the
+    statistics run over those rows, each cloud's max over its own."""
     momentum = bn.momentum if bn.momentum is not None else 0.1
     nbt = _nbt(bn) if training else None
-    cfg = (int(B), int(N), bool(relu), bool(training), bn.eps, momentum, bn.running_mean, bn.running_var, nbt)
+    cfg = (int(B), int(N), bool(relu), bool(training), bn.eps, momentum, bn.running_mean, bn.running_var, nbt,
+           _pn_packed(lengths, int(B), int(N), a.device))
     return _PnPool.apply(a, conv.weight, conv.bias, bn.weight, bn.bias, cfg)
 
 
 class _PnTransform(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, t, k, ldy):
+    def forward(ctx, x, t, k, ldy, rag, BN):
         _need_gpu(x, "x")
         if x.dtype != torch.float32:
             raise TypeError(f"x must be float32, got {x.dtype}")
+        if rag is not None:
+            return _PnTransform._forward_ragged(ctx, x, t, k, ldy, rag, BN)
         if not (x.is_contiguous() or x.transpose(1, 2).is_contiguous()):
             x = x.contiguous()
         B, N, D = x.shape
@@ -1214,12 +1249,57 @@ class _PnTransform(torch.autograd.Function):
         y = torch.empty(B * N, ldy, device=x.device, dtype=torch.float32)
         sb, sn, sd = x.stride()
         L.check(L.lib().pnpp_pn_transform(x.data_ptr(), sb, sn, sd, _p(t), B, N, D, k, ldy, y.data_ptr(), _stream()))
-        ctx.k, ctx.ldy, ctx.has_t = k, ldy, t is not None
+        ctx.k, ctx.ldy, ctx.has_t, ctx.rag = k, ldy, t is not None, None
         ctx.save_for_backward(x, t if t is not None else x.new_empty(0))
         return y
 
     @staticmethod
+    def _forward_ragged(ctx, x, t, k, ldy, rag, BN):
+        """x (B, N, D) padded, read in place, or (M_total, D) packed rows -> (M_total, ldy) packed rows"""
+        B, N = BN
+        packed = x.dim() == 2
+        if packed:
+            x = x.contiguous()
+            if x.shape[0] != rag.M_total:
+                raise ValueError(f"pn_transform: expected ({rag.M_total}, D) packed rows, got {tuple(x.shape)}")
+            D, (sb, sn, sd) = x.shape[1], (0, x.stride(0), x.stride(1))
+        else:
+            if not (x.is_contiguous() or x.transpose(1, 2).is_contiguous()):
+                x = x.contiguous()
+            if tuple(x.shape[:2]) != (B, N):
+                raise ValueError(f"pn_transform: expected a ({B}, {N}, D) input, got {tuple(x.shape)}")
+            D, (sb, sn, sd) = x.shape[2], x.stride()
+        if t is not None:
+            t = _f32(t, "transform")
+            if tuple(t.shape) != (B, k, k):
+                raise ValueError(f"pn_transform: transform {tuple(t.shape)} is not ({B}, {k}, {k})")
+        y = torch.empty(rag.M_total, ldy, device=x.device, dtype=torch.float32)
+        L.check(L.lib().pnpp_pn_transform_ragged(x.data_ptr(), int(packed), sb, sn, sd, _p(t), rag.offs_dev.data_ptr(), B, N, D, k, ldy,
+                                                 y.data_ptr(), _stream()))
+        ctx.k, ctx.ldy, ctx.has_t, ctx.rag = k, ldy, t is not None, rag
+        ctx.geom = (packed, B, N, D, sb, sn, sd)
+        ctx.save_for_backward(x, t if t is not None else x.new_empty(0))
+        return y
+
+    @staticmethod
+    def _backward_ragged(ctx, dy):
+        x, t = ctx.saved_tensors
+        t = t if ctx.has_t else None
+        dy = _f32(dy, "dy")
+        packed, B, N, D, sb, sn, sd = ctx.geom
+        # every element of dx is written: the padding rows of a padded input get exact zeros
+        dx = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        dt = torch.empty_like(t) if (t is not None and ctx.needs_input_grad[1]) else None
+        if dx is None and dt is None:
+            return None, None, None, None, None, None
+        L.check(L.lib().pnpp_pn_transform_bwd_ragged(x.data_ptr(), int(packed), sb, sn, sd, _p(t), dy.data_ptr(), ctx.rag.offs_dev.data_ptr(),
+                                                     B, N, D, ctx.k, ctx.ldy, _p(dx), _p(dt), _stream()))
+        return dx, dt, None, None, None, None
+
+    @staticmethod
     def backward(ctx, dy):
+        if ctx.rag is not None:
+            return _PnTransform._backward_ragged(ctx, dy)
         x, t = ctx.saved_tensors
         t = t if ctx.has_t else None
         dy = _f32(dy, "dy")
@@ -1227,19 +1307,29 @@ class _PnTransform(torch.autograd.Function):
         dx = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
         dt = torch.empty_like(t) if (t is not None and ctx.needs_input_grad[1]) else None
         if dx is None and dt is None:
-            return None, None, None, None
+            return None, None, None, None, None, None
         sb, sn, sd = x.stride()
         L.check(L.lib().pnpp_pn_transform_bwd(x.data_ptr(), sb, sn, sd, _p(t), dy.data_ptr(), B, N, D, ctx.k, ctx.ldy, _p(dx), _p(dt),
                                               _stream()))
-        return dx, dt, None, None
+        return dx, dt, None, None, None, None
 
 
-def pn_transform(x: torch.Tensor, t: Optional[torch.Tensor], ldy: int) -> torch.Tensor:
+def pn_transform(x: torch.Tensor, t: Optional[torch.Tensor], ldy: int, lengths=None, B: Optional[int] = None,
+                 N: Optional[int] = None) -> torch.Tensor:
     """x (B, N, D) -- any dense layout, e.g. the transpose of a (B, D, N) input, read in place -- times the per-cloud transform
     t (B, k, k) on its first k columns, the other D - k columns passed through, zero columns up to ldy: (B*N, ldy) rows.
-    t None: the strided copy into (B*N, ldy) rows alone."""
+    t None: the strided copy into (B*N, ldy) rows alone.
+    lengths (B,): the batch is ragged, cloud b its first lengths[b] points.  The result is the (sum(lengths), ldy) PACKED rows, cloud
+    after cloud; the padding of x is never read and its gradient there is an exact zero.  x may also be (sum(lengths), D) packed
+    rows already (a later layer of the same batch): pass the padded geometry as B and N then."""
     k = t.shape[-1] if t is not None else 0
-    return _PnTransform.apply(x, t, k, int(ldy))
+    if lengths is None:
+        return _PnTransform.apply(x, t, k, int(ldy), None, None)
+    if x.dim() == 3:
+        B, N = x.shape[0], x.shape[1]
+    elif B is None or N is None:
+        raise ValueError("pn_transform: packed rows need the padded geometry B and N")
+    return _PnTransform.apply(x, t, k, int(ldy), packed_lengths(lengths, int(B), int(N), x.device), (int(B), int(N)))
 
 
 class _PnRegularizer(torch.autograd.Function):
@@ -1295,15 +1385,20 @@ def pn_add_identity(x: torch.Tensor, k: int) -> torch.Tensor:
 
 class _PnConcat(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, g, pf, N):
+    def forward(ctx, g, pf, N, rag, pf_padded):
         g, pf = _f32(g, "global feature"), _f32(pf, "point features")
         B, C1 = g.shape
         C2 = pf.shape[1]
-        if pf.shape[0] != B * N:
-            raise ValueError(f"pn_concat: point features {tuple(pf.shape)} are not ({B * N}, C)")
+        rows = B * N if (rag is None or pf_padded) else rag.M_total
+        if pf.shape[0] != rows:
+            raise ValueError(f"pn_concat: point features {tuple(pf.shape)} are not ({rows}, C)")
         out = torch.empty(B, C1 + C2, N, device=g.device, dtype=torch.float32)
-        L.check(L.lib().pnpp_pn_concat(g.data_ptr(), pf.data_ptr(), B, N, C1, C2, out.data_ptr(), _stream()))
-        ctx.dims = (B, N, C1, C2)
+        if rag is None:
+            L.check(L.lib().pnpp_pn_concat(g.data_ptr(), pf.data_ptr(), B, N, C1, C2, out.data_ptr(), _stream()))
+        else:
+            L.check(L.lib().pnpp_pn_concat_ragged(g.data_ptr(), pf.data_ptr(), int(pf_padded), rag.offs_dev.data_ptr(), B, N, C1, C2,
+                                                  out.data_ptr(), _stream()))
+        ctx.dims, ctx.rag, ctx.pf_padded = (B, N, C1, C2), rag, pf_padded
         return out
 
     @staticmethod
@@ -1311,16 +1406,25 @@ class _PnConcat(torch.autograd.Function):
         B, N, C1, C2 = ctx.dims
         dout = _f32(dout, "dout")
         dg = torch.empty(B, C1, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        dpf = torch.empty(B * N, C2, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        rag = ctx.rag
+        if rag is not None and ctx.pf_padded and ctx.needs_input_grad[1]:
+            raise RuntimeError("pn_concat: padded point features are a forward-only input")
+        dpf = torch.empty(_pn_rows(rag, B, N), C2, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
         if dg is None and dpf is None:
-            return None, None, None
-        L.check(L.lib().pnpp_pn_concat_bwd(dout.data_ptr(), B, N, C1, C2, _p(dg), _p(dpf), _stream()))
-        return dg, dpf, None
+            return None, None, None, None, None
+        if rag is None:
+            L.check(L.lib().pnpp_pn_concat_bwd(dout.data_ptr(), B, N, C1, C2, _p(dg), _p(dpf), _stream()))
+        else:
+            L.check(L.lib().pnpp_pn_concat_bwd_ragged(dout.data_ptr(), rag.offs_dev.data_ptr(), B, N, C1, C2, _p(dg), _p(dpf), _stream()))
+        return dg, dpf, None, None, None
 
 
-def pn_concat(g: torch.Tensor, pf: torch.Tensor, N: int) -> torch.Tensor:
-    """cat([g (B, C1) repeated over the N points, pf (B*N, C2) rows transposed], 1) -> (B, C1 + C2, N)."""
-    return _PnConcat.apply(g, pf, int(N))
+def pn_concat(g: torch.Tensor, pf: torch.Tensor, N: int, lengths=None, pf_padded: bool = False) -> torch.Tensor:
+    """cat([g (B, C1) repeated over the N points, pf (B*N, C2) rows transposed], 1) -> (B, C1 + C2, N).
+    lengths (B,): pf holds the (sum(lengths), C2) packed rows of a ragged batch (pf_padded: the padded B*N rows, forward only); the
+    columns n >= lengths[b] of the output are exact zeros and the incoming gradient there is not read."""
+    rag = None if lengths is None else packed_lengths(lengths, g.shape[0], int(N), g.device, need_total=not pf_padded)
+    return _PnConcat.apply(g, pf, int(N), rag, bool(pf_padded))
 
 
 class _PnBnRelu(torch.autograd.Function):
@@ -1368,9 +1472,9 @@ class _PnTrunk(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rows, cfg, *params):
-        B, N, nl, pool_relu, training, eps, mom, running, nbts, sinks = cfg
+        B, N, nl, pool_relu, training, eps, mom, running, nbts, sinks, rag = cfg
         rows = _f32(rows, "rows")
-        M = B * N
+        M = _pn_rows(rag, B, N)
         if rows.dim() != 2 or rows.shape[0] != M:
             raise ValueError(f"pn_trunk: expected ({M}, K) rows, got {tuple(rows.shape)}")
         if M <= 32:
@@ -1400,21 +1504,21 @@ class _PnTrunk(torch.autograd.Function):
             x = y
         w, b, nw, nb = (_f32(t, "pooled layer parameter") for t in params[4 * nl:4 * nl + 4])
         pd = _pn_pool_desc(B, N, x.shape[1], w.shape[0], pool_relu, training, eps[nl], mom[nl])
-        sb = lib.pnpp_pn_pool_saved_bytes(C.byref(pd))
+        sb, scb = _pn_pool_sizes(pd, rag)
         if sb == 0:
             L.check(L.PNPP_ERR_ARG)
         psaved = torch.empty(sb, dtype=torch.uint8, device=rows.device)
-        scratch = _scratch(lib.pnpp_pn_pool_scratch_bytes(C.byref(pd)), rows.device)
+        scratch = _scratch(scb, rows.device)
         out = torch.empty(B, pd.C, device=rows.device, dtype=torch.float32)
         a = L.PnPoolFwdArgs()
         a.a, a.w, a.b, a.gamma, a.beta = x.data_ptr(), w.data_ptr(), b.data_ptr(), nw.data_ptr(), nb.data_ptr()
         a.rm, a.rv, a.nbt = running[2 * nl].data_ptr(), running[2 * nl + 1].data_ptr(), _p(nbts[nl])
         a.out, a.saved, a.scratch = out.data_ptr(), psaved.data_ptr(), scratch.data_ptr()
-        L.check(lib.pnpp_pn_pool_forward(C.byref(pd), C.byref(a), _stream()))
+        _pn_pool_forward(pd, a, rag)
         if pn_pool_tap is not None:
             r = lib.pnpp_pn_pool_saved_route(C.byref(pd), psaved.data_ptr()) - psaved.data_ptr()
             pn_pool_tap.append({"route": psaved[r:r + 4 * B * pd.C].view(torch.int32).view(B, pd.C)})
-        ctx.descs, ctx.pdesc, ctx.sinks, ctx.nl = descs, pd, sinks, nl
+        ctx.descs, ctx.pdesc, ctx.sinks, ctx.nl, ctx.rag = descs, pd, sinks, nl, rag
         ctx.save_for_backward(rows, psaved, *saveds, *params)
         return out
 
@@ -1443,13 +1547,13 @@ class _PnTrunk(torch.autograd.Function):
         a_in = ys[-1] if nl else rows
         da = torch.empty_like(a_in) if (nl or ctx.needs_input_grad[0]) else None
         w, _, nw, _ = params[4 * nl:4 * nl + 4]
-        scratch = _scratch(lib.pnpp_pn_pool_scratch_bytes(C.byref(pd)), dev)
+        scratch = _scratch(_pn_pool_sizes(pd, ctx.rag)[1], dev)
         a = L.PnPoolBwdArgs()
         a.a, a.w, a.gamma, a.dout, a.saved, a.scratch = a_in.data_ptr(), w.data_ptr(), nw.data_ptr(), dout.data_ptr(), \
             psaved.data_ptr(), scratch.data_ptr()
         a.da = _p(da)
         a.dw, a.db, a.dgamma, a.dbeta = (dest(4 * nl + j).data_ptr() for j in range(4))
-        L.check(lib.pnpp_pn_pool_backward(C.byref(pd), C.byref(a), _stream()))
+        _pn_pool_backward(pd, a, ctx.rag)
         dy = da
         for l in reversed(range(nl)):
             d = descs[l]
@@ -1467,10 +1571,15 @@ class _PnTrunk(torch.autograd.Function):
         return (dy, None, *grads)
 
 
-def pn_trunk(rows: torch.Tensor, B: int, N: int, layers, pooled, pool_relu: bool, training: bool) -> torch.Tensor:
+def pn_trunk(rows: torch.Tensor, B: int, N: int, layers, pooled, pool_relu: bool, training: bool, lengths=None) -> torch.Tensor:
     """(B*N, K) point rows -> relu(bn(conv)) for each (conv, bn) of `layers` (0 - 2 of them, 1x1 nn.Conv1d + nn.BatchNorm1d) ->
     the pooled wide layer `pooled` = (conv, bn) with its max over each cloud's N points: (B, C).  Keeps for the backward pass
-    only the rows, the narrow layers' pre-BatchNorm outputs and O(B*C + K^2) for the pooled layer."""
+    only the rows, the narrow layers' pre-BatchNorm outputs and O(B*C + K^2) for the pooled layer.
+    lengths (B,): rows are the M = sum(lengths) PACKED valid rows of a ragged batch padded to N (pn_transform(..., lengths=)); every
+    BatchNorm takes its statistics over those M rows, each cloud's max runs over its own, and M > 32 takes the place of B*N > 32."""
+    rag = _pn_packed(lengths, int(B), int(N), rows.device)
+    if rag is not None and rag.M_total <= 32:
+        raise ValueError(f"pn_trunk: the lengths of the {B} clouds sum to {rag.M_total} point rows; the per-point layers need more than 32")
     params, running, nbts, eps, mom = [], [], [], [], []
     for conv, bn in list(layers) + [pooled]:
         params += [conv.weight, conv.bias, bn.weight, bn.bias]
@@ -1480,5 +1589,5 @@ def pn_trunk(rows: torch.Tensor, B: int, N: int, layers, pooled, pool_relu: bool
         mom.append(bn.momentum if bn.momentum is not None else 0.1)
     sinks = [grad_sink(p) for p in params]
     cfg = (int(B), int(N), len(layers), bool(pool_relu), bool(training), eps, mom, running, nbts,
-           sinks if any(s is not None for s in sinks) else None)
+           sinks if any(s is not None for s in sinks) else None, rag)
     return _PnTrunk.apply(rows, cfg, *params)

@@ -20,6 +20,12 @@ model, no CPU fallback.  Sizes that model.eval() itself refuses (B * N <= 32 poi
 kernel takes any B >= 1, N >= 1; a trunk on the eval path raises the same ValueError as the model.  Non-finite inputs are outside
 the contract: the fused max is a plain fmax over the rows, which drops a NaN beside a number (the eval path's scan skips NaN rows
 too; torch.max would propagate them).
+
+Ragged batches: predictor(x, lengths=(B,)) takes cloud b as the first lengths[b] points of its row, whatever the padding holds;
+row b of every output is what the call on x[b:b+1, :, :lengths[b]] returns, and global_feat=False's (B, 1088, N) output is zero in
+the padding columns.  A fused trunk keeps every buffer at its padded shape and reads the lengths on the device (pnpp_pn_infer_ragged:
+tiles beyond a cloud's length leave at once), so the call has static shapes, makes no synchronisation with a device lengths tensor
+and stays capturable; a trunk on the eval path packs its rows and reads the row count back.
 """
 from __future__ import annotations
 
@@ -33,6 +39,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .inference import Predictor, _tracked, planes_to_float32
+from .lengths import packed_lengths
 
 
 class PointNetPredictor(Predictor):
@@ -141,7 +148,7 @@ class PointNetPredictor(Predictor):
         return w[:, :cin].clone(), b.clone(), w[:, cin:].clone()
 
     # ---- one call --------------------------------------------------------------------------------------------------------
-    def _fused_trunk(self, name, d, xr, trans, trans_feat, want_feat, fresh_out):
+    def _fused_trunk(self, name, d, xr, trans, trans_feat, want_feat, fresh_out, pk=None):
         B, N = d.B, d.N
         a = L.PnInferArgs()
         a.x = xr.data_ptr()
@@ -156,38 +163,44 @@ class PointNetPredictor(Predictor):
         if want_feat:
             feat = self._buf(name + ".feat", (B * N, d.C[0]), torch.float32)
             a.feat_out, a.feat_layer = feat.data_ptr(), 0
-        L.check(L.lib().pnpp_pn_infer(C.byref(d), C.byref(a), ops._stream()))
+        if pk is None:
+            L.check(L.lib().pnpp_pn_infer(C.byref(d), C.byref(a), ops._stream()))
+        else:   # feat keeps its padded (B*N, 64) rows, zero beyond each cloud's length
+            L.check(L.lib().pnpp_pn_infer_ragged(C.byref(d), C.byref(a), pk.offs_dev.data_ptr(), ops._stream()))
         return out, feat
 
-    def _eval_trunk(self, name, xr, trans, trans_feat):
+    def _eval_trunk(self, name, xr, trans, trans_feat, pk=None):
         """the trunk through the library's existing eval-mode operators, as models/pointnet.py runs it, on the snapshot's parameters:
-        -> (pooled (B, C), the 64-wide point features the encoder's global_feat=False output carries or None)"""
+        -> (pooled (B, C), the 64-wide point features the encoder's global_feat=False output carries or None; packed rows with pk)"""
         from models.pointnet import _first_layer, _pad4
         enc = self._enc(self._snap)
         B, N, D = xr.shape
         width = _pad4(D)
+        if pk is not None:
+            pk = packed_lengths(pk, B, N, xr.device)   # this path allocates by the packed row count
         if name == "stn":
             m = enc.stn
-            rows = ops.pn_transform(xr, None, width)
-            return ops.pn_trunk(rows, B, N, [(_first_layer(m.conv1, width), m.bn1), (m.conv2, m.bn2)], (m.conv3, m.bn3), True, False), None
-        rows = ops.pn_transform(xr, trans, width)
+            rows = ops.pn_transform(xr, None, width, lengths=pk)
+            return ops.pn_trunk(rows, B, N, [(_first_layer(m.conv1, width), m.bn1), (m.conv2, m.bn2)], (m.conv3, m.bn3), True, False,
+                                lengths=pk), None
+        rows = ops.pn_transform(xr, trans, width, lengths=pk)
         h = ops.fc_block(rows, _first_layer(enc.conv1, width), enc.bn1, relu=True, training=False)
         if name == "fstn":
             m = enc.fstn
-            return ops.pn_trunk(h, B, N, [(m.conv1, m.bn1), (m.conv2, m.bn2)], (m.conv3, m.bn3), True, False), None
+            return ops.pn_trunk(h, B, N, [(m.conv1, m.bn1), (m.conv2, m.bn2)], (m.conv3, m.bn3), True, False, lengths=pk), None
         if trans_feat is not None:
-            h = ops.pn_transform(h.view(B, N, 64), trans_feat, 64)
-        return ops.pn_trunk(h, B, N, [(enc.conv2, enc.bn2)], (enc.conv3, enc.bn3), False, False), h
+            h = ops.pn_transform(h.view(B, N, 64), trans_feat, 64) if pk is None else ops.pn_transform(h, trans_feat, 64, lengths=pk, B=B, N=N)
+        return ops.pn_trunk(h, B, N, [(enc.conv2, enc.bn2)], (enc.conv3, enc.bn3), False, False, lengths=pk), h
 
-    def _trunk(self, name, xr, trans=None, trans_feat=None, want_feat=False, fresh_out=False):
+    def _trunk(self, name, xr, trans=None, trans_feat=None, want_feat=False, fresh_out=False, pk=None):
         B, N, _ = xr.shape
         d = self._trunk_desc(self._enc(self.model), name, B, N) if name in self._blobs else None
         if d is not None and not L.lib().pnpp_pn_infer_supported(C.byref(d)):
             d = None
         self.last_plan[name] = "fused" if d is not None else "eval-path"
         if d is None:
-            return self._eval_trunk(name, xr, trans, trans_feat)
-        return self._fused_trunk(name, d, xr, trans, trans_feat, want_feat, fresh_out)
+            return self._eval_trunk(name, xr, trans, trans_feat, pk)
+        return self._fused_trunk(name, d, xr, trans, trans_feat, want_feat, fresh_out, pk)
 
     def _eval_head(self, name, x):
         fc, bn = self._head_modules(self._snap, name)
@@ -199,13 +212,13 @@ class PointNetPredictor(Predictor):
         self.last_plan[name] = self.plan[name]
         return self._run_head(name, x, self._eval_head)
 
-    def _tnet(self, name, xr, trans, k):
-        g, _ = self._trunk(name, xr, trans)
+    def _tnet(self, name, xr, trans, k, pk=None):
+        g, _ = self._trunk(name, xr, trans, pk=pk)
         g = self._head(f"{name}.fc2", self._head(f"{name}.fc1", g))
         fc3 = getattr(self._enc(self._snap), name).fc3
         return ops.pn_add_identity(ops.fc_block(g, fc3, training=False), k)
 
-    def _encode(self, x):
+    def _encode(self, x, lengths=None):
         from models.pointnet import _check_channels
         enc = self._enc(self.model)
         ops._need_gpu(x, "x")
@@ -218,25 +231,30 @@ class PointNetPredictor(Predictor):
         xr = x.transpose(1, 2)   # (B, N, D) view, read in place through its strides
         if not (xr.is_contiguous() or x.is_contiguous()):
             xr = xr.contiguous()
-        trans = self._tnet("stn", xr, None, 3)
-        trans_feat = self._tnet("fstn", xr, trans, 64) if enc.feature_transform else None
+        pk = None if lengths is None else packed_lengths(lengths, B, N, self.device, need_total=False)
+        trans = self._tnet("stn", xr, None, 3, pk)
+        trans_feat = self._tnet("fstn", xr, trans, 64, pk) if enc.feature_transform else None
         # the encoder's pooled feature is returned by a Predictor of a PointNetEncoder: not a reused buffer then
-        g, feat = self._trunk("encoder", xr, trans, trans_feat, want_feat=not enc.global_feat, fresh_out=not self._whole)
+        g, feat = self._trunk("encoder", xr, trans, trans_feat, want_feat=not enc.global_feat, fresh_out=not self._whole, pk=pk)
         if enc.global_feat:
             return g, trans, trans_feat
-        return ops.pn_concat(g, feat, N), trans, trans_feat
+        if pk is None:
+            return ops.pn_concat(g, feat, N), trans, trans_feat
+        # a fused trunk tapped padded rows, the eval path returned packed ones
+        return ops.pn_concat(g, feat, N, lengths=pk, pf_padded=self.last_plan["encoder"] == "fused"), trans, trans_feat
 
     @torch.no_grad()
-    def __call__(self, x: torch.Tensor, return_transforms: bool = False):
+    def __call__(self, x: torch.Tensor, return_transforms: bool = False, lengths=None):
         """PointNet: x (B, D, N) or (B, N, 3|6) -> (B, 3), or (out, trans, trans_feat | None) with return_transforms.
-        PointNetEncoder: x (B, D, N) -> (global (B, 1024) | (B, 1088, N), trans, trans_feat | None)."""
+        PointNetEncoder: x (B, D, N) -> (global (B, 1024) | (B, 1088, N), trans, trans_feat | None).
+        lengths (B,): a ragged batch, cloud b its first lengths[b] points (the module docstring)."""
         ops._need_gpu(x, "x")
         with torch.cuda.device(self.device):
             if not self._whole:
-                return self._encode(x)
+                return self._encode(x, lengths)
             if x.dim() == 3 and x.shape[2] in (3, 6):
                 x = x.transpose(1, 2)
-            g, trans, trans_feat = self._encode(x)
+            g, trans, trans_feat = self._encode(x, lengths)
             h = self._head("fc2", self._head("fc1", g))
             out = ops.fc_block(h, self._snap.fc3, training=False)
             return (out, trans, trans_feat) if return_transforms else out

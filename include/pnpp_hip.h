@@ -550,6 +550,36 @@ int pnpp_pn_bn_relu(const float *x, int M, int C, const float *gamma, const floa
 int pnpp_pn_bn_relu_bwd(const float *x, const float *y, const float *dy, int M, int C, const float *gamma, const float *mean,
                         const float *istd, int training, float *dx, float *dgamma, float *dbeta, void *stream);
 
+/* Ragged batches (additive to ABI 5): cloud b holds the first len_b of its N padded points, 1 <= len_b <= N.  The valid point rows
+ * are PACKED, cloud after cloud: offs (B + 1) int32 on the device is the exclusive prefix sum of the lengths, row n of cloud b is
+ * packed row offs[b] + n, and M_total = offs[B] = sum of the lengths is the row count of every packed (M_total, width) array (A, dA,
+ * the transforms' y / dy, the concat's pf / dpf).  Padded arrays keep their (B, N) addressing; what they hold at n >= len_b is
+ * never read (NaN included), and what is written there is an exact 0.  The BatchNorm statistics of the pooled layer run over the
+ * M_total packed rows (running variance scaled by M_total / (M_total - 1)), each cloud's max and its route (still local to the cloud)
+ * over its own rows.  Descriptors, argument structs and workspace layouts are those of the namesakes; d->N is the padded N, which
+ * sizes the grids and the Gram slices, so offs == {0, N, 2N, ...} reproduces the uniform call bit for bit.
+ *   pnpp_pn_pool_*_ragged        M_total in [B, B*N], > 1 when training
+ *   pnpp_pn_transform*_ragged    x_packed == 0: x / dx are the padded strided input (dx zero at padding); x_packed == 1: x / dx are
+ *                                packed rows of pitch sn themselves (sb unused): the feature transform of an already packed layer
+ *   pnpp_pn_concat_ragged        pf_padded == 1: pf has the padded B*N rows (the tapped rows of pnpp_pn_infer_ragged)
+ *   pnpp_pn_concat_bwd_ragged    dout at padding columns is not read; dpf packed
+ *   pnpp_pn_infer_ragged         x and feat_out padded (feat_out rows n >= len_b zero); out[b] bit-equal to the call on cloud b alone */
+/* lengths (B) int32 on the device -> lens_out (B) = min(max(lengths[b], 1), N) and offs (B + 1), their exclusive prefix sum: one
+ * small launch, no synchronisation (a host that knows the lengths writes both arrays itself) */
+int pnpp_pn_offsets(const int32_t *lengths, int B, int N, int32_t *lens_out, int32_t *offs, void *stream);
+size_t pnpp_pn_pool_saved_bytes_ragged(const pnpp_pn_pool_desc *d, int M_total);
+size_t pnpp_pn_pool_scratch_bytes_ragged(const pnpp_pn_pool_desc *d, int M_total);
+int pnpp_pn_pool_forward_ragged(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_fwd_args *a, const int32_t *offs, int M_total, void *stream);
+int pnpp_pn_pool_backward_ragged(const pnpp_pn_pool_desc *d, const pnpp_pn_pool_bwd_args *a, const int32_t *offs, int M_total,
+                                 void *stream);
+int pnpp_pn_transform_ragged(const float *x, int x_packed, int64_t sb, int64_t sn, int64_t sd, const float *t, const int32_t *offs, int B,
+                             int N, int D, int k, int ldy, float *y, void *stream);
+int pnpp_pn_transform_bwd_ragged(const float *x, int x_packed, int64_t sb, int64_t sn, int64_t sd, const float *t, const float *dy,
+                                 const int32_t *offs, int B, int N, int D, int k, int ldy, float *dx, float *dt, void *stream);
+int pnpp_pn_concat_ragged(const float *g, const float *pf, int pf_padded, const int32_t *offs, int B, int N, int C1, int C2, float *out,
+                          void *stream);
+int pnpp_pn_concat_bwd_ragged(const float *dout, const int32_t *offs, int B, int N, int C1, int C2, float *dg, float *dpf, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Forward-only (inference) path of the set-abstraction levels (additive to ABI 5; csrc/sa_infer_kernels.hip).
  * models/pointnet_pp_8dir.py:21-43 with the BatchNorms in eval mode: running statistics make each BatchNorm an affine map,
@@ -658,6 +688,8 @@ size_t pnpp_pn_infer_scratch_bytes(const pnpp_pn_infer_desc *d);
 /* reads conv_w / conv_b / bn_w / bn_b / bn_rm / bn_rv [0 .. L) of `params` (every other member is ignored) and writes the blob */
 int pnpp_pn_infer_fold(const pnpp_pn_infer_desc *d, const pnpp_sa_fwd_args *params, void *weights, void *stream);
 int pnpp_pn_infer(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, void *stream);
+/* ... of a ragged batch (offs as for pnpp_pn_pool_forward_ragged; d->N the padded N, which sizes the scratch) */
+int pnpp_pn_infer_ragged(const pnpp_pn_infer_desc *d, const pnpp_pn_infer_args *a, const int32_t *offs, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Forward-only (inference) path of the point transformer (additive to ABI 5; csrc/transformer_infer_kernels.hip).

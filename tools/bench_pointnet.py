@@ -6,6 +6,14 @@ the wide kernel's share of the float32 matrix peak) and, as a side line, the sam
 restatement (F.conv1d / F.batch_norm on the same state_dict, torch.optim.Adam) on the same GPU.  Not the driver's bench line.
 
     python tools/bench_pointnet.py [--steps 50] [--warmup 10] [--no-stock]
+    python tools/bench_pointnet.py --lengths [--out profiles/pn_ragged.json]
+
+--lengths times the eager training step (forward + loss + backward + fused Adam; a ragged step's row count depends on the data,
+so it is not captured) on a RAGGED batch at 32 x 1024 -- DeviceCloudBank.padded(ids) of a bank whose clouds have seeded lengths,
+uniform on [N/4, N] -- against the same clouds resampled to N rows (bank.sample(ids, N)) run without lengths.  The two alternate
+in one process, in windows; one JSON line (appended to --out) in the format of tools/bench_inference.py --lengths.  The bank hands
+out a device lengths tensor, which costs the step one read-back per forward (the packed row count sizes allocations);
+`ragged_host_lengths` is the same step given the lengths as a host list, which costs none.
 """
 import argparse
 import json
@@ -95,12 +103,61 @@ def stock_step(state, x, t):
     return step
 
 
+def ragged_main(args):
+    import datetime
+    import benchline
+    from bench_inference import launches, ragged_bank_batch
+    from bench_pt_inference import alternate, ragged_record
+    from models.pointnet import PointNet
+    from pnpp_hip import ops, optim
+    B, N = 32, 1024
+    torch.manual_seed(42)
+    model = PointNet(True).cuda().train()
+    opt = optim.FlatAdam(model.parameters(), lr=1e-3)
+    xyz, dev_lengths, lengths, full = ragged_bank_batch(B, N)
+    host = [int(n) for n in lengths]
+    t = torch.randn(B, 3, generator=torch.Generator().manual_seed(7)).cuda()
+
+    def step(x, L):
+        opt.zero_grad()
+        out, _, tf = model(x, return_transforms=True, lengths=L)
+        (ops.mse_rows(out, t).mean() + 0.001 * ops.feature_transform_regularizer(tf)).backward()
+        opt.step()
+
+    runs = {"ragged": lambda: step(xyz, dev_lengths), "resampled": lambda: step(full, None), "ragged_host_lengths": lambda: step(xyz, host)}
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    rec = {"model": "PointNet(feature_transform=True)", "B": B, "N": N, "date": datetime.date.today().isoformat(),
+           "device": torch.cuda.get_device_name(0), "windows": args.windows, "window_s": args.window,
+           "workload": "PointNet forward + MSE + 0.001 x regulariser + backward + fused Adam, eager; ragged batch (DeviceCloudBank.padded) "
+                       "against every cloud resampled to N rows (DeviceCloudBank.sample)",
+           "launches": {k: launches(fn) for k, fn in runs.items()},
+           # device time of the library's kernels alone (instrumented, serialised launches): what packing saves on the device
+           "kernel_ms_per_step": {k: round(sum(r[2] for r in benchline.profiled_rows(fn, 5)) / 5, 4) for k, fn in runs.items()}}
+    line = json.dumps(ragged_record(rec, alternate(runs, args.windows, args.window, 4), lengths, N))
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--no-stock", action="store_true")
+    ap.add_argument("--lengths", action="store_true", help="the eager step on a ragged batch (seeded lengths, uniform on [N/4, N], from a "
+                                                           "DeviceCloudBank) against every cloud resampled to N rows, at 32 x 1024")
+    ap.add_argument("--windows", type=int, default=5, help="--lengths: timing windows per path")
+    ap.add_argument("--window", type=float, default=0.5, help="--lengths: seconds of device time per window")
+    ap.add_argument("--out", default=None, help="--lengths: append the JSON line to this file")
     args = ap.parse_args()
+    if args.lengths:
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_pointnet: no GPU (this measurement has no CPU form)")
+        return ragged_main(args)
     import benchline
     import synthetic
     from models.pointnet import PointNet

@@ -5,6 +5,11 @@ one process (window() / launches() of tools/bench_inference.py).
     python tools/bench_pointnet_inference.py                  # PointNet(True), PointNet(False) at B=32 N=1024; PointNet(True) at B=256
     python tools/bench_pointnet_inference.py --out profiles/pointnet_inference_forward.json
     python tools/bench_pointnet_inference.py --trace-only 20  # ~20 Predictor forwards of PointNet(True), B=32 N=1024, and nothing else
+    python tools/bench_pointnet_inference.py --lengths --out profiles/pn_ragged.json   # appends one line
+
+--lengths times the Predictor of PointNet(True) on a RAGGED batch at 32 x 1024 -- DeviceCloudBank.padded(ids), seeded lengths uniform
+on [N/4, N] -- against the same clouds resampled to N rows (bank.sample(ids, N)) run without lengths, alternately in one process
+(the format of tools/bench_inference.py --lengths), with the largest difference to each cloud run alone.
 
 One JSON line per case in the format of profiles/inference_forward.json: ms per forward and clouds/s of both paths (median over the
 windows), each path's min / max, library launches per forward, the Predictor's algorithmic FLOPs and compulsory HBM bytes per
@@ -92,14 +97,48 @@ def case(feature_transform, B, N, windows, seconds):
     }
 
 
+def ragged_case(B, N, windows, seconds):
+    import benchline
+    from bench_inference import ragged_bank_batch
+    from bench_pt_inference import alternate, ragged_record
+    from pnpp_hip import Predictor
+    pred = Predictor(make(True))
+    xyz, dev_lengths, lengths, full = ragged_bank_batch(B, N)
+    runs = {"ragged": lambda: pred(xyz, lengths=dev_lengths), "resampled": lambda: pred(full)}
+    alone = torch.cat([pred(xyz[b:b + 1, :int(n)].contiguous()) for b, n in enumerate(lengths)])
+    diff = float((runs["ragged"]() - alone).abs().max())
+    for _ in range(3):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    rec = {"model": "PointNet(feature_transform=True)", "B": B, "N": N, "date": datetime.date.today().isoformat(),
+           "device": torch.cuda.get_device_name(0), "windows": windows, "window_s": seconds,
+           "workload": "Predictor(PointNet) forward, ragged batch (DeviceCloudBank.padded) against every cloud resampled to N rows "
+                       "(DeviceCloudBank.sample)",
+           "plan": pred.last_plan, "launches": {k: launches(fn) for k, fn in runs.items()}, "max_abs_diff_to_each_cloud_alone": diff,
+           # device time of the library's kernels alone (instrumented, serialised launches): what the early-leaving tiles save
+           "kernel_ms_per_forward": {k: round(sum(r[2] for r in benchline.profiled_rows(fn, 5)) / 5, 4) for k, fn in runs.items()}}
+    return ragged_record(rec, alternate(runs, windows, seconds, 8), lengths, N)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.5, help="seconds of device time per window")
     ap.add_argument("--out", default=None, help="also write the JSON lines to this file (overwritten)")
     ap.add_argument("--trace-only", type=int, default=0, help="run this many Predictor forwards (PointNet(True), B=32, N=1024) and exit")
+    ap.add_argument("--lengths", action="store_true",
+                    help="a ragged batch (seeded lengths, uniform on [N/4, N], from a DeviceCloudBank) against every cloud resampled to N "
+                         "rows, at 32 x 1024; --out is appended to")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_pointnet_inference needs an AMD GPU"
+    if args.lengths:
+        line = json.dumps(ragged_case(32, 1024, args.windows, args.window))
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+        return
     if args.trace_only:
         from pnpp_hip import Predictor
         pred = Predictor(make(True))
