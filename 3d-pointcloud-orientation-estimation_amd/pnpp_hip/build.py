@@ -46,6 +46,7 @@ SOURCES = {
     "runtime.hip": [],
     "sa_api.hip": [],
     "sa_infer_kernels.hip": [],
+    "fc_kernels.hip": [],
     "fc_api.hip": [],
     "transformer_kernels.hip": [],
     "pointnet_kernels.hip": [],

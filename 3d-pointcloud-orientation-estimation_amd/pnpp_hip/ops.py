@@ -6,7 +6,7 @@ Every function here requires float32 tensors on an AMD GPU; there is no CPU impl
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -99,6 +99,29 @@ def _scratch(nbytes: int, device: torch.device) -> torch.Tensor:
         buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
         _scratch_cache[key] = buf
     return buf
+
+
+def _workspace(nbytes: int, device: torch.device) -> torch.Tensor:
+    """A call's kept workspace.  The size queries answer a descriptor the library rejects with 0 bytes (and its message)."""
+    if nbytes == 0:
+        L.check(L.PNPP_ERR_ARG)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _bn_momentum(bn) -> float:
+    return bn.momentum if bn.momentum is not None else 0.1
+
+
+def _grad_dests(params, sinks):
+    """Where the backward kernels write the gradients of `params` (None entries: no such parameter): a parameter's flat-buffer sink
+    when an optimiser registered one (autograd then has nothing to accumulate), else a fresh tensor, allocated in the order given.
+    Returns (dests, returned): the destinations, and what goes back to autograd -- None wherever a sink took the gradient."""
+    dests, returned = [], []
+    for p, s in zip(params, sinks or [None] * len(params)):
+        fresh = torch.empty_like(p) if (p is not None and s is None) else None
+        dests.append(s if s is not None else fresh)
+        returned.append(fresh)
+    return dests, returned
 
 
 def set_matmul_precision(mode: str) -> None:
@@ -430,14 +453,12 @@ class _SetAbstraction(torch.autograd.Function):
             raise ValueError("set_abstraction: matmul precision or SyncBN was switched between this level's forward pass and its "
                              "backward pass; the kept workspace belongs to the kernels the forward pass took")
         scratch = _scratch(lib.pnpp_sa_scratch_bytes(C.byref(desc)), xyz.device)
-        # gradient destinations: a parameter's flat-buffer sink when an optimiser registered one (the kernels then
-        # write straight into the flat gradient buffer and autograd has nothing to accumulate), else fresh tensors
+        # gradient destinations, kind by kind (a conv bias is not kept for the backward pass: it has its BatchNorm weight's shape)
         sinks = ctx.sinks or [None] * (4 * Lh)
-        d_conv_w = [sinks[4 * l] if sinks[4 * l] is not None else torch.empty_like(conv_w[l]) for l in range(Lh)]
-        d_conv_b = [sinks[4 * l + 1] if sinks[4 * l + 1] is not None else
-                    torch.empty(conv_w[l].shape[0], device=xyz.device, dtype=torch.float32) for l in range(Lh)]
-        d_bn_w = [sinks[4 * l + 2] if sinks[4 * l + 2] is not None else torch.empty_like(bn_w[l]) for l in range(Lh)]
-        d_bn_b = [sinks[4 * l + 3] if sinks[4 * l + 3] is not None else torch.empty_like(bn_b[l]) for l in range(Lh)]
+        d_conv_w, r_conv_w = _grad_dests(conv_w, sinks[0::4])
+        d_conv_b, r_conv_b = _grad_dests(bn_w, sinks[1::4])
+        d_bn_w, r_bn_w = _grad_dests(bn_w, sinks[2::4])
+        d_bn_b, r_bn_b = _grad_dests(bn_b, sinks[3::4])
         dpoints = torch.empty_like(points) if (points is not None and ctx.needs_input_grad[1]) else None
         a = L.SaBwdArgs()
         a.xyz, a.points = xyz.data_ptr(), _p(points)
@@ -447,10 +468,7 @@ class _SetAbstraction(torch.autograd.Function):
         a.d_bn_w, a.d_bn_b = _ptr_array(d_bn_w), _ptr_array(d_bn_b)
         a.dpoints = _p(dpoints)
         L.check(lib.pnpp_sa_backward(C.byref(desc), C.byref(a), _stream()))
-        grads: List[Optional[torch.Tensor]] = []
-        for l in range(Lh):
-            for j, t in enumerate((d_conv_w[l], d_conv_b[l], d_bn_w[l], d_bn_b[l])):
-                grads.append(None if sinks[4 * l + j] is not None else t)
+        grads = [g for layer in zip(r_conv_w, r_conv_b, r_bn_w, r_bn_b) for g in layer]
         return (None, dpoints, None, None, None, None, *grads)
 
 
@@ -471,10 +489,7 @@ def group_pair(xyz, centre1, centre2, nsample1, convs1, nsample2, convs2, traini
     lib = L.lib()
     pres = []
     for d, S in ((d1, S1), (d2, S2)):
-        sb = lib.pnpp_sa_saved_bytes(C.byref(d))
-        if sb == 0:
-            L.check(L.PNPP_ERR_ARG)
-        pres.append({"saved": torch.empty(sb, dtype=torch.uint8, device=xyz.device),
+        pres.append({"saved": _workspace(lib.pnpp_sa_saved_bytes(C.byref(d)), xyz.device),
                      "new_xyz": torch.empty(B, S, 3, device=xyz.device, dtype=torch.float32)})
     tail = (c1.data_ptr(), c2.data_ptr(), pres[0]["saved"].data_ptr(), pres[0]["new_xyz"].data_ptr(), pres[1]["saved"].data_ptr(),
             pres[1]["new_xyz"].data_ptr(), _stream())
@@ -498,11 +513,9 @@ def set_abstraction(xyz, points, centre_idx, nsample, group_all, training, convs
     for conv, bn in zip(convs, bns):
         params += [conv.weight, conv.bias, bn.weight, bn.bias]
         running += [bn.running_mean, bn.running_var]
-    eps = bns[0].eps
-    momentum = bns[0].momentum if bns[0].momentum is not None else 0.1
     sinks = [grad_sink(p) for p in params]
     nbt = [_nbt(bn) for bn in bns] if training else None   # bumped by the statistics kernels themselves
-    cfg = (nsample, bool(group_all), bool(training), eps, momentum, sinks if any(s is not None for s in sinks) else None, nbt, pre)
+    cfg = (nsample, bool(group_all), bool(training), bns[0].eps, _bn_momentum(bns[0]), sinks if any(s is not None for s in sinks) else None, nbt, pre)
     new_xyz, out, nbr = _SetAbstraction.apply(xyz, points, centre_idx, neighbour_idx, cfg, running, *params)
     if return_neighbours:
         return new_xyz, out, (None if group_all else nbr)
@@ -512,36 +525,58 @@ def set_abstraction(xyz, points, centre_idx, nsample, group_all, training, convs
 # ------------------------------------------------------------------------------------------------
 # fully connected block
 # ------------------------------------------------------------------------------------------------
+def _fc_desc(M, K, N, norm, relu, training, eps, momentum, drop_scale):
+    d = L.FcDesc()
+    d.M, d.K, d.N, d.norm, d.relu, d.training = int(M), int(K), int(N), norm, int(relu), int(training)
+    d.eps, d.momentum, d.drop_scale = float(eps), float(momentum), float(drop_scale)
+    return d
+
+
+def _fc_forward_call(d, x, w, b, nw, nb, rm, rv, nbt, mask, draw):
+    """pnpp_fc_forward on checked tensors -> (y, the kept workspace, the keep-mask the backward pass needs).  draw = (p, seed,
+    counter): the kernel draws the keep-mask itself (no RNG launch, graph-replayable) and hands it back."""
+    lib = L.lib()
+    saved = _workspace(lib.pnpp_fc_saved_bytes(C.byref(d)), x.device)
+    scratch = _scratch(lib.pnpp_fc_scratch_bytes(C.byref(d)), x.device)
+    y = torch.empty(d.M, d.N, device=x.device, dtype=torch.float32)
+    if mask is not None:
+        mask = mask.contiguous()
+    a = L.FcFwdArgs()
+    a.x, a.w, a.b, a.nw, a.nb = x.data_ptr(), w.data_ptr(), b.data_ptr(), _p(nw), _p(nb)
+    a.rm, a.rv, a.nbt, a.mask = _p(rm), _p(rv), _p(nbt), _p(mask)
+    if draw is not None:
+        p_drop, seed, counter = draw
+        mask = torch.empty(d.M, d.N, device=x.device, dtype=torch.uint8)
+        a.mask_out, a.drop_p, a.rng_seed, a.rng_counter = mask.data_ptr(), float(p_drop), int(seed) & (2**64 - 1), counter.data_ptr()
+    a.y, a.saved, a.scratch = y.data_ptr(), saved.data_ptr(), scratch.data_ptr()
+    L.check(lib.pnpp_fc_forward(C.byref(d), C.byref(a), _stream()))
+    return y, saved, mask
+
+
+def _fc_backward_call(d, x, w, b, nw, nb, mask, dy, saved, want_dx, sinks):
+    """pnpp_fc_backward -> (dx or None, the gradients of (w, b, nw, nb) for autograd: None where a sink of `sinks` took one)"""
+    lib = L.lib()
+    scratch = _scratch(lib.pnpp_fc_scratch_bytes(C.byref(d)), x.device)
+    dx = torch.empty_like(x) if want_dx else None
+    (dw, db, dnw, dnb), returned = _grad_dests((w, b, nw, nb), sinks)
+    a = L.FcBwdArgs()
+    a.x, a.w, a.b, a.nw, a.nb, a.mask = x.data_ptr(), w.data_ptr(), b.data_ptr(), _p(nw), _p(nb), _p(mask)
+    a.dy, a.saved, a.scratch = dy.data_ptr(), saved.data_ptr(), scratch.data_ptr()
+    a.dx, a.dw, a.db, a.dnw, a.dnb = _p(dx), dw.data_ptr(), db.data_ptr(), _p(dnw), _p(dnb)
+    L.check(lib.pnpp_fc_backward(C.byref(d), C.byref(a), _stream()))
+    return dx, returned
+
+
 class _FcBlock(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, nw, nb, rm, rv, mask, cfg):
         norm, relu, training, eps, momentum, drop_scale, sinks, nbt, draw = cfg
         x, w, b = _f32(x, "x"), _f32(w, "weight"), _f32(b, "bias")
-        M, K = x.shape
-        N = w.shape[0]
-        d = L.FcDesc()
-        d.M, d.K, d.N, d.norm, d.relu, d.training = M, K, N, norm, int(relu), int(training)
-        d.eps, d.momentum, d.drop_scale = float(eps), float(momentum), float(drop_scale)
-        lib = L.lib()
-        sb = lib.pnpp_fc_saved_bytes(C.byref(d))
-        if sb == 0:
-            L.check(L.PNPP_ERR_ARG)
-        saved = torch.empty(sb, dtype=torch.uint8, device=x.device)
-        scratch = _scratch(lib.pnpp_fc_scratch_bytes(C.byref(d)), x.device)
-        y = torch.empty(M, N, device=x.device, dtype=torch.float32)
         if nw is not None:
             nw, nb = _f32(nw, "norm weight"), _f32(nb, "norm bias")
-        if mask is not None:
-            mask = mask.contiguous()
-        a = L.FcFwdArgs()
-        a.x, a.w, a.b, a.nw, a.nb = x.data_ptr(), w.data_ptr(), b.data_ptr(), _p(nw), _p(nb)
-        a.rm, a.rv, a.nbt, a.mask = _p(rm), _p(rv), _p(nbt), _p(mask)
-        if draw is not None:   # the kernel draws the keep-mask itself (no RNG launch, graph-replayable) and hands it back
-            p_drop, seed, counter = draw
-            mask = torch.empty(M, N, device=x.device, dtype=torch.uint8)
-            a.mask_out, a.drop_p, a.rng_seed, a.rng_counter = mask.data_ptr(), float(p_drop), int(seed) & (2**64 - 1), counter.data_ptr()
-        a.y, a.saved, a.scratch = y.data_ptr(), saved.data_ptr(), scratch.data_ptr()
-        L.check(lib.pnpp_fc_forward(C.byref(d), C.byref(a), _stream()))
+        M, K = x.shape
+        d = _fc_desc(M, K, w.shape[0], norm, relu, training, eps, momentum, drop_scale)
+        y, saved, mask = _fc_forward_call(d, x, w, b, nw, nb, rm, rv, nbt, mask, draw)
         ctx.desc = d
         ctx.sinks = sinks
         ctx.has_norm, ctx.has_mask = nw is not None, mask is not None
@@ -552,26 +587,11 @@ class _FcBlock(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        d = ctx.desc
         x, w, b, nw, nb, mask, saved = ctx.saved_tensors
         nw, nb = (nw, nb) if ctx.has_norm else (None, None)
         mask = mask if ctx.has_mask else None
-        dy = _f32(dy, "dy")
-        lib = L.lib()
-        scratch = _scratch(lib.pnpp_fc_scratch_bytes(C.byref(d)), x.device)
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        sk = ctx.sinks or (None, None, None, None)
-        dw = sk[0] if sk[0] is not None else torch.empty_like(w)
-        db = sk[1] if sk[1] is not None else torch.empty_like(b)
-        dnw = (sk[2] if sk[2] is not None else torch.empty_like(nw)) if nw is not None else None
-        dnb = (sk[3] if sk[3] is not None else torch.empty_like(nb)) if nb is not None else None
-        a = L.FcBwdArgs()
-        a.x, a.w, a.b, a.nw, a.nb, a.mask = x.data_ptr(), w.data_ptr(), b.data_ptr(), _p(nw), _p(nb), _p(mask)
-        a.dy, a.saved, a.scratch = dy.data_ptr(), saved.data_ptr(), scratch.data_ptr()
-        a.dx, a.dw, a.db, a.dnw, a.dnb = _p(dx), dw.data_ptr(), db.data_ptr(), _p(dnw), _p(dnb)
-        L.check(lib.pnpp_fc_backward(C.byref(d), C.byref(a), _stream()))
-        keep = lambda t, i: None if sk[i] is not None else t
-        return dx, keep(dw, 0), keep(db, 1), keep(dnw, 2), keep(dnb, 3), None, None, None, None
+        dx, grads = _fc_backward_call(ctx.desc, x, w, b, nw, nb, mask, _f32(dy, "dy"), saved, ctx.needs_input_grad[0], ctx.sinks)
+        return (dx, *grads, None, None, None, None)
 
 
 def fc_block(x, linear, norm=None, relu=False, dropout=None, training=True, mask=None):
@@ -584,8 +604,7 @@ def fc_block(x, linear, norm=None, relu=False, dropout=None, training=True, mask
     nw = nb = rm = rv = None
     kind, eps, momentum = L.NORM_NONE, 1e-5, 0.1
     if isinstance(norm, nn.BatchNorm1d):
-        kind, eps = L.NORM_BATCH, norm.eps
-        momentum = norm.momentum if norm.momentum is not None else 0.1
+        kind, eps, momentum = L.NORM_BATCH, norm.eps, _bn_momentum(norm)
         nw, nb, rm, rv = norm.weight, norm.bias, norm.running_mean, norm.running_var
     elif isinstance(norm, nn.LayerNorm):
         kind, eps = L.NORM_LAYER, norm.eps
@@ -1138,26 +1157,48 @@ def _pn_pool_desc(B, N, K, C_, relu, training, eps, momentum):
     return d
 
 
-def _pn_pool_sizes(d, rag):
-    """(saved bytes, scratch bytes) of a pooled-layer call; rag: None or the batch's PackedLengths"""
+def _pn_pool_forward_call(d, a, w, b, gamma, beta, rm, rv, nbt, rag):
+    """pnpp_pn_pool_forward(_ragged) on checked tensors -> (out (B, C), the kept workspace); rag: None or the batch's PackedLengths"""
     lib = L.lib()
     if rag is None:
-        return lib.pnpp_pn_pool_saved_bytes(C.byref(d)), lib.pnpp_pn_pool_scratch_bytes(C.byref(d))
-    return (lib.pnpp_pn_pool_saved_bytes_ragged(C.byref(d), rag.M_total), lib.pnpp_pn_pool_scratch_bytes_ragged(C.byref(d), rag.M_total))
-
-
-def _pn_pool_forward(d, x, rag) -> None:
-    if rag is None:
-        L.check(L.lib().pnpp_pn_pool_forward(C.byref(d), C.byref(x), _stream()))
+        sb, scb = lib.pnpp_pn_pool_saved_bytes(C.byref(d)), lib.pnpp_pn_pool_scratch_bytes(C.byref(d))
     else:
-        L.check(L.lib().pnpp_pn_pool_forward_ragged(C.byref(d), C.byref(x), rag.offs_dev.data_ptr(), rag.M_total, _stream()))
-
-
-def _pn_pool_backward(d, x, rag) -> None:
+        sb, scb = lib.pnpp_pn_pool_saved_bytes_ragged(C.byref(d), rag.M_total), lib.pnpp_pn_pool_scratch_bytes_ragged(C.byref(d), rag.M_total)
+    saved = _workspace(sb, a.device)
+    scratch = _scratch(scb, a.device)
+    out = torch.empty(d.B, d.C, device=a.device, dtype=torch.float32)
+    x = L.PnPoolFwdArgs()
+    x.a, x.w, x.b, x.gamma, x.beta = a.data_ptr(), w.data_ptr(), b.data_ptr(), gamma.data_ptr(), beta.data_ptr()
+    x.rm, x.rv, x.nbt = rm.data_ptr(), rv.data_ptr(), _p(nbt)
+    x.out, x.saved, x.scratch = out.data_ptr(), saved.data_ptr(), scratch.data_ptr()
     if rag is None:
-        L.check(L.lib().pnpp_pn_pool_backward(C.byref(d), C.byref(x), _stream()))
+        L.check(lib.pnpp_pn_pool_forward(C.byref(d), C.byref(x), _stream()))
     else:
-        L.check(L.lib().pnpp_pn_pool_backward_ragged(C.byref(d), C.byref(x), rag.offs_dev.data_ptr(), rag.M_total, _stream()))
+        L.check(lib.pnpp_pn_pool_forward_ragged(C.byref(d), C.byref(x), rag.offs_dev.data_ptr(), rag.M_total, _stream()))
+    if pn_pool_tap is not None:
+        r = lib.pnpp_pn_pool_saved_route(C.byref(d), saved.data_ptr()) - saved.data_ptr()
+        z = lib.pnpp_pn_pool_saved_zsel(C.byref(d), saved.data_ptr()) - saved.data_ptr()
+        pn_pool_tap.append({"route": saved[r:r + 4 * d.B * d.C].view(torch.int32).view(d.B, d.C),
+                            "zsel": saved[z:z + 4 * d.B * d.C].view(torch.float32).view(d.B, d.C)})
+    return out, saved
+
+
+def _pn_pool_backward_call(d, a, w, gamma, dout, saved, rag, want_da, sinks):
+    """pnpp_pn_pool_backward(_ragged) -> (da or None, the gradients of (w, b, gamma, beta) for autograd: None where a sink took one)"""
+    lib = L.lib()
+    scb = lib.pnpp_pn_pool_scratch_bytes(C.byref(d)) if rag is None else lib.pnpp_pn_pool_scratch_bytes_ragged(C.byref(d), rag.M_total)
+    scratch = _scratch(scb, a.device)
+    da = torch.empty_like(a) if want_da else None
+    (dw, db, dgamma, dbeta), returned = _grad_dests((w, gamma, gamma, gamma), sinks)   # the conv bias and beta have gamma's shape
+    x = L.PnPoolBwdArgs()
+    x.a, x.w, x.gamma, x.dout, x.saved, x.scratch = a.data_ptr(), w.data_ptr(), gamma.data_ptr(), dout.data_ptr(), \
+        saved.data_ptr(), scratch.data_ptr()
+    x.da, x.dw, x.db, x.dgamma, x.dbeta = _p(da), dw.data_ptr(), db.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
+    if rag is None:
+        L.check(lib.pnpp_pn_pool_backward(C.byref(d), C.byref(x), _stream()))
+    else:
+        L.check(lib.pnpp_pn_pool_backward_ragged(C.byref(d), C.byref(x), rag.offs_dev.data_ptr(), rag.M_total, _stream()))
+    return da, returned
 
 
 def _pn_rows(rag, B: int, N: int) -> int:
@@ -1181,23 +1222,7 @@ class _PnPool(torch.autograd.Function):
         if w.numel() != Cc * K:
             raise ValueError(f"pn_pool: weight {tuple(w.shape)} does not map {K} inputs")
         d = _pn_pool_desc(B, N, K, Cc, relu, training, eps, momentum)
-        lib = L.lib()
-        sb, scb = _pn_pool_sizes(d, rag)
-        if sb == 0:
-            L.check(L.PNPP_ERR_ARG)
-        saved = torch.empty(sb, dtype=torch.uint8, device=a.device)
-        scratch = _scratch(scb, a.device)
-        out = torch.empty(B, Cc, device=a.device, dtype=torch.float32)
-        x = L.PnPoolFwdArgs()
-        x.a, x.w, x.b, x.gamma, x.beta = a.data_ptr(), w.data_ptr(), b.data_ptr(), gamma.data_ptr(), beta.data_ptr()
-        x.rm, x.rv, x.nbt = rm.data_ptr(), rv.data_ptr(), _p(nbt)
-        x.out, x.saved, x.scratch = out.data_ptr(), saved.data_ptr(), scratch.data_ptr()
-        _pn_pool_forward(d, x, rag)
-        if pn_pool_tap is not None:
-            r = lib.pnpp_pn_pool_saved_route(C.byref(d), saved.data_ptr()) - saved.data_ptr()
-            z = lib.pnpp_pn_pool_saved_zsel(C.byref(d), saved.data_ptr()) - saved.data_ptr()
-            pn_pool_tap.append({"route": saved[r:r + 4 * B * Cc].view(torch.int32).view(B, Cc),
-                                "zsel": saved[z:z + 4 * B * Cc].view(torch.float32).view(B, Cc)})
+        out, saved = _pn_pool_forward_call(d, a, w, b, gamma, beta, rm, rv, nbt, rag)
         ctx.desc, ctx.rag = d, rag
         ctx.save_for_backward(a, w, gamma, saved)
         return out
@@ -1205,18 +1230,8 @@ class _PnPool(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         a, w, gamma, saved = ctx.saved_tensors
-        d = ctx.desc
-        dout = _f32(dout, "dout")
-        scratch = _scratch(_pn_pool_sizes(d, ctx.rag)[1], a.device)
-        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        dw, db = torch.empty_like(w), torch.empty(d.C, device=a.device, dtype=torch.float32)
-        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
-        x = L.PnPoolBwdArgs()
-        x.a, x.w, x.gamma, x.dout, x.saved, x.scratch = a.data_ptr(), w.data_ptr(), gamma.data_ptr(), dout.data_ptr(), \
-            saved.data_ptr(), scratch.data_ptr()
-        x.da, x.dw, x.db, x.dgamma, x.dbeta = _p(da), dw.data_ptr(), db.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
-        _pn_pool_backward(d, x, ctx.rag)
-        return da, dw, db, dgamma, dbeta, None
+        da, grads = _pn_pool_backward_call(ctx.desc, a, w, gamma, _f32(dout, "dout"), saved, ctx.rag, ctx.needs_input_grad[0], None)
+        return (da, *grads, None)
 
 
 def pn_pool(a: torch.Tensor, B: int, N: int, conv, bn, relu: bool, training: bool, lengths=None) -> torch.Tensor:
@@ -1224,9 +1239,8 @@ def pn_pool(a: torch.Tensor, B: int, N: int, conv, bn, relu: bool, training: boo
     statistics updated in place when training).  Returns (B, C).  Keeps O(B*C + K*K) for the backward pass, not (B*N) x C.
     lengths (B,) (pnpp_hip.lengths.packed_lengths): a holds the sum(lengths) PACKED valid rows of a ragged batch padded to N; the
     statistics run over those rows, each cloud's max over its own."""
-    momentum = bn.momentum if bn.momentum is not None else 0.1
     nbt = _nbt(bn) if training else None
-    cfg = (int(B), int(N), bool(relu), bool(training), bn.eps, momentum, bn.running_mean, bn.running_var, nbt,
+    cfg = (int(B), int(N), bool(relu), bool(training), bn.eps, _bn_momentum(bn), bn.running_mean, bn.running_var, nbt,
            _pn_packed(lengths, int(B), int(N), a.device))
     return _PnPool.apply(a, conv.weight, conv.bias, bn.weight, bn.bias, cfg)
 
@@ -1237,28 +1251,11 @@ class _PnTransform(torch.autograd.Function):
         _need_gpu(x, "x")
         if x.dtype != torch.float32:
             raise TypeError(f"x must be float32, got {x.dtype}")
-        if rag is not None:
-            return _PnTransform._forward_ragged(ctx, x, t, k, ldy, rag, BN)
-        if not (x.is_contiguous() or x.transpose(1, 2).is_contiguous()):
-            x = x.contiguous()
-        B, N, D = x.shape
-        if t is not None:
-            t = _f32(t, "transform")
-            if tuple(t.shape) != (B, k, k):
-                raise ValueError(f"pn_transform: transform {tuple(t.shape)} is not ({B}, {k}, {k})")
-        y = torch.empty(B * N, ldy, device=x.device, dtype=torch.float32)
-        sb, sn, sd = x.stride()
-        L.check(L.lib().pnpp_pn_transform(x.data_ptr(), sb, sn, sd, _p(t), B, N, D, k, ldy, y.data_ptr(), _stream()))
-        ctx.k, ctx.ldy, ctx.has_t, ctx.rag = k, ldy, t is not None, None
-        ctx.save_for_backward(x, t if t is not None else x.new_empty(0))
-        return y
-
-    @staticmethod
-    def _forward_ragged(ctx, x, t, k, ldy, rag, BN):
-        """x (B, N, D) padded, read in place, or (M_total, D) packed rows -> (M_total, ldy) packed rows"""
-        B, N = BN
-        packed = x.dim() == 2
+        # rag None: x (B, N, D) -> (B*N, ldy) rows.  Ragged: x (B, N, D) padded, read in place, or (M_total, D) packed rows (the
+        # padded geometry is BN then) -> (M_total, ldy) packed rows
+        packed = rag is not None and x.dim() == 2
         if packed:
+            B, N = BN
             x = x.contiguous()
             if x.shape[0] != rag.M_total:
                 raise ValueError(f"pn_transform: expected ({rag.M_total}, D) packed rows, got {tuple(x.shape)}")
@@ -1266,51 +1263,41 @@ class _PnTransform(torch.autograd.Function):
         else:
             if not (x.is_contiguous() or x.transpose(1, 2).is_contiguous()):
                 x = x.contiguous()
-            if tuple(x.shape[:2]) != (B, N):
-                raise ValueError(f"pn_transform: expected a ({B}, {N}, D) input, got {tuple(x.shape)}")
-            D, (sb, sn, sd) = x.shape[2], x.stride()
+            if rag is not None and tuple(x.shape[:2]) != tuple(BN):
+                raise ValueError(f"pn_transform: expected a ({BN[0]}, {BN[1]}, D) input, got {tuple(x.shape)}")
+            (B, N, D), (sb, sn, sd) = x.shape, x.stride()
         if t is not None:
             t = _f32(t, "transform")
             if tuple(t.shape) != (B, k, k):
                 raise ValueError(f"pn_transform: transform {tuple(t.shape)} is not ({B}, {k}, {k})")
-        y = torch.empty(rag.M_total, ldy, device=x.device, dtype=torch.float32)
-        L.check(L.lib().pnpp_pn_transform_ragged(x.data_ptr(), int(packed), sb, sn, sd, _p(t), rag.offs_dev.data_ptr(), B, N, D, k, ldy,
-                                                 y.data_ptr(), _stream()))
+        y = torch.empty(_pn_rows(rag, B, N), ldy, device=x.device, dtype=torch.float32)
+        if rag is None:
+            L.check(L.lib().pnpp_pn_transform(x.data_ptr(), sb, sn, sd, _p(t), B, N, D, k, ldy, y.data_ptr(), _stream()))
+        else:
+            L.check(L.lib().pnpp_pn_transform_ragged(x.data_ptr(), int(packed), sb, sn, sd, _p(t), rag.offs_dev.data_ptr(), B, N, D, k, ldy,
+                                                     y.data_ptr(), _stream()))
         ctx.k, ctx.ldy, ctx.has_t, ctx.rag = k, ldy, t is not None, rag
         ctx.geom = (packed, B, N, D, sb, sn, sd)
         ctx.save_for_backward(x, t if t is not None else x.new_empty(0))
         return y
 
     @staticmethod
-    def _backward_ragged(ctx, dy):
+    def backward(ctx, dy):
         x, t = ctx.saved_tensors
         t = t if ctx.has_t else None
         dy = _f32(dy, "dy")
         packed, B, N, D, sb, sn, sd = ctx.geom
-        # every element of dx is written: the padding rows of a padded input get exact zeros
+        # every element of dx is written: the padding rows of a padded ragged input get exact zeros
         dx = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
         dt = torch.empty_like(t) if (t is not None and ctx.needs_input_grad[1]) else None
         if dx is None and dt is None:
             return None, None, None, None, None, None
-        L.check(L.lib().pnpp_pn_transform_bwd_ragged(x.data_ptr(), int(packed), sb, sn, sd, _p(t), dy.data_ptr(), ctx.rag.offs_dev.data_ptr(),
-                                                     B, N, D, ctx.k, ctx.ldy, _p(dx), _p(dt), _stream()))
-        return dx, dt, None, None, None, None
-
-    @staticmethod
-    def backward(ctx, dy):
-        if ctx.rag is not None:
-            return _PnTransform._backward_ragged(ctx, dy)
-        x, t = ctx.saved_tensors
-        t = t if ctx.has_t else None
-        dy = _f32(dy, "dy")
-        B, N, D = x.shape
-        dx = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        dt = torch.empty_like(t) if (t is not None and ctx.needs_input_grad[1]) else None
-        if dx is None and dt is None:
-            return None, None, None, None, None, None
-        sb, sn, sd = x.stride()
-        L.check(L.lib().pnpp_pn_transform_bwd(x.data_ptr(), sb, sn, sd, _p(t), dy.data_ptr(), B, N, D, ctx.k, ctx.ldy, _p(dx), _p(dt),
-                                              _stream()))
+        if ctx.rag is None:
+            L.check(L.lib().pnpp_pn_transform_bwd(x.data_ptr(), sb, sn, sd, _p(t), dy.data_ptr(), B, N, D, ctx.k, ctx.ldy, _p(dx), _p(dt),
+                                                  _stream()))
+        else:
+            L.check(L.lib().pnpp_pn_transform_bwd_ragged(x.data_ptr(), int(packed), sb, sn, sd, _p(t), dy.data_ptr(),
+                                                         ctx.rag.offs_dev.data_ptr(), B, N, D, ctx.k, ctx.ldy, _p(dx), _p(dt), _stream()))
         return dx, dt, None, None, None, None
 
 
@@ -1456,9 +1443,8 @@ class _PnBnRelu(torch.autograd.Function):
 
 def pn_bn_relu(x: torch.Tensor, bn, training: bool) -> torch.Tensor:
     """relu(bn(x)) for (M, C) rows with an nn.BatchNorm1d on its own (running statistics updated in place when training)."""
-    momentum = bn.momentum if bn.momentum is not None else 0.1
     nbt = _nbt(bn) if training else None
-    return _PnBnRelu.apply(x, bn.weight, bn.bias, (bool(training), bn.eps, momentum, bn.running_mean, bn.running_var, nbt))
+    return _PnBnRelu.apply(x, bn.weight, bn.bias, (bool(training), bn.eps, _bn_momentum(bn), bn.running_mean, bn.running_var, nbt))
 
 
 # set to a list to receive, per narrow layer of a pn_trunk call, its (B*N, C) ReLU decisions (y > 0, on the host) in call order
@@ -1479,24 +1465,11 @@ class _PnTrunk(torch.autograd.Function):
             raise ValueError(f"pn_trunk: expected ({M}, K) rows, got {tuple(rows.shape)}")
         if M <= 32:
             raise ValueError(f"pn_trunk: {B} clouds x {N} points = {M} point rows; the per-point layers need more than 32")
-        lib = L.lib()
         x, descs, saveds = rows, [], []
         for l in range(nl):
             w, b, nw, nb = (_f32(t, "trunk parameter") for t in params[4 * l:4 * l + 4])
-            d = L.FcDesc()
-            d.M, d.K, d.N, d.norm, d.relu, d.training = M, x.shape[1], w.shape[0], L.NORM_BATCH, 1, int(training)
-            d.eps, d.momentum, d.drop_scale = float(eps[l]), float(mom[l]), 1.0
-            sb = lib.pnpp_fc_saved_bytes(C.byref(d))
-            if sb == 0:
-                L.check(L.PNPP_ERR_ARG)
-            saved = torch.empty(sb, dtype=torch.uint8, device=rows.device)
-            scratch = _scratch(lib.pnpp_fc_scratch_bytes(C.byref(d)), rows.device)
-            y = torch.empty(M, d.N, device=rows.device, dtype=torch.float32)
-            a = L.FcFwdArgs()
-            a.x, a.w, a.b, a.nw, a.nb = x.data_ptr(), w.data_ptr(), b.data_ptr(), nw.data_ptr(), nb.data_ptr()
-            a.rm, a.rv, a.nbt = running[2 * l].data_ptr(), running[2 * l + 1].data_ptr(), _p(nbts[l])
-            a.y, a.saved, a.scratch = y.data_ptr(), saved.data_ptr(), scratch.data_ptr()
-            L.check(lib.pnpp_fc_forward(C.byref(d), C.byref(a), _stream()))
+            d = _fc_desc(M, x.shape[1], w.shape[0], L.NORM_BATCH, 1, training, eps[l], mom[l], 1.0)
+            y, saved, _ = _fc_forward_call(d, x, w, b, nw, nb, running[2 * l], running[2 * l + 1], nbts[l], None, None)
             if pn_relu_tap is not None:
                 pn_relu_tap.append((y > 0).cpu())
             descs.append(d)
@@ -1504,20 +1477,7 @@ class _PnTrunk(torch.autograd.Function):
             x = y
         w, b, nw, nb = (_f32(t, "pooled layer parameter") for t in params[4 * nl:4 * nl + 4])
         pd = _pn_pool_desc(B, N, x.shape[1], w.shape[0], pool_relu, training, eps[nl], mom[nl])
-        sb, scb = _pn_pool_sizes(pd, rag)
-        if sb == 0:
-            L.check(L.PNPP_ERR_ARG)
-        psaved = torch.empty(sb, dtype=torch.uint8, device=rows.device)
-        scratch = _scratch(scb, rows.device)
-        out = torch.empty(B, pd.C, device=rows.device, dtype=torch.float32)
-        a = L.PnPoolFwdArgs()
-        a.a, a.w, a.b, a.gamma, a.beta = x.data_ptr(), w.data_ptr(), b.data_ptr(), nw.data_ptr(), nb.data_ptr()
-        a.rm, a.rv, a.nbt = running[2 * nl].data_ptr(), running[2 * nl + 1].data_ptr(), _p(nbts[nl])
-        a.out, a.saved, a.scratch = out.data_ptr(), psaved.data_ptr(), scratch.data_ptr()
-        _pn_pool_forward(pd, a, rag)
-        if pn_pool_tap is not None:
-            r = lib.pnpp_pn_pool_saved_route(C.byref(pd), psaved.data_ptr()) - psaved.data_ptr()
-            pn_pool_tap.append({"route": psaved[r:r + 4 * B * pd.C].view(torch.int32).view(B, pd.C)})
+        out, psaved = _pn_pool_forward_call(pd, x, w, b, nw, nb, running[2 * nl], running[2 * nl + 1], nbts[nl], rag)
         ctx.descs, ctx.pdesc, ctx.sinks, ctx.nl, ctx.rag = descs, pd, sinks, nl, rag
         ctx.save_for_backward(rows, psaved, *saveds, *params)
         return out
@@ -1537,37 +1497,13 @@ class _PnTrunk(torch.autograd.Function):
             L.check(lib.pnpp_fc_recompute_output(C.byref(descs[l]), saveds[l].data_ptr(), None, y.data_ptr(), _stream()))
             ys.append(y)
         grads = [None] * len(params)
-
-        def dest(i):
-            if sinks[i] is not None:
-                return sinks[i]
-            grads[i] = torch.empty_like(params[i])
-            return grads[i]
-
-        a_in = ys[-1] if nl else rows
-        da = torch.empty_like(a_in) if (nl or ctx.needs_input_grad[0]) else None
         w, _, nw, _ = params[4 * nl:4 * nl + 4]
-        scratch = _scratch(_pn_pool_sizes(pd, ctx.rag)[1], dev)
-        a = L.PnPoolBwdArgs()
-        a.a, a.w, a.gamma, a.dout, a.saved, a.scratch = a_in.data_ptr(), w.data_ptr(), nw.data_ptr(), dout.data_ptr(), \
-            psaved.data_ptr(), scratch.data_ptr()
-        a.da = _p(da)
-        a.dw, a.db, a.dgamma, a.dbeta = (dest(4 * nl + j).data_ptr() for j in range(4))
-        _pn_pool_backward(pd, a, ctx.rag)
-        dy = da
+        dy, grads[4 * nl:] = _pn_pool_backward_call(pd, ys[-1] if nl else rows, w, nw, dout, psaved, ctx.rag,
+                                                    nl or ctx.needs_input_grad[0], sinks[4 * nl:])
         for l in reversed(range(nl)):
-            d = descs[l]
-            x = ys[l - 1] if l else rows
             w, b, nw, nb = params[4 * l:4 * l + 4]
-            dx = torch.empty_like(x) if (l or ctx.needs_input_grad[0]) else None
-            scratch = _scratch(lib.pnpp_fc_scratch_bytes(C.byref(d)), dev)
-            bw = L.FcBwdArgs()
-            bw.x, bw.w, bw.b, bw.nw, bw.nb, bw.mask = x.data_ptr(), w.data_ptr(), b.data_ptr(), nw.data_ptr(), nb.data_ptr(), None
-            bw.dy, bw.saved, bw.scratch = dy.data_ptr(), saveds[l].data_ptr(), scratch.data_ptr()
-            bw.dx = _p(dx)
-            bw.dw, bw.db, bw.dnw, bw.dnb = (dest(4 * l + j).data_ptr() for j in range(4))
-            L.check(lib.pnpp_fc_backward(C.byref(d), C.byref(bw), _stream()))
-            dy = dx
+            dy, grads[4 * l:4 * l + 4] = _fc_backward_call(descs[l], ys[l - 1] if l else rows, w, b, nw, nb, None, dy, saveds[l],
+                                                            l or ctx.needs_input_grad[0], sinks[4 * l:4 * l + 4])
         return (dy, None, *grads)
 
 
@@ -1586,7 +1522,7 @@ def pn_trunk(rows: torch.Tensor, B: int, N: int, layers, pooled, pool_relu: bool
         running += [bn.running_mean, bn.running_var]
         nbts.append(_nbt(bn) if training else None)
         eps.append(bn.eps)
-        mom.append(bn.momentum if bn.momentum is not None else 0.1)
+        mom.append(_bn_momentum(bn))
     sinks = [grad_sink(p) for p in params]
     cfg = (int(B), int(N), len(layers), bool(pool_relu), bool(training), eps, mom, running, nbts,
            sinks if any(s is not None for s in sinks) else None, rag)
