@@ -21,6 +21,23 @@ __device__ __forceinline__ unsigned philox_key(unsigned c0, unsigned c1, unsigne
     return c0;
 }
 
+// the same rounds and constants, all four output words (augment_kernels.hip)
+__device__ __forceinline__ uint4 philox4(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
+        unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
+        unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
+        unsigned n1 = (unsigned)p1;
+        unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        unsigned n3 = (unsigned)p0;
+        c0 = n0, c1 = n1, c2 = n2, c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
 // One workgroup per cloud.  Only the npoint smallest keys matter, so the keys are first cut at a threshold that keeps
 // about npoint + 4 sqrt(npoint) + 16 of them (all of them when that is >= N); the survivors go to LDS as 64-bit (key, index) words --
 // the lexicographic order of the reference rank -- and each survivor counts the survivors below it.  A cloud whose

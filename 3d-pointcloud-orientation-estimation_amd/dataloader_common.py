@@ -170,12 +170,18 @@ class DeviceCloudBank:
 
 class BankLoader:
     """Iterates (xyz (B,num_points,3), *targets[ids]) batches entirely on the device: the loaders' shuffle + the bank's
-    on-device subsampling; drop-in for a torch DataLoader in pnpp_hip.trainer.fit / evaluate."""
+    on-device subsampling; drop-in for a torch DataLoader in pnpp_hip.trainer.fit / evaluate.
+    augment (a pnpp_hip.augment.Augment) with kinds (one per target: "angle", "vm", "axis", "dir8", "keep"): every batch is the
+    bank's draw followed by one augmentation launch -- the cloud in a fresh pose, its targets moved along.  None: nothing changes.
+    counts: index of the target that holds the number of real rows of the multi-row "vm" / "angle" targets (the multi-peak K)."""
 
     def __init__(self, bank: DeviceCloudBank, targets, num_points: int, batch: int, shuffle: bool, seed: int = 0,
-                 drop_last: bool = False):
+                 drop_last: bool = False, augment=None, kinds=None, counts=None):
         import torch
         self.bank, self.num_points, self.batch, self.shuffle, self.drop_last = bank, num_points, batch, shuffle, drop_last
+        if augment is not None and (kinds is None or len(kinds) != len(targets)):
+            raise ValueError(f"BankLoader: augment needs one kind per target ({len(targets)}), got {kinds}")
+        self.augment, self.kinds, self.counts = augment, (None if kinds is None else tuple(kinds)), counts
         self.targets = [t.to(bank.bank.device) for t in targets]
         self.gen = torch.Generator().manual_seed(seed)
 
@@ -192,4 +198,8 @@ class BankLoader:
             if self.drop_last and len(ids) < self.batch:
                 break
             dev_ids = ids.to(self.bank.bank.device)
-            yield (self.bank.sample(dev_ids, self.num_points), *(t[dev_ids] for t in self.targets))
+            batch = (self.bank.sample(dev_ids, self.num_points), *(t[dev_ids] for t in self.targets))
+            if self.augment is None:
+                yield batch
+            else:
+                yield self.augment(*batch, kinds=self.kinds, counts=None if self.counts is None else batch[1 + self.counts])

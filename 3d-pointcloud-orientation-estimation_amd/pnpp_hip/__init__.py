@@ -6,8 +6,9 @@
     optim   flat-buffer Adam / gradient clipping on the device
     dist    one-process-per-GPU data parallelism (RCCL all-reduce of one flat gradient buffer)
     inference  Predictor: forward-only evaluation, one fused launch per set-abstraction level
+    augment Augment: a fresh yaw per cloud and draw on the device, orientation targets moved along
 """
-__all__ = ["ops", "build", "optim", "dist", "sampling", "inference", "Predictor"]
+__all__ = ["ops", "build", "optim", "dist", "sampling", "inference", "augment", "Predictor"]
 
 
 def __getattr__(name):

@@ -98,6 +98,20 @@ class PnPoolBwdArgs(C.Structure):
                 ("db", _fp), ("dgamma", _fp), ("dbeta", _fp)]
 
 
+PNPP_AUG_MAX_TARGETS = 4
+AUG_YAW, AUG_SCALE, AUG_JITTER = 1, 2, 4
+AUG_ANGLE, AUG_VM, AUG_AXIS, AUG_DIR8 = range(4)
+
+
+class AugmentTarget(C.Structure):
+    _fields_ = [("kind", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("inp", _fp), ("out", _fp), ("counts", _fp)]
+
+
+class AugmentDesc(C.Structure):
+    _fields_ = [("flags", C.c_uint), ("scale_lo", C.c_float), ("scale_hi", C.c_float), ("sigma", C.c_float), ("clip", C.c_float),
+                ("n_targets", C.c_int), ("targets", AugmentTarget * PNPP_AUG_MAX_TARGETS), ("dirs8", _fp)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 _i, _f, _u64, _sz = C.c_int, C.c_float, C.c_uint64, C.c_size_t
 # int fn(double *buf, size_t n_doubles, void *stream, void *user): sums buf over the ranks in place (SyncBN, pnpp_set_stats_exchange)
@@ -113,6 +127,7 @@ SIGNATURES = {
     "pnpp_ball_query": (_i, [_fp, _fp, _i, _i, _i, _f, _i, _fp, _fp]),
     "pnpp_sample_random": (_i, [_u64, _u64, _i, _i, _i, _fp, _fp]),
     "pnpp_subsample_points": (_i, [_u64, _u64, _fp, _fp, _fp, _i, _i, _i, _fp, _fp]),
+    "pnpp_augment_clouds": (_i, [_u64, _u64, _fp, _fp, _fp, _i, C.c_int64, _i, C.POINTER(AugmentDesc), _fp, _fp]),
     "pnpp_sample_random_dev": (_i, [_u64, _fp, _u64, _i, _i, _i, _fp, _fp]),
     "pnpp_sample_random_dev2": (_i, [_u64, _fp, _u64, _i, _i, _i, _fp, _i, _i, _fp, _fp]),
     "pnpp_index_points": (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp]),

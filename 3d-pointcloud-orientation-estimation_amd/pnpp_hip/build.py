@@ -28,6 +28,7 @@ COMMON = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wno-unused-v
 _NOSLP = [] if os.environ.get("PNPP_SLP") else ["-fno-slp-vectorize"]
 SOURCES = {
     "index_kernels.hip": ["-ffp-contract=off"],
+    "augment_kernels.hip": ["-ffp-contract=off"],   # float32 steps reproducible on the CPU (tests/augment_ref.py)
     "gemm_kernels.hip": [],
     "gemm_ws_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
     "dw_kernels.hip": [],

@@ -307,6 +307,117 @@ def subsample_points(seed: int, stream_id: int, bank: torch.Tensor, lengths: tor
     return out
 
 
+AUGMENT_KINDS = ("angle", "vm", "axis", "dir8", "keep")
+
+
+def augment_plan(xyz_shape, targets, kinds, counts=None, scale=None, jitter=None):
+    """Host-side validation of an augment_clouds call, from shapes alone (runs without a GPU): -> one entry per target, None for
+    "keep" and (kind code, rows, cols, output shape, counts tensor or None) otherwise.  Mismatches raise ValueError."""
+    if len(xyz_shape) != 3 or xyz_shape[2] not in (3, 6) or xyz_shape[0] < 1 or xyz_shape[1] < 1:
+        raise ValueError(f"augment_clouds: xyz must be (B, N, 3) or (B, N, 6) with B, N >= 1, got {tuple(xyz_shape)}")
+    B = xyz_shape[0]
+    targets, kinds = list(targets), list(kinds)
+    if len(targets) != len(kinds):
+        raise ValueError(f"augment_clouds: {len(targets)} targets but {len(kinds)} kinds")
+    if isinstance(counts, torch.Tensor) or counts is None:
+        counts = [counts if k in ("angle", "vm") and t.dim() > (1 if k == "angle" else 2) else None for t, k in zip(targets, kinds)]
+    counts = list(counts)
+    if len(counts) != len(targets):
+        raise ValueError(f"augment_clouds: {len(targets)} targets but {len(counts)} counts entries")
+    plan = []
+    for i, (t, k, cnt) in enumerate(zip(targets, kinds, counts)):
+        if k not in AUGMENT_KINDS:
+            raise ValueError(f"augment_clouds: target {i} has unknown kind {k!r}; kinds are {AUGMENT_KINDS}")
+        if k == "keep":
+            plan.append(None)
+            continue
+        shp = tuple(t.shape)
+        if not shp or shp[0] != B:
+            raise ValueError(f"augment_clouds: target {i} ({k}) has shape {shp}, the batch has {B} clouds")
+        if t.dtype != torch.float32:
+            raise ValueError(f"augment_clouds: target {i} ({k}) must be float32, got {t.dtype}")
+        if k == "angle" and len(shp) in (1, 2):
+            code, rows, cols, out = L.AUG_ANGLE, (shp[1] if len(shp) == 2 else 1), 1, shp
+        elif k == "vm" and ((len(shp) == 2 and shp[1] == 2) or (len(shp) == 3 and shp[2] in (2, 3))):
+            code, rows, cols, out = L.AUG_VM, (shp[1] if len(shp) == 3 else 1), shp[-1], shp
+        elif k == "axis" and len(shp) in (2, 3) and shp[-1] == 3:
+            code, rows, cols, out = L.AUG_AXIS, (shp[1] if len(shp) == 3 else 1), 3, shp
+        elif k == "dir8" and shp == (B, 3):
+            code, rows, cols, out = L.AUG_DIR8, 1, 3, (B, 8)
+        else:
+            raise ValueError(f"augment_clouds: target {i} of kind {k!r} cannot have shape {shp}")
+        if rows < 1:
+            raise ValueError(f"augment_clouds: target {i} ({k}) has no rows")
+        if cnt is not None and (tuple(cnt.shape) != (B,) or cnt.dtype not in (torch.int32, torch.int64)):
+            raise ValueError(f"augment_clouds: counts of target {i} must be an integer tensor of shape ({B},)")
+        plan.append((code, rows, cols, out, cnt))
+    if sum(p is not None for p in plan) > L.PNPP_AUG_MAX_TARGETS:
+        raise ValueError(f"augment_clouds: at most {L.PNPP_AUG_MAX_TARGETS} transformed targets per launch")
+    if scale is not None:
+        lo, hi = (float(v) for v in scale)
+        if not (0.0 < lo <= hi < float("inf")):
+            raise ValueError(f"augment_clouds: scale=(lo, hi) needs 0 < lo <= hi, got {scale}")
+    if jitter is not None:
+        sigma, clip = (float(v) for v in jitter)
+        if not (0.0 <= sigma < float("inf") and clip >= 0.0):
+            raise ValueError(f"augment_clouds: jitter=(sigma, clip) needs sigma >= 0 and clip >= 0, got {jitter}")
+    return plan
+
+
+def augment_clouds(xyz: torch.Tensor, seed: int, stream_id: int, targets=(), kinds=(), counts=None, lengths=None, yaw: bool = True,
+                   scale=None, jitter=None, dirs8: Optional[torch.Tensor] = None):
+    """A batch in a new pose, targets moved along, in one launch (pnpp_augment_clouds): -> (xyz', [targets'], params).
+
+    xyz (B,N,3) or (B,N,6) float32; cloud b is turned by theta_b about +Y (yaw), scaled by a factor from scale=(lo, hi) and
+    jittered per point with jitter=(sigma, clip) -- each only when asked for, out of place.  kinds[i] says what targets[i] is:
+    "angle" (B,) / (B,k): mu - theta wrapped into (-pi, pi]; "vm" (B,2) / (B,K,2) / (B,K,3): column 0 as angle; "axis" (B,3) /
+    (B,k,3): rotated; "dir8" (B,3) forward axis -> (B,8) soft labels over dirs8 (8,3); "keep": returned as it is.  counts: per
+    target (or one tensor for every multi-row angle / vm target) the (B,) number of leading rows that are real.  lengths (B,):
+    rows at or beyond lengths[b] are copied.  params (B,4) = [cos, sin, scale, theta].  A pure function of (seed, stream_id)."""
+    plan = augment_plan(xyz.shape, targets, kinds, counts, scale, jitter)
+    xyz = _f32(xyz, "xyz")
+    B, N, Cc = xyz.shape
+    d = L.AugmentDesc()
+    d.flags = (L.AUG_YAW if yaw else 0) | (L.AUG_SCALE if scale is not None else 0) | (L.AUG_JITTER if jitter is not None else 0)
+    if scale is not None:
+        d.scale_lo, d.scale_hi = float(scale[0]), float(scale[1])
+    if jitter is not None:
+        d.sigma, d.clip = float(jitter[0]), float(jitter[1])
+    outs = []
+    held = []   # converted copies (contiguous, int32) must stay allocated until the launch that reads them is enqueued
+    n = 0
+    for t, p in zip(targets, plan):
+        if p is None:
+            outs.append(t)
+            continue
+        code, rows, cols, out_shape, cnt = p
+        tin = _f32(t, "target")
+        tout = torch.empty(out_shape, device=xyz.device, dtype=torch.float32)
+        g = d.targets[n]
+        g.kind, g.rows, g.cols, g.inp, g.out = code, rows, cols, tin.data_ptr(), tout.data_ptr()
+        if cnt is not None:
+            cnt = _i32(cnt, "counts")
+            g.counts = cnt.data_ptr()
+        if code == L.AUG_DIR8:
+            if dirs8 is None or tuple(dirs8.shape) != (8, 3):
+                raise ValueError("augment_clouds: a dir8 target needs dirs8 of shape (8, 3)")
+            dirs8 = _f32(dirs8, "dirs8")
+            d.dirs8 = dirs8.data_ptr()
+        held += [tin, cnt]
+        outs.append(tout)
+        n += 1
+    d.n_targets = n
+    if lengths is not None:
+        if not isinstance(lengths, torch.Tensor) or tuple(lengths.shape) != (B,):
+            raise ValueError(f"augment_clouds: lengths must be a tensor of shape ({B},)")
+        lengths = _i32(lengths, "lengths")
+    out = torch.empty_like(xyz)
+    params = torch.empty(B, 4, device=xyz.device, dtype=torch.float32)
+    L.check(L.lib().pnpp_augment_clouds(int(seed) & (2**64 - 1), int(stream_id) & (2**64 - 1), xyz.data_ptr(), out.data_ptr(), _p(lengths),
+                                        B, N, Cc, C.byref(d), params.data_ptr(), _stream()))
+    return out, outs, params
+
+
 class _IndexPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, idx):

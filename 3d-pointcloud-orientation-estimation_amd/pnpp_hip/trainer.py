@@ -45,6 +45,27 @@ class SyntheticLoader:
             yield tuple(t[sel] for t in self.tensors)
 
 
+class AugmentedLoader:
+    """Any loader that yields (xyz, *targets, labels), each batch passed through `augment` (pnpp_hip.augment.Augment): one launch
+    that turns the clouds and moves the targets along.  kinds: one per target ("angle", "vm", "axis", "dir8", "keep"); the labels
+    column is kept.  device: move the batch there first (a host DataLoader); None: the batch is already on the device.
+    counts: index of the target that holds the number of real rows of the multi-row "vm" / "angle" targets (the multi-peak K)."""
+
+    def __init__(self, loader, augment, kinds, device=None, counts=None):
+        self.loader, self.augment, self.kinds, self.device, self.counts = loader, augment, tuple(kinds) + ("keep",), device, counts
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for batch in self.loader:
+            if len(batch) != len(self.kinds) + 1:
+                raise ValueError(f"AugmentedLoader: a batch of {len(batch)} entries, expected xyz, {len(self.kinds) - 1} targets and labels")
+            if self.device is not None:
+                batch = tuple(b.to(self.device, non_blocking=True) for b in batch)
+            yield self.augment(*batch, kinds=self.kinds, counts=None if self.counts is None else batch[1 + self.counts])
+
+
 LossFn = Union[Callable, Tuple[Callable, Callable]]
 
 

@@ -16,6 +16,7 @@ from torch.utils.data import DataLoader
 from dataloader_8dir_sampled import PointCloudDataset
 from models.pointnet_pp_8dir import DIRS_8, PointNetPP8Dir
 from pnpp_hip import sampling, dist as pdist, ops, trainer
+from pnpp_hip.augment import Augment
 
 ROOT = trainer.env_path("PNPP_ROOT", "/home/pablo/ForwardNet/data/2d_1to8_sampled")
 RES = trainer.env_path("PNPP_RES", "/home/pablo/ForwardNet/results/8dir_KLdiv_0926")
@@ -70,27 +71,40 @@ def _dataset_loaders(rank, world):
                           num_workers=4, pin_memory=True) for k, v in parts.items()}
 
 
-def _synthetic_loaders(n, rank):
+def _synthetic_loaders(n, rank, augment=False):
     import synthetic
     out = {}
     for i, (name, frac) in enumerate((("train", 0.7), ("val", 0.15), ("test", 0.15))):
         m = max(BATCH, int(n * frac))
         xyz, _, _, fwd = synthetic.rotated_clouds(m, NUM_POINTS, seed=SEED + 1000 * i + rank)
-        out[name] = trainer.SyntheticLoader([xyz, synthetic.dir8_soft_labels(fwd, DIRS_8)], BATCH, name == "train", device)
+        if augment and name == "train":   # the loader keeps the forward axis; the labels come out of the augmentation launch
+            out[name] = trainer.AugmentedLoader(trainer.SyntheticLoader([xyz, fwd], BATCH, True, device), Augment(SEED + rank), ("dir8",))
+        else:
+            out[name] = trainer.SyntheticLoader([xyz, synthetic.dir8_soft_labels(fwd, DIRS_8)], BATCH, name == "train", device)
     return ["synthetic"], out
 
 
-def main(argv=None):
+def _parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--sampler", default=os.environ.get("PNPP_SAMPLER", "randperm"), choices=["randperm", "device", "fps"])
+    ap.add_argument("--augment", action="store_true",
+                    help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
+    return ap
+
+
+def main(argv=None):
+    ap = _parser()
     args = ap.parse_args(argv)
+    if args.augment and not args.synthetic:
+        ap.error("--augment needs --synthetic: the 8-direction label files (*_8dir.txt) carry no forward axis to turn with the cloud, "
+                 "and eight soft labels cannot be rotated as numbers")
     rank, _, world = pdist.init_from_env()
     torch.manual_seed(SEED), np.random.seed(SEED), random.seed(SEED)
     sampling.reset(0)   # the device-side centre sampler restarts its stream too: a run is a function of SEED
     RES.mkdir(parents=True, exist_ok=True), FIGS.mkdir(parents=True, exist_ok=True)
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else device
-    labels, loaders = _synthetic_loaders(args.synthetic, rank) if args.synthetic else _dataset_loaders(rank, world)
+    labels, loaders = _synthetic_loaders(args.synthetic, rank, args.augment) if args.synthetic else _dataset_loaders(rank, world)
     model = PointNetPP8Dir(sampler=args.sampler).to(dev)
     hist, best_state, best_ep = trainer.fit(model, _loss, loaders, EPOCHS, LR, dev, label="8-dir soft CE", label_index=2,
                                             n_labels=len(labels))

@@ -23,6 +23,7 @@ from torch.utils.data import DataLoader
 from dataloader_multi_peak_vonMises import PointCloudDatasetMvM
 from models.pointnet_pp_mvM import PointNetPPMvM
 from pnpp_hip import sampling, dist as pdist, ops, trainer
+from pnpp_hip.augment import Augment
 
 ROOT = trainer.env_path("PNPP_ROOT", "/home/pablo/ForwardNet/data/MN40_multi_peak_vM_gt")
 PLY_ROOT = trainer.env_path("PNPP_PLY_ROOT", "/home/pablo/ForwardNet/data/full_mn40_normal_resampled_2d_rotated_ply")
@@ -172,17 +173,26 @@ def _synthetic_loaders(n, rank):
     return ["synthetic"], out
 
 
-def main(argv=None):
+def _parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--sampler", default=os.environ.get("PNPP_SAMPLER", "randperm"), choices=["randperm", "device", "fps"])
-    args = ap.parse_args(argv)
+    ap.add_argument("--augment", action="store_true",
+                    help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
+    return ap
+
+
+def main(argv=None):
+    args = _parser().parse_args(argv)
     rank, _, world = pdist.init_from_env()
     torch.manual_seed(SEED), np.random.seed(SEED), random.seed(SEED)
     sampling.reset(0)   # the device-side centre sampler restarts its stream too: a run is a function of SEED
     RES.mkdir(parents=True, exist_ok=True), FIGS.mkdir(parents=True, exist_ok=True)
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else device
     categories, loaders = _synthetic_loaders(args.synthetic, rank) if args.synthetic else _dataset_loaders(rank, world)
+    if args.augment:   # every real peak of the (B,4,3) table shifts with the cloud; rows beyond K stay the zero padding
+        loaders["train"] = trainer.AugmentedLoader(loaders["train"], Augment(SEED + rank), ("vm", "keep"),
+                                                   None if args.synthetic else dev, counts=1)
     model = PointNetPPMvM(sampler=args.sampler).to(dev)
     h, best_state, best_ep = trainer.fit(model, _loss, loaders, EPOCHS, LR, dev, clip_norm=1.0, label="multi-peak vM KL",
                                          label_index=3, n_labels=len(categories))

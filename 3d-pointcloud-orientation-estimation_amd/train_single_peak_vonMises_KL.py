@@ -23,6 +23,7 @@ from torch.utils.data import DataLoader
 from dataloader_single_peak_vonMises import PointCloudDatasetVonMises
 from models.pointnet_pp_vonMises import PointNetPPVonMises
 from pnpp_hip import sampling, dist as pdist, ops, trainer
+from pnpp_hip.augment import Augment
 
 ROOT = trainer.env_path("PNPP_ROOT", "/home/pablo/ForwardNet/data/chair_toilet_sofa_plant_bowl_bottle")
 RES = trainer.env_path("PNPP_RES", "/home/pablo/ForwardNet/results/single_peak_vonMises_KL_1006_2")
@@ -92,17 +93,25 @@ def _synthetic_loaders(n, rank):
     return out
 
 
-def main(argv=None):
+def _parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--synthetic", type=int, default=0, help="train on this many generated clouds instead of ROOT")
     ap.add_argument("--sampler", default=os.environ.get("PNPP_SAMPLER", "randperm"), choices=["randperm", "device", "fps"])
-    args = ap.parse_args(argv)
+    ap.add_argument("--augment", action="store_true",
+                    help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
+    return ap
+
+
+def main(argv=None):
+    args = _parser().parse_args(argv)
     rank, _, world = pdist.init_from_env()
     torch.manual_seed(SEED), np.random.seed(SEED), random.seed(SEED)
     sampling.reset(0)   # the device-side centre sampler restarts its stream too: a run is a function of SEED
     RES.mkdir(parents=True, exist_ok=True), FIGS.mkdir(parents=True, exist_ok=True)
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else device
     loaders = _synthetic_loaders(args.synthetic, rank) if args.synthetic else _dataset_loaders(rank, world)
+    if args.augment:   # vm_gt rows are [mu, kappa]: mu follows the cloud; a host DataLoader's batch goes to the device first
+        loaders["train"] = trainer.AugmentedLoader(loaders["train"], Augment(SEED + rank), ("vm",), None if args.synthetic else dev)
     model = PointNetPPVonMises(sampler=args.sampler).to(dev)
     hist, best_state, _ = trainer.fit(model, _loss, loaders, EPOCHS, LR, dev, label="von Mises KL")
     if rank == 0:

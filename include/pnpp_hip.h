@@ -848,6 +848,47 @@ int pnpp_adam_step_dev_clip(float *param, float *grad, float *exp_avg, float *ex
 /* sum of squares of a flat buffer into out[0] (double), deterministic two-level reduction. */
 int pnpp_sumsq(const float *x, size_t n, double *out, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training-time augmentation of a device-resident batch: a fresh yaw about +Y per cloud (optionally a scale and a
+ * clipped Gaussian jitter per point) with the orientation targets moved along, in one launch.
+ * The reference rotates its training sets offline (data_process/rotate_without_normals.py:5-15,112 and the GT writers);
+ * the conventions are those restated in synthetic.py.
+ * ---------------------------------------------------------------------------------------- */
+#define PNPP_AUG_MAX_TARGETS 4
+#define PNPP_AUG_YAW 1u    /* flags */
+#define PNPP_AUG_SCALE 2u
+#define PNPP_AUG_JITTER 4u
+typedef enum {
+    PNPP_AUG_ANGLE = 0, /* (B, rows) angles, cols = 1: mu' = wrap(mu - theta) into (-pi, pi]                              */
+    PNPP_AUG_VM = 1,    /* (B, rows, cols) rows [mu, kappa] or [mu, kappa, weight], cols 2 or 3: column 0 as ANGLE, rest copied */
+    PNPP_AUG_AXIS = 2,  /* (B, rows, 3) vectors: f' = R f in the points' float32 arithmetic                               */
+    PNPP_AUG_DIR8 = 3   /* in (B, 3) forward axis, out (B, 8): relu(dirs8 . R f) / sum, 0.125 each for a zero sum         */
+} pnpp_augment_kind;
+typedef struct {
+    int kind, rows, cols;
+    const float *in;
+    float *out;
+    const int32_t *counts; /* optional (B): only the first counts[b] rows of cloud b are transformed, the rest copied     */
+} pnpp_augment_target;
+typedef struct {
+    unsigned flags;            /* PNPP_AUG_YAW | PNPP_AUG_SCALE | PNPP_AUG_JITTER                                          */
+    float scale_lo, scale_hi;  /* SCALE: 0 < lo <= hi, scale = lo + (hi - lo) w1 / 2^32                                     */
+    float sigma, clip;         /* JITTER: j = clamp(sigma z, -clip, clip), z standard normal (Box-Muller), both >= 0        */
+    int n_targets;             /* <= PNPP_AUG_MAX_TARGETS                                                                   */
+    pnpp_augment_target targets[PNPP_AUG_MAX_TARGETS];
+    const float *dirs8;        /* (8, 3) unit directions of the DIR8 targets (models/pointnet_pp_8dir.py: DIRS_8)           */
+} pnpp_augment_desc;
+/* xyz_in (B,N,C) -> xyz_out (B,N,C), out of place, C = 3 (xyz) or 6 (xyz + normal: rotated only).  Rows:
+ *   x' = fl(fl(c x) + fl(s z)), y' = y, z' = fl(fl(c z) - fl(s x)), then * scale, then + jitter -- IEEE float32 in this order.
+ * Random words are Philox4x32-10 with key (seed) and counter (n, b, stream_id): n = 0xFFFFFFFF gives the cloud's words
+ * (w0: theta = w0 2 pi / 2^32, w1: scale), n = point index the point's four (two Box-Muller pairs -> three jitter values);
+ * theta, c = cos, s = sin, scale and the jitter are evaluated in float64 and rounded to float32 once.  Without a switch its
+ * step is skipped, so with no flag set the output is a copy.  lengths (B) or NULL: rows n >= lengths[b] are copied bit for bit
+ * (lengths[b] = 0: the whole cloud; its targets are still transformed).  params_out (B,4) receives [c, s, scale, (float)theta].
+ * A pure function of (seed, stream_id, b, n).  B <= 65535, N < 2^32 - 1. */
+int pnpp_augment_clouds(uint64_t seed, uint64_t stream_id, const float *xyz_in, float *xyz_out, const int32_t *lengths, int B,
+                        int64_t N, int C, const pnpp_augment_desc *desc, float *params_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

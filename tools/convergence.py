@@ -14,6 +14,10 @@ reaches KL = 0 within an epoch by moving the mixture weight to the unmatched com
 the reference's own code does on the same inputs.
 
     python tools/convergence.py [--clouds 8192] [--epochs 40] > profiles/<round>_convergence.json
+    python tools/convergence.py --augment > profiles/augment_convergence.json
+
+--augment trains the single-peak model twice from the same initial state, on the same clouds: as above, and with the training loader
+wrapped in trainer.AugmentedLoader (pnpp_hip.augment.Augment: a fresh yaw per cloud and draw, mu moved along); held-out clouds untouched.
 """
 import argparse
 import json
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("--points", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"], help="bf16: the opt-in bf16-operand MFMA mode")
+    ap.add_argument("--augment", action="store_true", help="single-peak model only: without and with device-side yaw augmentation")
     args = ap.parse_args()
     from models.pointnet_pp_8dir import DIRS_8, PointNetPP8Dir
     from models.pointnet_pp_vonMises import PointNetPPVonMises
@@ -66,38 +71,48 @@ def main():
                        f"{args.epochs} epochs, Adam lr 1e-3, device-side centre sampling, hipGraph step, matmul precision {args.precision}",
            "runs": {}}
 
-    # --- single-peak von Mises KL (train_single_peak_vonMises_KL.py's loss) ---
-    torch.manual_seed(42)
-    sampling.reset(0)
-    model = PointNetPPVonMises(sampler="device").to(dev)
-    kap = torch.full_like(mu_tr, 8.0)
-    loaders = {"train": trainer.SyntheticLoader([xyz_tr, torch.stack([mu_tr, kap], 1)], args.batch, True, dev),
-               "val": trainer.SyntheticLoader([xyz_va, torch.stack([mu_va, torch.full_like(mu_va, 8.0)], 1)], args.batch, False, dev)}
-    loss = lambda m, b: ops.vm_head_kl_loss(m.features(b[0]), b[1][:, 0].contiguous(), b[1][:, 1].contiguous(), reduction="none")
-    hist, best, best_ep = trainer.fit(model, loss, loaders, args.epochs, 1e-3, dev, label="von Mises KL", log=lambda *_: None)
-    model.eval()
+    def single_peak(augment):
+        """train_single_peak_vonMises_KL.py's loss; augment: the training loader's batches in a fresh pose every draw"""
+        torch.manual_seed(42)
+        sampling.reset(0)
+        model = PointNetPPVonMises(sampler="device").to(dev)
+        kap = torch.full_like(mu_tr, 8.0)
+        loaders = {"train": trainer.SyntheticLoader([xyz_tr, torch.stack([mu_tr, kap], 1)], args.batch, True, dev),
+                   "val": trainer.SyntheticLoader([xyz_va, torch.stack([mu_va, torch.full_like(mu_va, 8.0)], 1)], args.batch, False, dev)}
+        if augment:
+            from pnpp_hip.augment import Augment
+            loaders["train"] = trainer.AugmentedLoader(loaders["train"], Augment(seed=42), ("vm",))
+        loss = lambda m, b: ops.vm_head_kl_loss(m.features(b[0]), b[1][:, 0].contiguous(), b[1][:, 1].contiguous(), reduction="none")
+        hist, best, best_ep = trainer.fit(model, loss, loaders, args.epochs, 1e-3, dev, label="von Mises KL", log=lambda *_: None)
+        model.eval()
 
-    def held_out():
-        errs, kaps = [], []
-        with torch.no_grad():
-            for i in range(0, 1024, args.batch):
-                mu, kappa = model(xyz_va[i:i + args.batch].to(dev))
-                errs.append(ang_err_deg(mu.cpu(), mu_va[i:i + args.batch]))
-                kaps.append(kappa.cpu())
-        return torch.cat(errs), torch.cat(kaps)
+        def held_out():
+            errs, kaps = [], []
+            with torch.no_grad():
+                for i in range(0, 1024, args.batch):
+                    mu, kappa = model(xyz_va[i:i + args.batch].to(dev))
+                    errs.append(ang_err_deg(mu.cpu(), mu_va[i:i + args.batch]))
+                    kaps.append(kappa.cpu())
+            return torch.cat(errs), torch.cat(kaps)
 
-    e, k = held_out()                 # the LAST epoch's model (its validation KL swings from epoch to epoch at this learning rate)
-    model.load_state_dict(best)       # the checkpoint of the best validation epoch (trainer.fit keeps a copy)
-    eb, kb = held_out()
-    out["runs"]["single_peak_vonMises_KL"] = {
-        "train_kl": [round(v, 4) for v in hist["train"]], "val_kl": [round(v, 4) for v in hist["val"]], "best_val_epoch": best_ep,
-        "steps": hist["steps"], "train_seconds_per_epoch": round(sum(hist["seconds"]["train"]) / args.epochs, 3),
-        "held_out_angular_error_deg": {"mean": round(float(e.mean()), 2), "median": round(float(e.median()), 2),
-                                       "p90": round(float(e.kthvalue(int(0.9 * len(e))).values), 2)},
-        "held_out_mean_kappa": round(float(k.mean()), 2),
-        "best_checkpoint": {"held_out_angular_error_deg": {"mean": round(float(eb.mean()), 2), "median": round(float(eb.median()), 2),
-                                                           "p90": round(float(eb.kthvalue(int(0.9 * len(eb))).values), 2)},
-                            "held_out_mean_kappa": round(float(kb.mean()), 2)}}
+        e, k = held_out()                 # the LAST epoch's model (its validation KL swings from epoch to epoch at this learning rate)
+        model.load_state_dict(best)       # the checkpoint of the best validation epoch (trainer.fit keeps a copy)
+        eb, kb = held_out()
+        return {
+            "train_kl": [round(v, 4) for v in hist["train"]], "val_kl": [round(v, 4) for v in hist["val"]], "best_val_epoch": best_ep,
+            "steps": hist["steps"], "train_seconds_per_epoch": round(sum(hist["seconds"]["train"]) / args.epochs, 3),
+            "held_out_angular_error_deg": {"mean": round(float(e.mean()), 2), "median": round(float(e.median()), 2),
+                                           "p90": round(float(e.kthvalue(int(0.9 * len(e))).values), 2)},
+            "held_out_mean_kappa": round(float(k.mean()), 2),
+            "best_checkpoint": {"held_out_angular_error_deg": {"mean": round(float(eb.mean()), 2), "median": round(float(eb.median()), 2),
+                                                               "p90": round(float(eb.kthvalue(int(0.9 * len(eb))).values), 2)},
+                                "held_out_mean_kappa": round(float(kb.mean()), 2)}}
+
+    out["runs"]["single_peak_vonMises_KL"] = single_peak(False)
+    if args.augment:
+        out["runs"]["single_peak_vonMises_KL_augmented"] = single_peak(True)
+        print(json.dumps(out))
+        return
 
     # --- 8-direction soft-label cross entropy (train_8dir_KL.py's loss) ---
     torch.manual_seed(42)
