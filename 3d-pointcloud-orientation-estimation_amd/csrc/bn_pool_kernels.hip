@@ -112,13 +112,18 @@ __global__ void __launch_bounds__(256) slab_reduce2_kernel(SlabReduceArgs R1, in
     else slab_reduce_block<EPB2>(R2, blockIdx.x - n1);
 }
 
-int launch_slab_reduce2(const float *slab1, int nsplit1, int Nc1, int kp_pad1, int Kvalid1, float *out1, int ldo1, const float *slab2,
-                        int nsplit2, int Nc2, int kp_pad2, int Kvalid2, float *out2, int ldo2, hipStream_t st) {
-    const SlabReduceArgs R1{slab1, nsplit1, Nc1, kp_pad1, Kvalid1, -1, out1, ldo1}, R2{slab2, nsplit2, Nc2, kp_pad2, Kvalid2, -1, out2, ldo2};
-    const int t1 = Nc1 * Kvalid1, t2 = Nc2 * Kvalid2;
-    const bool w1 = slab_reduce_wide(t1, nsplit1), w2 = slab_reduce_wide(t2, nsplit2);
-    const int n1 = cdiv(t1, w1 ? 64 : 16), n2 = cdiv(t2, w2 ? 64 : 16);
-    ProfScope ps(st, "slab_reduce2_kernel N=%d K=%d split=%d | N=%d K=%d split=%d", Nc1, Kvalid1, nsplit1, Nc2, Kvalid2, nsplit2);
+// the blocks of the two-reduction launch and the form it takes (wide: 64 outputs per block, else 16)
+static inline void slab_reduce2_plan(const SlabReduceArgs &R1, const SlabReduceArgs &R2, bool *w1, bool *w2, int *n1, int *n2) {
+    const int t1 = R1.Nc * R1.Kvalid, t2 = R2.Nc * R2.Kvalid;
+    *w1 = slab_reduce_wide(t1, R1.nsplit), *w2 = slab_reduce_wide(t2, R2.nsplit);
+    *n1 = cdiv(t1, *w1 ? 64 : 16), *n2 = cdiv(t2, *w2 ? 64 : 16);
+}
+
+static int launch_slab_reduce2(const SlabReduceArgs &R1, const SlabReduceArgs &R2, hipStream_t st) {
+    bool w1, w2;
+    int n1, n2;
+    slab_reduce2_plan(R1, R2, &w1, &w2, &n1, &n2);
+    ProfScope ps(st, "slab_reduce2_kernel N=%d K=%d split=%d | N=%d K=%d split=%d", R1.Nc, R1.Kvalid, R1.nsplit, R2.Nc, R2.Kvalid, R2.nsplit);
     if (w1 && w2) hipLaunchKernelGGL((slab_reduce2_kernel<64, 64>), dim3(n1 + n2), dim3(256), 0, st, R1, n1, R2);
     else if (w1) hipLaunchKernelGGL((slab_reduce2_kernel<64, 16>), dim3(n1 + n2), dim3(256), 0, st, R1, n1, R2);
     else if (w2) hipLaunchKernelGGL((slab_reduce2_kernel<16, 64>), dim3(n1 + n2), dim3(256), 0, st, R1, n1, R2);
@@ -126,12 +131,15 @@ int launch_slab_reduce2(const float *slab1, int nsplit1, int Nc1, int kp_pad1, i
     PNPP_CHECK_LAUNCH("slab_reduce2");
     return PNPP_OK;
 }
+int launch_slab_reduce2(const float *slab1, int nsplit1, int Nc1, int kp_pad1, int Kvalid1, float *out1, int ldo1, const float *slab2,
+                        int nsplit2, int Nc2, int kp_pad2, int Kvalid2, float *out2, int ldo2, hipStream_t st) {
+    const SlabReduceArgs R1{slab1, nsplit1, Nc1, kp_pad1, Kvalid1, -1, out1, ldo1}, R2{slab2, nsplit2, Nc2, kp_pad2, Kvalid2, -1, out2, ldo2};
+    return launch_slab_reduce2(R1, R2, st);
+}
 
-int launch_slab_reduce(const float *slab, int nsplit, int Nc, int kp_pad, int Kvalid, int perm_D, float *out, int ldo,
-                       hipStream_t st) {
-    const int total = Nc * Kvalid;
-    const SlabReduceArgs R{slab, nsplit, Nc, kp_pad, Kvalid, perm_D, out, ldo};
-    ProfScope ps(st, "slab_reduce_kernel N=%d K=%d split=%d", Nc, Kvalid, nsplit);
+static int launch_slab_reduce(const SlabReduceArgs &R, hipStream_t st) {
+    const int total = R.Nc * R.Kvalid, nsplit = R.nsplit;
+    ProfScope ps(st, "slab_reduce_kernel N=%d K=%d split=%d", R.Nc, R.Kvalid, nsplit);
     if (slab_reduce_vec4(R)) {
         const int groups = total / 4, epb = slab_reduce_epb4(nsplit);
         if (epb == 64) hipLaunchKernelGGL((slab_reduce_kernel<64, true>), dim3(cdiv(groups, 64)), dim3(256), 0, st, R);
@@ -142,6 +150,47 @@ int launch_slab_reduce(const float *slab, int nsplit, int Nc, int kp_pad, int Kv
     else
         hipLaunchKernelGGL(slab_reduce_kernel<16>, dim3(cdiv(total, 16)), dim3(256), 0, st, R);
     PNPP_CHECK_LAUNCH("slab_reduce");
+    return PNPP_OK;
+}
+int launch_slab_reduce(const float *slab, int nsplit, int Nc, int kp_pad, int Kvalid, int perm_D, float *out, int ldo,
+                       hipStream_t st) {
+    return launch_slab_reduce(SlabReduceArgs{slab, nsplit, Nc, kp_pad, Kvalid, perm_D, out, ldo}, st);
+}
+
+// ---- a level's trailing reduction handed on (SaTail, kernels.h) ----
+// The two forms the merged pooling launch exists for are the two the training step runs: one scalar reduction at 64 outputs per
+// block (layer 0 of the group_all level: permuted columns), and the <16, 64> pair of a delayed layer 0 (few coordinate outputs
+// over many partials, then the wide feature block).  Every other form runs as its own launch.
+static inline bool slab_tail_rides(const SaTail &T) {
+    if (T.kind == PNPP_SA_TAIL_SLAB_REDUCE) return !slab_reduce_vec4(T.R1) && slab_reduce_wide(T.R1.Nc * T.R1.Kvalid, T.R1.nsplit);
+    if (T.kind == PNPP_SA_TAIL_SLAB_REDUCE2) {
+        bool w1, w2;
+        int n1, n2;
+        slab_reduce2_plan(T.R1, T.R2, &w1, &w2, &n1, &n2);
+        return !w1 && w2;
+    }
+    return false;
+}
+
+int slab_tail_blocks(const SaTail &T) {
+    if (T.kind == PNPP_SA_TAIL_SLAB_REDUCE) {
+        const int total = T.R1.Nc * T.R1.Kvalid;
+        if (slab_reduce_vec4(T.R1)) return cdiv(total / 4, slab_reduce_epb4(T.R1.nsplit));
+        return cdiv(total, slab_reduce_wide(total, T.R1.nsplit) ? 64 : 16);
+    }
+    if (T.kind == PNPP_SA_TAIL_SLAB_REDUCE2) {
+        bool w1, w2;
+        int n1, n2;
+        slab_reduce2_plan(T.R1, T.R2, &w1, &w2, &n1, &n2);
+        return n1 + n2;
+    }
+    return 0;
+}
+
+int launch_slab_tail(const SaTail &T, hipStream_t st) {
+    if (T.kind == PNPP_SA_TAIL_SLAB_REDUCE) return launch_slab_reduce(T.R1, st);
+    if (T.kind == PNPP_SA_TAIL_SLAB_REDUCE2) return launch_slab_reduce2(T.R1, T.R2, st);
+    PNPP_REQUIRE(T.kind == PNPP_SA_TAIL_NONE, PNPP_ERR_ARG, "sa tail: unknown kind %d", T.kind);
     return PNPP_OK;
 }
 
@@ -675,18 +724,19 @@ int launch_pool_fwd(const float *z, const float *scale, const float *shift, int 
 // backward of max + ReLU: the dense gradient (zero except at the arg-max row when the pooled value is > 0)
 // is NOT written; this kernel emits the masked pooled gradient dm (G x C) and the two BatchNorm-backward
 // column sums, and the consumers rebuild dy from (dm, arg) on the fly.  block = 64 channels x 4 group lanes.
-__global__ void __launch_bounds__(256)
-pool_bwd_kernel(const float *__restrict__ dout, const int32_t *__restrict__ arg, const float *__restrict__ z,
-                const float *__restrict__ scale, const float *__restrict__ shift, const float *__restrict__ mean,
-                const float *__restrict__ istd, int G, int K, int C, float *__restrict__ dm, double *__restrict__ slab,
-                const float *__restrict__ zsel, int policy) {
+// (bx, by) of ny: the block's place in the (channel blocks, group lanes) grid
+__device__ __forceinline__ void pool_bwd_block(const float *__restrict__ dout, const int32_t *__restrict__ arg, const float *__restrict__ z,
+                                               const float *__restrict__ scale, const float *__restrict__ shift,
+                                               const float *__restrict__ mean, const float *__restrict__ istd, int G, int K, int C,
+                                               float *__restrict__ dm, double *__restrict__ slab, const float *__restrict__ zsel,
+                                               int policy, unsigned bx, unsigned by, unsigned ny) {
     __shared__ double red[4][2][64];
     const int cl = threadIdx.x & 63, gl = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
+    const int c = bx * 64 + cl;
     double s1 = 0.0, s2 = 0.0;
     if (c < C) {
         const float mu = mean[c], is = istd[c], sc = scale[c], sh = shift[c];
-        for (int g = blockIdx.y * 4 + gl; g < G; g += gridDim.y * 4) {
+        for (int g = by * 4 + gl; g < G; g += ny * 4) {
             const size_t gi = (size_t)g * C + c;
             // the pre-BN value behind the pooled output: kept by the forward pass (zsel, a coalesced stream), or gathered --
             // one 4-byte element per (group, channel) out of a row of Z, a 64-byte line each
@@ -704,18 +754,75 @@ pool_bwd_kernel(const float *__restrict__ dout, const int32_t *__restrict__ arg,
         double a = 0.0, b = 0.0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) a += red[i][0][cl], b += red[i][1][cl];
-        sp_store(slab + ((size_t)blockIdx.y * 2 + 0) * C + c, a, (policy & ST_STAT_SLABS) != 0);
-        sp_store(slab + ((size_t)blockIdx.y * 2 + 1) * C + c, b, (policy & ST_STAT_SLABS) != 0);
+        sp_store(slab + ((size_t)by * 2 + 0) * C + c, a, (policy & ST_STAT_SLABS) != 0);
+        sp_store(slab + ((size_t)by * 2 + 1) * C + c, b, (policy & ST_STAT_SLABS) != 0);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+pool_bwd_kernel(const float *__restrict__ dout, const int32_t *__restrict__ arg, const float *__restrict__ z,
+                const float *__restrict__ scale, const float *__restrict__ shift, const float *__restrict__ mean,
+                const float *__restrict__ istd, int G, int K, int C, float *__restrict__ dm, double *__restrict__ slab,
+                const float *__restrict__ zsel, int policy) {
+    pool_bwd_block(dout, arg, z, scale, shift, mean, istd, G, K, C, dm, slab, zsel, policy, blockIdx.x, blockIdx.y, gridDim.y);
+}
+
+// The pooling backward of a level with the trailing weight-gradient reduction of the level above in the same grid: the reduction is
+// read by nobody before the optimiser, the pooling launch does not read it, and as two launches each paid the launch floor alone.
+// Blocks [0, nx * ny) are the pooling blocks in the order of the (nx, ny) grid -- they feed the next launch and start first; the
+// rest run the reduction exactly as its own launch would (same blocks, same order of sums, same stores).  PAIR: the <16, 64> form
+// of slab_reduce2_kernel, else one slab_reduce_kernel<64>.
+struct PoolBwdArgs {
+    const float *dout;
+    const int32_t *arg;
+    const float *z, *scale, *shift, *mean, *istd;
+    int G, K, C;
+    float *dm;
+    double *slab;
+    const float *zsel;
+    int policy;
+};
+template <bool PAIR>
+__global__ void __launch_bounds__(256) pool_bwd_ride_kernel(PoolBwdArgs P, int nx, int ny, SlabReduceArgs R1, int n1, SlabReduceArgs R2) {
+    const int bid = blockIdx.x, npool = nx * ny;
+    if (bid < npool) {
+        pool_bwd_block(P.dout, P.arg, P.z, P.scale, P.shift, P.mean, P.istd, P.G, P.K, P.C, P.dm, P.slab, P.zsel, P.policy, bid % nx, bid / nx, ny);
+    } else if constexpr (PAIR) {
+        if (bid - npool < n1) slab_reduce_block<16>(R1, bid - npool);
+        else slab_reduce_block<64>(R2, bid - npool - n1);
+    } else {
+        slab_reduce_block<64>(R1, bid - npool);
     }
 }
 
 int launch_pool_bwd(const float *dout, const int32_t *arg, const float *z, const float *scale, const float *shift,
                     const float *mean, const float *istd, int G, int K, int C, float *dm, double *slab, int *nslab,
-                    hipStream_t st, const float *zsel) {
+                    hipStream_t st, const float *zsel, const SaTail *ride) {
     int gy = cdiv(G, 16);  // four groups per lane-row and pass
     if (gy > kMaxStatBlocks) gy = kMaxStatBlocks;
     if (gy < 1) gy = 1;
     *nslab = gy;
+    if (ride && ride->kind != PNPP_SA_TAIL_NONE) {
+        if (!slab_tail_rides(*ride)) PNPP_TRY(launch_slab_tail(*ride, st));   // no merged kernel for this form: its own launch, first
+        else {
+            const SlabReduceArgs &R1 = ride->R1, &R2 = ride->R2;
+            const PoolBwdArgs P{dout, arg, z, scale, shift, mean, istd, G, K, C, dm, slab, zsel, store_policy()};
+            const int nx = cdiv(C, 64), nride = slab_tail_blocks(*ride);
+            if (ride->kind == PNPP_SA_TAIL_SLAB_REDUCE2) {
+                bool w1, w2;
+                int n1, n2;
+                slab_reduce2_plan(R1, R2, &w1, &w2, &n1, &n2);
+                ProfScope ps(st, "pool_bwd_kernel G=%d K=%d C=%d + slab_reduce2 N=%d K=%d split=%d | N=%d K=%d split=%d", G, K, C, R1.Nc,
+                             R1.Kvalid, R1.nsplit, R2.Nc, R2.Kvalid, R2.nsplit);
+                hipLaunchKernelGGL(pool_bwd_ride_kernel<true>, dim3(nx * gy + nride), dim3(256), 0, st, P, nx, gy, R1, n1, R2);
+            } else {
+                ProfScope ps(st, "pool_bwd_kernel G=%d K=%d C=%d + slab_reduce N=%d K=%d split=%d", G, K, C, R1.Nc, R1.Kvalid, R1.nsplit);
+                hipLaunchKernelGGL(pool_bwd_ride_kernel<false>, dim3(nx * gy + nride), dim3(256), 0, st, P, nx, gy, R1, 0, R1);
+            }
+            PNPP_CHECK_LAUNCH("pool_bwd(+tail)");
+            return PNPP_OK;
+        }
+    }
     ProfScope ps(st, "pool_bwd_kernel G=%d K=%d C=%d", G, K, C);
     hipLaunchKernelGGL(pool_bwd_kernel, dim3(cdiv(C, 64), gy), dim3(256), 0, st, dout, arg, z, scale, shift, mean, istd, G, K, C,
                        dm, slab, zsel, store_policy());

@@ -247,6 +247,14 @@ int launch_slab_reduce2(const float *slab1, int nsplit1, int Nc1, int kp_pad1, i
                         int nsplit2, int Nc2, int kp_pad2, int Kvalid2, float *out2, int ldo2, hipStream_t st);
 int launch_slab_reduce(const float *slab, int nsplit, int Nc, int kp_pad, int Kvalid, int perm_D, float *out, int ldo,
                        hipStream_t st);
+// A level's trailing reduction handed on instead of launched (pnpp_sa_tail): kind SLAB_REDUCE is R1 alone, SLAB_REDUCE2 is R1 then R2
+// in one launch.  launch_slab_tail makes the launch the level would have made; launch_pool_bwd(..., ride) runs it in extra blocks.
+struct SaTail {
+    int kind = PNPP_SA_TAIL_NONE;
+    SlabReduceArgs R1{}, R2{};
+};
+int slab_tail_blocks(const SaTail &T);
+int launch_slab_tail(const SaTail &T, hipStream_t st);
 
 int launch_bn_finalize_fwd(const StatsView &V, double count, const BnLayer &bn, const BnHyper &h, hipStream_t st,
                            const PoolTail *tail = nullptr);
@@ -281,10 +289,12 @@ int launch_pool_fwd(const float *z, const float *scale, const float *shift, int 
                     hipStream_t st, float *origin_a = nullptr, float *origin_b = nullptr, int norigin = 0, void *part = nullptr,
                     float *zsel = nullptr);
 // backward of max + ReLU without materialising the dense gradient: writes the masked pooled gradient dm (G x C)
-// and collects the BatchNorm-backward column sums; consumers rebuild dy on the fly (A_DZ_POOL)
+// and collects the BatchNorm-backward column sums; consumers rebuild dy on the fly (A_DZ_POOL).  ride (optional): a deferred
+// reduction that runs in extra blocks behind the pooling blocks (or, in a form the merged kernel does not exist for, as its own
+// launch first)
 int launch_pool_bwd(const float *dout, const int32_t *arg, const float *z, const float *scale, const float *shift,
                     const float *mean, const float *istd, int G, int K, int C, float *dm, double *slab, int *nslab,
-                    hipStream_t st, const float *zsel = nullptr);
+                    hipStream_t st, const float *zsel = nullptr, const SaTail *ride = nullptr);
 
 int launch_fill_zero(void *p, size_t bytes, hipStream_t st);
 

@@ -84,6 +84,8 @@ struct SaLevel {
     BnGrads dbn[PNPP_MAX_LAYERS];   // backward calls
     BnHyper hyper;
     bool want_dpoints = false;      // backward calls
+    const SaTail *ride = nullptr;   // backward calls: a reduction deferred by the level above, run behind this level's opening launch
+    SaTail *defer = nullptr;        // backward calls: where the level's last reduction is described instead of launched
 
     double count() const { return (double)g.M; }
     AOperand layer0_operand() const {
@@ -359,6 +361,18 @@ static int sa_bwd_stats(const SaLevel &L, int l, int nslab, StatsView *V) {
     return PNPP_OK;
 }
 
+// A ridden reduction reads its partial slabs in the launch that writes this level's statistics slabs and dm.  The two levels may
+// share one scratch buffer (the layouts differ, and everything else this level writes is ordered behind that launch): true when
+// neither region lies over what the tail reads.  The regions are taken up to the next carved one (sa_scratch_layout's order).
+static bool tail_clear_of(const SaTail &T, const SaScratch &sc) {
+    auto hits = [&](const SlabReduceArgs &R) {
+        const char *lo = (const char *)R.slab, *hi = lo + (size_t)R.nsplit * R.Nc * R.kp_pad * sizeof(float);
+        auto over = [&](const void *b, const void *e) { return lo < (const char *)e && (const char *)b < hi; };
+        return over(sc.slab, sc.dy[0]) || over(sc.dm, sc.cst);
+    };
+    return !(hits(T.R1) || (T.kind == PNPP_SA_TAIL_SLAB_REDUCE2 && hits(T.R2)));
+}
+
 // The top: the pooled gradient through max + ReLU, and the top layer's BatchNorm-backward constants (sc.cst).
 // A level with few groups (group_all: one per cloud) whose dZ is materialised anyway: the finalisation launch takes the pooled
 // gradient as it is -- no pool_bwd launch, no dm tensor (PNPP_NO_POOL_BWD_FUSION=1 keeps the launch)
@@ -373,17 +387,30 @@ static int sa_bwd_top(const SaLevel &L, const pnpp_sa_bwd_args *a, SaBwdState *S
     AOperand dz_top = L.dz_operand(Lm, 0);
     S->dz_ready = L.small;
     if (pooled_src) {
+        if (L.ride) PNPP_TRY(launch_slab_tail(*L.ride, L.st));   // no pooling launch to ride in: the launch it would have been
         dz_top.a = a->dout;   // the dZ job masks it itself
         PooledSource ps;
         ps.dout = a->dout, ps.zsel = sv.zmax, ps.scale = sv.scale[Lm], ps.shift = sv.shift[Lm], ps.G = g.G;
         return launch_bn_finalize_bwd(StatsView(), L.count(), d->training, L.bn[Lm], sc.cst, L.dbn[Lm], L.st, L.dz_side(&dz_top), &ps);
     }
     int nslab = 0;
+    const SaTail *ride = L.ride;
+    if (ride && !tail_clear_of(*ride, sc)) {   // this level's workspace lies over the slabs the tail reads: the tail goes first
+        PNPP_TRY(launch_slab_tail(*ride, L.st));
+        ride = nullptr;
+    }
     PNPP_TRY(launch_pool_bwd(a->dout, sv.arg, sv.z[Lm], sv.scale[Lm], sv.shift[Lm], sv.mean[Lm], sv.istd[Lm], g.G, d->K, d->C[Lm], sc.dm,
-                             sc.slab, &nslab, L.st, L.keeps_zmax ? sv.zmax : nullptr));
+                             sc.slab, &nslab, L.st, L.keeps_zmax ? sv.zmax : nullptr, ride));
     StatsView V;
     PNPP_TRY(sa_bwd_stats(L, Lm, nslab, &V));
     return launch_bn_finalize_bwd(V, L.count(), d->training, L.bn[Lm], sc.cst, L.dbn[Lm], L.st, L.dz_side(&dz_top));
+}
+
+// The level's last reduction, which nothing in the backward pass reads: launched here, or handed to the caller (pnpp_sa_backward_ex)
+static int sa_bwd_tail(const SaLevel &L, const SaTail &T) {
+    if (!L.defer) return launch_slab_tail(T, L.st);
+    *L.defer = T;
+    return PNPP_OK;
 }
 
 // dZ_l as layer l's launches read it: rebuilt on the fly, or -- small-M levels, where every consumer would rebuild it per
@@ -434,8 +461,11 @@ static int sa_bwd_delayed0(const SaLevel &L, const pnpp_sa_bwd_args *a, const AO
     }
     if (!paired) PNPP_TRY(launch_dw(G, C, F, d->D, R, sc.dwslab, nsplit, kp_pad, L.st));
     // both partial sets of W_0 -- coordinate columns 0..2, feature columns 3.. -- in one launch
-    PNPP_TRY(launch_slab_reduce2(sc.xslab, scatter_dz_splits(R), C, 4, 3, a->d_conv_w[0], ldw, sc.dwslab, nsplit, C, kp_pad, d->D,
-                                 a->d_conv_w[0] + 3, ldw, L.st));
+    SaTail T;
+    T.kind = PNPP_SA_TAIL_SLAB_REDUCE2;
+    T.R1 = SlabReduceArgs{sc.xslab, scatter_dz_splits(R), C, 4, 3, -1, a->d_conv_w[0], ldw};
+    T.R2 = SlabReduceArgs{sc.dwslab, nsplit, C, kp_pad, d->D, -1, a->d_conv_w[0] + 3, ldw};
+    PNPP_TRY(sa_bwd_tail(L, T));
     if (L.want_dpoints && !paired) PNPP_TRY(launch_gemm(G, Wf, R, d->D, C, E, nullptr, L.st));
     return PNPP_OK;
 }
@@ -482,7 +512,12 @@ static int sa_bwd_layer(const SaLevel &L, const pnpp_sa_bwd_args *a, int l, cons
         }
         if (!S->dpoints_done) PNPP_TRY(launch_dw(dz, C, a2, g.Cin[l], g.M, sc.dwslab, nsplit, kp_pad, L.st));
     }
-    if (l == 0) return launch_slab_reduce(sc.dwslab, nsplit, C, kp_pad, g.Cin[l], d->D, a->d_conv_w[l], g.Cin[l], L.st);
+    if (l == 0) {
+        SaTail T;
+        T.kind = PNPP_SA_TAIL_SLAB_REDUCE;
+        T.R1 = SlabReduceArgs{sc.dwslab, nsplit, C, kp_pad, g.Cin[l], d->D, a->d_conv_w[l], g.Cin[l]};
+        return sa_bwd_tail(L, T);
+    }
     // reduce dW_l's partials and finalise layer l-1's BatchNorm-backward sums in one launch
     const AOperand dz_next = L.dz_operand(l - 1, S->cur ^ 1);  // dY_{l-1} was just written to sc.dy[cur ^ 1]
     StatsView V;
@@ -510,9 +545,12 @@ static int sa_bwd_dpoints(const SaLevel &L, const pnpp_sa_bwd_args *a, const AOp
     return launch_scatter_rows_bwd(rows, L.sv.idx, d->B, d->N, d->D, d->S * d->K, a->dpoints, L.st);
 }
 
-static int sa_backward_impl(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, hipStream_t st) {
+static int sa_backward_impl(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, hipStream_t st, const SaTail *ride = nullptr,
+                            SaTail *defer = nullptr) {
     SaLevel L;
     PNPP_TRY(sa_level_bwd(d, a, st, &L));
+    L.ride = ride && ride->kind != PNPP_SA_TAIL_NONE ? ride : nullptr;
+    L.defer = defer;
     SaBwdState S;
     PNPP_TRY(sa_bwd_top(L, a, &S));
     for (int l = d->L - 1; l >= 0; --l) {
@@ -587,3 +625,37 @@ extern "C" int pnpp_sa_group_pair_ragged(const pnpp_sa_desc *d1, const pnpp_sa_d
 
 extern "C" int pnpp_sa_forward(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, void *stream) { return sa_forward_impl(d, a, as_stream(stream)); }
 extern "C" int pnpp_sa_backward(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, void *stream) { return sa_backward_impl(d, a, as_stream(stream)); }
+
+// ---- a level's trailing reduction handed on (pnpp_sa_tail; the contract is in the header) ----
+static SlabReduceArgs tail_args(const pnpp_slab_reduce &r) { return SlabReduceArgs{r.slab, r.nsplit, r.Nc, r.kp_pad, r.Kvalid, r.perm_D, r.out, r.ldo}; }
+static pnpp_slab_reduce tail_args(const SlabReduceArgs &R) { return pnpp_slab_reduce{R.slab, R.nsplit, R.Nc, R.kp_pad, R.Kvalid, R.perm_D, R.out, R.ldo}; }
+static int tail_in(const pnpp_sa_tail *t, SaTail *T) {
+    *T = SaTail();
+    if (!t || t->kind == PNPP_SA_TAIL_NONE) return PNPP_OK;
+    PNPP_REQUIRE(t->kind == PNPP_SA_TAIL_SLAB_REDUCE || t->kind == PNPP_SA_TAIL_SLAB_REDUCE2, PNPP_ERR_ARG, "sa tail: unknown kind %d", t->kind);
+    const int n = t->kind == PNPP_SA_TAIL_SLAB_REDUCE2 ? 2 : 1;
+    for (int i = 0; i < n; ++i)
+        PNPP_REQUIRE(t->r[i].slab && t->r[i].out && t->r[i].nsplit > 0 && t->r[i].Nc > 0 && t->r[i].Kvalid > 0 && t->r[i].kp_pad >= t->r[i].Kvalid &&
+                         t->r[i].ldo > 0, PNPP_ERR_ARG, "sa tail: reduction %d is not one a backward call wrote", i);
+    T->kind = t->kind, T->R1 = tail_args(t->r[0]);
+    if (n == 2) T->R2 = tail_args(t->r[1]);
+    PNPP_REQUIRE(slab_tail_blocks(*T) == t->blocks, PNPP_ERR_ARG, "sa tail: %d blocks, the reduction takes %d", t->blocks, slab_tail_blocks(*T));
+    return PNPP_OK;
+}
+extern "C" int pnpp_sa_backward_ex(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, const pnpp_sa_tail *ride, pnpp_sa_tail *defer, void *stream) {
+    SaTail in, out;
+    PNPP_TRY(tail_in(ride, &in));
+    if (defer) memset(defer, 0, sizeof(*defer));
+    PNPP_TRY(sa_backward_impl(d, a, as_stream(stream), &in, defer ? &out : nullptr));
+    if (defer && out.kind != PNPP_SA_TAIL_NONE) {
+        defer->kind = out.kind, defer->blocks = slab_tail_blocks(out);
+        defer->r[0] = tail_args(out.R1);
+        if (out.kind == PNPP_SA_TAIL_SLAB_REDUCE2) defer->r[1] = tail_args(out.R2);
+    }
+    return PNPP_OK;
+}
+extern "C" int pnpp_sa_run_tail(const pnpp_sa_tail *t, void *stream) {
+    SaTail T;
+    PNPP_TRY(tail_in(t, &T));
+    return launch_slab_tail(T, as_stream(stream));
+}

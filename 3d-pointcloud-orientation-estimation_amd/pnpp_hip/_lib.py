@@ -39,6 +39,18 @@ class SaBwdArgs(C.Structure):
                 ("d_conv_w", _PL), ("d_conv_b", _PL), ("d_bn_w", _PL), ("d_bn_b", _PL), ("dpoints", _fp)]
 
 
+class SlabReduce(C.Structure):
+    _fields_ = [("slab", _fp), ("nsplit", C.c_int), ("Nc", C.c_int), ("kp_pad", C.c_int), ("Kvalid", C.c_int), ("perm_D", C.c_int),
+                ("out", _fp), ("ldo", C.c_int)]
+
+
+SA_TAIL_NONE, SA_TAIL_SLAB_REDUCE, SA_TAIL_SLAB_REDUCE2 = 0, 1, 2
+
+
+class SaTail(C.Structure):   # a level's trailing dW reduction handed on (pnpp_sa_backward_ex / pnpp_sa_run_tail)
+    _fields_ = [("kind", C.c_int), ("blocks", C.c_int), ("r", SlabReduce * 2)]
+
+
 class SaInferArgs(C.Structure):
     _fields_ = [("xyz", _fp), ("points", _fp), ("centre_idx", _fp), ("neighbour_idx", _fp), ("idx_out", _fp), ("weights", _fp),
                 ("new_xyz", _fp), ("out", _fp)]
@@ -136,6 +148,8 @@ SIGNATURES = {
     "pnpp_sa_scratch_bytes": (_sz, [C.POINTER(SaDesc)]),
     "pnpp_sa_forward": (_i, [C.POINTER(SaDesc), C.POINTER(SaFwdArgs), _fp]),
     "pnpp_sa_backward": (_i, [C.POINTER(SaDesc), C.POINTER(SaBwdArgs), _fp]),
+    "pnpp_sa_backward_ex": (_i, [C.POINTER(SaDesc), C.POINTER(SaBwdArgs), C.POINTER(SaTail), C.POINTER(SaTail), _fp]),
+    "pnpp_sa_run_tail": (_i, [C.POINTER(SaTail), _fp]),
     "pnpp_sa_saved_neighbours": (_fp, [C.POINTER(SaDesc), _fp]),
     "pnpp_knn_pair": (_i, [_fp, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp]),
     "pnpp_knn_pair_partials": (_i, [_i, _i, _i]),

@@ -6,6 +6,7 @@ Every function here requires float32 tensors on an AMD GPU; there is no CPU impl
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -69,7 +70,12 @@ def grad_sink(p: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     if p is None or not torch.is_grad_enabled():
         return None
     sink = getattr(p, "_pnpp_grad_sink", None)
-    if sink is None or getattr(p, "_pnpp_sink_claimed", False):
+    if sink is None:
+        return None
+    if getattr(p, "_pnpp_sink_claimed", False):
+        # a second use in this window: autograd will ADD its gradient to the sink's memory, possibly in the same backward pass as
+        # the first use's overwrite (two passes summed into one loss) -- the overwrite must then be in place when its node returns
+        p._pnpp_sink_shared = True
         return None
     p._pnpp_sink_claimed = True
     return sink
@@ -91,9 +97,14 @@ def _dropout_counter(device: torch.device) -> torch.Tensor:
 _scratch_cache = {}
 
 
-def _scratch(nbytes: int, device: torch.device) -> torch.Tensor:
-    """Transient workspace, reused per (device, stream): all consumers are ordered on that stream."""
+def _scratch(nbytes: int, device: torch.device, keep_tail: bool = False) -> torch.Tensor:
+    """Transient workspace, reused per (device, stream): all consumers are ordered on that stream.  A deferred reduction that still
+    reads its slabs out of it (_TailSlot) is launched first, unless the caller is the level that takes it over (keep_tail)."""
     key = (device.index, _stream())
+    if not keep_tail:
+        slot = _tail_slots.get(key)
+        if slot is not None and slot.pending is not None:
+            slot.run_pending()
     buf = _scratch_cache.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
@@ -465,6 +476,74 @@ def _ptr_array(tensors: Sequence[Optional[torch.Tensor]]):
     return arr
 
 
+# ---- a level's trailing dW reduction rides in the next level's pooling launch (pnpp_sa_backward_ex) ----
+# PNPP_RIDE_TAILS=0 (read once): every level launches its own reductions, as pnpp_sa_backward does -- the A/B switch
+_RIDE_TAILS = os.environ.get("PNPP_RIDE_TAILS", "1") != "0"
+
+
+class _TailSlot:
+    """What one (device, stream) carries from one set-abstraction backward call to the next inside a backward pass.
+
+    pending: the deferred reduction of the level that ran last (L.SaTail), with `keep` -- the scratch buffer it reads and the
+    gradient buffer it writes -- held until it has run.  The next level's call takes it as `ride`; whatever is still pending when
+    the engine finishes the pass (the lower level frozen, the graph cut between the levels, one level alone) is launched by the
+    callback registered on the pass's first deferral.  The levels share the stream's scratch buffer: the level that takes a tail
+    over checks its own layout against the slabs the tail reads (pnpp_sa_backward_ex); any other user of the buffer runs the tail
+    first (_scratch)."""
+
+    def __init__(self):
+        self.task = -1          # the backward pass (graph task id) whose end-of-pass callback is registered
+        self.pending = None     # (L.SaTail, stream handle, torch stream, keep)
+
+    def take(self):
+        t, self.pending = self.pending, None
+        return t
+
+    def flush(self) -> None:   # the end of the pass
+        self.task = -1
+        self.run_pending()
+
+    def run_pending(self) -> None:
+        t = self.take()
+        if t is None:
+            return
+        tail, stream, tstream, _keep = t
+        L.check(L.lib().pnpp_sa_run_tail(C.byref(tail), stream))
+        cur = torch.cuda.current_stream(tstream.device)
+        if cur != tstream:   # the pass ran on another stream than the one its caller goes on with
+            cur.wait_stream(tstream)
+
+
+_tail_slots = {}
+
+
+def _tail_slot(device: torch.device):
+    """The slot to defer into, or None where nothing may be deferred: riding switched off, or no backward pass of the autograd
+    engine around this call whose end would flush it (a direct call of backward(), a custom driver)."""
+    if not _RIDE_TAILS or not hasattr(torch._C, "_current_graph_task_id"):
+        return None
+    task = torch._C._current_graph_task_id()
+    if task < 0:
+        return None
+    key = (device.index, _stream())
+    slot = _tail_slots.get(key)
+    if slot is None:
+        slot = _tail_slots[key] = _TailSlot()
+    if slot.task != task:
+        slot.run_pending()   # left by a pass that ended without its callback (an exception between two levels): never lost
+        try:
+            torch.autograd.Variable._execution_engine.queue_callback(slot.flush)
+        except RuntimeError:
+            return None
+        slot.task = task
+    return slot
+
+
+def pending_tails() -> int:
+    """How many deferred reductions are waiting to run (0 outside a backward pass)."""
+    return sum(1 for s in _tail_slots.values() if s.pending is not None)
+
+
 # set to a list to receive, per set-abstraction forward call, {"neighbours": (B,S,K) int32 | None, "argmax": (B,S,C) int32}
 # (views into the call's saved workspace) -- used by the parity tests to hand the fp64 oracle the same max-pool routing
 sa_tap: Optional[list] = None
@@ -524,6 +603,7 @@ class _SetAbstraction(torch.autograd.Function):
         L.check(lib.pnpp_sa_forward(C.byref(desc), C.byref(a), _stream()))
         ctx.desc = desc
         ctx.sinks = sinks
+        ctx.w0 = params[0]   # backward asks it whether its sink has had a second user since (grad_sink)
         ctx.has_points = points is not None
         # which kernels a level takes depends on process-wide switches (bf16 operands, SyncBN); a level on raw coordinates keeps no
         # Z_0 for the generic backward kernels, so its backward pass must run under the switches its forward pass ran under
@@ -563,7 +643,6 @@ class _SetAbstraction(torch.autograd.Function):
         if ctx.path_state != (lib.pnpp_get_matmul_precision(), lib.pnpp_stats_exchange_enabled(), lib.pnpp_get_split_products()):
             raise ValueError("set_abstraction: matmul precision or SyncBN was switched between this level's forward pass and its "
                              "backward pass; the kept workspace belongs to the kernels the forward pass took")
-        scratch = _scratch(lib.pnpp_sa_scratch_bytes(C.byref(desc)), xyz.device)
         # gradient destinations, kind by kind (a conv bias is not kept for the backward pass: it has its BatchNorm weight's shape)
         sinks = ctx.sinks or [None] * (4 * Lh)
         d_conv_w, r_conv_w = _grad_dests(conv_w, sinks[0::4])
@@ -574,11 +653,25 @@ class _SetAbstraction(torch.autograd.Function):
         a = L.SaBwdArgs()
         a.xyz, a.points = xyz.data_ptr(), _p(points)
         a.conv_w, a.bn_w, a.bn_b = _ptr_array(conv_w), _ptr_array(bn_w), _ptr_array(bn_b)
-        a.dout, a.saved, a.scratch = dout.data_ptr(), saved.data_ptr(), scratch.data_ptr()
+        a.dout, a.saved = dout.data_ptr(), saved.data_ptr()
         a.d_conv_w, a.d_conv_b = _ptr_array(d_conv_w), _ptr_array(d_conv_b)
         a.d_bn_w, a.d_bn_b = _ptr_array(d_bn_w), _ptr_array(d_bn_b)
         a.dpoints = _p(dpoints)
-        L.check(lib.pnpp_sa_backward(C.byref(desc), C.byref(a), _stream()))
+        # The level's last reduction (dW_0) may wait for the next level's pooling launch only where nothing reads it before the pass
+        # ends: its destination is an optimiser's buffer.  A gradient returned to autograd is accumulated as soon as this returns.
+        # Nor where a second use of the weight adds to that buffer during the pass (grad_sink marks the sink shared).
+        slot = _tail_slot(xyz.device) if (r_conv_w[0] is None and not getattr(ctx.w0, "_pnpp_sink_shared", False)) else None
+        if slot is None:
+            a.scratch = _scratch(lib.pnpp_sa_scratch_bytes(C.byref(desc)), xyz.device).data_ptr()   # runs what the level before left
+            L.check(lib.pnpp_sa_backward(C.byref(desc), C.byref(a), _stream()))
+        else:
+            scratch = _scratch(lib.pnpp_sa_scratch_bytes(C.byref(desc)), xyz.device, keep_tail=True)
+            a.scratch = scratch.data_ptr()
+            ride, defer = slot.take(), L.SaTail()
+            L.check(lib.pnpp_sa_backward_ex(C.byref(desc), C.byref(a), C.byref(ride[0]) if ride is not None else None, C.byref(defer),
+                                            _stream()))
+            if defer.kind != L.SA_TAIL_NONE:
+                slot.pending = (defer, _stream(), torch.cuda.current_stream(xyz.device), (scratch, d_conv_w[0]))
         grads = [g for layer in zip(r_conv_w, r_conv_b, r_bn_w, r_bn_b) for g in layer]
         return (None, dpoints, None, None, None, None, *grads)
 

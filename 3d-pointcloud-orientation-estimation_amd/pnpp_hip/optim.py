@@ -80,6 +80,7 @@ class FlatAdam:
         """A new accumulation window: the first backward write of every parameter may overwrite again (ops.grad_sink)."""
         for p in self.params:
             p._pnpp_sink_claimed = False
+            p._pnpp_sink_shared = False
 
     def _sumsq(self) -> torch.Tensor:
         """Sum of squares of the flat gradient buffer into a persistent device word (float64); one stream-ordered launch pair."""

@@ -181,6 +181,42 @@ size_t pnpp_sa_saved_bytes(const pnpp_sa_desc *d);
 size_t pnpp_sa_scratch_bytes(const pnpp_sa_desc *d);
 int pnpp_sa_forward(const pnpp_sa_desc *d, const pnpp_sa_fwd_args *a, void *stream);
 int pnpp_sa_backward(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, void *stream);
+
+/* A level's trailing weight-gradient reduction as a value.  The last reduction of a level's backward pass (layer 0's dW partials
+ * summed into d_conv_w[0]) is read by nobody until the optimiser runs, and the level below opens its backward pass with a pooling
+ * launch that does not read it either: the two can share one launch.  pnpp_sa_backward_ex can leave that reduction out and describe
+ * it here instead; the next level's call takes the description and runs it in extra workgroups behind its pooling launch
+ * ("rides"), or pnpp_sa_run_tail launches it on its own.  The arithmetic, the summation order and the stores are those of the
+ * launch pnpp_sa_backward makes: results are bit-identical whichever way the tail runs.
+ *
+ * CONTRACT.  A tail points into the `scratch` of the call that deferred it (the partial slabs) and into that call's d_conv_w[0].
+ * Both must stay allocated and UNTOUCHED until the tail has run: whatever else would use that scratch buffer runs the tail first
+ * (pnpp_sa_run_tail).  The one exception is the call that takes the tail as `ride`: it may be given the same buffer, because it
+ * checks its own layout against the slabs the tail reads and launches the tail on its own, first, where its opening launch would
+ * write over them.  Every deferred tail must be run -- ridden or flushed -- before the gradients are read, at the latest when
+ * the backward pass ends.  A tail that is never run is a gradient that is never written. */
+typedef enum { PNPP_SA_TAIL_NONE = 0, PNPP_SA_TAIL_SLAB_REDUCE = 1, PNPP_SA_TAIL_SLAB_REDUCE2 = 2 } pnpp_sa_tail_kind;
+typedef struct {            /* out[c][perm(k)] = sum over s < nsplit of slab[s][c][k], c < Nc, k < Kvalid                  */
+    const float *slab;      /* nsplit partials of Nc x kp_pad floats                                                        */
+    int nsplit, Nc, kp_pad, Kvalid;
+    int perm_D;             /* < 0: k as it is; else features-first -> xyz-first columns (k < perm_D -> k + 3, else k - perm_D) */
+    float *out;
+    int ldo;
+} pnpp_slab_reduce;
+typedef struct {
+    int kind;               /* pnpp_sa_tail_kind                                                                            */
+    int blocks;             /* workgroups (of 256 threads) the reduction takes, as its own launch or as riders             */
+    pnpp_slab_reduce r[2];  /* SLAB_REDUCE: r[0]; SLAB_REDUCE2: r[0] (coordinate columns) then r[1] (feature columns)       */
+} pnpp_sa_tail;
+/* pnpp_sa_backward with the trailing reduction handed on.  ride (may be NULL, may be of kind NONE): a tail deferred by an earlier
+ * call; it is run by this call -- behind the opening pooling launch where the level has one and the merged kernel exists for the
+ * tail's form, else as an ordinary launch of its own ahead of the level's first.  defer (may be NULL): the level's last reduction
+ * is not launched but described in *defer; a level that ends another way (layers 1 and 0 of a level on raw coordinates, a
+ * gradient written in place) returns kind NONE and has launched everything.  With both NULL this is pnpp_sa_backward. */
+int pnpp_sa_backward_ex(const pnpp_sa_desc *d, const pnpp_sa_bwd_args *a, const pnpp_sa_tail *ride, pnpp_sa_tail *defer, void *stream);
+/* launches a deferred tail on its own (the flush): the launch pnpp_sa_backward would have made.  Kind NONE: nothing. */
+int pnpp_sa_run_tail(const pnpp_sa_tail *t, void *stream);
+
 /* Grouping of two stacked levels ahead of their forward passes, in ONE launch (models/pointnet_pp_8dir.py:28-31 of sa1 and of
  * sa2: index_points + query_ball_point twice).  Level 2 searches among level 1's centres, which are rows of the same cloud, so
  * once both levels' centre indices are drawn neither search waits for anything: d1 / d2 describe the two levels (d2->N == d1->S),
