@@ -42,7 +42,9 @@ SOURCES = {
     "gemm_wsx_kernels.hip": [],
     "gemm_wsf03_kernels.hip": _NOSLP,
     "gemm_wsq_kernels.hip": [],
-    "loss_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
+    "loss_kernels.hip": [],
+    "step_tail_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
+    "optim_kernels.hip": [],
     "cls_loss_kernels.hip": [],
     "runtime.hip": [],
     "sa_api.hip": [],

@@ -842,14 +842,33 @@ def fc_block(x, linear, norm=None, relu=False, dropout=None, training=True, mask
 # ------------------------------------------------------------------------------------------------
 # heads and losses
 # ------------------------------------------------------------------------------------------------
+def _vm_head_kl_call(who, o, mu_gt=None, kappa_gt=None, mean=False):
+    """The single-peak head of the raw fc3 output `o` (B,2) and, where targets are given, its KL against them, in one launch:
+    pnpp_vm_head_kl (mu, kappa, the loss per sample, d loss / d o) or, mean=True, pnpp_vm_head_kl_mean (the batch mean, d mean / d o).
+    Returns (o as float32, mu, kappa, loss, d_o) with None for what the launch does not produce."""
+    o = _f32(o, "o")
+    gt = mu_gt is not None
+    mu_gt, kappa_gt = (_f32(mu_gt, "mu_gt"), _f32(kappa_gt, "kappa_gt")) if gt else (None, None)
+    B = o.shape[0]
+    if o.dim() != 2 or o.shape[1] != 2 or (gt and (mu_gt.numel() != B or kappa_gt.numel() != B)):
+        raise ValueError(f"{who}: o must be (B,2) and the targets (B,), got {[tuple(t.shape) for t in (o, mu_gt, kappa_gt) if t is not None]}")
+    new = lambda *shape: torch.empty(shape, device=o.device, dtype=torch.float32)
+    mu, kappa = (None, None) if mean else (new(B), new(B))
+    loss = new() if mean else new(B) if gt else None
+    d_o = torch.empty_like(o) if gt else None
+    if mean:
+        L.check(L.lib().pnpp_vm_head_kl_mean(o.data_ptr(), mu_gt.data_ptr(), kappa_gt.data_ptr(), B, None, None, None, loss.data_ptr(),
+                                             d_o.data_ptr(), _stream()))
+    else:
+        L.check(L.lib().pnpp_vm_head_kl(o.data_ptr(), _p(mu_gt), _p(kappa_gt), B, mu.data_ptr(), kappa.data_ptr(), _p(loss), _p(d_o),
+                                        _stream()))
+    return o, mu, kappa, loss, d_o
+
+
 class _VmHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, o):
-        o = _f32(o, "o")
-        B = o.shape[0]
-        mu = torch.empty(B, device=o.device, dtype=torch.float32)
-        kappa = torch.empty_like(mu)
-        L.check(L.lib().pnpp_vm_head_kl(o.data_ptr(), None, None, B, mu.data_ptr(), kappa.data_ptr(), None, None, _stream()))
+        o, mu, kappa, _, _ = _vm_head_kl_call("vm_head", o)
         ctx.save_for_backward(o)
         return mu, kappa
 
@@ -894,13 +913,7 @@ def kl_von_mises_single(mu_p, kappa_p, mu_q, kappa_q):
 
 def vm_head_kl_fused(o, mu_gt, kappa_gt):
     """fc3 output -> (mu, kappa, loss_vec, d loss_vec/d o) in ONE launch (no autograd graph)."""
-    o, mu_gt, kappa_gt = _f32(o, "o"), _f32(mu_gt, "mu_gt"), _f32(kappa_gt, "kappa_gt")
-    B = o.shape[0]
-    mu = torch.empty(B, device=o.device, dtype=torch.float32)
-    kappa, lv, d_o = torch.empty_like(mu), torch.empty_like(mu), torch.empty_like(o)
-    L.check(L.lib().pnpp_vm_head_kl(o.data_ptr(), mu_gt.data_ptr(), kappa_gt.data_ptr(), B, mu.data_ptr(), kappa.data_ptr(),
-                                    lv.data_ptr(), d_o.data_ptr(), _stream()))
-    return mu, kappa, lv, d_o
+    return _vm_head_kl_call("vm_head_kl_fused", o, mu_gt, kappa_gt)[1:]
 
 
 class _VmHeadKlLoss(torch.autograd.Function):
@@ -908,22 +921,8 @@ class _VmHeadKlLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, o, mu_gt, kappa_gt, mean):
-        o, mu_gt, kappa_gt = _f32(o, "o"), _f32(mu_gt, "mu_gt"), _f32(kappa_gt, "kappa_gt")
-        B = o.shape[0]
-        if o.dim() != 2 or o.shape[1] != 2 or mu_gt.numel() != B or kappa_gt.numel() != B:
-            raise ValueError(f"vm_head_kl_loss: o must be (B,2) and the targets (B,), got {tuple(o.shape)}, "
-                             f"{tuple(mu_gt.shape)}, {tuple(kappa_gt.shape)}")
-        d_o = torch.empty_like(o)
         ctx.mean = bool(mean)
-        if mean:
-            loss = torch.empty((), device=o.device, dtype=torch.float32)
-            L.check(L.lib().pnpp_vm_head_kl_mean(o.data_ptr(), mu_gt.data_ptr(), kappa_gt.data_ptr(), B, None, None, None,
-                                                 loss.data_ptr(), d_o.data_ptr(), _stream()))
-        else:
-            loss = torch.empty(B, device=o.device, dtype=torch.float32)
-            mu, kappa = torch.empty_like(loss), torch.empty_like(loss)
-            L.check(L.lib().pnpp_vm_head_kl(o.data_ptr(), mu_gt.data_ptr(), kappa_gt.data_ptr(), B, mu.data_ptr(),
-                                            kappa.data_ptr(), loss.data_ptr(), d_o.data_ptr(), _stream()))
+        *_, loss, d_o = _vm_head_kl_call("vm_head_kl_loss", o, mu_gt, kappa_gt, mean=ctx.mean)
         ctx.save_for_backward(d_o)
         return loss
 
@@ -946,14 +945,7 @@ def vm_head_kl_loss_backward(o, mu_gt, kappa_gt) -> torch.Tensor:
     d loss / d o, so the backward pass is seeded with it directly (autograd would otherwise launch a fill for the
     scalar's unit gradient and a multiply by it).  Returns the detached mean loss; gradients of everything upstream of
     `o` are accumulated exactly as by loss.backward()."""
-    o32, mu_gt, kappa_gt = _f32(o, "o"), _f32(mu_gt, "mu_gt"), _f32(kappa_gt, "kappa_gt")
-    B = o32.shape[0]
-    if o32.dim() != 2 or o32.shape[1] != 2 or mu_gt.numel() != B or kappa_gt.numel() != B:
-        raise ValueError("vm_head_kl_loss_backward: o must be (B,2) and the targets (B,)")
-    loss = torch.empty((), device=o32.device, dtype=torch.float32)
-    d_o = torch.empty_like(o32)
-    L.check(L.lib().pnpp_vm_head_kl_mean(o32.data_ptr(), mu_gt.data_ptr(), kappa_gt.data_ptr(), B, None, None, None,
-                                         loss.data_ptr(), d_o.data_ptr(), _stream()))
+    *_, loss, d_o = _vm_head_kl_call("vm_head_kl_loss_backward", o, mu_gt, kappa_gt, mean=True)
     if o.requires_grad:
         torch.autograd.backward([o], [d_o])
     return loss
@@ -962,14 +954,38 @@ def vm_head_kl_loss_backward(o, mu_gt, kappa_gt) -> torch.Tensor:
 def _draw_centres(job) -> None:
     """The centre draw of sampling.CentreRing.job() as a launch of its own: the same draws from the same counter as when it rides in
     a tail launch (a tail that does not take the one-launch form, or a cloud whose candidate table exceeds that launch's LDS)."""
-    seed, counter, offset, Bs, N1, c1, N2, c2 = job
-    L.check(L.lib().pnpp_sample_random_dev2(int(seed) & (2**64 - 1), counter.data_ptr(), int(offset), Bs, N1, c1.shape[1],
-                                            c1.data_ptr(), N2, c2.shape[1], c2.data_ptr(), _stream()))
+    L.check(L.lib().pnpp_sample_random_dev2(*job.c_args(), _stream()))
 
 
 def _rider_fits(job, lds_limit: int) -> bool:
     """The riding draw keeps an (N + 1)-entry table of 8-byte candidates in the tail launch's LDS."""
-    return 8 * (max(job[4], job[6]) + 1) <= lds_limit
+    return 8 * (max(job.N1, job.N2) + 1) <= lds_limit
+
+
+_NO_RIDER = (0, None, 0, 0, 0, 0, None, 0, 0, None)
+
+
+def _place_rider(next_centres, lds_limit: Optional[int]):
+    """The sampler arguments of a tail's C entry.  The draw `next_centres` (sampling.CentreRing.job(), or None) rides in the tail's launch if
+    its table fits `lds_limit` bytes of LDS; else (or lds_limit None: a tail in separate launches) it is launched here: _NO_RIDER, as for None."""
+    if next_centres is not None and lds_limit is not None and _rider_fits(next_centres, lds_limit):
+        return next_centres.c_args()
+    if next_centres is not None:
+        _draw_centres(next_centres)
+    return _NO_RIDER
+
+
+def _finish_tail(x, dx, params, fresh) -> None:
+    """What is left of `loss.backward()` after a tail's launch: a gradient that no sink took (fresh: _grad_dests' second result) is
+    accumulated into its parameter's .grad with plain autograd semantics, and dx seeds the backward pass of everything before x."""
+    for p, g in zip(params, fresh):
+        if g is not None and p.requires_grad:
+            if p.grad is None:
+                p.grad = g.view_as(p)
+            else:
+                p.grad.add_(g.view_as(p))                        # in place: .grad may be a view of a flat buffer
+    if dx is not None:
+        torch.autograd.backward([x], [dx])
 
 
 def vm_fc_head_kl_loss_backward(x, linear, mu_gt, kappa_gt, next_centres=None) -> torch.Tensor:
@@ -984,34 +1000,20 @@ def vm_fc_head_kl_loss_backward(x, linear, mu_gt, kappa_gt, next_centres=None) -
         raise ValueError("vm_fc_head_kl_loss_backward: linear must map K -> 2 and the targets must be (B,)")
     if 4 * (2 * B + 2 * K + 8 + (B * K if B * K <= 12288 else 0)) > 56 * 1024:
         # the one-launch form stages fc3's weights and the outputs in LDS (56 KB); wider heads take the three launches it fuses
-        if next_centres is not None:
-            _draw_centres(next_centres)
+        _place_rider(next_centres, None)
         return vm_head_kl_loss_backward(fc_block(x, linear, training=True), mu_gt, kappa_gt)
-    if next_centres is not None and not _rider_fits(next_centres, 56 * 1024):   # clouds of N >= 7168: the draw takes its own launch
-        _draw_centres(next_centres)
-        next_centres = None
+    rider = _place_rider(next_centres, 56 * 1024)   # clouds of N >= 7168: the draw takes its own launch
     loss = torch.empty((), device=x32.device, dtype=torch.float32)
-    sinks = [grad_sink(p) for p in (linear.weight, linear.bias)]
-    dw = sinks[0] if sinks[0] is not None else torch.empty_like(w)
-    db = sinks[1] if sinks[1] is not None else torch.empty_like(b)
+    params = (linear.weight, linear.bias)
+    (dw, db), fresh = _grad_dests((w, b), [grad_sink(p) for p in params])
     dx = torch.empty_like(x32) if x.requires_grad else None
-    if next_centres is not None:   # sampling.CentreRing.job(): the next step's centre draw rides in this launch's idle CUs
-        seed, counter, offset, Bs, N1, c1, N2, c2 = next_centres
-        L.check(L.lib().pnpp_vm_fc_head_kl_step_sample(x32.data_ptr(), w.data_ptr(), b.data_ptr(), mu_gt.data_ptr(), kappa_gt.data_ptr(),
-                                                       B, K, loss.data_ptr(), dw.data_ptr(), db.data_ptr(), _p(dx), int(seed) & (2**64 - 1),
-                                                       counter.data_ptr(), int(offset), Bs, N1, c1.shape[1], c1.data_ptr(), N2, c2.shape[1],
-                                                       c2.data_ptr(), _stream()))
+    tail = (x32.data_ptr(), w.data_ptr(), b.data_ptr(), mu_gt.data_ptr(), kappa_gt.data_ptr(), B, K, loss.data_ptr(), dw.data_ptr(),
+            db.data_ptr(), _p(dx))
+    if rider is _NO_RIDER:
+        L.check(L.lib().pnpp_vm_fc_head_kl_step(*tail, _stream()))
     else:
-        L.check(L.lib().pnpp_vm_fc_head_kl_step(x32.data_ptr(), w.data_ptr(), b.data_ptr(), mu_gt.data_ptr(), kappa_gt.data_ptr(), B, K,
-                                                loss.data_ptr(), dw.data_ptr(), db.data_ptr(), _p(dx), _stream()))
-    for p, g, sink in ((linear.weight, dw, sinks[0]), (linear.bias, db, sinks[1])):
-        if sink is None and p.requires_grad:                     # plain autograd semantics: accumulate into .grad
-            if p.grad is None:
-                p.grad = g.view_as(p)
-            else:
-                p.grad.add_(g.view_as(p))                        # in place: .grad may be a view of a flat buffer
-    if dx is not None:
-        torch.autograd.backward([x], [dx])
+        L.check(L.lib().pnpp_vm_fc_head_kl_step_sample(*tail, *rider, _stream()))
+    _finish_tail(x, dx, params, fresh)
     return loss
 
 
@@ -1034,42 +1036,23 @@ def mvm_heads_match_loss_backward(x, head_pi, head_mu, head_kappa, vm_gt, K_gt, 
             or tuple(vm_gt.shape) != (B, maxK, 3)):
         raise ValueError("mvm_heads_match_loss_backward: heads must map K -> max_K / 2 max_K / max_K and vm_gt must be (B, max_K, 3)")
     if not fits:
-        if next_centres is not None:
-            _draw_centres(next_centres)
+        _place_rider(next_centres, None)
         mu, kappa, weight = mvm_head(*[fc_block(x, h, training=True) for h in heads], temp, kappa_max)
         loss = match_loss(mu, kappa, weight, vm_gt, K_gt).mean()
         loss.backward()
         loss = loss.detach()
         return (loss, mu.detach(), kappa.detach(), weight.detach()) if outputs else loss
-    if next_centres is not None and not _rider_fits(next_centres, 96 * 1024):   # clouds of N >= 12288: the draw takes its own launch
-        _draw_centres(next_centres)
-        next_centres = None
-    ws = [_f32(h.weight, "weight") for h in heads]
-    bs = [_f32(h.bias, "bias") for h in heads]
+    rider = _place_rider(next_centres, 96 * 1024)   # clouds of N >= 12288: the draw takes its own launch
+    params = [p for h in heads for p in (h.weight, h.bias)]
+    wb = [_f32(t, name) for h in heads for t, name in ((h.weight, "weight"), (h.bias, "bias"))]
     loss = torch.empty((), device=x32.device, dtype=torch.float32)
-    sinks = [grad_sink(p) for h in heads for p in (h.weight, h.bias)]
-    grads = [sinks[i] if sinks[i] is not None else torch.empty_like(t) for i, t in enumerate(t for pair in zip(ws, bs) for t in pair)]
+    grads, fresh = _grad_dests(wb, [grad_sink(p) for p in params])
     dx = torch.empty_like(x32) if x.requires_grad else None
     outs = [torch.empty(B, maxK, device=x32.device, dtype=torch.float32) for _ in range(3)] if outputs else [None] * 3
-    if next_centres is not None:   # sampling.CentreRing.job(): the next step's centre draw rides in this launch's idle CUs
-        seed, counter, offset, Bs, N1, c1, N2, c2 = next_centres
-        samp = (int(seed) & (2**64 - 1), counter.data_ptr(), int(offset), Bs, N1, c1.shape[1], c1.data_ptr(), N2, c2.shape[1], c2.data_ptr())
-    else:
-        samp = (0, None, 0, 0, 0, 0, None, 0, 0, None)
-    L.check(L.lib().pnpp_mvm_fc_head_match_step(x32.data_ptr(), ws[0].data_ptr(), bs[0].data_ptr(), ws[1].data_ptr(), bs[1].data_ptr(),
-                                                ws[2].data_ptr(), bs[2].data_ptr(), vm_gt.data_ptr(), K32.data_ptr(), B, K, maxK, float(temp),
-                                                float(kappa_max), loss.data_ptr(), grads[0].data_ptr(), grads[1].data_ptr(),
-                                                grads[2].data_ptr(), grads[3].data_ptr(), grads[4].data_ptr(), grads[5].data_ptr(), _p(dx),
-                                                _p(outs[0]), _p(outs[1]), _p(outs[2]), *samp, _stream()))
-    params = [p for h in heads for p in (h.weight, h.bias)]
-    for p, g, sink in zip(params, grads, sinks):
-        if sink is None and p.requires_grad:                         # plain autograd semantics: accumulate into .grad
-            if p.grad is None:
-                p.grad = g.view_as(p)
-            else:
-                p.grad.add_(g.view_as(p))
-    if dx is not None:
-        torch.autograd.backward([x], [dx])
+    L.check(L.lib().pnpp_mvm_fc_head_match_step(x32.data_ptr(), *[t.data_ptr() for t in wb], vm_gt.data_ptr(), K32.data_ptr(), B, K, maxK,
+                                                float(temp), float(kappa_max), loss.data_ptr(), *[g.data_ptr() for g in grads], _p(dx),
+                                                *[_p(t) for t in outs], *rider, _stream()))
+    _finish_tail(x, dx, params, fresh)
     return (loss, *outs) if outputs else loss
 
 

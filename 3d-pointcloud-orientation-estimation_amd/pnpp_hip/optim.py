@@ -104,18 +104,24 @@ class FlatAdam:
         self._pending_clip = float(max_norm)
         return self._ss.sqrt()[0] if return_norm else None
 
+    def _update(self, step, dev: bool, grad_scale: float, zero_grad: bool) -> None:
+        """One launch of the update.  step: the host's count, or (dev) the device words; a pending clip_grad_norm_() picks the _clip entry."""
+        self._release_sinks()
+        clip, self._pending_clip = self._pending_clip, None
+        lib, zero = L.lib(), int(bool(zero_grad))
+        head = (self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                self.flat_p.numel(), step, self.lr, self.betas[0], self.betas[1], self.eps, float(grad_scale))
+        if clip is not None:
+            L.check((lib.pnpp_adam_step_dev_clip if dev else lib.pnpp_adam_step_clip)(*head, self._ss.data_ptr(), clip, zero, _stream()))
+        elif dev:
+            L.check(lib.pnpp_adam_step_dev(*head, zero, _stream()))
+        else:
+            L.check((lib.pnpp_adam_step_zero if zero else lib.pnpp_adam_step)(*head, _stream()))
+
     def step(self, grad_scale: float = 1.0, zero_grad: bool = False) -> None:
         """zero_grad=True clears the flat gradient buffer in the same launch (the next iteration's zero_grad())."""
         self.step_count += 1
-        self._release_sinks()
-        clip, self._pending_clip = self._pending_clip, None
-        args = (self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                self.flat_p.numel(), self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, float(grad_scale))
-        if clip is not None:
-            L.check(L.lib().pnpp_adam_step_clip(*args, self._ss.data_ptr(), clip, int(bool(zero_grad)), _stream()))
-        else:
-            fn = L.lib().pnpp_adam_step_zero if zero_grad else L.lib().pnpp_adam_step
-            L.check(fn(*args, _stream()))
+        self._update(self.step_count, False, grad_scale, zero_grad)
 
     def seed_dev_steps(self) -> None:
         """Copies the host step count into the device word step_dev() reads, if they differ (not capturable: call it
@@ -131,12 +137,5 @@ class FlatAdam:
         callers that replay a captured step_dev bump `step_count` themselves."""
         self.seed_dev_steps()
         self.step_count += 1
-        self._release_sinks()
         self._dev_steps = self.step_count
-        clip, self._pending_clip = self._pending_clip, None
-        head = (self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                self.flat_p.numel(), self._step_state.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps, float(grad_scale))
-        if clip is not None:
-            L.check(L.lib().pnpp_adam_step_dev_clip(*head, self._ss.data_ptr(), clip, int(bool(zero_grad)), _stream()))
-        else:
-            L.check(L.lib().pnpp_adam_step_dev(*head, int(bool(zero_grad)), _stream()))
+        self._update(self._step_state.data_ptr(), True, grad_scale, zero_grad)

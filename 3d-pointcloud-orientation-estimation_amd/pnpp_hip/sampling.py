@@ -4,6 +4,8 @@
 counter is (rank << 40) + a call counter.  The call counter lives in DEVICE memory and is post-incremented by the
 sampling kernel itself, so a step captured into a hipGraph draws fresh, reproducible centres on every replay and
 every rank under data parallelism gets an independent stream -- all without touching the host generator."""
+from typing import NamedTuple
+
 import torch
 
 from . import ops
@@ -56,6 +58,23 @@ def device_random_centres_pair(B: int, N1: int, npoint1: int, N2: int, npoint2: 
                                   lengths=lengths)
 
 
+class CentreJob(NamedTuple):
+    """A two-level centre draw into given buffers: what CentreRing.job() hands to a step tail (ops.*_loss_backward(next_centres=))."""
+    seed: int
+    counter: torch.Tensor   # [call counter, ticket word], on the device
+    offset: int
+    B: int
+    N1: int
+    c1: torch.Tensor        # (B, npoint1) int32: sa1's centres, rows of the cloud
+    N2: int
+    c2: torch.Tensor        # (B, npoint2) int32: sa2's centres, rows of c1
+
+    def c_args(self):
+        """The ten sampler arguments of pnpp_sample_random_dev2, which the step tails' entries repeat."""
+        return (int(self.seed) & (2**64 - 1), self.counter.data_ptr(), int(self.offset), self.B, self.N1, self.c1.shape[1],
+                self.c1.data_ptr(), self.N2, self.c2.shape[1], self.c2.data_ptr())
+
+
 class CentreRing:
     """The centres of the NEXT forward pass, drawn one step ahead (throughput mode of a captured training loop).
 
@@ -81,11 +100,9 @@ class CentreRing:
     def prime(self) -> None:
         """Fills the buffers with the draw of the current counter value (one launch; the tail keeps them filled afterwards)."""
         from . import _lib as L
-        L.check(L.lib().pnpp_sample_random_dev2(torch.initial_seed() & (2**64 - 1), _counter(self.device).data_ptr(),
-                                                (_state["rank"] << 40) + 1, self.B, self.N1, self.c1.shape[1], self.c1.data_ptr(),
-                                                self.N2, self.c2.shape[1], self.c2.data_ptr(), ops._stream()))
+        L.check(L.lib().pnpp_sample_random_dev2(*self.job().c_args(), ops._stream()))
         self.primed = True
 
-    def job(self):
-        """Arguments of the draw that refills the buffers (for ops.vm_fc_head_kl_loss_backward(next_centres=))."""
-        return (torch.initial_seed(), _counter(self.device), (_state["rank"] << 40) + 1, self.B, self.N1, self.c1, self.N2, self.c2)
+    def job(self) -> CentreJob:
+        """The draw that refills the buffers (for ops.vm_fc_head_kl_loss_backward(next_centres=))."""
+        return CentreJob(torch.initial_seed(), _counter(self.device), (_state["rank"] << 40) + 1, self.B, self.N1, self.c1, self.N2, self.c2)

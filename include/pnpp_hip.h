@@ -314,7 +314,9 @@ int pnpp_fc_backward(const pnpp_fc_desc *d, const pnpp_fc_bwd_args *a, void *str
 int pnpp_fc_recompute_output(const pnpp_fc_desc *d, const void *saved, const uint8_t *mask, float *y, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * Output heads and losses (forward value and analytic gradient in one launch)
+ * Output heads and losses (forward value and analytic gradient in one launch): csrc/loss_kernels.hip; the one-launch step tails
+ * pnpp_vm_fc_head_kl_step(_sample), pnpp_mvm_fc_head_match_step and pnpp_vm_match_loss: csrc/step_tail_kernels.hip; the float64
+ * device math they share: csrc/vonmises.h
  * ---------------------------------------------------------------------------------------- */
 
 /* pointnet_pp_vonMises.py:36-37 + train_single_peak_vonMises_KL.py:23-28,83:
@@ -854,7 +856,7 @@ int pnpp_pt_infer_pool_ragged(const pnpp_pt_infer_desc *d, const int32_t *length
                               int n_out, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * Step glue on one flat parameter / gradient buffer
+ * Step glue on one flat parameter / gradient buffer (csrc/optim_kernels.hip)
  * (train_single_peak_vonMises_KL.py:80,85; train_multi_peaks_vonMises_KL.py:221,235-236)
  * ---------------------------------------------------------------------------------------- */
 /* torch.optim.Adam(lr, betas, eps, weight_decay=0) single fused update; step is 1-based. */

@@ -1,5 +1,5 @@
 """The tail of every training step -- output heads, von-Mises KL losses, matching, the fused tail launches with the riding
-centre draw, the flat-buffer Adam and its clip -- steered at the branches of csrc/loss_kernels.hip on purpose, against references
+centre draw, the flat-buffer Adam and its clip -- steered at the branches of csrc/loss_kernels.hip, step_tail_kernels.hip and optim_kernels.hip on purpose, against references
 that share nothing with the kernels: tests/golden/tail_edges.npz (mpmath, oracle/make_tail_golden.py; pinned on the CPU by
 tests/test_tail_golden_cpu.py), float64 autograd of the oracle's expressions, and float64 numpy restatements of torch.optim.Adam.
 

@@ -1,7 +1,7 @@
 """tests/golden/tail_edges.npz (oracle/make_tail_golden.py: mpmath, 60 digits) pinned on the CPU: it regenerates byte for byte
 where mpmath is installed, and it agrees with the three other statements of the same formulas this repository holds -- the
 float64 oracle (oracle.restatement.kl_single / kl_multi, ATen's Cephes series), the float64 captures of the reference's own
-functions (tests/golden/kl.npz) and the float64 formulas of csrc/loss_kernels.hip restated here and rounded once to float32."""
+functions (tests/golden/kl.npz) and the float64 formulas of csrc/vonmises.h restated here and rounded once to float32."""
 import math
 import os
 
@@ -88,7 +88,7 @@ def test_fixture_vs_reference_captures(golden):
 
 
 def _kernel_formulas(c):
-    """kl_single_eval / kl_multi_eval of csrc/loss_kernels.hip in float64 (torch.special.i0e / i1e are the same Cephes series)."""
+    """kl_single_eval / kl_multi_eval of csrc/vonmises.h in float64 (torch.special.i0e / i1e are the same Cephes series)."""
     mp_, kp_raw, mq, kq_raw = (c[:, i] for i in range(4))
     i0e, i1e = torch.special.i0e, torch.special.i1e
     log_i0 = lambda k: k + torch.log(i0e(k))
