@@ -124,6 +124,19 @@ class AugmentDesc(C.Structure):
                 ("n_targets", C.c_int), ("targets", AugmentTarget * PNPP_AUG_MAX_TARGETS), ("dirs8", _fp)]
 
 
+PNPP_OPTIM_MAX_GROUPS = 8
+SCHED_CONSTANT, SCHED_COSINE, SCHED_STEP = range(3)
+
+
+class OptimDesc(C.Structure):   # pnpp_optim_desc: the scheduled optimiser's update, passed to the kernel by value
+    _fields_ = [("n_groups", C.c_int), ("decoupled", C.c_int), ("end", C.c_uint64 * PNPP_OPTIM_MAX_GROUPS),
+                ("lr_mult", C.c_float * PNPP_OPTIM_MAX_GROUPS), ("weight_decay", C.c_float * PNPP_OPTIM_MAX_GROUPS),
+                ("sched_kind", C.c_int), ("warmup", C.c_uint64), ("total", C.c_uint64), ("every", C.c_uint64),
+                ("start_factor", C.c_double), ("min_factor", C.c_double), ("gamma", C.c_double),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("grad_scale", C.c_float),
+                ("max_norm", C.c_float), ("ema_decay", C.c_float), ("zero_grad", C.c_int)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 _i, _f, _u64, _sz = C.c_int, C.c_float, C.c_uint64, C.c_size_t
 # int fn(double *buf, size_t n_doubles, void *stream, void *user): sums buf over the ranks in place (SyncBN, pnpp_set_stats_exchange)
@@ -259,6 +272,8 @@ SIGNATURES = {
     "pnpp_adam_step_clip": (_i, [_fp, _fp, _fp, _fp, _sz, _i, _f, _f, _f, _f, _f, _fp, _f, _i, _fp]),
     "pnpp_adam_step_dev_clip": (_i, [_fp, _fp, _fp, _fp, _sz, _fp, _f, _f, _f, _f, _f, _fp, _f, _i, _fp]),
     "pnpp_sumsq": (_i, [_fp, _sz, _fp, _fp, _sz, _fp]),
+    "pnpp_adamw_step": (_i, [C.POINTER(OptimDesc), _fp, _fp, _fp, _fp, _fp, _sz, _fp, _fp, _fp]),
+    "pnpp_lr_factor": (_i, [C.POINTER(OptimDesc), _u64, C.POINTER(C.c_double)]),
     "pnpp_pn_pool_saved_bytes": (_sz, [C.POINTER(PnPoolDesc)]),
     "pnpp_pn_pool_scratch_bytes": (_sz, [C.POINTER(PnPoolDesc)]),
     "pnpp_pn_pool_forward": (_i, [C.POINTER(PnPoolDesc), C.POINTER(PnPoolFwdArgs), _fp]),

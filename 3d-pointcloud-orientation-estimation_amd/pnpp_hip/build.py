@@ -58,6 +58,7 @@ SOURCES = {
     "transformer_infer_kernels.hip": _NOSLP,
     "attention_infer_kernels.hip": _NOSLP,
     "attention_train_kernels.hip": _NOSLP,
+    "optim_sched_kernels.hip": ["-ffp-contract=off"],   # its float32 operations are written out one by one, the fused ones as fmaf
 }
 
 

@@ -107,6 +107,8 @@ class GraphedSplitStep:
         before the end of the graph), so a replay has no host launch and no graph boundary between backward and the
         collective; `__call__` then ignores its `all_reduce` argument.  Needs a capturable backend (RCCL; gloo moves
         device tensors through the host and cannot be captured)."""
+        if getattr(opt, "n_groups", 1) != 1:   # parameter groups reorder the flat buffer: stage2's parameters are no tail of it
+            raise ValueError("GraphedSplitStep needs an optimiser with one parameter group (stage2's parameters as a contiguous tail)")
         self.opt, self.tail_offset = opt, int(tail_offset)
         self.static_in = list(example_inputs) if adopt_inputs else [t.clone() for t in example_inputs]
         self.captured_collective = captured_all_reduce is not None

@@ -34,6 +34,19 @@ def restore(snap) -> None:
         c.copy_(v)
 
 
+def snapshot_values():
+    """snapshot() as plain data for a checkpoint: {"centres" | "dropout": {(device type, index): host tensor}}."""
+    return {"centres": {k: c.cpu() for k, c in _state["counters"].items()}, "dropout": {k: c.cpu() for k, c in ops._dropout_counters.items()}}
+
+
+def restore_values(values) -> None:
+    """Puts snapshot_values() back, in this or in a fresh process (a counter that does not exist yet is created)."""
+    for k, v in values["centres"].items():
+        _counter(torch.device(*k)).copy_(v)
+    for k, v in values["dropout"].items():
+        ops._dropout_counter(torch.device(*k)).copy_(v)
+
+
 def _counter(device) -> torch.Tensor:
     device = torch.device(device)
     key = (device.type, device.index if device.index is not None else torch.cuda.current_device())

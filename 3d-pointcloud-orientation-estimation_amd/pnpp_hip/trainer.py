@@ -11,6 +11,7 @@ losses kept on the device and read once per phase; with them come the reference'
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import os
 import time
@@ -239,8 +240,17 @@ class _PhaseLog:
 
 def fit(model: torch.nn.Module, loss_fn: LossFn, loaders: Dict[str, Iterable], epochs: int, lr: float,
         device: torch.device, clip_norm: Optional[float] = None, log: Callable = print, label: str = "KL",
-        label_index: Optional[int] = None, n_labels: int = 0, use_graph: Optional[bool] = None, timing: Optional[bool] = None):
+        label_index: Optional[int] = None, n_labels: int = 0, use_graph: Optional[bool] = None, timing: Optional[bool] = None,
+        weight_decay: float = 0.0, schedule: Optional[optim.Schedule] = None, ema_decay: Optional[float] = None,
+        checkpoint=None, resume=None):
     """Trains with FlatAdam; returns (history, best_state, best_val_epoch).
+
+    weight_decay > 0: decoupled (AdamW) decay of every tensor with two or more dimensions (optim.decay_groups).  schedule: an
+    optim.Schedule for the rate, evaluated on the device step by step; a cosine without `total` ends at epochs x steps per epoch.
+    ema_decay: an exponential moving average of the weights is kept, and the validation phase and best_state use it.  With any of the
+    three, hist["lr"] holds the rate of each epoch's last update as the device reported it (the constant lr otherwise).
+    checkpoint: a path written after every epoch (save_checkpoint); resume: such a file to continue from -- the run that results is
+    the uninterrupted one.
 
     loss_fn(model, batch) -> per-sample loss vector (B,) on the device (or a (forward, criterion) pair, see _split);
     batch tensors are already on `device` when it is called.  label_index: position of the class-index column in the
@@ -260,16 +270,25 @@ def fit(model: torch.nn.Module, loss_fn: LossFn, loaders: Dict[str, Iterable], e
         use_graph = os.environ.get("PNPP_NO_GRAPH") != "1"
     if timing is None:
         timing = os.environ.get("PNPP_TIMING") == "1"
-    opt = optim.FlatAdam(model.parameters(), lr=lr)
+    if schedule is not None and schedule.needs_total():
+        per_epoch = _common_steps(loaders["train"], device)
+        schedule = schedule.with_total(epochs * (per_epoch if per_epoch is not None else len(loaders["train"])))
+    params = [g for g in optim.decay_groups(model, weight_decay) if g["params"]] if weight_decay else model.parameters()
+    opt = optim.FlatAdam(params, lr=lr, schedule=schedule, ema_decay=ema_decay)
     pdist.broadcast_flat(opt.flat_p)
+    opt.reset_ema()
     _, _, plain_loss = _split(loss_fn)
     hist = {"train": [], "val": [], "labels": [{"train": [], "val": []} for _ in range(n_labels)], "timing": [],
-            "seconds": {"train": [], "val": []}, "samples": {"train": [], "val": []}}
-    best_val, best_state, best_ep = float("inf"), None, None
+            "seconds": {"train": [], "val": []}, "samples": {"train": [], "val": []}, "lr": [], "ema": opt.ema is not None}
+    best_val, best_state, best_ep, first_ep = float("inf"), None, None, 1
+    if resume is not None:
+        ck = load_checkpoint(resume, model, opt, device)
+        hist, first_ep = ck["hist"], ck["epoch"] + 1
+        best_val, best_state, best_ep = ck["best"]
     t0 = time.time()
     train_timer = PhaseTimer(timing)
     step = _TrainStep(model, loss_fn, opt, clip_norm, world, use_graph, train_timer)
-    for ep in range(1, epochs + 1):
+    for ep in range(first_ep, epochs + 1):
         ep_t = time.time()
         details = {}
         for phase in ("train", "val"):
@@ -282,27 +301,33 @@ def fit(model: torch.nn.Module, loss_fn: LossFn, loaders: Dict[str, Iterable], e
                 timer.sums, timer.n = {k: 0.0 for k in PhaseTimer.NAMES}, 0
             limit = _common_steps(loaders[phase], device) if phase == "train" else None
             ph_t = time.time()
-            for step_i, batch in enumerate(loaders[phase]):
-                if limit is not None and step_i >= limit:
-                    break   # every rank takes the same number of optimiser steps (one all-reduce each)
-                labels = batch[label_index] if label_index is not None else None
-                if phase == "train":
-                    lv = step(batch, device)
-                else:
-                    lv = _eval_batch(model, loss_fn, batch, device, timer)
-                plog.add(lv, labels)
-            avg, per = plog.reduce(device)                   # reads the losses back: the phase's work is finished here
-            hist["seconds"][phase].append(time.time() - ph_t)
-            hist["samples"][phase].append(sum(int(t.shape[0]) for t in plog.lv))
-            hist[phase].append(avg)
-            for i, v in enumerate(per):
-                hist["labels"][i][phase].append(v)
-            details[phase] = timer.detail(phase == "train")
-            if phase == "val" and avg < best_val:
-                best_val, best_ep = avg, ep
-                best_state = copy.deepcopy(model.state_dict())
+            # validation sees the averaged weights when there are any (and so does the copy kept as best_state)
+            with (opt.ema_weights() if phase == "val" and opt.ema is not None else contextlib.nullcontext()):
+                for step_i, batch in enumerate(loaders[phase]):
+                    if limit is not None and step_i >= limit:
+                        break   # every rank takes the same number of optimiser steps (one all-reduce each)
+                    labels = batch[label_index] if label_index is not None else None
+                    if phase == "train":
+                        lv = step(batch, device)
+                    else:
+                        lv = _eval_batch(model, loss_fn, batch, device, timer)
+                    plog.add(lv, labels)
+                avg, per = plog.reduce(device)                   # reads the losses back: the phase's work is finished here
+                if phase == "train":                             # the rate of the epoch's last update, from the device's own word
+                    hist["lr"].append(float(opt.last_lr) if opt._scheduled else float(lr))
+                hist["seconds"][phase].append(time.time() - ph_t)
+                hist["samples"][phase].append(sum(int(t.shape[0]) for t in plog.lv))
+                hist[phase].append(avg)
+                for i, v in enumerate(per):
+                    hist["labels"][i][phase].append(v)
+                details[phase] = timer.detail(phase == "train")
+                if phase == "val" and avg < best_val:
+                    best_val, best_ep = avg, ep
+                    best_state = copy.deepcopy(model.state_dict())
         va = hist["val"][-1] if hist["val"] else float("nan")
         hist["timing"].append(details)
+        if checkpoint is not None and pdist.rank() == 0:
+            save_checkpoint(checkpoint, model, opt, ep, hist, (best_val, best_state, best_ep), device)
         if pdist.rank() == 0:
             el = time.time() - ep_t
             eta = (time.time() - t0) / ep * (epochs - ep)
@@ -313,6 +338,49 @@ def fit(model: torch.nn.Module, loss_fn: LossFn, loaders: Dict[str, Iterable], e
     if best_state is None:
         best_state = copy.deepcopy(model.state_dict())
     return hist, best_state, best_ep
+
+
+def save_checkpoint(path, model, opt: optim.FlatAdam, epoch: int, hist: dict, best=(float("inf"), None, None), device=None) -> None:
+    """Everything a run needs to go on as if it had not stopped: the model (parameters and buffers), the optimiser (FlatAdam.state_dict:
+    step count, moments, averaged weights, schedule), the epoch just finished, the history, the best validation result so far, the
+    device-side random streams (centre sampler, in-kernel dropout) and torch's CPU and device generator states.  Written to a
+    temporary file and moved into place, so an interrupted write leaves the previous checkpoint."""
+    from . import sampling
+    device = opt.flat_p.device if device is None else device
+    ck = {"version": 1, "model": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "optimizer": _to_cpu(opt.state_dict()),
+          "epoch": int(epoch), "hist": copy.deepcopy(hist), "best": (best[0], _to_cpu(best[1]), best[2]),
+          "streams": sampling.snapshot_values(), "rng": {"cpu": torch.get_rng_state(), "device": torch.cuda.get_rng_state(device)}}
+    tmp = f"{path}.tmp"
+    torch.save(ck, tmp)
+    os.replace(tmp, path)
+
+
+def load_checkpoint(path, model, opt: optim.FlatAdam, device=None) -> dict:
+    """Puts save_checkpoint's file back into `model` and `opt` (built as for the run that wrote it) and into the random streams;
+    -> the checkpoint, for its "epoch", "hist" and "best" = (best_val, best_state, best_epoch)."""
+    from . import sampling
+    device = opt.flat_p.device if device is None else device
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    if not isinstance(ck, dict) or ck.get("version") != 1 or any(k not in ck for k in ("model", "optimizer", "epoch", "hist", "best")):
+        raise ValueError(f"{path}: not a checkpoint of this trainer")
+    model.load_state_dict(ck["model"])       # copies into the parameters in place: they stay views of the optimiser's flat buffer
+    opt.load_state_dict(ck["optimizer"])
+    sampling.restore_values(ck["streams"])
+    torch.set_rng_state(ck["rng"]["cpu"])
+    torch.cuda.set_rng_state(ck["rng"]["device"], device)
+    best_val, best_state, best_ep = ck["best"]
+    if best_state is not None:
+        best_state = {k: v.to(device) if torch.is_tensor(v) else v for k, v in best_state.items()}
+    ck["best"] = (best_val, best_state, best_ep)
+    return ck
+
+
+def _to_cpu(x):
+    if torch.is_tensor(x):
+        return x.detach().cpu()
+    if isinstance(x, dict):
+        return type(x)((k, _to_cpu(v)) for k, v in x.items())
+    return x
 
 
 def _eval_batch(model, loss_fn: LossFn, batch, device, timer: Optional[PhaseTimer] = None) -> torch.Tensor:
@@ -352,6 +420,36 @@ def _common_steps(loader, device):
     n = torch.tensor([len(loader)], dtype=torch.int64, device=device)
     tdist.all_reduce(n, op=tdist.ReduceOp.MIN)
     return int(n.item())
+
+
+def add_optim_args(ap) -> None:
+    """The optimiser options of the training scripts, each with its PNPP_* environment twin as default; all off unless given."""
+    env = os.environ.get
+    ap.add_argument("--weight-decay", type=float, default=float(env("PNPP_WEIGHT_DECAY", 0.0)),
+                    help="decoupled (AdamW) weight decay of conv / linear weights; biases and norm weights are left alone")
+    ap.add_argument("--lr-schedule", default=env("PNPP_LR_SCHEDULE", "constant"), choices=["constant", "cosine", "step"],
+                    help="after the warm-up: constant, cosine to zero over the run, or x --lr-gamma every --lr-step-every updates")
+    ap.add_argument("--warmup", type=int, default=int(env("PNPP_WARMUP", 0)), help="updates of linear warm-up from a third of the rate")
+    ap.add_argument("--lr-step-every", type=int, default=int(env("PNPP_LR_STEP_EVERY", 1000)))
+    ap.add_argument("--lr-gamma", type=float, default=float(env("PNPP_LR_GAMMA", 0.5)))
+    ap.add_argument("--ema", type=float, default=float(env("PNPP_EMA", 0.0)),
+                    help="decay of an exponential moving average of the weights, used for validation and the best checkpoint (0: none)")
+
+
+def optim_kwargs(args) -> dict:
+    """add_optim_args's options as fit()'s keyword arguments ({} when all are off: fit then launches what it always did)."""
+    kw = {}
+    if args.weight_decay:
+        kw["weight_decay"] = args.weight_decay
+    if args.lr_schedule == "cosine":
+        kw["schedule"] = optim.Schedule.cosine(warmup=args.warmup)
+    elif args.lr_schedule == "step":
+        kw["schedule"] = optim.Schedule.step(args.lr_step_every, args.lr_gamma, warmup=args.warmup)
+    elif args.warmup:
+        kw["schedule"] = optim.Schedule.constant(warmup=args.warmup)
+    if args.ema:
+        kw["ema_decay"] = args.ema
+    return kw
 
 
 def env_path(name: str, default: str):

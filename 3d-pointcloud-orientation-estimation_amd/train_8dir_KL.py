@@ -90,6 +90,7 @@ def _parser():
     ap.add_argument("--sampler", default=os.environ.get("PNPP_SAMPLER", "randperm"), choices=["randperm", "device", "fps"])
     ap.add_argument("--augment", action="store_true",
                     help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
+    trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
     return ap
 
 
@@ -107,7 +108,7 @@ def main(argv=None):
     labels, loaders = _synthetic_loaders(args.synthetic, rank, args.augment) if args.synthetic else _dataset_loaders(rank, world)
     model = PointNetPP8Dir(sampler=args.sampler).to(dev)
     hist, best_state, best_ep = trainer.fit(model, _loss, loaders, EPOCHS, LR, dev, label="8-dir soft CE", label_index=2,
-                                            n_labels=len(labels))
+                                            n_labels=len(labels), **trainer.optim_kwargs(args))
     model.load_state_dict(best_state)
     overall, per_label = trainer.evaluate(model, _loss, loaders["test"], dev, label_index=2, n_labels=len(labels))
     if rank == 0:

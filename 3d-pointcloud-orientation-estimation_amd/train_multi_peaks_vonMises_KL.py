@@ -179,6 +179,7 @@ def _parser():
     ap.add_argument("--sampler", default=os.environ.get("PNPP_SAMPLER", "randperm"), choices=["randperm", "device", "fps"])
     ap.add_argument("--augment", action="store_true",
                     help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
+    trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
     return ap
 
 
@@ -195,7 +196,7 @@ def main(argv=None):
                                                    None if args.synthetic else dev, counts=1)
     model = PointNetPPMvM(sampler=args.sampler).to(dev)
     h, best_state, best_ep = trainer.fit(model, _loss, loaders, EPOCHS, LR, dev, clip_norm=1.0, label="multi-peak vM KL",
-                                         label_index=3, n_labels=len(categories))
+                                         label_index=3, n_labels=len(categories), **trainer.optim_kwargs(args))
     hist = {"total": {"train": h["train"], "val": h["val"]}}
     for i, cat in enumerate(categories):
         hist[cat] = h["labels"][i]

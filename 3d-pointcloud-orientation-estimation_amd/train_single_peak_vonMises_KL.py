@@ -99,6 +99,7 @@ def _parser():
     ap.add_argument("--sampler", default=os.environ.get("PNPP_SAMPLER", "randperm"), choices=["randperm", "device", "fps"])
     ap.add_argument("--augment", action="store_true",
                     help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
+    trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
     return ap
 
 
@@ -113,7 +114,7 @@ def main(argv=None):
     if args.augment:   # vm_gt rows are [mu, kappa]: mu follows the cloud; a host DataLoader's batch goes to the device first
         loaders["train"] = trainer.AugmentedLoader(loaders["train"], Augment(SEED + rank), ("vm",), None if args.synthetic else dev)
     model = PointNetPPVonMises(sampler=args.sampler).to(dev)
-    hist, best_state, _ = trainer.fit(model, _loss, loaders, EPOCHS, LR, dev, label="von Mises KL")
+    hist, best_state, _ = trainer.fit(model, _loss, loaders, EPOCHS, LR, dev, label="von Mises KL", **trainer.optim_kwargs(args))
     if rank == 0:
         torch.save(best_state, RES / "vonMises_best.pth")
         try:

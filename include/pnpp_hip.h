@@ -887,6 +887,39 @@ int pnpp_adam_step_dev_clip(float *param, float *grad, float *exp_avg, float *ex
 int pnpp_sumsq(const float *x, size_t n, double *out, void *scratch, size_t scratch_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The scheduled optimiser (csrc/optim_sched_kernels.hip, csrc/lr_schedule.h): the update above with parameter groups,
+ * weight decay, a learning-rate schedule evaluated on the device and an exponential moving average of the weights, still
+ * one launch.  The step count lives in device memory, so a captured launch applies its own rate at every replay.
+ * ---------------------------------------------------------------------------------------- */
+#define PNPP_OPTIM_MAX_GROUPS 8
+enum { PNPP_SCHED_CONSTANT = 0, PNPP_SCHED_COSINE = 1, PNPP_SCHED_STEP = 2 };
+typedef struct {
+    int n_groups;                                   /* 1 .. PNPP_OPTIM_MAX_GROUPS */
+    int decoupled;                                  /* 1: AdamW, p *= 1 - lr_g wd_g; 0: L2 as torch.optim.Adam, g += wd_g p */
+    uint64_t end[PNPP_OPTIM_MAX_GROUPS];            /* exclusive end of each group in the flat buffers: strictly increasing,
+                                                       end[n_groups - 1] == n.  An element's group is the number of ends <= its index */
+    float lr_mult[PNPP_OPTIM_MAX_GROUPS], weight_decay[PNPP_OPTIM_MAX_GROUPS];
+    int sched_kind;                                 /* PNPP_SCHED_*: what follows the (optional) linear warm-up */
+    uint64_t warmup, total, every;                  /* updates of warm-up; cosine: where it ends; step: updates per decay */
+    double start_factor, min_factor, gamma;         /* warm-up starts at start_factor; cosine ends at / step is floored at min_factor */
+    float lr, beta1, beta2, eps, grad_scale;
+    float max_norm;                                 /* 0: no clipping; else grad_sumsq (pnpp_sumsq's word) is read as in pnpp_adam_step_clip */
+    float ema_decay;                                /* 0: no average; else ema = ema_decay ema + (1 - ema_decay) param after the update */
+    int zero_grad;                                  /* != 0: clear each gradient once consumed */
+} pnpp_optim_desc;
+/* One update.  step_state: four words in device memory -- [0] updates taken so far and [1] the ticket, exactly pnpp_adam_step_dev's two
+ * (the two entries may alternate on one state); [2] receives the bits of the float64 rate lr * f the update used (f: the schedule's
+ * factor at step_state[0], see pnpp_lr_factor); [3] is reserved and left alone.  With lr_g = lr f lr_mult[g] an element of group g sees
+ * Adam's update with step size lr_g / (1 - beta1^t), after p *= 1 - lr_g weight_decay[g] (decoupled) or with weight_decay[g] p added to
+ * its scaled, clipped gradient (L2).  With one group, lr_mult 1, weight_decay 0, a constant schedule without warm-up and no average the
+ * results equal pnpp_adam_step_dev's (pnpp_adam_step_dev_clip's) bit for bit.  ema is null exactly when ema_decay is 0. */
+int pnpp_adamw_step(const pnpp_optim_desc *d, float *param, float *grad, float *exp_avg, float *exp_avg_sq, float *ema, size_t n,
+                    uint64_t *step_state, const double *grad_sumsq, void *stream);
+/* The schedule's factor after steps_taken updates, by the function the kernel evaluates: host arithmetic only, needs no GPU.  Only the
+ * schedule fields of the descriptor are read (sched_kind .. gamma). */
+int pnpp_lr_factor(const pnpp_optim_desc *d, uint64_t steps_taken, double *factor);
+
+/* ------------------------------------------------------------------------------------------
  * Training-time augmentation of a device-resident batch: a fresh yaw about +Y per cloud (optionally a scale and a
  * clipped Gaussian jitter per point) with the orientation targets moved along, in one launch.
  * The reference rotates its training sets offline (data_process/rotate_without_normals.py:5-15,112 and the GT writers);

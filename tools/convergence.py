@@ -15,6 +15,11 @@ the reference's own code does on the same inputs.
 
     python tools/convergence.py [--clouds 8192] [--epochs 40] > profiles/<round>_convergence.json
     python tools/convergence.py --augment > profiles/augment_convergence.json
+    python tools/convergence.py --schedule > profiles/optim_convergence.json
+
+--schedule trains the single-peak model twice from the same initial state: as above, and with trainer.fit's optimiser options (linear
+warm-up then cosine, decoupled weight decay on conv / linear weights only, averaged weights).  Both runs report the validation curve, its
+swing over the last ten epochs, and the angular error on a third split (wedge_clouds(1024, N, 3)) that no checkpoint selection has seen.
 
 --augment trains the single-peak model twice from the same initial state, on the same clouds: as above, and with the training loader
 wrapped in trainer.AugmentedLoader (pnpp_hip.augment.Augment: a fresh yaw per cloud and draw, mu moved along); held-out clouds untouched.
@@ -58,6 +63,8 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"], help="bf16: the opt-in bf16-operand MFMA mode")
     ap.add_argument("--augment", action="store_true", help="single-peak model only: without and with device-side yaw augmentation")
+    ap.add_argument("--schedule", action="store_true",
+                    help="single-peak model only: constant-rate Adam, then warm-up + cosine, decoupled weight decay and averaged weights")
     args = ap.parse_args()
     from models.pointnet_pp_8dir import DIRS_8, PointNetPP8Dir
     from models.pointnet_pp_vonMises import PointNetPPVonMises
@@ -71,8 +78,9 @@ def main():
                        f"{args.epochs} epochs, Adam lr 1e-3, device-side centre sampling, hipGraph step, matmul precision {args.precision}",
            "runs": {}}
 
-    def single_peak(augment):
-        """train_single_peak_vonMises_KL.py's loss; augment: the training loader's batches in a fresh pose every draw"""
+    def single_peak(augment, fit_kw=None, unseen=None):
+        """train_single_peak_vonMises_KL.py's loss; augment: the training loader's batches in a fresh pose every draw; fit_kw: the
+        optimiser options of trainer.fit; unseen: (xyz, mu) of a split no checkpoint selection has looked at"""
         torch.manual_seed(42)
         sampling.reset(0)
         model = PointNetPPVonMises(sampler="device").to(dev)
@@ -83,22 +91,34 @@ def main():
             from pnpp_hip.augment import Augment
             loaders["train"] = trainer.AugmentedLoader(loaders["train"], Augment(seed=42), ("vm",))
         loss = lambda m, b: ops.vm_head_kl_loss(m.features(b[0]), b[1][:, 0].contiguous(), b[1][:, 1].contiguous(), reduction="none")
-        hist, best, best_ep = trainer.fit(model, loss, loaders, args.epochs, 1e-3, dev, label="von Mises KL", log=lambda *_: None)
+        hist, best, best_ep = trainer.fit(model, loss, loaders, args.epochs, 1e-3, dev, label="von Mises KL", log=lambda *_: None,
+                                          **(fit_kw or {}))
         model.eval()
 
-        def held_out():
+        def held_out(xyz=xyz_va, mu_true=mu_va):
             errs, kaps = [], []
             with torch.no_grad():
                 for i in range(0, 1024, args.batch):
-                    mu, kappa = model(xyz_va[i:i + args.batch].to(dev))
-                    errs.append(ang_err_deg(mu.cpu(), mu_va[i:i + args.batch]))
+                    mu, kappa = model(xyz[i:i + args.batch].to(dev))
+                    errs.append(ang_err_deg(mu.cpu(), mu_true[i:i + args.batch]))
                     kaps.append(kappa.cpu())
             return torch.cat(errs), torch.cat(kaps)
 
+        def summary(e):
+            return {"mean": round(float(e.mean()), 2), "median": round(float(e.median()), 2),
+                    "p90": round(float(e.kthvalue(int(0.9 * len(e))).values), 2)}
+
         e, k = held_out()                 # the LAST epoch's model (its validation KL swings from epoch to epoch at this learning rate)
+        eu = held_out(*unseen)[0] if unseen is not None else None
         model.load_state_dict(best)       # the checkpoint of the best validation epoch (trainer.fit keeps a copy)
         eb, kb = held_out()
+        extra = {}
+        if unseen is not None:            # a third split: neither trained on nor used to pick the checkpoint
+            last10 = hist["val"][-10:]
+            extra = {"lr": hist["lr"], "averaged_weights": hist["ema"], "val_kl_swing_last_10_epochs": round(max(last10) - min(last10), 4),
+                     "unseen_split_angular_error_deg": {"last_epoch": summary(eu), "best_checkpoint": summary(held_out(*unseen)[0])}}
         return {
+            **extra,
             "train_kl": [round(v, 4) for v in hist["train"]], "val_kl": [round(v, 4) for v in hist["val"]], "best_val_epoch": best_ep,
             "steps": hist["steps"], "train_seconds_per_epoch": round(sum(hist["seconds"]["train"]) / args.epochs, 3),
             "held_out_angular_error_deg": {"mean": round(float(e.mean()), 2), "median": round(float(e.median()), 2),
@@ -108,6 +128,17 @@ def main():
                                                                "p90": round(float(eb.kthvalue(int(0.9 * len(eb))).values), 2)},
                                 "held_out_mean_kappa": round(float(kb.mean()), 2)}}
 
+    if args.schedule:
+        from pnpp_hip import optim
+        unseen = wedge_clouds(1024, args.points, 3)[:2]
+        out["workload"] += "; second run: AdamW weight decay 1e-2 on conv / linear weights, 5 % linear warm-up then cosine to 0.01 x, " \
+                           "averaged weights (decay 0.999) for validation and the checkpoint; angular error also on a third, unseen split"
+        out["runs"]["single_peak_vonMises_KL"] = single_peak(False, None, unseen)
+        steps = args.epochs * ((args.clouds + args.batch - 1) // args.batch)
+        kw = dict(weight_decay=1e-2, schedule=optim.Schedule.cosine(warmup=steps // 20, start_factor=0.1, min_factor=0.01), ema_decay=0.999)
+        out["runs"]["single_peak_vonMises_KL_scheduled"] = single_peak(False, kw, unseen)
+        print(json.dumps(out))
+        return
     out["runs"]["single_peak_vonMises_KL"] = single_peak(False)
     if args.augment:
         out["runs"]["single_peak_vonMises_KL_augmented"] = single_peak(True)
