@@ -176,8 +176,14 @@ def test_bare_level_with_three_feature_channels(training):
 
 
 # ------------------------------------------------------------------------------------------------ (c) pnpp_sa_infer at the new sizes
-def _sa_infer(level, xyz, pts, centre, nbr, K, group_all):
-    """fold + one pnpp_sa_infer launch on a level's own tensors -> (new_xyz, out)"""
+GUARD_FILL = -12345.678
+
+
+def _sa_infer(level, xyz, pts, centre, nbr, K, group_all, guard=0, idx_out=None):
+    """fold + one pnpp_sa_infer launch on a level's own tensors -> (new_xyz, out), both pre-filled with NaN.
+    guard: that many more groups, filled with GUARD_FILL, lie behind the real ones in both buffers and are returned as a third
+    element (guard rows of new_xyz, guard rows of out).  nbr None with idx_out (B, S, K) int32: the level searches its own
+    neighbours and writes them there."""
     from pnpp_hip import _lib as L, ops
     lib = L.lib()
     B, N, _ = xyz.shape
@@ -198,13 +204,15 @@ def _sa_infer(level, xyz, pts, centre, nbr, K, group_all):
     ia = L.SaInferArgs()
     ia.xyz, ia.points, ia.weights = xyz.data_ptr(), ops._p(pts), blob.data_ptr()
     if not group_all:
-        ia.centre_idx, ia.neighbour_idx = centre.data_ptr(), nbr.data_ptr()
-    new_xyz = torch.full((B, S, 3), float("nan"), device="cuda")
-    out = torch.full((B, S, ch[-1]), float("nan"), device="cuda")
+        ia.centre_idx, ia.neighbour_idx, ia.idx_out = centre.data_ptr(), ops._p(nbr), ops._p(idx_out)
+    new_xyz = torch.full((B * S + guard, 3), float("nan"), device="cuda")
+    out = torch.full((B * S + guard, ch[-1]), float("nan"), device="cuda")
+    new_xyz[B * S:], out[B * S:] = GUARD_FILL, GUARD_FILL
     ia.new_xyz, ia.out = new_xyz.data_ptr(), out.data_ptr()
     L.check(lib.pnpp_sa_infer(C.byref(d), C.byref(ia), ops._stream()))
     torch.cuda.synchronize()
-    return new_xyz, out
+    res = new_xyz[:B * S].view(B, S, 3), out[:B * S].view(B, S, ch[-1])
+    return res + ((new_xyz[B * S:], out[B * S:]),) if guard else res
 
 
 WIDE = {

@@ -114,6 +114,99 @@ def test_refused_descriptors_name_the_reason(lib):
     assert lib.pnpp_sa_infer_weights_bytes(ctypes.byref(d)) == 0
 
 
+# ---- the plan's edges (the shapes tests/test_gpu_sa_infer_bands.py launches, and one step beyond them) ----------------------------------
+def _band_desc(c, **over):
+    kw = dict(B=c["B"], N=c["N"], S=c["S"], K=c["K"], D=c["D"], channels=c["ch"], group_all=c.get("group_all", False))
+    kw.update(over)
+    return _desc(**kw)
+
+
+def _layout(lib, d):
+    """[(w_offset, w_ld, b_offset)] of the three layers"""
+    out = []
+    for l in range(3):
+        woff, ld, boff = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_size_t()
+        assert lib.pnpp_sa_infer_weights_layout(ctypes.byref(d), l, ctypes.byref(woff), ctypes.byref(ld), ctypes.byref(boff)) == 0
+        out.append((woff.value, ld.value, boff.value))
+    return out
+
+
+def _up(x, a):
+    return (x + a - 1) // a * a
+
+
+def _blob_by_hand(D, ch):
+    """per layer three bf16 planes of C_l x ld_l, then C_l floats, every piece on a 256-byte boundary -> ([(woff, ld, boff)], bytes)"""
+    off, out = 0, []
+    for l in range(3):
+        ld = _up(D + 3, 16) if l == 0 else ch[l - 1]
+        woff = off
+        boff = _up(woff + ch[l] * ld * 3 * 2, 256)
+        off = _up(boff + ch[l] * 4, 256)
+        out.append((woff, ld, boff))
+    return out, off
+
+
+def test_every_band_case_is_taken_and_its_lds_is_what_the_table_says(lib):
+    from sa_infer_bands_cases import CASES, plan_lds
+    for name, c in CASES.items():
+        d = _band_desc(c)
+        assert lib.pnpp_sa_infer_supported(ctypes.byref(d)) == 1, (name, lib.pnpp_last_error())
+        assert plan_lds(c) <= 160 * 1024, name
+        if "lds" in c:
+            assert plan_lds(c) == c["lds"], name
+        if c["tm"] == 64:   # TM = 64 only where 64 rows fit 80 KiB, on more than 32 rows of neighbourhoods of at most 32
+            assert plan_lds(c) <= 80 * 1024 and c["B"] * c["S"] * c["K"] > 32 and c["K"] <= 32, name
+        else:
+            assert 2 * plan_lds(c) > 80 * 1024 or c["B"] * c["S"] * c["K"] <= 32 or c["K"] > 32, name
+        want, nbytes = _blob_by_hand(c["D"], c["ch"])
+        assert _layout(lib, d) == want and lib.pnpp_sa_infer_weights_bytes(ctypes.byref(d)) == nbytes, name
+
+
+@pytest.mark.parametrize("D,channels,need", [(0, [544, 320, 320], 168960), (798, [32, 64, 128], 165888)], ids=["C1-320", "D798"])
+def test_one_step_past_the_largest_tile_is_refused_for_lds(lib, D, channels, need):
+    for K in (32, 64):   # the narrow kernel's 32-row tile and the wide kernel's
+        d = _desc(B=2, N=100, S=3, K=K, D=D, channels=channels)
+        assert lib.pnpp_sa_infer_supported(ctypes.byref(d)) == 0
+        err = lib.pnpp_last_error()
+        assert b"LDS" in err and str(need).encode() in err, err
+        assert lib.pnpp_sa_infer_weights_bytes(ctypes.byref(d)) == 0
+        woff, ld, boff = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_size_t()
+        assert lib.pnpp_sa_infer_weights_layout(ctypes.byref(d), 0, ctypes.byref(woff), ctypes.byref(ld), ctypes.byref(boff)) != 0
+
+
+@pytest.mark.parametrize("K", [48, 288])
+def test_k_between_and_beyond_the_tiles_is_refused(lib, K):
+    d = _desc(B=2, N=300, S=3, K=K, D=0, channels=[64, 64, 128])
+    assert lib.pnpp_sa_infer_supported(ctypes.byref(d)) == 0
+    assert b"K=%d" % K in lib.pnpp_last_error()
+    assert lib.pnpp_sa_infer_weights_bytes(ctypes.byref(d)) == 0
+    d = _desc(B=2, N=K, S=1, K=K, D=0, channels=[64, 64, 128], group_all=True)
+    assert lib.pnpp_sa_infer_supported(ctypes.byref(d)) == 0
+    assert b"K=%d" % K in lib.pnpp_last_error()
+
+
+@pytest.mark.parametrize("channels", [[96, 96, 160], [544, 288, 320], [128, 160, 288], [32, 32, 32]], ids=lambda c: "-".join(map(str, c)))
+def test_blob_layout_at_odd_widths_and_d14(lib, channels):
+    D = 14
+    d = _desc(B=2, N=100, S=5, K=32, D=D, channels=channels)
+    lay, nbytes = _layout(lib, d), lib.pnpp_sa_infer_weights_bytes(ctypes.byref(d))
+    assert lay[0][1] == 32 == _up(D + 3, 16)
+    assert [ld for _, ld, _ in lay[1:]] == channels[:2]
+    assert all(woff % 256 == 0 and boff % 256 == 0 for woff, _, boff in lay)
+    pieces = [_up(c * ld * 3 * 2, 256) + _up(c * 4, 256) for c, (_, ld, _) in zip(channels, lay)]
+    assert nbytes == sum(pieces)
+    assert [woff for woff, _, _ in lay] == [0, pieces[0], pieces[0] + pieces[1]]
+    assert [boff - woff for woff, _, boff in lay] == [_up(c * ld * 3 * 2, 256) for c, (_, ld, _) in zip(channels, lay)]
+    # the blob belongs to the weights: B, N, S and K do not enter (K = 64 .. 256 are the wide kernel's, K = 16 the narrow one's)
+    for B, N, S, K in ((1, 40, 1, 32), (7, 333, 33, 16), (2, 300, 3, 64), (5, 300, 2, 256)):
+        d2 = _desc(B=B, N=N, S=S, K=K, D=D, channels=channels)
+        assert lib.pnpp_sa_infer_supported(ctypes.byref(d2)) == 1, lib.pnpp_last_error()
+        assert _layout(lib, d2) == lay and lib.pnpp_sa_infer_weights_bytes(ctypes.byref(d2)) == nbytes
+    dg = _desc(B=3, N=224, S=1, K=224, D=D, channels=channels, group_all=True)
+    assert _layout(lib, dg) == lay and lib.pnpp_sa_infer_weights_bytes(ctypes.byref(dg)) == nbytes
+
+
 def test_predictor_has_no_cpu_fallback():
     import pnpp_hip
     from pnpp_hip.inference import Predictor
