@@ -7,8 +7,9 @@
     dist    one-process-per-GPU data parallelism (RCCL all-reduce of one flat gradient buffer)
     inference  Predictor: forward-only evaluation, one fused launch per set-abstraction level
     augment Augment: a fresh yaw per cloud and draw on the device, orientation targets moved along
+    decode  decode / AngularErrors: von-Mises parameters to orientations, orientations to angular-error statistics, on the device
 """
-__all__ = ["ops", "build", "optim", "dist", "sampling", "inference", "augment", "Predictor"]
+__all__ = ["ops", "build", "optim", "dist", "sampling", "inference", "augment", "decode", "Predictor"]
 
 
 def __getattr__(name):

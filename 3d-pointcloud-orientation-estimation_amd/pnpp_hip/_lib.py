@@ -125,6 +125,7 @@ class AugmentDesc(C.Structure):
 
 
 PNPP_OPTIM_MAX_GROUPS = 8
+ORIENT_BINS, ORIENT_STRIDE, ORIENT_MAX_LABELS = 360, 728, 64   # pnpp_orient_eval's accumulator (include/pnpp_hip.h)
 SCHED_CONSTANT, SCHED_COSINE, SCHED_STEP = range(3)
 
 
@@ -234,6 +235,8 @@ SIGNATURES = {
     "pnpp_mvm_head": (_i, [_fp, _fp, _fp, _i, _i, _f, _f, _fp, _fp, _fp, _fp]),
     "pnpp_mvm_head_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _f, _f, _fp, _fp, _fp, _fp]),
     "pnpp_soft_ce": (_i, [_fp, _fp, _i, _i, _fp, _fp, _fp]),
+    "pnpp_mvm_decode": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _f, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "pnpp_orient_eval": (_i, [_fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _i, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp]),
     "pnpp_log_softmax": (_i, [_fp, _i, _i, _fp, _fp]),
     "pnpp_log_softmax_bwd": (_i, [_fp, _fp, _i, _i, _fp, _fp]),
     "pnpp_linear_log_softmax": (_i, [_fp, _fp, _fp, _i, _i, _i, _fp, _fp]),

@@ -46,6 +46,7 @@ SOURCES = {
     "step_tail_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
     "optim_kernels.hip": [],
     "cls_loss_kernels.hip": [],
+    "decode_kernels.hip": [],
     "runtime.hip": [],
     "sa_api.hip": [],
     "sa_infer_kernels.hip": [],

@@ -137,6 +137,20 @@ class Predictor:
         self.plan: Dict[str, str] = {}
         self.last_plan: Dict[str, str] = {}   # what the latest call ran (a call's sizes can refuse what was planned "fused")
 
+    @torch.no_grad()
+    def orientation(self, *args, num: int = 360, rel_height: float = 0.1, density: bool = False, **kwargs):
+        """self(*args, **kwargs) decoded on the device: the von-Mises parameters of a PointNetPPVonMises (one peak) or the mixture of
+        a PointNetPPMvM -> pnpp_hip.decode.Orientation(angle, modes, heights, n_modes, density), one more launch and no read-back."""
+        from models.pointnet_pp_mvM import PointNetPPMvM
+        from models.pointnet_pp_vonMises import PointNetPPVonMises
+        from . import decode
+        if not isinstance(self.model, (PointNetPPVonMises, PointNetPPMvM)):
+            raise TypeError(f"Predictor.orientation decodes the von-Mises outputs of a PointNetPPVonMises or a PointNetPPMvM, "
+                            f"not those of a {type(self.model).__name__}")
+        out = self(*args, **kwargs)
+        with torch.cuda.device(self.device):
+            return decode.decode(*out, num=num, rel_height=rel_height, density=density)
+
     def _plan_head(self, name: str, fc, bn) -> None:
         if _tracked(bn) and isinstance(fc, nn.Linear) and fc.bias is not None:
             self._heads[name] = _Folded(fc.weight.shape[0], fc.weight.shape[1], self.device)

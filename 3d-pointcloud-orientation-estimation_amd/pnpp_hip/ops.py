@@ -1113,6 +1113,76 @@ def mvm_head(pi_raw, mu_raw, kappa_raw, temp: float, kappa_max: Optional[float])
     return _MvmHead.apply(pi_raw, mu_raw, kappa_raw, temp, float("inf") if kappa_max is None else kappa_max)
 
 
+def _rows(t: torch.Tensor, name: str, shape) -> torch.Tensor:
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+@torch.no_grad()
+def mvm_decode(mu, kappa, weight=None, counts=None, num: int = 360, rel_height: float = 0.1, density: bool = False):
+    """pnpp_mvm_decode: mixture parameters (B,K) -> (modes (B,K), heights (B,K), n_modes (B,) int32, angle (B,), density (B,num-1) or
+    None); one launch, no host round trip.  mu, kappa (B,): the single-peak model, K = 1 and weight 1."""
+    mu, kappa = _f32(mu, "mu"), _f32(kappa, "kappa")
+    if mu.dim() == 1:
+        mu, kappa = mu[:, None], _rows(kappa, "kappa", mu.shape)[:, None]
+    if mu.dim() != 2:
+        raise ValueError(f"mu has shape {tuple(mu.shape)}, expected (B, K) or (B,)")
+    B, K = mu.shape
+    _rows(kappa, "kappa", (B, K))
+    weight = None if weight is None else _rows(_f32(weight, "weight"), "weight", (B, K))
+    counts = None if counts is None else _rows(_i32(counts, "counts"), "counts", (B,))
+    dev = mu.device
+    modes, heights = torch.empty(B, K, device=dev), torch.empty(B, K, device=dev)
+    n_modes, angle = torch.empty(B, device=dev, dtype=torch.int32), torch.empty(B, device=dev)
+    dens = torch.empty(B, max(int(num) - 1, 0), device=dev) if density else None
+    L.check(L.lib().pnpp_mvm_decode(mu.data_ptr(), kappa.data_ptr(), _p(weight), _p(counts), B, K, int(num), float(rel_height),
+                                    modes.data_ptr(), heights.data_ptr(), n_modes.data_ptr(), angle.data_ptr(), _p(dens), _stream()))
+    return modes, heights, n_modes, angle, dens
+
+
+@torch.no_grad()
+def orient_eval(modes, n_modes, angle, mu_gt=None, kappa_gt=None, vm_gt=None, K_gt=None, labels=None, n_labels: int = 1, acc=None,
+                sample_err=None, per_sample: bool = True):
+    """pnpp_orient_eval: angular errors of decoded orientations against (mu_gt, kappa_gt) (B,) or (vm_gt (B,Kmax,3), K_gt (B,)).
+    acc: the int64 accumulator of n_labels * ORIENT_STRIDE + 1 words to add to; sample_err (capacity, 2): the per-sample rows.
+    per_sample: also return (top1, cover, count_ok) of this batch (else None)."""
+    modes = _f32(modes, "modes")
+    if modes.dim() != 2:
+        raise ValueError(f"modes has shape {tuple(modes.shape)}, expected (B, K)")
+    B, K = modes.shape
+    n_modes, angle = _rows(_i32(n_modes, "n_modes"), "n_modes", (B,)), _rows(_f32(angle, "angle"), "angle", (B,))
+    Kmax = 0
+    if vm_gt is not None:
+        vm_gt = _f32(vm_gt, "vm_gt")
+        if vm_gt.dim() != 3 or vm_gt.size(0) != B or vm_gt.size(2) != 3:
+            raise ValueError(f"vm_gt has shape {tuple(vm_gt.shape)}, expected ({B}, Kmax, 3)")
+        Kmax = vm_gt.size(1)
+    K_gt = None if K_gt is None else _rows(_i32(K_gt, "K_gt"), "K_gt", (B,))
+    mu_gt = None if mu_gt is None else _rows(_f32(mu_gt, "mu_gt"), "mu_gt", (B,))
+    kappa_gt = None if kappa_gt is None else _rows(_f32(kappa_gt, "kappa_gt"), "kappa_gt", (B,))
+    labels = None if labels is None else _rows(_i32(labels, "labels"), "labels", (B,))
+    if acc is not None:
+        _need_gpu(acc, "acc")
+        if acc.dtype != torch.int64 or not acc.is_contiguous() or acc.numel() != int(n_labels) * L.ORIENT_STRIDE + 1:
+            raise ValueError(f"acc must be a contiguous int64 tensor of n_labels * {L.ORIENT_STRIDE} + 1 = "
+                             f"{int(n_labels) * L.ORIENT_STRIDE + 1} words, got {acc.dtype} x {acc.numel()}")
+    cap = 0
+    if sample_err is not None:
+        _need_gpu(sample_err, "sample_err")
+        if sample_err.dtype != torch.float32 or not sample_err.is_contiguous() or sample_err.dim() != 2 or sample_err.size(1) != 2:
+            raise ValueError(f"sample_err must be a contiguous float32 tensor of shape (capacity, 2), got {tuple(sample_err.shape)}")
+        cap = sample_err.size(0)
+    dev = modes.device
+    top1 = torch.empty(B, device=dev) if per_sample else None
+    cover = torch.empty(B, device=dev) if per_sample else None
+    ok = torch.empty(B, device=dev, dtype=torch.int32) if per_sample else None
+    L.check(L.lib().pnpp_orient_eval(modes.data_ptr(), n_modes.data_ptr(), angle.data_ptr(), B, K, _p(mu_gt), _p(kappa_gt), _p(vm_gt),
+                                     _p(K_gt), Kmax, _p(labels), int(n_labels), _p(acc), _p(sample_err), cap, _p(top1), _p(cover),
+                                     _p(ok), _stream()))
+    return top1, cover, ok
+
+
 class _SoftCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, p):

@@ -401,12 +401,31 @@ def _eval_batch(model, loss_fn: LossFn, batch, device, timer: Optional[PhaseTime
     return lv.detach()
 
 
-def evaluate(model, loss_fn: LossFn, loader, device, label_index: Optional[int] = None, n_labels: int = 0):
-    """Mean per-sample loss over `loader` (every rank's samples); with n_labels > 0 returns (mean, per-label means)."""
+def _eval_batch_metrics(model, loss_fn: LossFn, batch, device, metrics, label_index: Optional[int]) -> torch.Tensor:
+    """_eval_batch with the model's outputs also decoded into `metrics` (pnpp_hip.decode.AngularErrors): two more launches."""
+    fwd, crit, _ = _split(loss_fn)
+    if fwd is None:
+        raise ValueError("evaluate(metrics=) needs loss_fn as the (forward, criterion) pair: the metrics decode the forward's outputs")
+    batch = tuple(b.to(device, non_blocking=True) if torch.is_tensor(b) else b for b in batch)
+    with torch.no_grad():
+        out = fwd(model, batch)
+        lv = crit(out, batch)
+        metrics.update_outputs(out, batch, None if label_index is None else batch[label_index])
+    return lv.detach()
+
+
+def evaluate(model, loss_fn: LossFn, loader, device, label_index: Optional[int] = None, n_labels: int = 0, metrics=None):
+    """Mean per-sample loss over `loader` (every rank's samples); with n_labels > 0 returns (mean, per-label means).
+    metrics: an AngularErrors that every batch's decoded outputs are added to on the device (its summary() is the caller's to
+    take); the return value is the same with and without it."""
     model.eval()
     plog = _PhaseLog(n_labels)
     for batch in loader:
-        plog.add(_eval_batch(model, loss_fn, batch, device), batch[label_index] if label_index is not None else None)
+        if metrics is not None:
+            lv = _eval_batch_metrics(model, loss_fn, batch, device, metrics, label_index)
+        else:
+            lv = _eval_batch(model, loss_fn, batch, device)
+        plog.add(lv, batch[label_index] if label_index is not None else None)
     total, per = plog.reduce(device)
     return (total, per) if n_labels else total
 
@@ -450,6 +469,36 @@ def optim_kwargs(args) -> dict:
     if args.ema:
         kw["ema_decay"] = args.ema
     return kw
+
+
+def add_metrics_args(ap) -> None:
+    """--angular-metrics (PNPP_ANGULAR_METRICS=1): decode the test split's predictions on the device and report angular errors."""
+    ap.add_argument("--angular-metrics", action="store_true", default=os.environ.get("PNPP_ANGULAR_METRICS", "0") not in ("", "0"),
+                    help="after the run: angular errors of the test split (pnpp_hip.decode), printed and written to "
+                         "angular_errors.json beside the results; every other output file is unchanged")
+
+
+def report_angular_errors(path, summary: dict, names: Optional[Sequence[str]] = None) -> None:
+    """Prints an AngularErrors.summary() (overall line, then one per named label) and writes it as JSON to `path`."""
+    import json
+
+    def line(tag, e):
+        t, c = e["top1"], e["cover"]
+        if not e["n"]:
+            return f"  {tag}: no sample with an error ({e['excluded']} excluded)"
+        return (f"  {tag}: n {e['n']} (+{e['excluded']} excluded) | top-1 mean {t['mean']:.2f} median <= {t['median']:.1f} p90 <= {t['p90']:.1f} deg, "
+                f"within 5/10/22.5 deg {t['within_5']:.3f}/{t['within_10']:.3f}/{t['within_22.5']:.3f} | "
+                f"cover median <= {c['median']:.1f} p90 <= {c['p90']:.1f} deg | mode count right {e['count_ok_rate']:.3f}")
+
+    print("Angular errors (test split):")
+    print(line("overall", summary["overall"]))
+    out = dict(summary)
+    if names is not None and len(names) == len(summary["labels"]):
+        out["label_names"] = list(names)
+        for name, e in zip(names, summary["labels"]):
+            print(line(name, e))
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
 
 
 def env_path(name: str, default: str):

@@ -24,6 +24,7 @@ from dataloader_multi_peak_vonMises import PointCloudDatasetMvM
 from models.pointnet_pp_mvM import PointNetPPMvM
 from pnpp_hip import sampling, dist as pdist, ops, trainer
 from pnpp_hip.augment import Augment
+from pnpp_hip.decode import AngularErrors
 
 ROOT = trainer.env_path("PNPP_ROOT", "/home/pablo/ForwardNet/data/MN40_multi_peak_vM_gt")
 PLY_ROOT = trainer.env_path("PNPP_PLY_ROOT", "/home/pablo/ForwardNet/data/full_mn40_normal_resampled_2d_rotated_ply")
@@ -180,6 +181,7 @@ def _parser():
     ap.add_argument("--augment", action="store_true",
                     help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
     trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
+    trainer.add_metrics_args(ap)   # --angular-metrics (PNPP_ANGULAR_METRICS): off by default
     return ap
 
 
@@ -201,7 +203,15 @@ def main(argv=None):
     for i, cat in enumerate(categories):
         hist[cat] = h["labels"][i]
     model.load_state_dict(best_state)
-    test_kl = trainer.evaluate(model, _loss, loaders["test"], dev)
+    errs = None
+    if args.angular_metrics:   # decoded and accumulated on the device during the same pass; per category while the table takes them
+        errs = AngularErrors(n_labels=len(categories) if len(categories) <= 64 else 1)
+    test_kl = trainer.evaluate(model, _loss, loaders["test"], dev, label_index=3 if errs is not None and errs.n_labels > 1 else None,
+                               metrics=errs)
+    if errs is not None:
+        summary = errs.summary()   # every rank takes part in the all-reduce
+        if rank == 0:
+            trainer.report_angular_errors(RES / "angular_errors.json", summary, categories)
     if rank == 0:
         torch.save(best_state, RES / "mvM_best.pth")
         try:

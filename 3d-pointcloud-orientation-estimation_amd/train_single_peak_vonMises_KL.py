@@ -24,6 +24,7 @@ from dataloader_single_peak_vonMises import PointCloudDatasetVonMises
 from models.pointnet_pp_vonMises import PointNetPPVonMises
 from pnpp_hip import sampling, dist as pdist, ops, trainer
 from pnpp_hip.augment import Augment
+from pnpp_hip.decode import AngularErrors
 
 ROOT = trainer.env_path("PNPP_ROOT", "/home/pablo/ForwardNet/data/chair_toilet_sofa_plant_bowl_bottle")
 RES = trainer.env_path("PNPP_RES", "/home/pablo/ForwardNet/results/single_peak_vonMises_KL_1006_2")
@@ -100,7 +101,13 @@ def _parser():
     ap.add_argument("--augment", action="store_true",
                     help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
     trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
+    trainer.add_metrics_args(ap)   # --angular-metrics (PNPP_ANGULAR_METRICS): off by default
     return ap
+
+
+# the unfused (forward, criterion) form of _loss: evaluate(metrics=) decodes the forward's (mu, kappa)
+_loss_pair = (lambda model, batch: model(batch[0]),
+              lambda out, batch: ops.kl_von_mises_single(out[0], out[1], batch[1][:, 0].contiguous(), batch[1][:, 1].contiguous()))
 
 
 def main(argv=None):
@@ -126,6 +133,12 @@ def main(argv=None):
     if rank == 0:
         print(f"Test KL = {test_kl:.6f}")
         print(f"[steps: {hist['steps']}]")
+    if args.angular_metrics:   # a pass of its own over the test split, so that the figure above is the one it always was
+        errs = AngularErrors()
+        trainer.evaluate(model, _loss_pair, loaders["test"], dev, metrics=errs)
+        summary = errs.summary()   # every rank takes part in the all-reduce
+        if rank == 0:
+            trainer.report_angular_errors(RES / "angular_errors.json", summary)
     return hist, test_kl
 
 

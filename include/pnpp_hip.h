@@ -381,6 +381,43 @@ int pnpp_mvm_head_bwd(const float *pi_raw, const float *mu_raw, const float *kap
 /* train_8dir_KL.py:60-68: loss_vec[b] = -sum p * log_softmax(logits); dlogits = softmax*sum(p) - p. */
 int pnpp_soft_ce(const float *logits, const float *p, int B, int C, float *loss_vec, float *dlogits, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Orientation decoding and angular errors (csrc/decode_kernels.hip; additive to ABI 5)
+ * ---------------------------------------------------------------------------------------- */
+
+/* The modes of the mixture p(theta) = sum_k w_k exp(kappa_k (cos(theta - mu_k) - 1)) / (2 pi i0e(kappa_k)) of every sample, one
+ * launch, one workgroup per sample, float64 inside.  mu, kappa, weight (B,K), 1 <= K <= 8; weight NULL: weight 1, K = 1 (the
+ * single-peak model); counts (B) int32 or NULL: the components in use (clamped to 0..K); a negative or NaN kappa counts as 0.
+ * Grid: theta_i = i 2 pi / G, G = num - 1 (models/pointnet_pp_mvM.py:135-136, linspace(0, 2 pi, num)[:-1]), 2 <= G <= 1024.
+ * density (B,G) or NULL: p_i / (sum_i p_i + 1e-8), what mvm_density_on_grid returns, finite for kappa up to 500.
+ * A grid point is a candidate when p_i > p_{i-1} and p_i >= p_{i+1} (circular); each is refined inside [theta_{i-1}, theta_{i+1}] by
+ * 8 rounds of value sectioning on 65 equispaced points (first arg-max, clamped to the interior, the two sub-cells around it kept);
+ * the mode is the last bracket's midpoint, its height p there.  Modes are sorted by (height descending, angle in [0, 2 pi) ascending),
+ * those below rel_height x the top height are dropped, at most K are kept, angles are wrapped to (-pi, pi].
+ * modes, heights (B,K): unused slots NaN and 0; n_modes (B) int32; angle (B) or NULL = modes[:, 0] (NaN when n_modes = 0, which is
+ * what a flat density gives). */
+int pnpp_mvm_decode(const float *mu, const float *kappa, const float *weight, const int32_t *counts, int B, int K, int num,
+                    float rel_height, float *modes, float *heights, int32_t *n_modes, float *angle, float *density, void *stream);
+
+/* Angular errors of decoded orientations, in degrees, and their statistics: one single-workgroup launch.
+ * modes (B,K), n_modes (B), angle (B): pnpp_mvm_decode's outputs.  Ground truth: mu_gt, kappa_gt (B), or vm_gt (B,Kmax,3) = (mu, kappa,
+ * weight) rows with K_gt (B) int32 as pnpp_vm_match_loss takes them -- one of the two forms, the other's pointers NULL.
+ *   top1  = min_j |wrap(angle - mu_gt_j)|,   cover = max_j min_m |wrap(mode_m - mu_gt_j)|,   count_ok = (n_modes == K_gt)
+ * A sample with K_gt <= 0, with every ground-truth kappa <= 1e-6 (a symmetric class) or with n_modes = 0 has no error: -1 in both.
+ * top1, cover (B) float32 and count_ok (B) int32 may each be NULL.
+ * acc or NULL: the accumulator, n_labels * PNPP_ORIENT_STRIDE + 1 words of 64 bits, zeroed by the caller before the first call and
+ * added to with integer atomics (any order gives the same words).  Label l's block (labels (B) int32, NULL: all 0; a label outside
+ * 0..n_labels-1 is clamped) = [histogram of top1 in 0.5 degree bins (PNPP_ORIENT_BINS) | the same of cover | included | excluded |
+ * count_ok | sum of top1 in micro-degrees | sum of cover in micro-degrees | 3 spare]; the last word counts the samples seen.
+ * sample_err (capacity,2) or NULL: sample i's (top1, cover) at row (samples seen before this call) + i; rows beyond capacity are
+ * dropped and still counted. */
+#define PNPP_ORIENT_BINS 360
+#define PNPP_ORIENT_STRIDE 728
+#define PNPP_ORIENT_MAX_LABELS 64
+int pnpp_orient_eval(const float *modes, const int32_t *n_modes, const float *angle, int B, int K, const float *mu_gt,
+                     const float *kappa_gt, const float *vm_gt, const int32_t *K_gt, int Kmax, const int32_t *labels, int n_labels,
+                     uint64_t *acc, float *sample_err, int64_t capacity, float *top1, float *cover, int32_t *count_ok, void *stream);
+
 /* Classification head of PointNet++Demo.py (csrc/cls_loss_kernels.hip; additive to ABI 5).  One wave per row, any C; the row maximum
  * and the sums are wave reductions, sums in float64.
  * PointNet++Demo.py:234 F.log_softmax(x, dim=1): y (M,C) = x - logsumexp(x, 1);  backward dx = dy - exp(y) * sum_c dy. */
