@@ -132,11 +132,139 @@ struct alignas(16) KnnLds {   // one copy per workgroup, shared by the two insta
     unsigned long long pool[4][KNN_POOL];
 };
 
+// ---- surface normals (pnpp_estimate_normals): the epilogue of a query whose list has just been selected ----
+struct KnnNormals {
+    float *out;          // (B, N, stride): stride 3 = normal, stride 6 = the point in columns 0-2 and the normal in 3-5
+    float *curv;         // (B, N) surface variation, or nullptr
+    const float *ref;    // (B, 3) reference point of the orienting modes, or nullptr (mode 0)
+    int stride, mode;    // mode: PNPP_NORMALS_NONE / _AWAY / _TOWARD
+};
+
+// One Jacobi rotation of the symmetric 3 x 3 matrix in the plane (p, q), r the third index: annihilates a_pq and applies the same rotation
+// to the columns p and q of V.  Rutishauser's update (t = tan, tau = tan of the half angle); every operand is a named scalar, so the
+// matrices live in registers.  a_pq == 0 is skipped (the only input that would divide 0 by 0), and an a_pq that no longer changes either
+// diagonal entry when added to it a hundredfold is set to 0 without a rotation (a_pq < 1e-18 min(|a_pp|, |a_qq|): the rotation left out
+// is below 1e-18 divided by the two eigenvalues' relative gap), so a converged matrix ends the sweeps early.
+__device__ __forceinline__ void jacobi_rot(double &app, double &aqq, double &apq, double &arp, double &arq, double &v0p, double &v0q,
+                                           double &v1p, double &v1q, double &v2p, double &v2q) {
+    if (apq == 0.0) return;
+    const double small = 100.0 * fabs(apq);
+    if (fabs(app) + small == fabs(app) && fabs(aqq) + small == fabs(aqq)) {
+        apq = 0.0;
+        return;
+    }
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));   // theta^2 = inf gives t = 0
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+    const double h = t * apq;
+    app -= h, aqq += h, apq = 0.0;
+    double g = arp, f = arq;
+    arp = g - s * (f + tau * g), arq = f + s * (g - tau * f);
+    g = v0p, f = v0q, v0p = g - s * (f + tau * g), v0q = f + s * (g - tau * f);
+    g = v1p, f = v1q, v1p = g - s * (f + tau * g), v1q = f + s * (g - tau * f);
+    g = v2p, f = v2q, v2p = g - s * (f + tau * g), v2q = f + s * (g - tau * f);
+}
+
+constexpr int KNN_NRM_SWEEPS = 6;   // at most: cyclic Jacobi converges quadratically, a 3 x 3 matrix is diagonal after three to five
+
+// Zeros for a query at or beyond its cloud's length (ragged batches): every column of out, curv and idx the call writes.
+__device__ __forceinline__ void normals_zero_row(const KnnNormals &W, int32_t *__restrict__ idx, size_t row, int k, int lane) {
+    if (lane < W.stride) W.out[row * W.stride + lane] = 0.f;
+    if (lane == 6 && W.curv) W.curv[row] = 0.f;
+    if (idx)
+        for (int j = lane; j < k; j += 64) idx[row * k + j] = 0;
+}
+
+// The normals epilogue has two halves.  normals_covariance runs at the end of a pass, the whole wave on its query (ax, ay, az) and the
+// sorted list just selected: the covariance of d = neighbour - point in float64, its nine sums over the lanes by the fixed-order
+// butterfly, so every lane ends with the same bits in c = (xx, xy, xz, yy, yz, zz).  Lane p of the wave keeps pass p's six numbers, and
+// after the last pass normals_solve_store runs once per wave with one query per lane: the eigen-solve is scalar work, so the qpw
+// queries of a wave are solved side by side in its lanes and not one after the other, each in all 64 (measured: DESIGN section 17).
+// staged: the cloud's one tile is in LDS (sx, sy, sz), else the neighbours come from global memory.
+template <bool RAGGED>
+__device__ __forceinline__ void normals_covariance(const unsigned long long *list, int k, int N, bool staged, const float *sx,
+                                                   const float *sy, const float *sz, const float *__restrict__ cloud, float ax, float ay,
+                                                   float az, int lane, double (&c)[6]) {
+    double m[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {   // k <= 128: a lane holds list slots lane and lane + 64
+        const int j = lane + 64 * h;
+        if (j < k) {
+            const unsigned n = (unsigned)(list[RAGGED && j >= N ? 0 : j] & 0xffffffffu);
+            float nx, ny, nz;
+            if (staged) nx = sx[n], ny = sy[n], nz = sz[n];
+            else nx = cloud[(size_t)n * 3], ny = cloud[(size_t)n * 3 + 1], nz = cloud[(size_t)n * 3 + 2];
+            const double x = (double)nx - (double)ax, y = (double)ny - (double)ay, z = (double)nz - (double)az;
+            m[0] += x, m[1] += y, m[2] += z;
+            m[3] += x * x, m[4] += x * y, m[5] += x * z, m[6] += y * y, m[7] += y * z, m[8] += z * z;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+        double v = m[c];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += shfl_xor_f64(v, o);
+        m[c] = v;
+    }
+    const double inv = 1.0 / (double)k;
+    const double mx = m[0] * inv, my = m[1] * inv, mz = m[2] * inv;
+    c[0] = m[3] * inv - mx * mx, c[1] = m[4] * inv - mx * my, c[2] = m[5] * inv - mx * mz;
+    c[3] = m[6] * inv - my * my, c[4] = m[7] * inv - my * mz, c[5] = m[8] * inv - mz * mz;
+}
+
+// One lane, one query: point (ax, ay, az) = row `row` of the batch with covariance c.  Eigenvectors by cyclic Jacobi, the smallest
+// eigenvalue's column, sign, curvature, and every column of the row's outputs.
+__device__ __forceinline__ void normals_solve_store(const KnnNormals &W, const double (&c)[6], const float *__restrict__ ref, size_t row,
+                                                    float ax, float ay, float az) {
+    double a00 = c[0], a01 = c[1], a02 = c[2], a11 = c[3], a12 = c[4], a22 = c[5];
+    double nx = 0.0, ny = 0.0, nz = 0.0, cv = 0.0;
+    if ((a00 + a11) + a22 > 0.0) {   // a trace <= 0 (the k neighbours coincide) or NaN leaves the zeros
+        double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+#pragma unroll 1
+        for (int sweep = 0; sweep < KNN_NRM_SWEEPS && !(a01 == 0.0 && a02 == 0.0 && a12 == 0.0); ++sweep) {
+            jacobi_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+            jacobi_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+            jacobi_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+        }
+        const double den = (a00 + a11) + a22;
+        // the smallest eigenvalue's column (the lowest index among equal ones), by two conditional moves per entry
+        const bool s1 = a11 < a00;
+        double l0 = s1 ? a11 : a00;
+        nx = s1 ? v01 : v00, ny = s1 ? v11 : v10, nz = s1 ? v21 : v20;
+        const bool s2 = a22 < l0;
+        l0 = s2 ? a22 : l0;
+        nx = s2 ? v02 : nx, ny = s2 ? v12 : ny, nz = s2 ? v22 : nz;
+        cv = den > 0.0 ? fmax(l0, 0.0) / den : 0.0;
+        // canonical sign: the component of largest magnitude is positive, the lowest index among equal magnitudes
+        double big = nx;
+        if (fabs(ny) > fabs(big)) big = ny;
+        if (fabs(nz) > fabs(big)) big = nz;
+        bool flip = big < 0.0;
+        if (W.mode != 0) {
+            const double s = (nx * ((double)ax - (double)ref[0]) + ny * ((double)ay - (double)ref[1])) + nz * ((double)az - (double)ref[2]);
+            const double so = flip ? -s : s;   // n . (p - r) of the canonical n
+            if (W.mode == 1 ? so < 0.0 : so > 0.0) flip = !flip;
+        }
+        if (flip) nx = -nx, ny = -ny, nz = -nz;
+    }
+    float *o = W.out + row * W.stride;
+    if (W.stride == 6) {
+        o[0] = ax, o[1] = ay, o[2] = az;
+        o += 3;
+    }
+    o[0] = (float)nx, o[1] = (float)ny, o[2] = (float)nz;
+    if (W.curv) W.curv[row] = (float)cv;
+}
+
 // RAGGED: N below is the cloud's own extent Nv (one scalar load per workgroup); the host still sized TILE, qpw and the grid from the
 // padded J.N, so Nv <= J.N tiles are walked, `cur` flips once per tile actually walked, and a list asked for more neighbours than
 // the cloud has points (k > Nv, which the host refuses where it sees the lengths) repeats slot 0 in the slots >= Nv.
-template <bool GATHER, int TILE, bool MOM, bool RAGGED = false>
-__device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const int b, KnnLds &L) {
+// NRM (with W): every point of the cloud is a query (new_xyz == xyz, S == J.N) and each pass ends with the covariance of the list it
+// has just selected -- at the end of the pass, not after all of them, because best[][2][] keeps two passes' lists, so qpw is free on
+// a cloud of one tile (qpw <= 64: pass p's covariance waits in lane p for the solve after the last pass).  idx is then optional.
+// RAGGED: a query at or beyond Nv skips the search and writes zeros.
+template <bool GATHER, int TILE, bool MOM, bool RAGGED = false, bool NRM = false>
+__device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const int b, KnnLds &L, const KnnNormals *W = nullptr) {
     constexpr int CPL = TILE / 64;              // candidates per lane per tile
     constexpr int SPT = (TILE + 255) / 256;     // staged points per thread per tile
     const float *__restrict__ new_xyz = J.new_xyz;
@@ -157,9 +285,20 @@ __device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const in
     const float *cloud = xyz + (size_t)b * J.Nsrc * 3;
     const int qpw = J.qpw;   // > 1 only with N <= TILE: the one tile staged in the first pass serves every pass
 
+    if constexpr (NRM && RAGGED) {
+        if (bx * qpw * 4 >= N) {   // the workgroup lies wholly beyond its cloud: its zeros, and no tile is staged
+            for (int pass = 0; pass < qpw; ++pass) {
+                const int q = (bx * qpw + pass) * 4 + wave;
+                if (q < S) normals_zero_row(*W, idx, (size_t)b * S + q, k, lane);
+            }
+            return;
+        }
+    }
+
+    [[maybe_unused]] double cov[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // NRM: lane p holds pass p's covariance
     for (int pass = 0; pass < qpw; ++pass) {
         const int q = (bx * qpw + pass) * 4 + wave;
-        const bool active = q < S;  // wave-uniform
+        const bool active = q < S && (!NRM || q < N);  // wave-uniform
         float ax = 0.f, ay = 0.f, az = 0.f, sa = 0.f;
         if (active) {
             const float *a = new_xyz + ((size_t)b * S + q) * 3;
@@ -272,9 +411,24 @@ __device__ __forceinline__ void knn_body(const KnnJob &J, const int bx, const in
             cur ^= 1;
             have = true;
         }
-        if (active) {
+        if (active && (!NRM || idx)) {
             int32_t *o = idx + ((size_t)b * S + q) * k;
             for (int j = lane; j < k; j += 64) o[j] = (int32_t)(unsigned)(best[wave][cur][RAGGED && j >= N ? 0 : j] & 0xffffffffu);
+        }
+        if constexpr (NRM) {
+            if (active) {
+                double c[6];
+                normals_covariance<RAGGED>(best[wave][cur], k, N, N <= TILE, sx, sy, sz, cloud, ax, ay, az, lane, c);
+#pragma unroll
+                for (int i = 0; i < 6; ++i) cov[i] = lane == pass ? c[i] : cov[i];
+            } else if (RAGGED && q < S) normals_zero_row(*W, idx, (size_t)b * S + q, k, lane);
+        }
+    }
+    if constexpr (NRM) {
+        const int q = (bx * qpw + lane) * 4 + wave;   // lane p: the wave's query of pass p
+        if (lane < qpw && q < S && q < N) {
+            const float *a = xyz + ((size_t)b * S + q) * 3;
+            normals_solve_store(*W, cov, W->ref ? W->ref + (size_t)b * 3 : nullptr, (size_t)b * S + q, a[0], a[1], a[2]);
         }
     }
     if constexpr (MOM) {
@@ -324,6 +478,13 @@ template <bool RAGGED>
 __global__ void __launch_bounds__(256) knn_kernel(const KnnJob J) {
     __shared__ KnnLds L;
     knn_body<false, KNN_TILE, false, RAGGED>(J, blockIdx.x, blockIdx.y, L);
+}
+
+// Normals of every point of the cloud: the search above with S == N queries and the normals epilogue per query (KnnNormals).
+template <bool RAGGED>
+__global__ void __launch_bounds__(256) knn_normals_kernel(const KnnJob J, const KnnNormals W) {
+    __shared__ KnnLds L;
+    knn_body<false, KNN_TILE, false, RAGGED, true>(J, blockIdx.x, blockIdx.y, L, &W);
 }
 
 // The neighbour searches of two stacked levels in ONE launch (they are independent once both levels' centre indices are drawn:
@@ -781,6 +942,36 @@ int launch_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int 
     return PNPP_OK;
 }
 
+// queries per wave of the normals launch on a cloud of one tile: every point is a query, so a workgroup's 16 KiB of staging serves
+// 4 * qpw of them and a wave's one eigen-solve qpw of them.  Measured at 32 x 1024, k = 16 (kernel time): 2: 123.5 us, 4: 105.3 us,
+// 8: 96.7 us, 16: 107.7 us (128 workgroups per cloud become 16: too few to fill the CUs).  DESIGN section 17 has the table; the
+// macro is there so that a sweep can build the other values (-DKNN_NRM_QPW=n).
+#ifndef KNN_NRM_QPW
+#define KNN_NRM_QPW 8
+#endif
+
+// Normals of all N points of each cloud (include/pnpp_hip.h: pnpp_estimate_normals).  Every refusal comes before the launch.
+static int launch_estimate_normals(const float *xyz, int B, int N, int k, int mode, const float *ref, float *out, int stride, float *curv,
+                                   int32_t *idx, hipStream_t st, const int32_t *lengths = nullptr) {
+    PNPP_REQUIRE(xyz && out, PNPP_ERR_ARG, "estimate_normals: null pointer");
+    PNPP_REQUIRE(B > 0 && N > 0, PNPP_ERR_ARG, "estimate_normals: non-positive size (B=%d N=%d)", B, N);
+    PNPP_REQUIRE(k >= 3 && k <= KNN_KMAX, PNPP_ERR_ARG, "estimate_normals: k=%d outside the supported range 3..%d", k, KNN_KMAX);
+    PNPP_REQUIRE(k <= N, PNPP_ERR_RANGE, "selected index k out of range (k=%d > N=%d)", k, N);
+    PNPP_REQUIRE(stride == 3 || stride == 6, PNPP_ERR_ARG, "estimate_normals: output stride %d is neither 3 (normal) nor 6 (xyz, normal)", stride);
+    PNPP_REQUIRE(mode == PNPP_NORMALS_NONE || mode == PNPP_NORMALS_AWAY || mode == PNPP_NORMALS_TOWARD, PNPP_ERR_ARG,
+                 "estimate_normals: unknown orientation mode %d", mode);
+    PNPP_REQUIRE(mode == PNPP_NORMALS_NONE || ref, PNPP_ERR_ARG, "estimate_normals: orientation mode %d needs a reference point per cloud", mode);
+    PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "estimate_normals: batch %d exceeds grid limit", B);
+    const int qpw = N <= KNN_TILE ? KNN_NRM_QPW : 1, nb = cdiv(N, 4 * qpw);
+    ProfScope ps(st, "knn_normals_kernel B=%d N=%d k=%d%s", B, N, k, lengths ? " ragged" : "");
+    const KnnJob J{xyz, xyz, nullptr, N, N, N, k, idx, nullptr, nullptr, nullptr, nullptr, qpw, nb, lengths, 0};
+    const KnnNormals W{out, curv, ref, stride, mode};
+    if (lengths) hipLaunchKernelGGL(knn_normals_kernel<true>, dim3(nb, B), dim3(256), 0, st, J, W);
+    else hipLaunchKernelGGL(knn_normals_kernel<false>, dim3(nb, B), dim3(256), 0, st, J, W);
+    PNPP_CHECK_LAUNCH("estimate_normals");
+    return PNPP_OK;
+}
+
 int launch_gather_centres(const float *xyz, const int32_t *centre, int B, int N, int S, float *out_a, float *out_b,
                           hipStream_t st) {
     const int total = B * S;
@@ -822,6 +1013,17 @@ extern "C" int pnpp_knn_ragged(const float *new_xyz, const float *xyz, int B, in
                                void *stream) {
     PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "knn_ragged: null lengths");
     return launch_knn(new_xyz, xyz, B, S, N, k, idx, as_stream(stream), lengths);
+}
+
+extern "C" int pnpp_estimate_normals(const float *xyz, int B, int N, int k, int orient, const float *ref, float *out, int out_stride,
+                                     float *curv, int32_t *idx, void *stream) {
+    return launch_estimate_normals(xyz, B, N, k, orient, ref, out, out_stride, curv, idx, as_stream(stream));
+}
+
+extern "C" int pnpp_estimate_normals_ragged(const float *xyz, int B, int N, const int32_t *lengths, int k, int orient, const float *ref,
+                                            float *out, int out_stride, float *curv, int32_t *idx, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "estimate_normals_ragged: null lengths");
+    return launch_estimate_normals(xyz, B, N, k, orient, ref, out, out_stride, curv, idx, as_stream(stream), lengths);
 }
 
 extern "C" int pnpp_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int S1, int k1, int32_t *idx1, float *new_xyz1,

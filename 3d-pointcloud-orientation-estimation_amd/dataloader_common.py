@@ -173,12 +173,22 @@ class BankLoader:
     on-device subsampling; drop-in for a torch DataLoader in pnpp_hip.trainer.fit / evaluate.
     augment (a pnpp_hip.augment.Augment) with kinds (one per target: "angle", "vm", "axis", "dir8", "keep"): every batch is the
     bank's draw followed by one augmentation launch -- the cloud in a fresh pose, its targets moved along.  None: nothing changes.
-    counts: index of the target that holds the number of real rows of the multi-row "vm" / "angle" targets (the multi-peak K)."""
+    counts: index of the target that holds the number of real rows of the multi-row "vm" / "angle" targets (the multi-peak K).
+    normals=k: the first element of every batch is (B, num_points, 6) -- the draw in columns 0-2 and, in 3-5, the surface normals
+    pnpp_hip.normals.with_normals estimates from it (k neighbours, oriented by normals_orient: "centroid", a viewpoint tensor or
+    None), computed after the bank's draw and before `augment`, which then turns the normals with the cloud.  Augment's jitter moves
+    the points and not the normals: a jittered batch carries the normals of the surface the points were drawn from.
+    channels_first=True yields that element as its (B, 6, num_points) transpose (a view), what PointNetPlusPlusCls and the
+    six-channel PointNet take.  The default normals=None changes nothing: same tensors, same draws, same launches."""
 
     def __init__(self, bank: DeviceCloudBank, targets, num_points: int, batch: int, shuffle: bool, seed: int = 0,
-                 drop_last: bool = False, augment=None, kinds=None, counts=None):
+                 drop_last: bool = False, augment=None, kinds=None, counts=None, normals=None, normals_orient="centroid",
+                 channels_first: bool = False):
         import torch
         self.bank, self.num_points, self.batch, self.shuffle, self.drop_last = bank, num_points, batch, shuffle, drop_last
+        if normals is not None and not 3 <= int(normals) <= min(128, int(num_points)):
+            raise ValueError(f"BankLoader: normals={normals} must be a neighbourhood size between 3 and min(128, num_points={num_points})")
+        self.normals, self.normals_orient, self.channels_first = (None if normals is None else int(normals)), normals_orient, bool(channels_first)
         if augment is not None and (kinds is None or len(kinds) != len(targets)):
             raise ValueError(f"BankLoader: augment needs one kind per target ({len(targets)}), got {kinds}")
         self.augment, self.kinds, self.counts = augment, (None if kinds is None else tuple(kinds)), counts
@@ -199,7 +209,11 @@ class BankLoader:
                 break
             dev_ids = ids.to(self.bank.bank.device)
             batch = (self.bank.sample(dev_ids, self.num_points), *(t[dev_ids] for t in self.targets))
-            if self.augment is None:
-                yield batch
-            else:
-                yield self.augment(*batch, kinds=self.kinds, counts=None if self.counts is None else batch[1 + self.counts])
+            if self.normals is not None:
+                from pnpp_hip.normals import with_normals
+                batch = (with_normals(batch[0], self.normals, self.normals_orient), *batch[1:])
+            if self.augment is not None:
+                batch = self.augment(*batch, kinds=self.kinds, counts=None if self.counts is None else batch[1 + self.counts])
+            if self.channels_first:
+                batch = (batch[0].transpose(1, 2), *batch[1:])
+            yield batch

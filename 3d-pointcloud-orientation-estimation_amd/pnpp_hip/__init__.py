@@ -8,8 +8,9 @@
     inference  Predictor: forward-only evaluation, one fused launch per set-abstraction level
     augment Augment: a fresh yaw per cloud and draw on the device, orientation targets moved along
     decode  decode / AngularErrors: von-Mises parameters to orientations, orientations to angular-error statistics, on the device
+    normals estimate_normals / with_normals: surface normals of xyz-only clouds (fused kNN + PCA), on the device
 """
-__all__ = ["ops", "build", "optim", "dist", "sampling", "inference", "augment", "decode", "Predictor"]
+__all__ = ["ops", "build", "optim", "dist", "sampling", "inference", "augment", "decode", "normals", "Predictor"]
 
 
 def __getattr__(name):

@@ -124,6 +124,8 @@ class AugmentDesc(C.Structure):
                 ("n_targets", C.c_int), ("targets", AugmentTarget * PNPP_AUG_MAX_TARGETS), ("dirs8", _fp)]
 
 
+NORMALS_NONE, NORMALS_AWAY, NORMALS_TOWARD = range(3)   # pnpp_estimate_normals' orientation modes
+NORMALS_KMIN, NORMALS_KMAX = 3, 128
 PNPP_OPTIM_MAX_GROUPS = 8
 ORIENT_BINS, ORIENT_STRIDE, ORIENT_MAX_LABELS = 360, 728, 64   # pnpp_orient_eval's accumulator (include/pnpp_hip.h)
 SCHED_CONSTANT, SCHED_COSINE, SCHED_STEP = range(3)
@@ -217,6 +219,9 @@ SIGNATURES = {
     "pnpp_knn_pair_ragged": (_i, [_fp, _i, _i, _fp, _fp, _i, _i, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp]),
     "pnpp_sa_group_pair_ragged": (_i, [C.POINTER(SaDesc), C.POINTER(SaDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnpp_sa_infer_group_pair_ragged": (_i, [C.POINTER(SaDesc), C.POINTER(SaDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    # surface normals: xyz, B, N, [lengths,] k, orient, ref, out, out_stride, curv, idx, stream
+    "pnpp_estimate_normals": (_i, [_fp, _i, _i, _i, _i, _fp, _fp, _i, _fp, _fp, _fp]),
+    "pnpp_estimate_normals_ragged": (_i, [_fp, _i, _i, _fp, _i, _i, _fp, _fp, _i, _fp, _fp, _fp]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

@@ -204,6 +204,34 @@ def knn(new_xyz: torch.Tensor, xyz: torch.Tensor, k: int, lengths=None) -> torch
     return idx
 
 
+def estimate_normals(xyz: torch.Tensor, k: int, mode: int = L.NORMALS_NONE, ref: Optional[torch.Tensor] = None, lengths=None,
+                     stride: int = 3, curvature: bool = False, neighbours: bool = False):
+    """One launch: the neighbour search of knn(xyz, xyz, k, lengths) with every point as a query, the float64 covariance of each
+    neighbourhood and its smallest eigenvector (include/pnpp_hip.h: pnpp_estimate_normals; pnpp_hip.normals is the user-level module).
+    -> (out (B,N,stride) float32, curv (B,N) float32 or None, idx (B,N,k) int32 or None).  stride 3: the normal; stride 6: the point in
+    columns 0-2, the normal in 3-5.  mode: L.NORMALS_NONE / _AWAY / _TOWARD with ref (B,3) float32, the per-cloud reference point.
+    lengths (B,): a ragged batch as in knn; the rows at or beyond a cloud's length come back as zeros."""
+    xyz = _f32(xyz, "xyz")
+    if xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError(f"xyz must be (B, N, 3), got {tuple(xyz.shape)}")
+    B, N, _ = xyz.shape
+    if ref is not None:
+        ref = _f32(ref, "ref")
+        if tuple(ref.shape) != (B, 3):
+            raise ValueError(f"ref must be ({B}, 3), one reference point per cloud, got {tuple(ref.shape)}")
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, B, N, xyz.device, minimum=k)
+    out = torch.empty(B, N, int(stride), device=xyz.device, dtype=torch.float32)
+    curv = torch.empty(B, N, device=xyz.device, dtype=torch.float32) if curvature else None
+    idx = torch.empty(B, N, int(k), device=xyz.device, dtype=torch.int32) if neighbours else None
+    tail = (int(k), int(mode), _p(ref), out.data_ptr(), int(stride), _p(curv), _p(idx), _stream())
+    if lengths is not None:
+        L.check(L.lib().pnpp_estimate_normals_ragged(xyz.data_ptr(), B, N, lengths.data_ptr(), *tail))
+    else:
+        L.check(L.lib().pnpp_estimate_normals(xyz.data_ptr(), B, N, *tail))
+    return out, curv, idx
+
+
 def farthest_point_sample(xyz: torch.Tensor, npoint: int, start: Optional[torch.Tensor] = None, lengths=None) -> torch.Tensor:
     """lengths (B,): a ragged batch -- row b is the sampling of xyz[b, :lengths[b]] alone (npoint may exceed a length, as it may
     exceed N); start[b] < lengths[b].  Without `start` the first index of cloud b is torch.randint(0, lengths[b]) on the host

@@ -997,6 +997,29 @@ typedef struct {
 int pnpp_augment_clouds(uint64_t seed, uint64_t stream_id, const float *xyz_in, float *xyz_out, const int32_t *lengths, int B,
                         int64_t N, int C, const pnpp_augment_desc *desc, float *params_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Surface normals of xyz-only clouds (additive to ABI 5): the neighbour search of pnpp_knn with every point of the cloud as a query,
+ * and in the same launch the covariance of each neighbourhood and its smallest eigenvector.  For cloud b, point i:
+ *   neighbours    row i of pnpp_knn(xyz, xyz, k): the k smallest (distance, index) keys, the point itself included;
+ *   covariance    float64: d_j = (double)p_j - (double)p_i, m = (1/k) sum d_j, C = (1/k) sum d_j d_j^T - m m^T;
+ *   normal n      a unit eigenvector of C's smallest eigenvalue l0 (l0 <= l1 <= l2; cyclic Jacobi in float64), its component of
+ *                 largest magnitude positive (the lowest index among equal magnitudes), then oriented by s = n . (p_i - ref[b]):
+ *                 PNPP_NORMALS_AWAY flips n when s < 0, PNPP_NORMALS_TOWARD when s > 0; s == 0 or PNPP_NORMALS_NONE keep it;
+ *   curvature     max(l0, 0) / (l0 + l1 + l2), the surface variation; trace <= 0 (the k neighbours coincide): n = 0, curvature 0.
+ * Each is rounded to float32 once.  Where l0 and l1 nearly coincide n is some unit vector of that eigenspace.
+ * out (B,N,out_stride): out_stride 3 holds n; out_stride 6 holds the point in columns 0-2 and n in 3-5 (what pnpp_augment_clouds
+ * takes at C = 6).  curv (B,N) and idx (B,N,k) are optional.  ref (B,3) float32 is required by the two orienting modes.
+ * 3 <= k <= 128 and k <= N (PNPP_ERR_RANGE, as pnpp_knn); B <= 65535.  No atomics: two calls give the same bits.
+ * _ragged: lengths (B) int32 on the device as for pnpp_knn_ragged -- row b is the call on xyz[b, :lengths[b]] alone, bit for bit; the
+ * input rows at or beyond lengths[b] are never read and their rows of out, curv and idx are zeros. */
+#define PNPP_NORMALS_NONE 0
+#define PNPP_NORMALS_AWAY 1
+#define PNPP_NORMALS_TOWARD 2
+int pnpp_estimate_normals(const float *xyz, int B, int N, int k, int orient, const float *ref, float *out, int out_stride, float *curv,
+                          int32_t *idx, void *stream);
+int pnpp_estimate_normals_ragged(const float *xyz, int B, int N, const int32_t *lengths, int k, int orient, const float *ref, float *out,
+                                 int out_stride, float *curv, int32_t *idx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
