@@ -4,7 +4,7 @@
 
 namespace pnpp {
 
-// ---- index_kernels.hip ----
+// ---- knn_kernels.hip ----
 int launch_knn(const float *new_xyz, const float *xyz, int B, int S, int N, int k, int32_t *idx, hipStream_t st,
                const int32_t *lengths = nullptr);   // lengths: ragged batch, cloud b's candidates are its first lengths[b] rows
 int launch_knn_centres(const float *xyz, const int32_t *centre, int B, int S, int N, int k, int32_t *idx, float *out_a,
@@ -14,6 +14,7 @@ int launch_knn_pair(const float *xyz, int B, int N, const int32_t *centre1, int 
                     const int32_t *lengths = nullptr);   // lengths: of level 1's clouds (level 2 searches level 1's centres)
 int knn_pair_moment_partials(int B, int S1, int N);      // how many partials launch_knn_pair writes into `mom`
 size_t knn_pair_moment_doubles(int B, int S1, int N);   // ... and the doubles they take
+// ---- group_kernels.hip ----
 int launch_gather_centres(const float *xyz, const int32_t *centre, int B, int N, int S, float *out_a, float *out_b, hipStream_t st);
 int launch_scatter_rows_bwd(const float *dout, const int32_t *idx, int B, int N, int C, int M, float *dpoints, hipStream_t st);
 

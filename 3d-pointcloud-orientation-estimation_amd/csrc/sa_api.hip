@@ -1,5 +1,5 @@
 // sa_api.hip -- host-side orchestration of PointNetSetAbstraction forward / backward on top of the fused kernels
-// (gemm_*_kernels.hip, index_kernels.hip).  The library's runtime -- errors, launch timing, the SyncBN exchange -- is runtime.hip.
+// (gemm_*_kernels.hip, knn_kernels.hip, sampling_kernels.hip, group_kernels.hip).  The library's runtime -- errors, launch timing, the SyncBN exchange -- is runtime.hip.
 // Reference: models/pointnet_pp_8dir.py:21-43 (forward) and its autograd graph.
 //
 // Everything is stream-ordered: these functions only enqueue work on `stream`; they never allocate,

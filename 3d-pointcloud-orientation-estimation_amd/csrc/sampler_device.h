@@ -1,4 +1,4 @@
-// sampler_device.h -- device-side centre sampling body, shared by sample_random_kernel (index_kernels.hip) and the step tails
+// sampler_device.h -- device-side centre sampling body, shared by sample_random_kernel (sampling_kernels.hip) and the step tails
 // (step_tail_kernels.hip), which draw the next step's centres in the otherwise idle CUs of its launch.
 #pragma once
 #include "common.h"

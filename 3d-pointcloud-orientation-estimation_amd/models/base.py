@@ -1,7 +1,7 @@
 """models/base.py -- drop-in for the reference's point-set primitives (models/base.py:4-35).
 
 Same names, argument meaning and return types (int64 indices); the work is done by the HIP
-kernels in csrc/index_kernels.hip through libpnpp_hip.so.  GPU tensors only.
+kernels in csrc/knn_kernels.hip, sampling_kernels.hip and group_kernels.hip through libpnpp_hip.so.  GPU tensors only.
 """
 import torch
 

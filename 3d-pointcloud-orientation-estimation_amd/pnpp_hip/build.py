@@ -27,7 +27,9 @@ COMMON = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wno-unused-v
 # MFMAs than the scalar forms (measured: 47.9 -> 42.1 us on the sa1 launch)
 _NOSLP = [] if os.environ.get("PNPP_SLP") else ["-fno-slp-vectorize"]
 SOURCES = {
-    "index_kernels.hip": ["-ffp-contract=off"],
+    "knn_kernels.hip": ["-ffp-contract=off"],
+    "sampling_kernels.hip": ["-ffp-contract=off"],
+    "group_kernels.hip": ["-ffp-contract=off"],
     "augment_kernels.hip": ["-ffp-contract=off"],   # float32 steps reproducible on the CPU (tests/augment_ref.py)
     "gemm_kernels.hip": [],
     "gemm_ws_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),

@@ -27,6 +27,7 @@ CASES = {
     "level2-tile-not-pow2": (777, 96, 32, 40, 32, "rand"),        # level-2 gather, S1 = 96
     "s-not-multiple-of-8": (512, 13, 32, 7, 13, "rand"),          # S1 % 4 != 0 and an odd number of four-query groups
     "duplicates": (200, 10, 16, 4, 10, "dups"),                   # exact ties between distinct rows: lowest index wins
+    "all-equal-two-tiles": (1100, 8, 32, 4, 8, "equal"),          # the fallback on the first tile, then a second tile with the previous list riding along
 }
 B = 2
 

@@ -128,8 +128,8 @@ def test_header_and_binding(h):
 
 def test_built_from_index_kernels():
     from pnpp_hip import build
-    assert "index_kernels.hip" in build.SOURCES
-    src = open(os.path.join(build.CSRC, "index_kernels.hip")).read()
+    assert "knn_kernels.hip" in build.SOURCES
+    src = open(os.path.join(build.CSRC, "knn_kernels.hip")).read()
     assert "knn_normals_kernel" in src and "pnpp_estimate_normals_ragged" in src
 
 
