@@ -29,11 +29,19 @@ def _as_points_last(xyz: torch.Tensor) -> torch.Tensor:
 
 
 class PointNetPPMvM(nn.Module):
-    """forward(xyz) -> mu (B,K) in [-pi,pi], kappa (B,K) >= 0, weight (B,K) summing to 1."""
+    """forward(xyz) -> mu (B,K) in [-pi,pi], kappa (B,K) >= 0, weight (B,K) summing to 1.
+
+    mu_init: "reference" is the reference's initialisation, head_mu all zero: every component sits on the degenerate-direction
+    fallback mu = 0, where the head passes no gradient, so mu never moves.  "spread" sets head_mu.bias of component k to
+    (cos, sin)(2 pi k / max_K) and leaves its weight zero: every component starts at its own angle with a live gradient (what
+    grid_kl needs to learn from).  state_dict keys and every other initial value are the same."""
 
     def __init__(self, max_K: int = 4, kappa_max: float = 80.0, p_drop: float = 0.4, temp: float = 0.7, sampler=None,
-                 grouper=None):
+                 grouper=None, mu_init: str = "reference"):
         super().__init__()
+        if mu_init not in ("reference", "spread"):
+            raise ValueError(f"mu_init={mu_init!r}: 'reference' or 'spread'")
+        self.mu_init = mu_init
         self.max_K, self.kappa_max, self.temp = max_K, float(kappa_max), float(temp)
         for i, (npoint, nsample, cin, mlp, whole) in enumerate(_BACKBONE, start=1):
             setattr(self, f"sa{i}", PointNetSetAbstraction(npoint, nsample, cin, list(mlp), group_all=whole,
@@ -48,6 +56,9 @@ class PointNetPPMvM(nn.Module):
         with torch.no_grad():                              # reference lines 69-73: uniform weights, undefined angles,
             for t in (self.head_pi.weight, self.head_pi.bias, self.head_mu.weight, self.head_mu.bias, self.head_kappa.bias):
                 t.zero_()                                  # kappa = softplus(W x) at the start
+            if mu_init == "spread":
+                ang = 2.0 * math.pi * torch.arange(max_K, dtype=torch.float64) / max_K
+                self.head_mu.bias.copy_(torch.stack((ang.cos(), ang.sin()), dim=1).flatten())
 
     _presampled = None
 
@@ -95,6 +106,13 @@ class PointNetPPMvM(nn.Module):
         feat = self.features(xyz, centres, drop_masks, lengths)
         return ops.mvm_heads_match_loss_backward(feat, self.head_pi, self.head_mu, self.head_kappa, vm_gt, K_gt, self.temp, self.kappa_max,
                                                  next_centres=next_centres, outputs=outputs)
+
+    def grid_kl(self, xyz: torch.Tensor, vm_gt: torch.Tensor, K_gt: torch.Tensor, centres=None, drop_masks=(None, None), lengths=None):
+        """features -> the three output heads -> ops.mvm_head_grid_kl: the per-sample KL (B,) of the ground-truth mixture from the
+        WHOLE predicted one, with the head activations, the loss and their backward in one launch.  Train on its mean."""
+        feat = self.features(xyz, centres, drop_masks, lengths)
+        raw = [ops.fc_block(feat, head, training=self.training) for head in (self.head_pi, self.head_mu, self.head_kappa)]
+        return ops.mvm_head_grid_kl(raw[0], raw[1], raw[2], vm_gt, K_gt, self.temp, self.kappa_max)
 
 
 @torch.no_grad()

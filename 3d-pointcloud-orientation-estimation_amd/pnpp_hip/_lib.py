@@ -239,6 +239,8 @@ SIGNATURES = {
     "pnpp_mvm_fc_head_match_step": (_i, [_fp] * 9 + [_i, _i, _i, _f, _f] + [_fp] * 11 + [_u64, _fp, _u64, _i, _i, _i, _fp, _i, _i, _fp, _fp]),
     "pnpp_mvm_head": (_i, [_fp, _fp, _fp, _i, _i, _f, _f, _fp, _fp, _fp, _fp]),
     "pnpp_mvm_head_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _f, _f, _fp, _fp, _fp, _fp]),
+    "pnpp_mvm_grid_kl": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
+    "pnpp_mvm_head_grid_kl": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _f, _f, _i] + [_fp] * 8),
     "pnpp_soft_ce": (_i, [_fp, _fp, _i, _i, _fp, _fp, _fp]),
     "pnpp_mvm_decode": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _f, _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnpp_orient_eval": (_i, [_fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _i, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp]),

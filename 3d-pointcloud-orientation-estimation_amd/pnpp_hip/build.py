@@ -45,6 +45,7 @@ SOURCES = {
     "gemm_wsf03_kernels.hip": _NOSLP,
     "gemm_wsq_kernels.hip": [],
     "loss_kernels.hip": [],
+    "mixture_loss_kernels.hip": [],   # the flags of loss_kernels.hip: its head form is held bit-equal to that file's head kernels
     "step_tail_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
     "optim_kernels.hip": [],
     "cls_loss_kernels.hip": [],

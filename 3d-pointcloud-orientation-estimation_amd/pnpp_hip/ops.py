@@ -1147,6 +1147,82 @@ def _rows(t: torch.Tensor, name: str, shape) -> torch.Tensor:
     return t
 
 
+def _grid_kl_args(first: torch.Tensor, name: str, vm_gt, K_gt, num):
+    """Shapes of the two mixture-KL ops: `first` (B, max_K) with max_K <= 8, vm_gt (B, max_K, 3), K_gt (B,), 2 <= num - 1 <= 1024."""
+    if first.dim() != 2:
+        raise ValueError(f"{name} has shape {tuple(first.shape)}, expected (B, max_K)")
+    B, maxK = first.shape
+    if B < 1 or not 1 <= maxK <= 8:
+        raise ValueError(f"{name} has shape {tuple(first.shape)}: 1 <= B and 1 <= max_K <= 8")
+    if not 2 <= int(num) - 1 <= 1024:
+        raise ValueError(f"num={num}: a grid of num - 1 points, 2 <= num - 1 <= 1024")
+    return B, maxK, _rows(_f32(vm_gt, "vm_gt"), "vm_gt", (B, maxK, 3)), _rows(_i32(K_gt, "K_gt"), "K_gt", (B,))
+
+
+class _MvmGridKl(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mu, kappa, w, vm_gt, K_gt, num):
+        mu = _f32(mu, "mu")
+        B, maxK, vm_gt, K32 = _grid_kl_args(mu, "mu", vm_gt, K_gt, num)
+        kappa, w = _rows(_f32(kappa, "kappa"), "kappa", (B, maxK)), _rows(_f32(w, "weight"), "weight", (B, maxK))
+        lv = torch.empty(B, device=mu.device, dtype=torch.float32)
+        grads = [torch.empty_like(mu) for _ in range(3)] if any(ctx.needs_input_grad[:3]) else [None] * 3
+        L.check(L.lib().pnpp_mvm_grid_kl(mu.data_ptr(), kappa.data_ptr(), w.data_ptr(), vm_gt.data_ptr(), K32.data_ptr(), B, maxK,
+                                         int(num), lv.data_ptr(), _p(grads[0]), _p(grads[1]), _p(grads[2]), _stream()))
+        if grads[0] is not None:
+            ctx.save_for_backward(*grads)
+        return lv
+
+    @staticmethod
+    def backward(ctx, g):
+        dmu, dk, dw = ctx.saved_tensors
+        g = g[:, None]
+        return g * dmu, g * dk, g * dw, None, None, None
+
+
+def mvm_grid_kl(mu, kappa, weight, vm_gt, K_gt, num: int = 360):
+    """KL(ground truth || prediction) of two von-Mises mixtures on decode's grid of num - 1 angles, per sample (B,): every predicted
+    component counts, with the weight the head gave it (pnpp_mvm_grid_kl).  Value and gradients in one launch, no host round trip."""
+    return _MvmGridKl.apply(mu, kappa, weight, vm_gt, K_gt, num)
+
+
+class _MvmHeadGridKl(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pi_raw, mu_raw, kappa_raw, vm_gt, K_gt, temp, kappa_max, num, outputs):
+        pi_raw = _f32(pi_raw, "pi_raw")
+        B, maxK, vm_gt, K32 = _grid_kl_args(pi_raw, "pi_raw", vm_gt, K_gt, num)
+        mu_raw = _rows(_f32(mu_raw, "mu_raw"), "mu_raw", (B, 2 * maxK))
+        kappa_raw = _rows(_f32(kappa_raw, "kappa_raw"), "kappa_raw", (B, maxK))
+        lv = torch.empty(B, device=pi_raw.device, dtype=torch.float32)
+        grads = [None] * 3
+        if any(ctx.needs_input_grad[:3]):
+            grads = [torch.empty_like(pi_raw), torch.empty_like(mu_raw), torch.empty_like(kappa_raw)]
+        outs = [torch.empty_like(pi_raw) for _ in range(3)] if outputs else [None] * 3
+        L.check(L.lib().pnpp_mvm_head_grid_kl(pi_raw.data_ptr(), mu_raw.data_ptr(), kappa_raw.data_ptr(), vm_gt.data_ptr(), K32.data_ptr(),
+                                              B, maxK, float(temp), float(kappa_max), int(num), lv.data_ptr(), _p(grads[0]), _p(grads[1]),
+                                              _p(grads[2]), _p(outs[0]), _p(outs[1]), _p(outs[2]), _stream()))
+        if grads[0] is not None:
+            ctx.save_for_backward(*grads)
+        if not outputs:
+            return lv
+        ctx.mark_non_differentiable(*outs)
+        return (lv, *outs)
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        dpi, dmr, dkr = ctx.saved_tensors
+        g = g[:, None]
+        return g * dpi, g * dmr, g * dkr, None, None, None, None, None, None
+
+
+def mvm_head_grid_kl(pi_raw, mu_raw, kappa_raw, vm_gt, K_gt, temp: float, kappa_max: Optional[float], num: int = 360,
+                     outputs: bool = False):
+    """mvm_head followed by mvm_grid_kl, and their backward, in one launch (pnpp_mvm_head_grid_kl): raw head outputs -> loss (B,), and
+    with outputs=True also the detached mu, kappa, weight (B, max_K) of the head."""
+    return _MvmHeadGridKl.apply(pi_raw, mu_raw, kappa_raw, vm_gt, K_gt, temp, float("inf") if kappa_max is None else kappa_max, num,
+                                outputs)
+
+
 @torch.no_grad()
 def mvm_decode(mu, kappa, weight=None, counts=None, num: int = 360, rel_height: float = 0.1, density: bool = False):
     """pnpp_mvm_decode: mixture parameters (B,K) -> (modes (B,K), heights (B,K), n_modes (B,) int32, angle (B,), density (B,num-1) or

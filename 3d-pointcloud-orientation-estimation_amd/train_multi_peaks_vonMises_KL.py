@@ -8,6 +8,10 @@ the reference's format (lines 127-146, per-category rows filled from the per-lab
 FIGS/loss_total.png and FIGS/loss_overview.png (lines 292-299).  match_loss is one HIP launch for the whole batch: K x K clamped/wrapped KL cost, optimal
 assignment and the weighted mean, value and gradients, with no per-sample host round trip (the reference crosses
 to the host for scipy's linear_sum_assignment once per sample, lines 74-75).
+
+Not in the reference, off by default: --loss grid-kl trains, validates and tests on the KL of the ground-truth mixture from the WHOLE
+predicted one (losses.mixture_grid_kl) instead of match_loss, and --mu-init spread starts the components at distinct angles
+(models/pointnet_pp_mvM.py says why the reference's model cannot learn mu).  The files written and their names are the same.
 """
 import argparse
 import math
@@ -20,6 +24,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
+import losses
 from dataloader_multi_peak_vonMises import PointCloudDatasetMvM
 from models.pointnet_pp_mvM import PointNetPPMvM
 from pnpp_hip import sampling, dist as pdist, ops, trainer
@@ -134,7 +139,13 @@ def _criterion(out, batch):
     return match_loss(mu_pred, kappa_pred, w_pred, batch[1], batch[1], batch[2])
 
 
-_loss = (lambda model, batch: model(batch[0]), _criterion)    # (forward, criterion): the reference times them separately
+def _criterion_grid_kl(out, batch):
+    return losses.mixture_grid_kl(out, batch[1], batch[2])
+
+
+_forward = lambda model, batch: model(batch[0])
+_loss = (_forward, _criterion)    # (forward, criterion): the reference times them separately
+_LOSSES = {"match": _loss, "grid-kl": (_forward, _criterion_grid_kl)}
 
 
 def _dataset_loaders(rank, world):
@@ -180,6 +191,10 @@ def _parser():
     ap.add_argument("--sampler", default=os.environ.get("PNPP_SAMPLER", "randperm"), choices=["randperm", "device", "fps"])
     ap.add_argument("--augment", action="store_true",
                     help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
+    ap.add_argument("--loss", default=os.environ.get("PNPP_MVM_LOSS", "match"), choices=sorted(_LOSSES),
+                    help="match: the reference's match_loss; grid-kl: KL(ground truth || whole predicted mixture) on decode's grid")
+    ap.add_argument("--mu-init", default="reference", choices=["reference", "spread"],
+                    help="reference: head_mu starts at zero (mu gets no gradient); spread: component k starts at 2 pi k / max_K")
     trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
     trainer.add_metrics_args(ap)   # --angular-metrics (PNPP_ANGULAR_METRICS): off by default
     return ap
@@ -196,8 +211,9 @@ def main(argv=None):
     if args.augment:   # every real peak of the (B,4,3) table shifts with the cloud; rows beyond K stay the zero padding
         loaders["train"] = trainer.AugmentedLoader(loaders["train"], Augment(SEED + rank), ("vm", "keep"),
                                                    None if args.synthetic else dev, counts=1)
-    model = PointNetPPMvM(sampler=args.sampler).to(dev)
-    h, best_state, best_ep = trainer.fit(model, _loss, loaders, EPOCHS, LR, dev, clip_norm=1.0, label="multi-peak vM KL",
+    model = PointNetPPMvM(sampler=args.sampler, mu_init=args.mu_init).to(dev)
+    loss = _LOSSES[args.loss]   # (forward, criterion) for train, val and test
+    h, best_state, best_ep = trainer.fit(model, loss, loaders, EPOCHS, LR, dev, clip_norm=1.0, label="multi-peak vM KL",
                                          label_index=3, n_labels=len(categories), **trainer.optim_kwargs(args))
     hist = {"total": {"train": h["train"], "val": h["val"]}}
     for i, cat in enumerate(categories):
@@ -206,7 +222,7 @@ def main(argv=None):
     errs = None
     if args.angular_metrics:   # decoded and accumulated on the device during the same pass; per category while the table takes them
         errs = AngularErrors(n_labels=len(categories) if len(categories) <= 64 else 1)
-    test_kl = trainer.evaluate(model, _loss, loaders["test"], dev, label_index=3 if errs is not None and errs.n_labels > 1 else None,
+    test_kl = trainer.evaluate(model, loss, loaders["test"], dev, label_index=3 if errs is not None and errs.n_labels > 1 else None,
                                metrics=errs)
     if errs is not None:
         summary = errs.summary()   # every rank takes part in the all-reduce

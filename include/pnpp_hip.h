@@ -378,6 +378,23 @@ int pnpp_mvm_head_bwd(const float *pi_raw, const float *mu_raw, const float *kap
                       const float *dmu, const float *dkappa, const float *dweight, int B, int K, float temp,
                       float kappa_max, float *dpi_raw, float *dmu_raw, float *dkappa_raw, void *stream);
 
+/* Mixture KL on the decode grid (csrc/mixture_loss_kernels.hip; additive to ABI 5): an objective on the WHOLE predicted mixture.
+ *   q(t) = sum_{j < K_gt} v_j vM(t; nu_j, lambda_j)   rows (nu, lambda, v) of vm_gt (B,maxK,3), v normalised by its sum over j < K_gt
+ *   p(t) = sum_{i < maxK} w_i vM(t; mu_i, kappa_i)    every predicted component, weights as given
+ *   loss_b = (2 pi / G) sum_g q(t_g) (log q(t_g) - log p(t_g)),   t_g = 2 pi g / G,  G = num - 1,  2 <= G <= 1024
+ * float64 inside, log-sum-exp over the components, so finite for every kappa <= 500; components of weight <= 0 are skipped; kappa is
+ * clamped into [0, 500] and a clamped value gets zero gradient; K_gt <= 0 or sum v <= 0: loss 0, zero gradients; K_gt > maxK is
+ * clamped.  mu, kappa, weight (B,maxK), 1 <= maxK <= 8; K_gt (B) int32.  loss_vec (B); dmu, dkappa, dweight (B,maxK) = d loss_b / d.,
+ * all three or none (NULL: evaluation only).  One launch, one workgroup per sample, no atomics: two calls are bit-identical. */
+int pnpp_mvm_grid_kl(const float *mu, const float *kappa, const float *weight, const float *vm_gt, const int32_t *K_gt, int B, int maxK,
+                     int num, float *loss_vec, float *dmu, float *dkappa, float *dweight, void *stream);
+/* The same kernel with the multi-peak head inside: pnpp_mvm_head in its prologue, pnpp_mvm_head_bwd in its epilogue (the same device
+ * functions).  dpi_raw (B,maxK), dmu_raw (B,2 maxK), dkappa_raw (B,maxK): all three or none; mu, kappa, weight (B,maxK): the head's
+ * outputs, all three or none. */
+int pnpp_mvm_head_grid_kl(const float *pi_raw, const float *mu_raw, const float *kappa_raw, const float *vm_gt, const int32_t *K_gt,
+                          int B, int maxK, float temp, float kappa_max, int num, float *loss_vec, float *dpi_raw, float *dmu_raw,
+                          float *dkappa_raw, float *mu, float *kappa, float *weight, void *stream);
+
 /* train_8dir_KL.py:60-68: loss_vec[b] = -sum p * log_softmax(logits); dlogits = softmax*sum(p) - p. */
 int pnpp_soft_ce(const float *logits, const float *p, int B, int C, float *loss_vec, float *dlogits, void *stream);
 
