@@ -167,6 +167,19 @@ class DeviceCloudBank:
         ids = torch.as_tensor(host_ids, dtype=torch.int64, device=self.bank.device)
         return self.bank[ids, :longest].contiguous(), self.lengths[ids].contiguous()
 
+    def symmetry(self, num_points: int = 1024, chunk: int = 256, **kw):
+        """The yaw symmetry of every cloud of the bank (pnpp_hip.symmetry.yaw_symmetry, which takes **kw): num_points per cloud drawn
+        with the bank's own on-device draw (counted like any other), analysed `chunk` clouds at a time -> one YawSymmetry for all
+        clouds, in bank order.  Its `order` is what symmetric_targets turns into multi-peak targets.  A cloud with fewer than num_points
+        points is drawn with replacement, and its repeated points lower the floor the profile is compared with."""
+        import torch
+        from pnpp_hip.symmetry import YawProfile, YawSymmetry, yaw_symmetry
+        parts = [yaw_symmetry(self.sample(torch.arange(i, min(i + chunk, len(self))), num_points), **kw)
+                 for i in range(0, len(self), chunk)]
+        cat = lambda pick: torch.cat([pick(p) for p in parts])
+        prof = YawProfile(cat(lambda p: p.profile.distance), cat(lambda p: p.profile.floor), parts[0].profile.table, None, None)
+        return YawSymmetry(cat(lambda p: p.order), cat(lambda p: p.count), cat(lambda p: p.angles), cat(lambda p: p.score), prof)
+
 
 class BankLoader:
     """Iterates (xyz (B,num_points,3), *targets[ids]) batches entirely on the device: the loaders' shuffle + the bank's

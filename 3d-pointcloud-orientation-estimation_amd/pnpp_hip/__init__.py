@@ -9,8 +9,9 @@
     augment Augment: a fresh yaw per cloud and draw on the device, orientation targets moved along
     decode  decode / AngularErrors: von-Mises parameters to orientations, orientations to angular-error statistics, on the device
     normals estimate_normals / with_normals: surface normals of xyz-only clouds (fused kNN + PCA), on the device
+    symmetry yaw_profile / yaw_symmetry / symmetric_targets: a cloud's yaw symmetry from its self-Chamfer profile, on the device
 """
-__all__ = ["ops", "build", "optim", "dist", "sampling", "inference", "augment", "decode", "normals", "Predictor"]
+__all__ = ["ops", "build", "optim", "dist", "sampling", "inference", "augment", "decode", "normals", "symmetry", "Predictor"]
 
 
 def __getattr__(name):

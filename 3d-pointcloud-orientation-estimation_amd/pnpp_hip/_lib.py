@@ -126,6 +126,7 @@ class AugmentDesc(C.Structure):
 
 NORMALS_NONE, NORMALS_AWAY, NORMALS_TOWARD = range(3)   # pnpp_estimate_normals' orientation modes
 NORMALS_KMIN, NORMALS_KMAX = 3, 128
+YAW_ANGLE_BLOCK, YAW_TILE, YAW_QUERIES, YAW_MAX_ORDERS = 8, 1024, 256, 16   # include/pnpp_hip.h: PNPP_YAW_*
 PNPP_OPTIM_MAX_GROUPS = 8
 ORIENT_BINS, ORIENT_STRIDE, ORIENT_MAX_LABELS = 360, 728, 64   # pnpp_orient_eval's accumulator (include/pnpp_hip.h)
 SCHED_CONSTANT, SCHED_COSINE, SCHED_STEP = range(3)
@@ -222,6 +223,12 @@ SIGNATURES = {
     # surface normals: xyz, B, N, [lengths,] k, orient, ref, out, out_stride, curv, idx, stream
     "pnpp_estimate_normals": (_i, [_fp, _i, _i, _i, _i, _fp, _fp, _i, _fp, _fp, _fp]),
     "pnpp_estimate_normals_ragged": (_i, [_fp, _i, _i, _fp, _i, _i, _fp, _fp, _i, _fp, _fp, _fp]),
+    # yaw symmetry: xyz, B, N, [lengths,] centre, table, G, workspace, bytes, nearest_dist, nearest_idx, stream
+    "pnpp_yaw_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pnpp_yaw_profile": (_i, [_fp, _i, _i, _fp, _fp, _i, _fp, _sz, _fp, _fp, _fp]),
+    "pnpp_yaw_profile_ragged": (_i, [_fp, _i, _i, _fp, _fp, _fp, _i, _fp, _sz, _fp, _fp, _fp]),
+    # workspace, bytes, B, N, lengths, G, tol, orders (host), n_orders, distance, floor, score, order, count, angles, angle_stride, stream
+    "pnpp_yaw_symmetry": (_i, [_fp, _sz, _i, _i, _fp, _i, _f, C.POINTER(C.c_int32), _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _fp]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

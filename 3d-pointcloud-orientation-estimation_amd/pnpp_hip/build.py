@@ -31,6 +31,7 @@ SOURCES = {
     "sampling_kernels.hip": ["-ffp-contract=off"],
     "group_kernels.hip": ["-ffp-contract=off"],
     "augment_kernels.hip": ["-ffp-contract=off"],   # float32 steps reproducible on the CPU (tests/augment_ref.py)
+    "symmetry_kernels.hip": ["-ffp-contract=off"],  # exact_dist.h's recipe and the rotation, restated in tests/symmetry_ref.py
     "gemm_kernels.hip": [],
     "gemm_ws_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
     "dw_kernels.hip": [],

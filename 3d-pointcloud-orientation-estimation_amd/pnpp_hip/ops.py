@@ -232,6 +232,51 @@ def estimate_normals(xyz: torch.Tensor, k: int, mode: int = L.NORMALS_NONE, ref:
     return out, curv, idx
 
 
+def yaw_profile(xyz: torch.Tensor, centre: torch.Tensor, table: torch.Tensor, lengths=None, nearest: bool = False, decide=None):
+    """Two launches: the self-Chamfer profile of every cloud against its own copy turned about +Y by each row (cos, sin) of `table`
+    (G, 2), about centre (B, 3), and the kernel that finishes its float64 partial sums (include/pnpp_hip.h: pnpp_yaw_profile,
+    pnpp_yaw_symmetry; pnpp_hip.symmetry is the user-level module).
+    -> dict: distance (B,G), floor (B,), nearest_dist (B,G,N) float32 and nearest_idx (B,G,N) int32 or None; with
+    decide=(tol, orders, angle_stride) -- the table then has to be the uniform grid, every order has to divide G -- also score (B,G),
+    order (B,) int32, count (B,) int32 and angles (B, angle_stride).  lengths (B,): a ragged batch, rows at or beyond a cloud's length
+    are never read.  No read-back: capturable once `lengths` is None or a device tensor."""
+    xyz, centre, table = _f32(xyz, "xyz"), _f32(centre, "centre"), _f32(table, "table")
+    if xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError(f"xyz must be (B, N, 3), got {tuple(xyz.shape)}")
+    B, N, _ = xyz.shape
+    if tuple(centre.shape) != (B, 3):
+        raise ValueError(f"centre must be ({B}, 3), one centre per cloud, got {tuple(centre.shape)}")
+    if table.dim() != 2 or table.shape[1] != 2:
+        raise ValueError(f"table must be (G, 2) rows of (cos, sin), got {tuple(table.shape)}")
+    G = table.shape[0]
+    dev = xyz.device
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, B, N, dev)
+    nbytes = L.lib().pnpp_yaw_workspace_bytes(B, N, G)
+    ws = _workspace(nbytes, dev)
+    r = {"distance": torch.empty(B, G, device=dev, dtype=torch.float32), "floor": torch.empty(B, device=dev, dtype=torch.float32),
+         "nearest_dist": torch.empty(B, G, N, device=dev, dtype=torch.float32) if nearest else None,
+         "nearest_idx": torch.empty(B, G, N, device=dev, dtype=torch.int32) if nearest else None}
+    tail = (centre.data_ptr(), table.data_ptr(), G, ws.data_ptr(), nbytes, _p(r["nearest_dist"]), _p(r["nearest_idx"]), _stream())
+    if lengths is not None:
+        L.check(L.lib().pnpp_yaw_profile_ragged(xyz.data_ptr(), B, N, lengths.data_ptr(), *tail))
+    else:
+        L.check(L.lib().pnpp_yaw_profile(xyz.data_ptr(), B, N, *tail))
+    tol, orders, n_orders, stride = 0.0, None, 0, 0
+    if decide is not None:
+        tol, order_list, stride = float(decide[0]), [int(m) for m in decide[1]], int(decide[2])
+        n_orders = len(order_list)
+        orders = (C.c_int32 * max(n_orders, 1))(*order_list)
+        r["score"] = torch.empty(B, G, device=dev, dtype=torch.float32)
+        r["order"] = torch.empty(B, device=dev, dtype=torch.int32)
+        r["count"] = torch.empty(B, device=dev, dtype=torch.int32)
+        r["angles"] = torch.empty(B, stride, device=dev, dtype=torch.float32)
+    L.check(L.lib().pnpp_yaw_symmetry(ws.data_ptr(), nbytes, B, N, _p(lengths), G, tol, orders, n_orders, r["distance"].data_ptr(),
+                                      r["floor"].data_ptr(), _p(r.get("score")), _p(r.get("order")), _p(r.get("count")),
+                                      _p(r.get("angles")), stride, _stream()))
+    return r
+
+
 def farthest_point_sample(xyz: torch.Tensor, npoint: int, start: Optional[torch.Tensor] = None, lengths=None) -> torch.Tensor:
     """lengths (B,): a ragged batch -- row b is the sampling of xyz[b, :lengths[b]] alone (npoint may exceed a length, as it may
     exceed N); start[b] < lengths[b].  Without `start` the first index of cloud b is torch.randint(0, lengths[b]) on the host

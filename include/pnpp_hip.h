@@ -1037,6 +1037,41 @@ int pnpp_estimate_normals(const float *xyz, int B, int N, int k, int orient, con
 int pnpp_estimate_normals_ragged(const float *xyz, int B, int N, const int32_t *lengths, int k, int orient, const float *ref, float *out,
                                  int out_stride, float *curv, int32_t *idx, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Yaw symmetry of a cloud from its own geometry (additive to ABI 5): under which rotations about +Y does the cloud map onto itself?
+ * For cloud b with valid points p_i (i < Nv), centre c = centre[b] (x and z are used) and table rows (cs_g, sn_g), g < G -- every
+ * float32 step one IEEE operation, in this order, unfused:
+ *   centre       q_i = (p_i.x - c.x, p_i.y, p_i.z - c.z);
+ *   rotate       x' = fl(fl(cs x) + fl(sn z)), z' = fl(fl(cs z) - fl(sn x)), y' = y       (pnpp_augment_clouds' order);
+ *   nearest      d[g,i] = min over j < Nv of (dx dx + dy dy) + dz dz between rot_g(q_i) and q_j, the lowest j among equal distances;
+ *   profile      D[b,g] = (float) (sum_i (double) d[g,i] / Nv), the sum in float64 in a fixed order;
+ *   floor        nu[b]: the same at the identity rotation (1, 0) with j != i -- the mean squared distance to the nearest OTHER point;
+ *                0 when Nv = 1.
+ * pnpp_yaw_profile leaves per-workgroup float64 partial sums in `workspace` (pnpp_yaw_workspace_bytes(B, N, G) bytes, 0 with a message
+ * for non-positive sizes); nearest_dist / nearest_idx (B,G,N), both or neither, receive d[g,i] and its j (0 and -1 for i >= Nv).
+ * _ragged: lengths (B) int32 on the device, Nv = min(max(lengths[b], 1), N); rows at or beyond Nv are never read (they may hold NaN).
+ * pnpp_yaw_symmetry finishes the sums of that workspace (same B, N, lengths, G) into distance (B,G) and floor (B) and, when the four
+ * decision outputs are given (all or none), forms
+ *   S[g] = D[g] + D[(G - g) % G]      the symmetric Chamfer distance: the mirror index is the other direction;
+ *   score[g] = S[g] / (2 nu)          reported only (inf or nan where nu = 0);
+ *   bound = fl(fl(2 nu) tol);         order 0 (continuous) if S[g] <= bound for every g >= 1; else the largest m of `orders` with
+ *                                     S[k G / m] <= bound for k = 1..m-1; else 1.  The table is taken to be the uniform grid 2 pi g / G.
+ * count (B) = order; angles (B, angle_stride) = (float) (2 pi k / order) for k < order, zeros beyond.  `orders` is a HOST array of
+ * n_orders <= PNPP_YAW_MAX_ORDERS values, each >= 2 and dividing G; angle_stride >= the largest of them; tol finite and >= 0.
+ * No atomics: two calls give the same bits.  Both launches can be captured in a graph; nothing is read back.  B <= 65535. */
+#define PNPP_YAW_ANGLE_BLOCK 8   /* rotations a lane holds for its query (one of them the floor, in a cloud's first block)     */
+#define PNPP_YAW_TILE 1024       /* candidates staged in LDS per pass: N above it loops                                       */
+#define PNPP_YAW_QUERIES 256     /* queries per workgroup                                                                     */
+#define PNPP_YAW_MAX_ORDERS 16
+size_t pnpp_yaw_workspace_bytes(int B, int N, int G);
+int pnpp_yaw_profile(const float *xyz, int B, int N, const float *centre, const float *table, int G, void *workspace,
+                     size_t workspace_bytes, float *nearest_dist, int32_t *nearest_idx, void *stream);
+int pnpp_yaw_profile_ragged(const float *xyz, int B, int N, const int32_t *lengths, const float *centre, const float *table, int G,
+                            void *workspace, size_t workspace_bytes, float *nearest_dist, int32_t *nearest_idx, void *stream);
+int pnpp_yaw_symmetry(const void *workspace, size_t workspace_bytes, int B, int N, const int32_t *lengths, int G, float tol,
+                      const int32_t *orders, int n_orders, float *distance, float *floor, float *score, int32_t *order, int32_t *count,
+                      float *angles, int angle_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,8 +76,26 @@ def multi_peak_clouds(B, N, seed):
     return torch.cat([xw, xb])[order].contiguous(), vm[order].contiguous(), K[order].contiguous(), kind[order].contiguous()
 
 
+def derived_targets(data, dev, points):
+    """The training table of a user who has one heading per cloud and no K: the clouds go into a DeviceCloudBank, bank.symmetry reads
+    each cloud's yaw symmetry from its own geometry and symmetric_targets turns heading + order into (vm_gt, K_gt).
+    -> (the data with the derived table, the share of clouds whose derived order equals the generator's K)"""
+    from dataloader_common import DeviceCloudBank
+    from pnpp_hip.symmetry import symmetric_targets
+    xyz, vm, K, kind = data
+    sym = DeviceCloudBank(list(xyz.numpy()), dev).symmetry(num_points=points)
+    vm_d, K_d = symmetric_targets(vm[:, 0, 0].to(dev), sym)
+    orders = sym.order.cpu()
+    return (xyz, vm_d.cpu().contiguous(), K_d.cpu().contiguous(), kind), {
+        "order_equals_generator": round(float((orders == K).float().mean()), 4),
+        "order_histogram": {str(int(o)): int((orders == o).sum()) for o in orders.unique()},
+        "wedge_order_1": round(float((orders[kind == 0] == 1).float().mean()), 4),
+        "box_order_2": round(float((orders[kind == 1] == 2).float().mean()), 4)}
+
+
 def multi_peak(args, dev):
-    """match_loss + mu_init="reference" against grid_kl + mu_init="spread", same seed, same clouds."""
+    """match_loss + mu_init="reference" against grid_kl + mu_init="spread", same seed, same clouds.  --derived-gt: the training table
+    comes from derived_targets; the held-out errors are still measured against the generator's own targets."""
     from models.pointnet_pp_mvM import PointNetPPMvM
     from pnpp_hip import ops, sampling, trainer
     from pnpp_hip.decode import AngularErrors
@@ -89,6 +107,9 @@ def multi_peak(args, dev):
                        f"{args.epochs} epochs, Adam lr 1e-3, clip 1.0, device-side centre sampling, hipGraph step; held-out errors by "
                        f"Predictor.orientation + AngularErrors (decode: num 360, rel_height 0.1), label 0 = wedge, 1 = box",
            "runs": {}}
+    if args.derived_gt:
+        train, out["derived_gt"] = derived_targets(train, dev, args.points)
+        out["workload"] += "; TRAINING targets derived from the clouds (bank.symmetry, 72 angles, tol 1.3 -> symmetric_targets)"
     losses = {"match": lambda m, b: ops.match_loss(*m(b[0]), b[1], b[2]), "grid-kl": lambda m, b: m.grid_kl(b[0], b[1], b[2])}
     for loss_name, mu_init in (("match", "reference"), ("grid-kl", "spread")):
         torch.manual_seed(42)
@@ -137,6 +158,8 @@ def main():
                     help="single-peak model only: constant-rate Adam, then warm-up + cosine, decoupled weight decay and averaged weights")
     ap.add_argument("--multi-peak", action="store_true",
                     help="the multi-peak model only: match_loss + reference initialisation against grid_kl + spread initialisation")
+    ap.add_argument("--derived-gt", action="store_true",
+                    help="with --multi-peak: K and the peak set of the training clouds come from DeviceCloudBank.symmetry, not the generator")
     args = ap.parse_args()
     if args.multi_peak:
         from pnpp_hip import ops
