@@ -192,11 +192,16 @@ class BankLoader:
     None), computed after the bank's draw and before `augment`, which then turns the normals with the cloud.  Augment's jitter moves
     the points and not the normals: a jittered batch carries the normals of the surface the points were drawn from.
     channels_first=True yields that element as its (B, 6, num_points) transpose (a view), what PointNetPlusPlusCls and the
-    six-channel PointNet take.  The default normals=None changes nothing: same tensors, same draws, same launches."""
+    six-channel PointNet take.  The default normals=None changes nothing: same tensors, same draws, same launches.
+    view (a pnpp_hip.views.SingleView): the bank's draw takes view_points rows (default 2 num_points) and the view removes what one
+    viewer cannot see of them, before the normals and the augmentation.  With view.resample == num_points the batch is again
+    (B, num_points, 3) and everything after it is as without a view; without resampling the batch is ragged -- survivors first, zeros
+    after -- its per-cloud lengths are appended as the batch's last element and `augment` gets them as lengths= (normals= needs the
+    uniform batch).  The default view=None changes nothing: same tensors, same draws, same launches."""
 
     def __init__(self, bank: DeviceCloudBank, targets, num_points: int, batch: int, shuffle: bool, seed: int = 0,
                  drop_last: bool = False, augment=None, kinds=None, counts=None, normals=None, normals_orient="centroid",
-                 channels_first: bool = False):
+                 channels_first: bool = False, view=None, view_points=None):
         import torch
         self.bank, self.num_points, self.batch, self.shuffle, self.drop_last = bank, num_points, batch, shuffle, drop_last
         if normals is not None and not 3 <= int(normals) <= min(128, int(num_points)):
@@ -205,6 +210,12 @@ class BankLoader:
         if augment is not None and (kinds is None or len(kinds) != len(targets)):
             raise ValueError(f"BankLoader: augment needs one kind per target ({len(targets)}), got {kinds}")
         self.augment, self.kinds, self.counts = augment, (None if kinds is None else tuple(kinds)), counts
+        if view is not None:
+            if view.resample is not None and view.resample != num_points:
+                raise ValueError(f"BankLoader: view.resample={view.resample} must be num_points={num_points} (or None: a ragged batch)")
+            if view.resample is None and normals is not None:
+                raise ValueError("BankLoader: normals= needs uniform clouds: give the view resample=num_points")
+        self.view, self.view_points = view, (2 * int(num_points) if view_points is None else int(view_points))
         self.targets = [t.to(bank.bank.device) for t in targets]
         self.gen = torch.Generator().manual_seed(seed)
 
@@ -221,12 +232,20 @@ class BankLoader:
             if self.drop_last and len(ids) < self.batch:
                 break
             dev_ids = ids.to(self.bank.bank.device)
-            batch = (self.bank.sample(dev_ids, self.num_points), *(t[dev_ids] for t in self.targets))
+            lengths = None
+            if self.view is None:
+                batch = (self.bank.sample(dev_ids, self.num_points), *(t[dev_ids] for t in self.targets))
+            else:
+                seen = self.view(self.bank.sample(dev_ids, self.view_points))
+                if self.view.resample is None:
+                    seen, lengths = seen
+                batch = (seen, *(t[dev_ids] for t in self.targets))
             if self.normals is not None:
                 from pnpp_hip.normals import with_normals
                 batch = (with_normals(batch[0], self.normals, self.normals_orient), *batch[1:])
             if self.augment is not None:
-                batch = self.augment(*batch, kinds=self.kinds, counts=None if self.counts is None else batch[1 + self.counts])
+                kw = {} if lengths is None else {"lengths": lengths}
+                batch = self.augment(*batch, kinds=self.kinds, counts=None if self.counts is None else batch[1 + self.counts], **kw)
             if self.channels_first:
                 batch = (batch[0].transpose(1, 2), *batch[1:])
-            yield batch
+            yield batch if lengths is None else (*batch, lengths)

@@ -124,7 +124,15 @@ class AugmentDesc(C.Structure):
                 ("n_targets", C.c_int), ("targets", AugmentTarget * PNPP_AUG_MAX_TARGETS), ("dirs8", _fp)]
 
 
-NORMALS_NONE, NORMALS_AWAY, NORMALS_TOWARD = range(3)   # pnpp_estimate_normals' orientation modes
+VIEW_MAX_G, VIEW_DIRS, VIEW_ANGLES = 128, 1, 2
+
+
+class ViewDesc(C.Structure):   # pnpp_view_desc
+    _fields_ = [("G", C.c_int), ("splat", C.c_int), ("thickness", C.c_float), ("elev_lo", C.c_float), ("elev_hi", C.c_float),
+                ("drop", C.c_float), ("min_keep", C.c_int), ("flags", C.c_uint), ("view_dirs", _fp)]
+
+
+NORMALS_NONE, NORMALS_AWAY, NORMALS_TOWARD = range(3)  # pnpp_estimate_normals' orientation modes
 NORMALS_KMIN, NORMALS_KMAX = 3, 128
 YAW_ANGLE_BLOCK, YAW_TILE, YAW_QUERIES, YAW_MAX_ORDERS = 8, 1024, 256, 16   # include/pnpp_hip.h: PNPP_YAW_*
 PNPP_OPTIM_MAX_GROUPS = 8
@@ -229,6 +237,8 @@ SIGNATURES = {
     "pnpp_yaw_profile_ragged": (_i, [_fp, _i, _i, _fp, _fp, _fp, _i, _fp, _sz, _fp, _fp, _fp]),
     # workspace, bytes, B, N, lengths, G, tol, orders (host), n_orders, distance, floor, score, order, count, angles, angle_stride, stream
     "pnpp_yaw_symmetry": (_i, [_fp, _sz, _i, _i, _fp, _i, _f, C.POINTER(C.c_int32), _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _fp]),
+    # single-view scan: seed, stream id, xyz_in, xyz_out, lengths_in, lengths_out, index_out, B, N, C, desc, params, stream
+    "pnpp_view_clouds": (_i, [_u64, _u64, _fp, _fp, _fp, _fp, _fp, _i, C.c_int64, _i, C.POINTER(ViewDesc), _fp, _fp]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

@@ -502,6 +502,91 @@ def augment_clouds(xyz: torch.Tensor, seed: int, stream_id: int, targets=(), kin
     return out, outs, params
 
 
+VIEW_ELEVATION = (-0.5235987755982988, 1.0471975511965976)   # (-pi/6, pi/3): from slightly below to well above
+
+
+def view_resolution(N: int) -> int:
+    """The default depth-buffer side for clouds of N rows: about one point per cell, at most the kernel's 128."""
+    import math
+    return min(L.VIEW_MAX_G, max(1, math.isqrt(max(int(N), 1) - 1) + 1))
+
+
+def view_plan(xyz_shape, resolution=None, splat: int = 1, thickness: float = 0.1, elevation=VIEW_ELEVATION, drop: float = 0.0,
+              min_keep: int = 1, lengths=None, view_dirs=None, angles=None):
+    """Host-side validation of a view_clouds call, from shapes and numbers alone (runs without a GPU): -> (G, splat, thickness,
+    (lo, hi), drop, min_keep, flags).  What pnpp_view_clouds would refuse raises ValueError here, before anything is counted."""
+    import math
+    if len(xyz_shape) != 3 or xyz_shape[2] not in (3, 6):
+        raise ValueError(f"view_clouds: xyz must be (B, N, 3) or (B, N, 6), got {tuple(xyz_shape)}")
+    B, N = int(xyz_shape[0]), int(xyz_shape[1])
+    if not 1 <= B <= 65535 or not 1 <= N <= 1 << 24:
+        raise ValueError(f"view_clouds: B must be 1..65535 and N 1..2^24, got B={B} N={N}")
+    G = view_resolution(N) if resolution is None else int(resolution)
+    if not 1 <= G <= L.VIEW_MAX_G:
+        raise ValueError(f"view_clouds: resolution={resolution} must be 1..{L.VIEW_MAX_G}")
+    if int(splat) != splat or not 0 <= int(splat) <= 2:
+        raise ValueError(f"view_clouds: splat={splat} must be 0, 1 or 2")
+    thickness = float(thickness)
+    if not 0.0 <= thickness < float("inf"):
+        raise ValueError(f"view_clouds: thickness={thickness} must be finite and >= 0")
+    try:
+        lo, hi = (float(v) for v in elevation)
+    except (TypeError, ValueError):
+        raise ValueError(f"view_clouds: elevation must be a (lo, hi) pair, got {elevation!r}") from None
+    if not -math.pi / 2 <= lo <= hi <= math.pi / 2:
+        raise ValueError(f"view_clouds: elevation=(lo, hi) needs -pi/2 <= lo <= hi <= pi/2, got {elevation}")
+    drop = float(drop)
+    if not 0.0 <= drop < 1.0:
+        raise ValueError(f"view_clouds: drop={drop} must be in [0, 1)")
+    if int(min_keep) != min_keep or not 0 <= int(min_keep) <= N:
+        raise ValueError(f"view_clouds: min_keep={min_keep} must be 0..N={N}")
+    if lengths is not None and (not isinstance(lengths, torch.Tensor) or tuple(lengths.shape) != (B,)
+                                or lengths.dtype not in (torch.int32, torch.int64)):
+        raise ValueError(f"view_clouds: lengths must be an integer tensor of shape ({B},)")
+    if view_dirs is not None and angles is not None:
+        raise ValueError("view_clouds: view_dirs or angles, not both")
+    flags = 0
+    for t, cols, flag, name in ((view_dirs, 3, L.VIEW_DIRS, "view_dirs"), (angles, 2, L.VIEW_ANGLES, "angles")):
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, cols) or t.dtype != torch.float32:
+                raise ValueError(f"view_clouds: {name} must be a float32 tensor of shape ({B}, {cols})")
+            flags = flag
+    return G, int(splat), thickness, (lo, hi), drop, int(min_keep), flags
+
+
+def view_clouds(xyz: torch.Tensor, seed: int, stream_id: int, lengths=None, resolution=None, splat: int = 1, thickness: float = 0.1,
+                elevation=VIEW_ELEVATION, drop: float = 0.0, min_keep: int = 1, view_dirs=None, angles=None, index: bool = False):
+    """What one viewer at infinity sees of each cloud, in one launch (pnpp_view_clouds): -> (xyz', lengths', params[, index]).
+
+    xyz (B,N,3) or (B,N,6) float32, lengths (B,) or None.  Cloud b is seen from a direction drawn per cloud (azimuth uniform about
+    +Y, elevation uniform in `elevation`), or from view_dirs (B,3) -- towards the viewer -- or angles (B,2) = [azimuth, elevation].  A
+    depth buffer of resolution^2 cells over the view plane (None: about one point per cell) keeps, per cell and its `splat`
+    neighbours, the depth nearest the viewer; a point survives when it lies within thickness x extent of it, and then with the
+    cloud's own probability 1 - ratio, ratio uniform in [0, drop).  xyz' holds the survivors in their input order followed by exact
+    zeros, lengths' (B,) int32 their number; a cloud left with fewer than min_keep passes through whole.  params (B,8) = [v_x, v_y,
+    v_z, azimuth, elevation, cell, kept, passed_through]; index (B,N) int32: the source row of each output row, -1 in the padding.
+    A pure function of (seed, stream_id); nothing is read back."""
+    G, splat, thickness, (lo, hi), drop, min_keep, flags = view_plan(xyz.shape, resolution, splat, thickness, elevation, drop, min_keep,
+                                                                     lengths, view_dirs, angles)
+    xyz = _f32(xyz, "xyz")
+    B, N, Cc = xyz.shape
+    d = L.ViewDesc()
+    d.G, d.splat, d.thickness, d.elev_lo, d.elev_hi, d.drop, d.min_keep, d.flags = G, splat, thickness, lo, hi, drop, min_keep, flags
+    given = view_dirs if view_dirs is not None else angles
+    if given is not None:
+        given = _f32(given, "view_dirs")   # held until the launch is enqueued
+        d.view_dirs = given.data_ptr()
+    if lengths is not None:
+        lengths = _i32(lengths, "lengths")
+    out = torch.empty_like(xyz)
+    lengths_out = torch.empty(B, device=xyz.device, dtype=torch.int32)
+    params = torch.empty(B, 8, device=xyz.device, dtype=torch.float32)
+    idx = torch.empty(B, N, device=xyz.device, dtype=torch.int32) if index else None
+    L.check(L.lib().pnpp_view_clouds(int(seed) & (2**64 - 1), int(stream_id) & (2**64 - 1), xyz.data_ptr(), out.data_ptr(), _p(lengths),
+                                     lengths_out.data_ptr(), _p(idx), B, N, Cc, C.byref(d), params.data_ptr(), _stream()))
+    return (out, lengths_out, params, idx) if index else (out, lengths_out, params)
+
+
 class _IndexPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, idx):

@@ -67,6 +67,27 @@ class AugmentedLoader:
             yield self.augment(*batch, kinds=self.kinds, counts=None if self.counts is None else batch[1 + self.counts])
 
 
+class ViewLoader:
+    """Any loader that yields (xyz, ...), the first element of each batch passed through `view` (pnpp_hip.views.SingleView): one
+    launch that removes what a viewer on one side cannot see.  The cloud is not moved, so the targets stay as they are, and an
+    AugmentedLoader goes around this one.  A resampling view (resample=num) yields uniform (B, num, 3) clouds and batches of the
+    loader's own layout; a ragged one appends the per-cloud lengths as the batch's last element.  device: move the batch there
+    first (a host DataLoader); None: the batch is already on the device."""
+
+    def __init__(self, loader, view, device=None):
+        self.loader, self.view, self.device = loader, view, device
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for batch in self.loader:
+            if self.device is not None:
+                batch = tuple(b.to(self.device, non_blocking=True) for b in batch)
+            seen = self.view(batch[0])
+            yield (seen, *batch[1:]) if self.view.resample is not None else (seen[0], *batch[1:], seen[1])
+
+
 LossFn = Union[Callable, Tuple[Callable, Callable]]
 
 

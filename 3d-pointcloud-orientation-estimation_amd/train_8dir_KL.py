@@ -17,6 +17,7 @@ from dataloader_8dir_sampled import PointCloudDataset
 from models.pointnet_pp_8dir import DIRS_8, PointNetPP8Dir
 from pnpp_hip import sampling, dist as pdist, ops, trainer
 from pnpp_hip.augment import Augment
+from pnpp_hip.views import SingleView
 
 ROOT = trainer.env_path("PNPP_ROOT", "/home/pablo/ForwardNet/data/2d_1to8_sampled")
 RES = trainer.env_path("PNPP_RES", "/home/pablo/ForwardNet/results/8dir_KLdiv_0926")
@@ -71,16 +72,21 @@ def _dataset_loaders(rank, world):
                           num_workers=4, pin_memory=True) for k, v in parts.items()}
 
 
-def _synthetic_loaders(n, rank, augment=False):
+def _synthetic_loaders(n, rank, augment=False, views=False):
     import synthetic
     out = {}
     for i, (name, frac) in enumerate((("train", 0.7), ("val", 0.15), ("test", 0.15))):
         m = max(BATCH, int(n * frac))
         xyz, _, _, fwd = synthetic.rotated_clouds(m, NUM_POINTS, seed=SEED + 1000 * i + rank)
         if augment and name == "train":   # the loader keeps the forward axis; the labels come out of the augmentation launch
-            out[name] = trainer.AugmentedLoader(trainer.SyntheticLoader([xyz, fwd], BATCH, True, device), Augment(SEED + rank), ("dir8",))
+            plain = trainer.SyntheticLoader([xyz, fwd], BATCH, True, device)
+            if views:   # the cloud is not moved by the view: the forward axis stays, and the augmentation goes around it
+                plain = trainer.ViewLoader(plain, SingleView(SEED + rank, resample=NUM_POINTS))
+            out[name] = trainer.AugmentedLoader(plain, Augment(SEED + rank), ("dir8",))
         else:
             out[name] = trainer.SyntheticLoader([xyz, synthetic.dir8_soft_labels(fwd, DIRS_8)], BATCH, name == "train", device)
+            if views and name == "train":
+                out[name] = trainer.ViewLoader(out[name], SingleView(SEED + rank, resample=NUM_POINTS))
     return ["synthetic"], out
 
 
@@ -90,6 +96,9 @@ def _parser():
     ap.add_argument("--sampler", default=os.environ.get("PNPP_SAMPLER", "randperm"), choices=["randperm", "device", "fps"])
     ap.add_argument("--augment", action="store_true",
                     help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
+    ap.add_argument("--views", action="store_true", default=os.environ.get("PNPP_VIEWS") == "1",
+                    help="every training cloud as one viewer sees it: a fresh direction per cloud and draw, the hidden side removed on the device, "
+                         "resampled to NUM_POINTS (train split only; in front of --augment)")
     trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
     return ap
 
@@ -105,7 +114,9 @@ def main(argv=None):
     sampling.reset(0)   # the device-side centre sampler restarts its stream too: a run is a function of SEED
     RES.mkdir(parents=True, exist_ok=True), FIGS.mkdir(parents=True, exist_ok=True)
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else device
-    labels, loaders = _synthetic_loaders(args.synthetic, rank, args.augment) if args.synthetic else _dataset_loaders(rank, world)
+    labels, loaders = _synthetic_loaders(args.synthetic, rank, args.augment, args.views) if args.synthetic else _dataset_loaders(rank, world)
+    if args.views and not args.synthetic:   # a host DataLoader's batch goes to the device first
+        loaders["train"] = trainer.ViewLoader(loaders["train"], SingleView(SEED + rank, resample=NUM_POINTS), dev)
     model = PointNetPP8Dir(sampler=args.sampler).to(dev)
     hist, best_state, best_ep = trainer.fit(model, _loss, loaders, EPOCHS, LR, dev, label="8-dir soft CE", label_index=2,
                                             n_labels=len(labels), **trainer.optim_kwargs(args))

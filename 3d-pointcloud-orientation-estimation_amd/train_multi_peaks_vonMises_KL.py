@@ -29,6 +29,7 @@ from dataloader_multi_peak_vonMises import PointCloudDatasetMvM
 from models.pointnet_pp_mvM import PointNetPPMvM
 from pnpp_hip import sampling, dist as pdist, ops, trainer
 from pnpp_hip.augment import Augment
+from pnpp_hip.views import SingleView
 from pnpp_hip.decode import AngularErrors
 
 ROOT = trainer.env_path("PNPP_ROOT", "/home/pablo/ForwardNet/data/MN40_multi_peak_vM_gt")
@@ -195,6 +196,9 @@ def _parser():
                     help="match: the reference's match_loss; grid-kl: KL(ground truth || whole predicted mixture) on decode's grid")
     ap.add_argument("--mu-init", default="reference", choices=["reference", "spread"],
                     help="reference: head_mu starts at zero (mu gets no gradient); spread: component k starts at 2 pi k / max_K")
+    ap.add_argument("--views", action="store_true", default=os.environ.get("PNPP_VIEWS") == "1",
+                    help="every training cloud as one viewer sees it: a fresh direction per cloud and draw, the hidden side removed on the device, "
+                         "resampled to NUM_POINTS (train split only; in front of --augment)")
     trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
     trainer.add_metrics_args(ap)   # --angular-metrics (PNPP_ANGULAR_METRICS): off by default
     return ap
@@ -208,6 +212,8 @@ def main(argv=None):
     RES.mkdir(parents=True, exist_ok=True), FIGS.mkdir(parents=True, exist_ok=True)
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else device
     categories, loaders = _synthetic_loaders(args.synthetic, rank) if args.synthetic else _dataset_loaders(rank, world)
+    if args.views:   # the cloud is not moved: the targets stay, and the augmentation goes around the view
+        loaders["train"] = trainer.ViewLoader(loaders["train"], SingleView(SEED + rank, resample=NUM_POINTS), None if args.synthetic else dev)
     if args.augment:   # every real peak of the (B,4,3) table shifts with the cloud; rows beyond K stay the zero padding
         loaders["train"] = trainer.AugmentedLoader(loaders["train"], Augment(SEED + rank), ("vm", "keep"),
                                                    None if args.synthetic else dev, counts=1)

@@ -24,6 +24,7 @@ from dataloader_single_peak_vonMises import PointCloudDatasetVonMises
 from models.pointnet_pp_vonMises import PointNetPPVonMises
 from pnpp_hip import sampling, dist as pdist, ops, trainer
 from pnpp_hip.augment import Augment
+from pnpp_hip.views import SingleView
 from pnpp_hip.decode import AngularErrors
 
 ROOT = trainer.env_path("PNPP_ROOT", "/home/pablo/ForwardNet/data/chair_toilet_sofa_plant_bowl_bottle")
@@ -100,6 +101,9 @@ def _parser():
     ap.add_argument("--sampler", default=os.environ.get("PNPP_SAMPLER", "randperm"), choices=["randperm", "device", "fps"])
     ap.add_argument("--augment", action="store_true",
                     help="a fresh random yaw about +Y for every training cloud and draw, on the device, with the target moved along (train split only)")
+    ap.add_argument("--views", action="store_true", default=os.environ.get("PNPP_VIEWS") == "1",
+                    help="every training cloud as one viewer sees it: a fresh direction per cloud and draw, the hidden side removed on the device, "
+                         "resampled to NUM_POINTS (train split only; in front of --augment)")
     trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
     trainer.add_metrics_args(ap)   # --angular-metrics (PNPP_ANGULAR_METRICS): off by default
     return ap
@@ -118,6 +122,8 @@ def main(argv=None):
     RES.mkdir(parents=True, exist_ok=True), FIGS.mkdir(parents=True, exist_ok=True)
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else device
     loaders = _synthetic_loaders(args.synthetic, rank) if args.synthetic else _dataset_loaders(rank, world)
+    if args.views:   # the cloud is not moved: the targets stay, and the augmentation goes around the view
+        loaders["train"] = trainer.ViewLoader(loaders["train"], SingleView(SEED + rank, resample=NUM_POINTS), None if args.synthetic else dev)
     if args.augment:   # vm_gt rows are [mu, kappa]: mu follows the cloud; a host DataLoader's batch goes to the device first
         loaders["train"] = trainer.AugmentedLoader(loaders["train"], Augment(SEED + rank), ("vm",), None if args.synthetic else dev)
     model = PointNetPPVonMises(sampler=args.sampler).to(dev)

@@ -1072,6 +1072,51 @@ int pnpp_yaw_symmetry(const void *workspace, size_t workspace_bytes, int B, int 
                       const int32_t *orders, int n_orders, float *distance, float *floor, float *score, int32_t *order, int32_t *count,
                       float *angles, int angle_stride, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Single-view scan simulation (additive to ABI 5): what one viewer at infinity sees of each cloud -- an orthographic depth-buffer
+ * visibility test, survivors compacted in input order.  For cloud b with valid rows n < Nv (Nv = min(max(lengths_in[b], 1), N), or N
+ * when lengths_in is NULL); every float32 step one IEEE operation, in this order, unfused:
+ *   direction    Philox4x32-10 words w of counter (0xFFFFFFFF, b, stream_id), key seed (pnpp_augment_clouds' cloud words):
+ *                azimuth phi = w0 2 pi / 2^32 about +Y, elevation eps = lo + (hi - lo) w1 / 2^32; ca, sa, ce, se = cos / sin of the
+ *                two in float64, each rounded to float32 once; v = (ce sa, se, -ce ca) towards the viewer, r = (ca, 0, sa),
+ *                u = (-se sa, ce, se ca).  PNPP_VIEW_ANGLES: view_dirs (B,2) holds [phi, eps] and nothing is drawn; PNPP_VIEW_DIRS:
+ *                view_dirs (B,3) holds a direction towards the viewer, normalised in float64 to (nx, ny, nz): se = ny,
+ *                ce = sqrt(nx^2 + nz^2), sa = nx / ce, ca = -nz / ce (ce = 0, straight up or down: sa = 0, ca = 1; a zero or
+ *                non-finite direction: phi = eps = 0), and phi = atan2(sa, ca), eps = atan2(se, ce) are reported;
+ *   projection   d = p . v, a = p . r, t = p . u, each fl(fl(fl(x e_x) + fl(y e_y)) + fl(z e_z));
+ *   extent       amin, amax, tmin, tmax over the valid rows (a zero taken as +0), ext = max(amax - amin, tmax - tmin), cell = ext / G,
+ *                ia = min(G - 1, floor((a - amin) / cell)), it likewise from t and tmin; both 0 unless cell > 0;
+ *   depth buffer zmax[i, j] = the largest d among the points whose own cell lies within `splat` cells of (i, j) in both directions;
+ *   test         a point is visible iff fl(zmax[ia, it] - d) <= fl(thickness ext);
+ *   thinning     drop > 0: the cloud's ratio is drop w2 / 2^32, and a visible point survives iff word 0 of its own Philox words
+ *                (counter (n, b, stream_id)) is >= fl64(drop w2) -- the ratio times 2^32;
+ *   compaction   survivors keep their order: rows 0 .. kept-1 of xyz_out (C = 6: the normal travels untouched), rows kept .. N-1 exact
+ *                zeros; lengths_out[b] = kept; index_out (B,N), optional: the source row of each output row, -1 in the padding;
+ *   floor        kept < min_keep: the cloud passes through whole -- its Nv rows, lengths_out[b] = Nv, index n.
+ * params_out (B,8) = [v_x, v_y, v_z, (float) phi, (float) eps, cell, kept, passed_through (1 or 0)].  Rows at or beyond Nv are never
+ * read (they may hold NaN).  One launch, one workgroup per cloud, no global atomics, nothing read back: two calls give the same bits and
+ * the call can be captured in a graph.  A pure function of (seed, stream_id, b, n).
+ * PNPP_ERR_ARG: a null xyz_in, xyz_out, lengths_out, desc or params_out; xyz_in == xyz_out; C not 3 or 6; B outside 1..65535; N outside
+ * 1..2^24; G outside 1..PNPP_VIEW_MAX_G; splat outside 0..2; thickness negative or not finite; an elevation range outside
+ * [-pi/2, pi/2] (as float32) or reversed; drop outside [0, 1); min_keep outside 0..N; unknown flag bits, both view flags, or view_dirs
+ * without its flag. */
+#define PNPP_VIEW_MAX_G 128
+#define PNPP_VIEW_DIRS 1u   /* flags: view_dirs is (B,3), directions towards the viewer */
+#define PNPP_VIEW_ANGLES 2u /*        view_dirs is (B,2), [azimuth, elevation] in radians */
+typedef struct {
+    int G;                  /* cells a side of the depth buffer, 1..PNPP_VIEW_MAX_G                                          */
+    int splat;              /* a point covers the (2 splat + 1)^2 cells around its own, 0..2                                  */
+    float thickness;        /* visible within this fraction of the extent behind the front surface, >= 0                     */
+    float elev_lo, elev_hi; /* the drawn elevation's range, -pi/2 <= lo <= hi <= pi/2                                        */
+    float drop;             /* thinning of the visible points, [0, 1): the cloud's ratio is uniform in [0, drop)             */
+    int min_keep;           /* fewer survivors than this: the cloud passes through whole, 0..N                               */
+    unsigned flags;         /* PNPP_VIEW_DIRS or PNPP_VIEW_ANGLES, or 0: the direction is drawn                              */
+    const float *view_dirs; /* device pointer, or NULL with flags 0                                                          */
+} pnpp_view_desc;
+int pnpp_view_clouds(uint64_t seed, uint64_t stream_id, const float *xyz_in, float *xyz_out, const int32_t *lengths_in,
+                     int32_t *lengths_out, int32_t *index_out, int B, int64_t N, int C, const pnpp_view_desc *desc, float *params_out,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

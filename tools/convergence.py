@@ -25,6 +25,13 @@ swing over the last ten epochs, and the angular error on a third split (wedge_cl
 
 --augment trains the single-peak model twice from the same initial state, on the same clouds: as above, and with the training loader
 wrapped in trainer.AugmentedLoader (pnpp_hip.augment.Augment: a fresh yaw per cloud and draw, mu moved along); held-out clouds untouched.
+
+    python tools/convergence.py --views > profiles/views_convergence.json
+
+--views trains the single-peak model twice from the same initial state, on the same clouds: on the whole clouds, and with the training
+loader wrapped in trainer.ViewLoader (pnpp_hip.views.SingleView: a fresh viewing direction per cloud and draw, the hidden side removed,
+resampled to --points).  Both models are then asked for the orientation of the held-out clouds whole and as one viewer sees them (one
+fixed view per held-out cloud, the same for both models).
 """
 import argparse
 import json
@@ -154,6 +161,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"], help="bf16: the opt-in bf16-operand MFMA mode")
     ap.add_argument("--augment", action="store_true", help="single-peak model only: without and with device-side yaw augmentation")
+    ap.add_argument("--views", action="store_true", help="single-peak model only: trained on whole clouds and on single views of them")
     ap.add_argument("--schedule", action="store_true",
                     help="single-peak model only: constant-rate Adam, then warm-up + cosine, decoupled weight decay and averaged weights")
     ap.add_argument("--multi-peak", action="store_true",
@@ -177,9 +185,10 @@ def main():
                        f"{args.epochs} epochs, Adam lr 1e-3, device-side centre sampling, hipGraph step, matmul precision {args.precision}",
            "runs": {}}
 
-    def single_peak(augment, fit_kw=None, unseen=None):
+    def single_peak(augment, fit_kw=None, unseen=None, views=False, viewed=None):
         """train_single_peak_vonMises_KL.py's loss; augment: the training loader's batches in a fresh pose every draw; fit_kw: the
-        optimiser options of trainer.fit; unseen: (xyz, mu) of a split no checkpoint selection has looked at"""
+        optimiser options of trainer.fit; unseen: (xyz, mu) of a split no checkpoint selection has looked at; views: the training
+        loader's clouds as one viewer sees them, a fresh direction every draw; viewed: the held-out clouds seen from one side"""
         torch.manual_seed(42)
         sampling.reset(0)
         model = PointNetPPVonMises(sampler="device").to(dev)
@@ -189,6 +198,9 @@ def main():
         if augment:
             from pnpp_hip.augment import Augment
             loaders["train"] = trainer.AugmentedLoader(loaders["train"], Augment(seed=42), ("vm",))
+        if views:
+            from pnpp_hip.views import SingleView
+            loaders["train"] = trainer.ViewLoader(loaders["train"], SingleView(seed=42, resample=args.points))
         loss = lambda m, b: ops.vm_head_kl_loss(m.features(b[0]), b[1][:, 0].contiguous(), b[1][:, 1].contiguous(), reduction="none")
         hist, best, best_ep = trainer.fit(model, loss, loaders, args.epochs, 1e-3, dev, label="von Mises KL", log=lambda *_: None,
                                           **(fit_kw or {}))
@@ -209,9 +221,12 @@ def main():
 
         e, k = held_out()                 # the LAST epoch's model (its validation KL swings from epoch to epoch at this learning rate)
         eu = held_out(*unseen)[0] if unseen is not None else None
+        ev = held_out(viewed, mu_va)[0] if viewed is not None else None
         model.load_state_dict(best)       # the checkpoint of the best validation epoch (trainer.fit keeps a copy)
         eb, kb = held_out()
         extra = {}
+        if viewed is not None:            # the same held-out clouds, one side of each
+            extra = {"held_out_viewed_angular_error_deg": {"last_epoch": summary(ev), "best_checkpoint": summary(held_out(viewed, mu_va)[0])}}
         if unseen is not None:            # a third split: neither trained on nor used to pick the checkpoint
             last10 = hist["val"][-10:]
             extra = {"lr": hist["lr"], "averaged_weights": hist["ema"], "val_kl_swing_last_10_epochs": round(max(last10) - min(last10), 4),
@@ -236,6 +251,18 @@ def main():
         steps = args.epochs * ((args.clouds + args.batch - 1) // args.batch)
         kw = dict(weight_decay=1e-2, schedule=optim.Schedule.cosine(warmup=steps // 20, start_factor=0.1, min_factor=0.01), ema_decay=0.999)
         out["runs"]["single_peak_vonMises_KL_scheduled"] = single_peak(False, kw, unseen)
+        print(json.dumps(out))
+        return
+    if args.views:
+        from pnpp_hip.views import SingleView
+        held = SingleView(seed=7, resample=args.points)
+        viewed = held(xyz_va.to(dev)).cpu()
+        kept = held.last_params[:, 6].cpu()
+        out["workload"] += (f"; second run: every training batch through SingleView(resample={args.points}) (defaults: elevation -30..60 degrees, "
+                            f"resolution {ops.view_resolution(args.points)}, splat 1, thickness 0.1); held-out clouds whole and as one fixed view each, "
+                            f"which keeps {float(kept.mean()) / args.points:.3f} of a cloud's points on average before resampling")
+        out["runs"]["single_peak_vonMises_KL"] = single_peak(False, viewed=viewed)
+        out["runs"]["single_peak_vonMises_KL_views"] = single_peak(False, views=True, viewed=viewed)
         print(json.dumps(out))
         return
     out["runs"]["single_peak_vonMises_KL"] = single_peak(False)
