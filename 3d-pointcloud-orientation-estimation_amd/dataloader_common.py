@@ -197,11 +197,15 @@ class BankLoader:
     viewer cannot see of them, before the normals and the augmentation.  With view.resample == num_points the batch is again
     (B, num_points, 3) and everything after it is as without a view; without resampling the batch is ragged -- survivors first, zeros
     after -- its per-cloud lengths are appended as the batch's last element and `augment` gets them as lengths= (normals= needs the
-    uniform batch).  The default view=None changes nothing: same tensors, same draws, same launches."""
+    uniform batch).  The default view=None changes nothing: same tensors, same draws, same launches.
+    prepare (a pnpp_hip.scans.ScanPrep with resample=): the bank's clouds are raw scans -- every batch takes the clouds themselves
+    (bank.padded, no draw of the bank's counted) through the preparation (voxel grid, outliers, unit frame) and its resampling draw,
+    before `view` and `augment`; prepare.resample has to be the row count the next stage takes (view_points with a view, else
+    num_points).  The default prepare=None changes nothing."""
 
     def __init__(self, bank: DeviceCloudBank, targets, num_points: int, batch: int, shuffle: bool, seed: int = 0,
                  drop_last: bool = False, augment=None, kinds=None, counts=None, normals=None, normals_orient="centroid",
-                 channels_first: bool = False, view=None, view_points=None):
+                 channels_first: bool = False, view=None, view_points=None, prepare=None):
         import torch
         self.bank, self.num_points, self.batch, self.shuffle, self.drop_last = bank, num_points, batch, shuffle, drop_last
         if normals is not None and not 3 <= int(normals) <= min(128, int(num_points)):
@@ -216,6 +220,10 @@ class BankLoader:
             if view.resample is None and normals is not None:
                 raise ValueError("BankLoader: normals= needs uniform clouds: give the view resample=num_points")
         self.view, self.view_points = view, (2 * int(num_points) if view_points is None else int(view_points))
+        drawn = int(num_points) if view is None else self.view_points
+        if prepare is not None and prepare.resample != drawn:
+            raise ValueError(f"BankLoader: prepare.resample={prepare.resample} must be {drawn}, the rows the next stage takes")
+        self.prepare = prepare
         self.targets = [t.to(bank.bank.device) for t in targets]
         self.gen = torch.Generator().manual_seed(seed)
 
@@ -233,10 +241,11 @@ class BankLoader:
                 break
             dev_ids = ids.to(self.bank.bank.device)
             lengths = None
+            draw = self.bank.sample if self.prepare is None else (lambda _, num: self.prepare(*self.bank.padded(ids))[0])
             if self.view is None:
-                batch = (self.bank.sample(dev_ids, self.num_points), *(t[dev_ids] for t in self.targets))
+                batch = (draw(dev_ids, self.num_points), *(t[dev_ids] for t in self.targets))
             else:
-                seen = self.view(self.bank.sample(dev_ids, self.view_points))
+                seen = self.view(draw(dev_ids, self.view_points))
                 if self.view.resample is None:
                     seen, lengths = seen
                 batch = (seen, *(t[dev_ids] for t in self.targets))

@@ -132,6 +132,8 @@ class ViewDesc(C.Structure):   # pnpp_view_desc
                 ("drop", C.c_float), ("min_keep", C.c_int), ("flags", C.c_uint), ("view_dirs", _fp)]
 
 
+VOXEL_MAX_GRID, OUTLIER_MAX_K = 1024, 127                # include/pnpp_hip.h: PNPP_VOXEL_MAX_GRID, PNPP_OUTLIER_MAX_K
+SCAN_NONE, SCAN_CENTROID, SCAN_SPHERE, SCAN_BOX = 0, 1, 1, 2   # pnpp_normalize_clouds' centre / scale modes
 NORMALS_NONE, NORMALS_AWAY, NORMALS_TOWARD = range(3)  # pnpp_estimate_normals' orientation modes
 NORMALS_KMIN, NORMALS_KMAX = 3, 128
 YAW_ANGLE_BLOCK, YAW_TILE, YAW_QUERIES, YAW_MAX_ORDERS = 8, 1024, 256, 16   # include/pnpp_hip.h: PNPP_YAW_*
@@ -239,6 +241,16 @@ SIGNATURES = {
     "pnpp_yaw_symmetry": (_i, [_fp, _sz, _i, _i, _fp, _i, _f, C.POINTER(C.c_int32), _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _fp]),
     # single-view scan: seed, stream id, xyz_in, xyz_out, lengths_in, lengths_out, index_out, B, N, C, desc, params, stream
     "pnpp_view_clouds": (_i, [_u64, _u64, _fp, _fp, _fp, _fp, _fp, _i, C.c_int64, _i, C.POINTER(ViewDesc), _fp, _fp]),
+    # raw-scan preparation: B, N -> bytes
+    "pnpp_voxel_workspace_bytes": (_sz, [_i, C.c_int64]),
+    # xyz_in, xyz_out, lengths_in, lengths_out, index_out, B, N, C, cell, grid, workspace, bytes, stream
+    "pnpp_voxel_downsample": (_i, [_fp, _fp, _fp, _fp, _fp, _i, C.c_int64, _i, _f, _i, _fp, _sz, _fp]),
+    # xyz, lists, lengths, B, N, C, k, statistic, stream
+    "pnpp_outlier_statistic": (_i, [_fp, _fp, _fp, _i, C.c_int64, _i, _i, _fp, _fp]),
+    # xyz_in, xyz_out, statistic, lengths_in, lengths_out, index_out, stats_out, B, N, C, k, std_ratio, stream
+    "pnpp_outlier_filter": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, C.c_int64, _i, _i, C.c_double, _fp]),
+    # xyz_in, xyz_out, lengths, B, N, C, centre mode, scale mode, centre_out, scale_out, stream
+    "pnpp_normalize_clouds": (_i, [_fp, _fp, _fp, _i, C.c_int64, _i, _i, _i, _fp, _fp, _fp]),
     "pnpp_build_flags": (C.c_uint, []),
     "pnpp_debug_wsd3_timeouts": (_i, []),
     "pnpp_fc_saved_bytes": (_sz, [C.POINTER(FcDesc)]),

@@ -33,6 +33,7 @@ SOURCES = {
     "augment_kernels.hip": ["-ffp-contract=off"],   # float32 steps reproducible on the CPU (tests/augment_ref.py)
     "symmetry_kernels.hip": ["-ffp-contract=off"],  # exact_dist.h's recipe and the rotation, restated in tests/symmetry_ref.py
     "view_kernels.hip": ["-ffp-contract=off"],      # projection, cells and the depth test, restated in tests/view_ref.py
+    "scan_kernels.hip": ["-ffp-contract=off"],      # cells, keys, the statistic and the unit frame, restated in tests/scan_ref.py
     "gemm_kernels.hip": [],
     "gemm_ws_kernels.hip": (["-DPNPP_STAMPS"] if os.environ.get("PNPP_STAMPS") else []),
     "dw_kernels.hip": [],

@@ -587,6 +587,148 @@ def view_clouds(xyz: torch.Tensor, seed: int, stream_id: int, lengths=None, reso
     return (out, lengths_out, params, idx) if index else (out, lengths_out, params)
 
 
+SCAN_CENTRES = {None: L.SCAN_NONE, "centroid": L.SCAN_CENTROID, "box": L.SCAN_BOX}
+SCAN_SCALES = {None: L.SCAN_NONE, "sphere": L.SCAN_SPHERE, "box": L.SCAN_BOX}
+_SCAN_UNSET = object()
+
+
+def scan_plan(xyz_shape, cell=None, grid=None, k=None, std_ratio=2.0, centre=_SCAN_UNSET, scale=_SCAN_UNSET, lengths=None):
+    """Host-side validation of the raw-scan steps, from shapes and numbers alone (runs without a GPU): what pnpp_voxel_downsample
+    (cell or grid given), pnpp_outlier_statistic / _filter (k given) and pnpp_normalize_clouds (centre or scale given) would refuse
+    raises ValueError here, in the entry's own words.  -> dict of the checked values (cell, grid, k, std_ratio, centre, scale codes)."""
+    if len(xyz_shape) != 3 or xyz_shape[2] not in (3, 6):
+        raise ValueError(f"scan: xyz must be (B, N, 3) or (B, N, 6), got {tuple(xyz_shape)}")
+    B, N = int(xyz_shape[0]), int(xyz_shape[1])
+    if not 1 <= B <= 65535 or not 1 <= N <= 1 << 24:
+        raise ValueError(f"scan: B must be 1..65535 and N 1..2^24, got B={B} N={N}")
+    if lengths is not None and (not isinstance(lengths, torch.Tensor) or tuple(lengths.shape) != (B,)
+                                or lengths.dtype not in (torch.int32, torch.int64)):
+        raise ValueError(f"scan: lengths must be an integer tensor of shape ({B},)")
+    plan = {}
+    if cell is not None or grid is not None:
+        if cell is not None and grid is not None:
+            raise ValueError(f"voxel_downsample: exactly one of cell and grid is given, got cell={cell} grid={grid}")
+        if cell is not None:
+            cell = float(cell)
+            if not 0.0 < cell < float("inf"):
+                raise ValueError(f"voxel_downsample: cell={cell} must be finite and > 0")
+        else:
+            if int(grid) != grid or not 1 <= int(grid) <= L.VOXEL_MAX_GRID:
+                raise ValueError(f"voxel_downsample: grid={grid} must be 1..{L.VOXEL_MAX_GRID}")
+            grid = int(grid)
+        plan["cell"], plan["grid"] = cell, grid
+    if k is not None:
+        if int(k) != k or not 1 <= int(k) <= L.OUTLIER_MAX_K:
+            raise ValueError(f"remove_outliers: k={k} must be 1..{L.OUTLIER_MAX_K}")
+        if lengths is None and N < int(k) + 1:
+            raise ValueError(f"remove_outliers: clouds of N={N} rows have no k + 1 = {int(k) + 1} neighbours to list")
+        std_ratio = float(std_ratio)
+        if not 0.0 <= std_ratio < float("inf"):
+            raise ValueError(f"remove_outliers: std_ratio={std_ratio} must be finite and >= 0")
+        plan["k"], plan["std_ratio"] = int(k), std_ratio
+    if centre is not _SCAN_UNSET or scale is not _SCAN_UNSET:
+        centre = None if centre is _SCAN_UNSET else centre
+        scale = None if scale is _SCAN_UNSET else scale
+        if centre not in SCAN_CENTRES:
+            raise ValueError(f"normalize_clouds: centre={centre!r} must be 'centroid', 'box' or None")
+        if scale not in SCAN_SCALES:
+            raise ValueError(f"normalize_clouds: scale={scale!r} must be 'sphere', 'box' or None")
+        plan["centre"], plan["scale"] = SCAN_CENTRES[centre], SCAN_SCALES[scale]
+    return plan
+
+
+def _scan_outputs(xyz: torch.Tensor, index: bool):
+    B, N, _ = xyz.shape
+    return (torch.empty_like(xyz), torch.empty(B, device=xyz.device, dtype=torch.int32),
+            torch.empty(B, N, device=xyz.device, dtype=torch.int32) if index else None)
+
+
+def voxel_downsample(xyz: torch.Tensor, cell=None, grid=None, lengths=None, index: bool = False):
+    """One point per occupied cell of a per-cloud grid (pnpp_voxel_downsample): -> (xyz', lengths'[, index]).
+
+    xyz (B,N,3) or (B,N,6) float32, lengths (B,) or None.  `cell` is the cells' edge; `grid` instead the number of cells along the
+    cloud's longest axis (1..1024).  The grid starts at the cloud's lower corner and has ten bits per axis: cells beyond index 1023
+    merge into the last; with `grid` the last index is grid - 1, so the cloud's far face belongs to the last cell and grid=1 keeps
+    one point.  A cell's survivor is the point nearest its centre (the lowest row among equals) -- a real point with its
+    own normal and source row, where Open3D and PCL return the cell's centroid.  Survivors keep their input order, exact zeros
+    follow, lengths' (B,) int32 counts them, index (B,N) int32 is the source row of each output row (-1 in the padding).  Integer
+    atomics only: two calls give the same bits; nothing is read back."""
+    plan = scan_plan(xyz.shape, cell=cell, grid=grid, lengths=lengths)
+    if "grid" not in plan:
+        raise ValueError("voxel_downsample: exactly one of cell and grid is given, got neither")
+    xyz = _f32(xyz, "xyz")
+    B, N, Cc = xyz.shape
+    if lengths is not None:
+        lengths = _i32(lengths, "lengths")
+    nbytes = L.lib().pnpp_voxel_workspace_bytes(B, N)
+    ws = _workspace(nbytes, xyz.device)
+    out, lengths_out, idx = _scan_outputs(xyz, index)
+    L.check(L.lib().pnpp_voxel_downsample(xyz.data_ptr(), out.data_ptr(), _p(lengths), lengths_out.data_ptr(), _p(idx), B, N, Cc,
+                                          plan["cell"] or 0.0, plan["grid"] or 0, ws.data_ptr(), nbytes, _stream()))
+    return (out, lengths_out, idx) if index else (out, lengths_out)
+
+
+def outlier_statistic(xyz: torch.Tensor, lists: torch.Tensor, lengths=None) -> torch.Tensor:
+    """(B,N) float64: per point the mean distance to its k listed neighbours, lists (B,N,k+1) int32 (pnpp_outlier_statistic)."""
+    xyz = _f32(xyz, "xyz")
+    B, N, Cc = xyz.shape
+    if lists.dim() != 3 or tuple(lists.shape[:2]) != (B, N) or lists.dtype != torch.int32 or lists.shape[2] < 2:
+        raise ValueError(f"outlier_statistic: lists must be int32 of shape ({B}, {N}, k + 1), got {lists.dtype} {tuple(lists.shape)}")
+    _need_gpu(lists, "lists")
+    lists = lists.contiguous()
+    if lengths is not None:
+        lengths = _i32(lengths, "lengths")
+    stat = torch.empty(B, N, device=xyz.device, dtype=torch.float64)
+    L.check(L.lib().pnpp_outlier_statistic(xyz.data_ptr(), lists.data_ptr(), _p(lengths), B, N, Cc, lists.shape[2] - 1, stat.data_ptr(),
+                                           _stream()))
+    return stat
+
+
+def remove_outliers(xyz: torch.Tensor, k: int = 16, std_ratio: float = 2.0, lengths=None, index: bool = False, stats: bool = False):
+    """Statistical outlier removal as PCL and Open3D define it: -> (xyz', lengths'[, index][, stats]).
+
+    Per point the mean distance s to its k nearest neighbours (ops.knn of the cloud on itself with k + 1: the search is brute force,
+    O(N^2) per cloud, so on a large scan this step belongs after voxel_downsample); per cloud the mean and population standard
+    deviation of s in float64; a point is kept when s <= mean + std_ratio std.  A cloud with no more than k points passes through
+    whole (decided on the device).  The mean / std rule is not robust: a heavy contamination raises its own threshold.  Output as
+    voxel_downsample's; stats (B,4) float64 = [mean, std, thr, kept] stays on the device."""
+    plan = scan_plan(xyz.shape, k=k, std_ratio=std_ratio, lengths=lengths)
+    xyz = _f32(xyz, "xyz")
+    B, N, Cc = xyz.shape
+    if lengths is not None:
+        lengths = _i32(lengths, "lengths")   # a device tensor: short clouds are the filter kernel's business, not the search's
+    pts = xyz if Cc == 3 else xyz[..., :3].contiguous()
+    kk = min(plan["k"] + 1, N)   # a ragged batch padded to fewer than k + 1 rows: every cloud passes through, the lists are never read
+    lists = knn(pts, pts, kk, lengths)
+    if kk < plan["k"] + 1:
+        lists = lists.new_zeros(B, N, plan["k"] + 1)
+    stat = outlier_statistic(xyz, lists, lengths)
+    out, lengths_out, idx = _scan_outputs(xyz, index)
+    st = torch.empty(B, 4, device=xyz.device, dtype=torch.float64) if stats else None
+    L.check(L.lib().pnpp_outlier_filter(xyz.data_ptr(), out.data_ptr(), stat.data_ptr(), _p(lengths), lengths_out.data_ptr(), _p(idx),
+                                        _p(st), B, N, Cc, plan["k"], plan["std_ratio"], _stream()))
+    return (out, lengths_out) + ((idx,) if index else ()) + ((st,) if stats else ())
+
+
+def normalize_clouds(xyz: torch.Tensor, lengths=None, centre="centroid", scale="sphere"):
+    """Every cloud in its own unit frame, one launch (pnpp_normalize_clouds): -> (xyz', centre (B,3), scale (B,)).
+
+    centre: "centroid" (the float64 mean of the valid rows, rounded to float32), "box" (the middle of the bounding box) or None;
+    scale: "sphere" (the largest distance from the centre), "box" (half the longest box edge) or None; a scale of 0 becomes 1.
+    x' = (x - centre) / scale; columns 3..5 are unchanged, padding rows come back as zeros.  centre and scale map a result back."""
+    plan = scan_plan(xyz.shape, centre=centre, scale=scale, lengths=lengths)
+    xyz = _f32(xyz, "xyz")
+    B, N, Cc = xyz.shape
+    if lengths is not None:
+        lengths = _i32(lengths, "lengths")
+    out = torch.empty_like(xyz)
+    c = torch.empty(B, 3, device=xyz.device, dtype=torch.float32)
+    r = torch.empty(B, device=xyz.device, dtype=torch.float32)
+    L.check(L.lib().pnpp_normalize_clouds(xyz.data_ptr(), out.data_ptr(), _p(lengths), B, N, Cc, plan["centre"], plan["scale"],
+                                          c.data_ptr(), r.data_ptr(), _stream()))
+    return out, c, r
+
+
 class _IndexPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, idx):

@@ -88,6 +88,27 @@ class ViewLoader:
             yield (seen, *batch[1:]) if self.view.resample is not None else (seen[0], *batch[1:], seen[1])
 
 
+class PrepLoader:
+    """Any loader that yields (xyz, ...), the first element of each batch passed through `prep` (pnpp_hip.scans.ScanPrep with
+    resample=num): voxel grid, outlier removal and the unit frame on the device, then `num` rows drawn from the survivors, so the
+    batches keep the loader's own layout.  Yaw is invariant under the frame, so the targets stay as they are; a ViewLoader and an
+    AugmentedLoader go around this one.  device: move the batch there first (a host DataLoader); None: it is already there."""
+
+    def __init__(self, loader, prep, device=None):
+        if prep.resample is None:
+            raise ValueError("PrepLoader: the preparation needs resample=num, the uniform batch the models take")
+        self.loader, self.prep, self.device = loader, prep, device
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for batch in self.loader:
+            if self.device is not None:
+                batch = tuple(b.to(self.device, non_blocking=True) for b in batch)
+            yield (self.prep(batch[0])[0], *batch[1:])
+
+
 LossFn = Union[Callable, Tuple[Callable, Callable]]
 
 
@@ -497,6 +518,20 @@ def add_metrics_args(ap) -> None:
     ap.add_argument("--angular-metrics", action="store_true", default=os.environ.get("PNPP_ANGULAR_METRICS", "0") not in ("", "0"),
                     help="after the run: angular errors of the test split (pnpp_hip.decode), printed and written to "
                          "angular_errors.json beside the results; every other output file is unchanged")
+
+
+def add_prepare_args(ap) -> None:
+    """--prepare (PNPP_PREPARE=1): every split's clouds through pnpp_hip.scans.ScanPrep on the device.  Off by default."""
+    ap.add_argument("--prepare", action="store_true", default=os.environ.get("PNPP_PREPARE") == "1",
+                    help="treat the clouds as raw scans: a 32-cell voxel grid, statistical outlier removal (k=16, 2 sigma) and the unit "
+                         "frame on the device, resampled to the loader's point count (every split; in front of --views and --augment)")
+
+
+def prepared(loaders: dict, num_points: int, seed: int, device=None) -> dict:
+    """Every loader of `loaders` behind a PrepLoader of its own (--prepare): test scans are as raw as training scans."""
+    from .scans import ScanPrep
+    return {k: PrepLoader(v, ScanPrep(grid=32, outlier_k=16, outlier_std=2.0, resample=num_points, seed=seed + i), device)
+            for i, (k, v) in enumerate(loaders.items())}
 
 
 def report_angular_errors(path, summary: dict, names: Optional[Sequence[str]] = None) -> None:

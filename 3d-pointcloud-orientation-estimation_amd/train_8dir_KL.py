@@ -72,7 +72,7 @@ def _dataset_loaders(rank, world):
                           num_workers=4, pin_memory=True) for k, v in parts.items()}
 
 
-def _synthetic_loaders(n, rank, augment=False, views=False):
+def _synthetic_loaders(n, rank, augment=False, views=False, prepare=False):
     import synthetic
     out = {}
     for i, (name, frac) in enumerate((("train", 0.7), ("val", 0.15), ("test", 0.15))):
@@ -80,11 +80,15 @@ def _synthetic_loaders(n, rank, augment=False, views=False):
         xyz, _, _, fwd = synthetic.rotated_clouds(m, NUM_POINTS, seed=SEED + 1000 * i + rank)
         if augment and name == "train":   # the loader keeps the forward axis; the labels come out of the augmentation launch
             plain = trainer.SyntheticLoader([xyz, fwd], BATCH, True, device)
+            if prepare:   # innermost: the raw cloud is prepared, then viewed, then turned
+                plain = trainer.prepared({name: plain}, NUM_POINTS, SEED + rank)[name]
             if views:   # the cloud is not moved by the view: the forward axis stays, and the augmentation goes around it
                 plain = trainer.ViewLoader(plain, SingleView(SEED + rank, resample=NUM_POINTS))
             out[name] = trainer.AugmentedLoader(plain, Augment(SEED + rank), ("dir8",))
         else:
             out[name] = trainer.SyntheticLoader([xyz, synthetic.dir8_soft_labels(fwd, DIRS_8)], BATCH, name == "train", device)
+            if prepare:
+                out[name] = trainer.prepared({name: out[name]}, NUM_POINTS, SEED + rank + i)[name]
             if views and name == "train":
                 out[name] = trainer.ViewLoader(out[name], SingleView(SEED + rank, resample=NUM_POINTS))
     return ["synthetic"], out
@@ -99,6 +103,7 @@ def _parser():
     ap.add_argument("--views", action="store_true", default=os.environ.get("PNPP_VIEWS") == "1",
                     help="every training cloud as one viewer sees it: a fresh direction per cloud and draw, the hidden side removed on the device, "
                          "resampled to NUM_POINTS (train split only; in front of --augment)")
+    trainer.add_prepare_args(ap)   # --prepare (PNPP_PREPARE): off by default
     trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
     return ap
 
@@ -114,7 +119,10 @@ def main(argv=None):
     sampling.reset(0)   # the device-side centre sampler restarts its stream too: a run is a function of SEED
     RES.mkdir(parents=True, exist_ok=True), FIGS.mkdir(parents=True, exist_ok=True)
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else device
-    labels, loaders = _synthetic_loaders(args.synthetic, rank, args.augment, args.views) if args.synthetic else _dataset_loaders(rank, world)
+    labels, loaders = (_synthetic_loaders(args.synthetic, rank, args.augment, args.views, args.prepare) if args.synthetic
+                       else _dataset_loaders(rank, world))
+    if args.prepare and not args.synthetic:   # a host DataLoader's batch goes to the device first
+        loaders = trainer.prepared(loaders, NUM_POINTS, SEED + rank, dev)
     if args.views and not args.synthetic:   # a host DataLoader's batch goes to the device first
         loaders["train"] = trainer.ViewLoader(loaders["train"], SingleView(SEED + rank, resample=NUM_POINTS), dev)
     model = PointNetPP8Dir(sampler=args.sampler).to(dev)

@@ -104,6 +104,7 @@ def _parser():
     ap.add_argument("--views", action="store_true", default=os.environ.get("PNPP_VIEWS") == "1",
                     help="every training cloud as one viewer sees it: a fresh direction per cloud and draw, the hidden side removed on the device, "
                          "resampled to NUM_POINTS (train split only; in front of --augment)")
+    trainer.add_prepare_args(ap)   # --prepare (PNPP_PREPARE): off by default
     trainer.add_optim_args(ap)   # --weight-decay, --lr-schedule, --warmup, --ema (PNPP_WEIGHT_DECAY, ...): all off by default
     trainer.add_metrics_args(ap)   # --angular-metrics (PNPP_ANGULAR_METRICS): off by default
     return ap
@@ -122,6 +123,8 @@ def main(argv=None):
     RES.mkdir(parents=True, exist_ok=True), FIGS.mkdir(parents=True, exist_ok=True)
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else device
     loaders = _synthetic_loaders(args.synthetic, rank) if args.synthetic else _dataset_loaders(rank, world)
+    if args.prepare:   # raw scans: voxel grid, outliers, unit frame, resampled -- every split, innermost
+        loaders = trainer.prepared(loaders, NUM_POINTS, SEED + rank, None if args.synthetic else dev)
     if args.views:   # the cloud is not moved: the targets stay, and the augmentation goes around the view
         loaders["train"] = trainer.ViewLoader(loaders["train"], SingleView(SEED + rank, resample=NUM_POINTS), None if args.synthetic else dev)
     if args.augment:   # vm_gt rows are [mu, kappa]: mu follows the cloud; a host DataLoader's batch goes to the device first

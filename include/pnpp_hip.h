@@ -1117,6 +1117,59 @@ int pnpp_view_clouds(uint64_t seed, uint64_t stream_id, const float *xyz_in, flo
                      int32_t *lengths_out, int32_t *index_out, int B, int64_t N, int C, const pnpp_view_desc *desc, float *params_out,
                      void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Raw-scan preparation (additive to ABI 5): voxel-grid downsample, statistical outlier removal, unit frame.  Each entry has
+ * pnpp_view_clouds' contract: rows (B,N,C) float32 with C 3 or 6 (columns 3..5 travel unchanged), cloud b's valid rows n < Nv
+ * (Nv = min(max(lengths_in[b], 1), N), or N when lengths_in is NULL) must be finite, rows at or beyond Nv are never read (they may hold
+ * NaN); survivors keep their order in rows 0 .. kept-1 of xyz_out, rows kept .. N-1 are exact zeros, lengths_out[b] = kept,
+ * index_out (B,N), optional: the source row of each output row, -1 in the padding.  Out of place; nothing is read back, no
+ * floating-point atomics: two calls give the same bits and the calls can be captured in a graph.  Every float32 step below is one IEEE
+ * operation, in this order, unfused (tests/scan_ref.py restates them).
+ *
+ * pnpp_voxel_downsample: one real point per occupied cell -- the one nearest the cell's centre (Open3D and PCL return the cell's
+ * centroid instead: an averaged point has no source row, its normal means nothing, and its bits depend on a summation order).
+ *   bounds   lo[a], hi[a]: min and max over the valid rows per axis, a zero of either sign taken as +0;
+ *   edge     h = cell, or with grid > 0  h = max_a(hi[a] - lo[a]) / (float) grid; h = 1 unless h > 0;
+ *   cell     c[a] = min(max(floor((x[a] - lo[a]) / h), 0), last), last = 1023: ten bits per axis, cells beyond index 1023 merge
+ *            into the last; with grid, last = grid - 1: the far face of the longest axis belongs to the last cell (grid = 1: one cell);
+ *   centre   m[a] = lo[a] + (c[a] + 0.5) h;  d = (x0 - m0)^2 + (x1 - m1)^2 + (x2 - m2)^2, summed in that order;
+ *   winner   per cell the row with the smallest 64-bit key (bits(d) << 32) | n: nearest the centre, lowest row among equals.
+ * Exactly one of cell (finite, > 0; grid = 0) and grid (1..PNPP_VOXEL_MAX_GRID; cell = 0).  workspace: pnpp_voxel_workspace_bytes(B, N)
+ * bytes (0: B or N refused), the per-cloud open-addressing table (at least 2 N slots) and the bounds; the call clears it itself.  Four
+ * launches: clear, bounds, insert (several workgroups per cloud; compare-and-swap claims a cell's slot, an unsigned 64-bit atomicMin
+ * takes the winner), compact (one workgroup per cloud).
+ *
+ * pnpp_outlier_statistic: lists (B,N,k+1) int32 neighbour rows of every point (pnpp_knn_ragged of the cloud on itself with k + 1);
+ * statistic[b, n] = (sum_j sqrt((double) d(x_n, x_list[j]))) / k in float64 in list order over all k + 1 entries (the point itself adds
+ * 0, listed or not), 0 for n >= Nv.  pnpp_outlier_filter: mean and population standard deviation of the statistic over the valid rows
+ * in float64 in a fixed order, thr = mean + std_ratio std, a row is kept iff statistic <= thr; a cloud with Nv <= k passes through
+ * whole.  stats_out (B,4) float64, optional: [mean, std, thr, kept] ([0, 0, inf, Nv] for a cloud that passed through).
+ * 1 <= k <= PNPP_OUTLIER_MAX_K; std_ratio finite and >= 0.
+ *
+ * pnpp_normalize_clouds: x' = (x - centre) / scale, one launch, one workgroup per cloud.  centre: PNPP_SCAN_NONE (0), PNPP_SCAN_CENTROID
+ * (the float64 mean of the valid rows, fixed order, rounded to float32) or PNPP_SCAN_BOX (0.5 (lo + hi)); scale: PNPP_SCAN_NONE (1),
+ * PNPP_SCAN_SPHERE (sqrt(max_n |x_n - centre|^2), the squares summed x, y, z) or PNPP_SCAN_BOX (0.5 max_a(hi[a] - lo[a])); 1 unless > 0.
+ * centre_out (B,3) and scale_out (B) map a result back.  Rows at or beyond Nv come back as zeros.
+ *
+ * PNPP_ERR_ARG: a null pointer other than lengths_in, index_out, stats_out; xyz_in == xyz_out; C not 3 or 6; B outside 1..65535;
+ * N outside 1..2^24; cell and grid both or neither, grid above PNPP_VOXEL_MAX_GRID; a workspace too small; k or std_ratio out of range;
+ * an unknown mode. */
+#define PNPP_VOXEL_MAX_GRID 1024
+#define PNPP_OUTLIER_MAX_K 127 /* the search lists k + 1 <= 128 rows */
+#define PNPP_SCAN_NONE 0
+#define PNPP_SCAN_CENTROID 1 /* centre */
+#define PNPP_SCAN_SPHERE 1   /* scale  */
+#define PNPP_SCAN_BOX 2      /* either */
+size_t pnpp_voxel_workspace_bytes(int B, int64_t N);
+int pnpp_voxel_downsample(const float *xyz_in, float *xyz_out, const int32_t *lengths_in, int32_t *lengths_out, int32_t *index_out, int B,
+                          int64_t N, int C, float cell, int grid, void *workspace, size_t workspace_bytes, void *stream);
+int pnpp_outlier_statistic(const float *xyz, const int32_t *lists, const int32_t *lengths, int B, int64_t N, int C, int k,
+                           double *statistic, void *stream);
+int pnpp_outlier_filter(const float *xyz_in, float *xyz_out, const double *statistic, const int32_t *lengths_in, int32_t *lengths_out,
+                        int32_t *index_out, double *stats_out, int B, int64_t N, int C, int k, double std_ratio, void *stream);
+int pnpp_normalize_clouds(const float *xyz_in, float *xyz_out, const int32_t *lengths, int B, int64_t N, int C, int centre_mode,
+                          int scale_mode, float *centre_out, float *scale_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

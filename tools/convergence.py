@@ -27,6 +27,7 @@ swing over the last ten epochs, and the angular error on a third split (wedge_cl
 wrapped in trainer.AugmentedLoader (pnpp_hip.augment.Augment: a fresh yaw per cloud and draw, mu moved along); held-out clouds untouched.
 
     python tools/convergence.py --views > profiles/views_convergence.json
+    python tools/convergence.py --scan-prep > profiles/scans_convergence.json
 
 --views trains the single-peak model twice from the same initial state, on the same clouds: on the whole clouds, and with the training
 loader wrapped in trainer.ViewLoader (pnpp_hip.views.SingleView: a fresh viewing direction per cloud and draw, the hidden side removed,
@@ -59,6 +60,24 @@ def wedge_clouds(B, N, seed, taper=True):
     xyz = torch.einsum("bnj,bij->bni", p, R).contiguous()
     f = torch.einsum("bij,j->bi", R, torch.tensor([0.0, 0.0, -1.0]))
     return xyz.float(), torch.atan2(f[:, 0], -f[:, 2]).float(), f.float()
+
+
+def raw_scans(dense, seed):
+    """Clean clouds (B,M,3) -> (xyz (B,Lmax,3) zero-padded, lengths (B,) int32) as a sensor might deliver them: 5 % of the rows
+    replaced by uniform strays in twice the cloud's box, the low-x half thinned to half the sampling density of the other, then a
+    scale in [0.5, 2] and an offset in [-5, 5]^3 per cloud."""
+    g = torch.Generator().manual_seed(seed)
+    B, M, _ = dense.shape
+    lo, hi = dense.amin(1, keepdim=True), dense.amax(1, keepdim=True)
+    mid, half = (lo + hi) / 2, (hi - lo) / 2
+    stray = torch.rand(B, M, generator=g) < 0.05
+    pts = torch.where(stray[..., None], mid + (torch.rand(B, M, 3, generator=g) * 2 - 1) * 2 * half, dense)
+    keep = ~((dense[..., 0] < mid[..., 0]) & (torch.rand(B, M, generator=g) < 0.5) & ~stray)
+    pts = pts * (0.5 + 1.5 * torch.rand(B, 1, 1, generator=g)) + (torch.rand(B, 1, 3, generator=g) * 2 - 1) * 5
+    order = torch.sort((~keep).to(torch.uint8), dim=1, stable=True).indices
+    lengths = keep.sum(1)
+    out = torch.gather(pts, 1, order[..., None].expand(-1, -1, 3)) * (torch.arange(M)[None, :] < lengths[:, None])[..., None]
+    return out[:, :int(lengths.max())].contiguous().float(), lengths.to(torch.int32)
 
 
 def ang_err_deg(a, b):
@@ -162,6 +181,8 @@ def main():
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"], help="bf16: the opt-in bf16-operand MFMA mode")
     ap.add_argument("--augment", action="store_true", help="single-peak model only: without and with device-side yaw augmentation")
     ap.add_argument("--views", action="store_true", help="single-peak model only: trained on whole clouds and on single views of them")
+    ap.add_argument("--scan-prep", action="store_true",
+                    help="single-peak model only, trained as always: held-out clouds clean, as raw scans, and as raw scans through ScanPrep")
     ap.add_argument("--schedule", action="store_true",
                     help="single-peak model only: constant-rate Adam, then warm-up + cosine, decoupled weight decay and averaged weights")
     ap.add_argument("--multi-peak", action="store_true",
@@ -185,10 +206,11 @@ def main():
                        f"{args.epochs} epochs, Adam lr 1e-3, device-side centre sampling, hipGraph step, matmul precision {args.precision}",
            "runs": {}}
 
-    def single_peak(augment, fit_kw=None, unseen=None, views=False, viewed=None):
+    def single_peak(augment, fit_kw=None, unseen=None, views=False, viewed=None, scans=None):
         """train_single_peak_vonMises_KL.py's loss; augment: the training loader's batches in a fresh pose every draw; fit_kw: the
         optimiser options of trainer.fit; unseen: (xyz, mu) of a split no checkpoint selection has looked at; views: the training
-        loader's clouds as one viewer sees them, a fresh direction every draw; viewed: the held-out clouds seen from one side"""
+        loader's clouds as one viewer sees them, a fresh direction every draw; viewed: the held-out clouds seen from one side; scans:
+        {name: (xyz, mu)} further held-out sets of 1,024 clouds, each read by the last epoch's model and the best checkpoint"""
         torch.manual_seed(42)
         sampling.reset(0)
         model = PointNetPPVonMises(sampler="device").to(dev)
@@ -222,9 +244,13 @@ def main():
         e, k = held_out()                 # the LAST epoch's model (its validation KL swings from epoch to epoch at this learning rate)
         eu = held_out(*unseen)[0] if unseen is not None else None
         ev = held_out(viewed, mu_va)[0] if viewed is not None else None
+        es = {name: summary(held_out(x, m)[0]) for name, (x, m) in (scans or {}).items()}
         model.load_state_dict(best)       # the checkpoint of the best validation epoch (trainer.fit keeps a copy)
         eb, kb = held_out()
         extra = {}
+        if scans:
+            extra = {"scan_angular_error_deg": {name: {"last_epoch": es[name], "best_checkpoint": summary(held_out(x, m)[0])}
+                                                for name, (x, m) in scans.items()}}
         if viewed is not None:            # the same held-out clouds, one side of each
             extra = {"held_out_viewed_angular_error_deg": {"last_epoch": summary(ev), "best_checkpoint": summary(held_out(viewed, mu_va)[0])}}
         if unseen is not None:            # a third split: neither trained on nor used to pick the checkpoint
@@ -251,6 +277,38 @@ def main():
         steps = args.epochs * ((args.clouds + args.batch - 1) // args.batch)
         kw = dict(weight_decay=1e-2, schedule=optim.Schedule.cosine(warmup=steps // 20, start_factor=0.1, min_factor=0.01), ema_decay=0.999)
         out["runs"]["single_peak_vonMises_KL_scheduled"] = single_peak(False, kw, unseen)
+        print(json.dumps(out))
+        return
+    if args.scan_prep:
+        from pnpp_hip.scans import ScanPrep
+        dense, mu_s, _ = wedge_clouds(1024, 4 * args.points, 4)
+        raw, raw_len = raw_scans(dense, 5)
+        rd, ld = raw.to(dev), raw_len.to(dev)
+        prep = ScanPrep(grid=32, outlier_k=8, outlier_std=1.0, resample=args.points, seed=7)
+        first = ScanPrep(grid=32, outlier_k=8, outlier_std=1.0, centre=None, scale=None)   # "twice": a ragged cleaning pass in front
+        again = ScanPrep(grid=32, outlier_k=8, outlier_std=1.0, resample=args.points, seed=7)
+        prepared, survivors, twice = [], [], []
+        for i in range(0, 1024, 128):
+            chunk, lens = rd[i:i + 128].contiguous(), ld[i:i + 128].contiguous()
+            prepared.append(prep(chunk, lens)[0].cpu())
+            survivors.append(prep.last_lengths.cpu())
+            twice.append(again(*first(chunk, lens)[:2])[0].cpu())
+        clean = dense[:, :args.points].contiguous()
+        sets = {"clean": (clean, mu_s),
+                "clean_unit_frame": (ops.normalize_clouds(clean.to(dev))[0].cpu(), mu_s),   # what the frame alone costs this model
+                "raw": (ops.subsample_points(7, 1, rd, ld, args.points).cpu(), mu_s),   # the same scans, resampled and nothing else
+                "prepared": (torch.cat(prepared), mu_s),
+                "prepared_twice": (torch.cat(twice), mu_s)}
+        out["median_point_norm"] = {k: round(float(v[0].norm(dim=2).median()), 3) for k, v in sets.items()}
+        out["workload"] += (f"; 1,024 further held-out clouds of {4 * args.points} points read three ways: clean ({args.points} of their rows), as "
+                            f"raw scans (5 % uniform strays in twice the box, the low-x half at half density, scale 0.5..2, offset up to 5; "
+                            f"{float(raw_len.float().mean()):.0f} rows on average) resampled to {args.points}, and the raw scans through "
+                            f"ScanPrep(grid=32, outlier_k=8, outlier_std=1.0, resample={args.points}), which keeps "
+                            f"{float(torch.cat(survivors).float().mean()):.0f} rows on average before resampling; also the clean clouds through "
+                            f"normalize_clouds alone (clean_unit_frame) and the raw scans through a ragged pass of the same voxel and outlier steps "
+                            f"in front of that ScanPrep (prepared_twice).  Not measured: real scans, "
+                            f"and clouds above 2^17 points")
+        out["runs"]["single_peak_vonMises_KL"] = single_peak(False, scans=sets)
         print(json.dumps(out))
         return
     if args.views:
