@@ -199,12 +199,12 @@ extern "C" int pnpp_square_distance(const float *src, const float *dst, int B, i
     return PNPP_OK;
 }
 
-static int ball_query_impl(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, float radius, int nsample,
+// r2 is the float32 threshold the kernel compares against: a member is a point with !(d > r2).
+static int ball_query_impl(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, float r2, int nsample,
                            int32_t *idx, void *stream) {
     PNPP_REQUIRE(new_xyz && xyz && idx, PNPP_ERR_ARG, "ball_query: null pointer");
     PNPP_REQUIRE(B > 0 && S > 0 && N > 0 && nsample > 0, PNPP_ERR_ARG, "ball_query: non-positive size");
     PNPP_REQUIRE(B <= 65535, PNPP_ERR_ARG, "ball_query: batch exceeds grid limit");
-    const float r2 = (float)((double)radius * (double)radius);  // Demo.py:65: python float squared, compared in float32
     ProfScope ps(as_stream(stream), "ball_query_kernel B=%d S=%d N=%d nsample=%d%s", B, S, N, nsample, lengths ? " ragged" : "");
     const auto kfn = lengths ? ball_query_kernel<true> : ball_query_kernel<false>;
     hipLaunchKernelGGL(kfn, dim3(cdiv(S, 4), B), dim3(256), 0, as_stream(stream), new_xyz, xyz, S, N, r2, nsample, idx, lengths);
@@ -212,14 +212,27 @@ static int ball_query_impl(const float *new_xyz, const float *xyz, int B, int S,
     return PNPP_OK;
 }
 
+// A float radius squared in double and rounded: the radius has been rounded to float32 before it is squared, so for most radii this
+// is NOT float32(radius ** 2) of the python float the reference squares (Demo.py:65).  The _r2 entries take that value as it is.
+static float r2_of_float_radius(float radius) { return (float)((double)radius * (double)radius); }
+
 extern "C" int pnpp_ball_query(const float *new_xyz, const float *xyz, int B, int S, int N, float radius, int nsample,
                                int32_t *idx, void *stream) {
-    return ball_query_impl(new_xyz, xyz, B, S, N, nullptr, radius, nsample, idx, stream);
+    return ball_query_impl(new_xyz, xyz, B, S, N, nullptr, r2_of_float_radius(radius), nsample, idx, stream);
 }
 extern "C" int pnpp_ball_query_ragged(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, float radius,
                                       int nsample, int32_t *idx, void *stream) {
     PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "ball_query_ragged: null lengths");
-    return ball_query_impl(new_xyz, xyz, B, S, N, lengths, radius, nsample, idx, stream);
+    return ball_query_impl(new_xyz, xyz, B, S, N, lengths, r2_of_float_radius(radius), nsample, idx, stream);
+}
+extern "C" int pnpp_ball_query_r2(const float *new_xyz, const float *xyz, int B, int S, int N, float r2, int nsample, int32_t *idx,
+                                  void *stream) {
+    return ball_query_impl(new_xyz, xyz, B, S, N, nullptr, r2, nsample, idx, stream);
+}
+extern "C" int pnpp_ball_query_r2_ragged(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, float r2,
+                                         int nsample, int32_t *idx, void *stream) {
+    PNPP_REQUIRE(lengths, PNPP_ERR_ARG, "ball_query_r2_ragged: null lengths");
+    return ball_query_impl(new_xyz, xyz, B, S, N, lengths, r2, nsample, idx, stream);
 }
 
 extern "C" int pnpp_index_points(const float *points, const int32_t *idx, int B, int N, int C, int M, float *out, void *stream) {

@@ -164,6 +164,7 @@ SIGNATURES = {
     "pnpp_knn": (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp]),
     "pnpp_fps": (_i, [_fp, _i, _i, _i, _fp, _fp, _fp]),
     "pnpp_ball_query": (_i, [_fp, _fp, _i, _i, _i, _f, _i, _fp, _fp]),
+    "pnpp_ball_query_r2": (_i, [_fp, _fp, _i, _i, _i, _f, _i, _fp, _fp]),
     "pnpp_sample_random": (_i, [_u64, _u64, _i, _i, _i, _fp, _fp]),
     "pnpp_subsample_points": (_i, [_u64, _u64, _fp, _fp, _fp, _i, _i, _i, _fp, _fp]),
     "pnpp_augment_clouds": (_i, [_u64, _u64, _fp, _fp, _fp, _i, C.c_int64, _i, C.POINTER(AugmentDesc), _fp, _fp]),
@@ -224,6 +225,7 @@ SIGNATURES = {
     "pnpp_knn_ragged": (_i, [_fp, _fp, _i, _i, _i, _fp, _i, _fp, _fp]),
     "pnpp_fps_ragged": (_i, [_fp, _i, _i, _fp, _i, _fp, _fp, _fp]),
     "pnpp_ball_query_ragged": (_i, [_fp, _fp, _i, _i, _i, _fp, _f, _i, _fp, _fp]),
+    "pnpp_ball_query_r2_ragged": (_i, [_fp, _fp, _i, _i, _i, _fp, _f, _i, _fp, _fp]),
     "pnpp_sample_random_ragged": (_i, [_u64, _u64, _i, _i, _fp, _i, _fp, _fp]),
     "pnpp_sample_random_dev_ragged": (_i, [_u64, _fp, _u64, _i, _i, _fp, _i, _fp, _fp]),
     "pnpp_sample_random_dev2_ragged": (_i, [_u64, _fp, _u64, _i, _i, _fp, _i, _fp, _i, _i, _fp, _fp]),

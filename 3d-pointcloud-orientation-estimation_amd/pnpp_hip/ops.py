@@ -302,18 +302,20 @@ def farthest_point_sample(xyz: torch.Tensor, npoint: int, start: Optional[torch.
 
 
 def ball_query(radius: float, nsample: int, xyz: torch.Tensor, new_xyz: torch.Tensor, lengths=None) -> torch.Tensor:
-    """lengths (B,): a ragged batch -- row b lists members of xyz[b, :lengths[b]] only, as the call on that slice alone does."""
+    """lengths (B,): a ragged batch -- row b lists members of xyz[b, :lengths[b]] only, as the call on that slice alone does.
+    The threshold is the reference's (PointNet++Demo.py:65, `sqrdists > radius ** 2`): the python float squared in double, rounded to
+    float32 once -- by the C float parameter of the _r2 entries.  (A float32 radius squared afterwards is a different number.)"""
     xyz, new_xyz = _f32(xyz, "xyz"), _f32(new_xyz, "new_xyz")
     B, N, _ = xyz.shape
     S = new_xyz.shape[1]
+    r2 = float(radius) ** 2
     idx = torch.empty(B, S, nsample, device=xyz.device, dtype=torch.int32)
     if lengths is not None:
         lengths = ragged_lengths(lengths, B, N, xyz.device)
-        L.check(L.lib().pnpp_ball_query_ragged(new_xyz.data_ptr(), xyz.data_ptr(), B, S, N, lengths.data_ptr(), float(radius),
-                                               int(nsample), idx.data_ptr(), _stream()))
+        L.check(L.lib().pnpp_ball_query_r2_ragged(new_xyz.data_ptr(), xyz.data_ptr(), B, S, N, lengths.data_ptr(), r2,
+                                                  int(nsample), idx.data_ptr(), _stream()))
         return idx
-    L.check(L.lib().pnpp_ball_query(new_xyz.data_ptr(), xyz.data_ptr(), B, S, N, float(radius), int(nsample),
-                                    idx.data_ptr(), _stream()))
+    L.check(L.lib().pnpp_ball_query_r2(new_xyz.data_ptr(), xyz.data_ptr(), B, S, N, r2, int(nsample), idx.data_ptr(), _stream()))
     return idx
 
 

@@ -67,9 +67,18 @@ int pnpp_knn(const float *new_xyz, const float *xyz, int B, int S, int N, int k,
  * xyz (B,N,3), start (B) -> out (B,npoint) int32. */
 int pnpp_fps(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out, void *stream);
 
-/* PointNet++Demo.py:49-70  query_ball_point(radius, nsample, xyz, new_xyz) -> idx (B,S,nsample) int32. */
+/* PointNet++Demo.py:49-70  query_ball_point(radius, nsample, xyz, new_xyz) -> idx (B,S,nsample) int32.
+ * A point is a member when !(d > r2), d the float32 squared distance and r2 a float32 threshold.
+ *   pnpp_ball_query      r2 = (float)((double)radius * (double)radius): the radius is a float32 BEFORE it is squared.  For a radius that
+ *                        float32 does not hold exactly (0.2, 0.4, ...) this can sit one float32 away from what the reference compares
+ *                        against, float32(radius ** 2) of the python float (Demo.py:65): above for 0.05, 0.1, 0.2, 0.4, 0.8, below
+ *                        for 0.35, 0.45.  Kept for callers whose radius is a float32 to begin with.
+ *   pnpp_ball_query_r2   takes the threshold itself; hand it float32(radius ** 2), rounded once from double, for the reference's rule
+ *                        (what pnpp_hip.ops.ball_query does). */
 int pnpp_ball_query(const float *new_xyz, const float *xyz, int B, int S, int N, float radius, int nsample,
                     int32_t *idx, void *stream);
+int pnpp_ball_query_r2(const float *new_xyz, const float *xyz, int B, int S, int N, float r2, int nsample, int32_t *idx,
+                       void *stream);
 
 /* models/pointnet_pp_8dir.py:28  per-cloud uniform random subset of size npoint out of N, without
  * replacement, in random order -- the device-side replacement of B host `torch.randperm(N)[:npoint]`
@@ -109,6 +118,8 @@ int pnpp_knn_ragged(const float *new_xyz, const float *xyz, int B, int S, int N,
 int pnpp_fps_ragged(const float *xyz, int B, int N, const int32_t *lengths, int npoint, const int32_t *start, int32_t *out, void *stream);
 int pnpp_ball_query_ragged(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, float radius, int nsample,
                            int32_t *idx, void *stream);
+int pnpp_ball_query_r2_ragged(const float *new_xyz, const float *xyz, int B, int S, int N, const int32_t *lengths, float r2, int nsample,
+                              int32_t *idx, void *stream);
 int pnpp_sample_random_ragged(uint64_t seed, uint64_t stream_id, int B, int N, const int32_t *lengths, int npoint, int32_t *out,
                               void *stream);
 int pnpp_sample_random_dev_ragged(uint64_t seed, uint64_t *stream_id_dev, uint64_t offset, int B, int N, const int32_t *lengths,

@@ -122,10 +122,12 @@ void oracle_fps(const float *xyz, int B, int N, int npoint, const int32_t *start
 
 /* Radius ball query, PointNet++Demo.py:49-70.
  *   d2 = sum((new - xyz)^2, -1); keep n with !(d2 > r2) in ascending n; first nsample;
- *   missing slots are filled with the first kept index (N when nothing is inside).      */
-void oracle_ball_query(const float *new_xyz, const float *xyz, int B, int S, int N, float radius,
-                       int nsample, int32_t *idx) {
-    const float r2 = (float)((double)radius * (double)radius);
+ *   missing slots are filled with the first kept index (N when nothing is inside).
+ *   r2 is the float32 the reference compares against: `radius ** 2` of the python float, formed in
+ *   double and rounded once (Demo.py:65).  The caller computes it; a C float radius squared here
+ *   would have been rounded twice (one float32 off for 0.05, 0.1, 0.2, 0.35, 0.4, 0.45, 0.8).       */
+void oracle_ball_query_r2(const float *new_xyz, const float *xyz, int B, int S, int N, float r2,
+                          int nsample, int32_t *idx) {
     for (int b = 0; b < B; ++b)
         for (int s = 0; s < S; ++s) {
             const float *a = new_xyz + ((size_t)b * S + s) * 3;
@@ -142,4 +144,13 @@ void oracle_ball_query(const float *new_xyz, const float *xyz, int B, int S, int
             int first = cnt ? o[0] : N;
             for (int j = cnt; j < nsample; ++j) o[j] = first;
         }
+}
+
+/* The same query for a radius that is a float32 to begin with: the rule of the C entries pnpp_ball_query /
+ * pnpp_ball_query_ragged (include/pnpp_hip.h), r2 = (float)((double)radius * (double)radius).  NOT the
+ * reference's rule for a python float radius (comment above); kept under its old name and signature so
+ * that a caller built against them still gets what it got.                                            */
+void oracle_ball_query(const float *new_xyz, const float *xyz, int B, int S, int N, float radius,
+                       int nsample, int32_t *idx) {
+    oracle_ball_query_r2(new_xyz, xyz, B, S, N, (float)((double)radius * (double)radius), nsample, idx);
 }

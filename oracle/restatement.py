@@ -40,8 +40,10 @@ _lib = None
 
 
 def build_c_oracle(force: bool = False) -> str:
-    """Compile oracle/index_ops.c (gcc) if the shared object is missing."""
-    if force or not os.path.exists(_SO):
+    """Compile oracle/index_ops.c (gcc) if the shared object is missing or older than its source (a stale object lacks the
+    entries added since, or restates an older rule)."""
+    src = os.path.join(_HERE, "index_ops.c")
+    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
         subprocess.run(["make", "-C", _HERE], check=True, capture_output=True)
     return _SO
 
@@ -62,6 +64,8 @@ def _c():
         lib.oracle_fps.restype = None
         lib.oracle_ball_query.argtypes = [fp, fp, ci, ci, ci, ctypes.c_float, ci, ip]
         lib.oracle_ball_query.restype = None
+        lib.oracle_ball_query_r2.argtypes = [fp, fp, ci, ci, ci, ctypes.c_float, ci, ip]
+        lib.oracle_ball_query_r2.restype = None
         _lib = lib
     return _lib
 
@@ -115,7 +119,20 @@ def farthest_point_sample(xyz, npoint: int, start) -> torch.Tensor:
 
 
 def ball_query(radius: float, nsample: int, xyz, new_xyz) -> torch.Tensor:
-    """PointNet++Demo.py:49-70 (argument order as in the demo)."""
+    """PointNet++Demo.py:49-70 (argument order as in the demo).  The threshold is `radius ** 2` of the python float, rounded to
+    float32 once (:65 compares a float32 tensor with that python scalar)."""
+    b, a = _f32(xyz), _f32(new_xyz)
+    B, N, _ = b.shape
+    S = a.shape[1]
+    out = np.empty((B, S, nsample), np.int32)
+    r2 = np.float32(float(radius) ** 2)
+    _c().oracle_ball_query_r2(_fp(a), _fp(b), B, S, N, float(r2), nsample, _ip(out))
+    return torch.from_numpy(out.astype(np.int64))
+
+
+def ball_query_float32_radius(radius: float, nsample: int, xyz, new_xyz) -> torch.Tensor:
+    """The rule of the C entries pnpp_ball_query / pnpp_ball_query_ragged, which take the radius as a float32 and square it
+    afterwards; for most radii one float32 off the reference's threshold (ball_query above is the reference's rule)."""
     b, a = _f32(xyz), _f32(new_xyz)
     B, N, _ = b.shape
     S = a.shape[1]

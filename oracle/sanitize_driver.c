@@ -12,6 +12,7 @@
 void oracle_square_distance(const float *src, const float *dst, int B, int S, int N, float *out);
 int oracle_knn(const float *new_xyz, const float *xyz, int B, int S, int N, int k, int32_t *idx);
 void oracle_fps(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out);
+void oracle_ball_query_r2(const float *new_xyz, const float *xyz, int B, int S, int N, float r2, int nsample, int32_t *idx);
 void oracle_ball_query(const float *new_xyz, const float *xyz, int B, int S, int N, float radius, int nsample, int32_t *idx);
 
 static unsigned lcg = 12345u;
@@ -42,11 +43,16 @@ static int run(int B, int S, int N, int k, int npoint, float radius, int dup) {
         acc += f[i];
     }
     int32_t *bq = malloc(sizeof(int32_t) * (size_t)B * S * k);
-    oracle_ball_query(q, xyz, B, S, N, radius, k, bq);
+    oracle_ball_query_r2(q, xyz, B, S, N, (float)((double)radius * (double)radius), k, bq);   /* the squared threshold */
     for (int i = 0; i < B * S * k; ++i) {
         if (bq[i] < 0 || bq[i] > N) return 3;   /* N itself marks "nothing inside the radius" (PointNet++Demo.py:67-69) */
         acc += bq[i];
     }
+    int32_t *bq2 = malloc(sizeof(int32_t) * (size_t)B * S * k);
+    oracle_ball_query(q, xyz, B, S, N, radius, k, bq2);   /* the float32-radius form: the same threshold here, so the same lists */
+    for (int i = 0; i < B * S * k; ++i)
+        if (bq2[i] != bq[i]) return 5;
+    free(bq2);
     free(xyz), free(q), free(d), free(idx), free(start), free(f), free(bq);
     return acc < 0;
 }
